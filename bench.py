@@ -175,12 +175,31 @@ def _watch_sigterm():
 
 
 PREROLL_PASSES = 8192        # untimed deferred passes before --warmup: several game lengths, so that the games' ages are mixed
-MIN_TIMED_S = 0.30           # the timed region is `reps` x --steps passes, reps chosen so that it lasts at least this long
 
 
-def _reps_for(per_pass_s, steps):
-    import math
-    return max(1, int(math.ceil(MIN_TIMED_S / max(per_pass_s * steps, 1e-9))))
+DUMP_STATE_GAMES = 4096      # --dump-outputs: a fixed, seeded sample of the games for the large per-game arrays (<= 64 MB in all)
+DUMP_MASK_GAMES = 8192
+
+
+def dump_outputs(env, out_dir, rank):
+    """What the timed loop computed in its last pass, as a caller of it reads it back: every game's decision counter, and for a fixed
+    seeded sample of the games the canonical state blob and the next legal-action masks.  Integer words are stored as float64 (exact)."""
+    import numpy as np
+    n = env.n
+    pick = lambda k, salt: np.sort(np.random.default_rng(salt).choice(n, size=min(k, n), replace=False))
+    sg, mg = pick(DUMP_STATE_GAMES, 1), pick(DUMP_MASK_GAMES, 2)
+    arrays = {
+        "policy_counters": env.policy_counters().cpu().numpy().astype(np.float64),
+        "state_games": sg.astype(np.float64),
+        "state": env.export_state(sg).cpu().numpy().astype(np.float64),
+        "mask_games": mg.astype(np.float64),
+        "masks": env.get_action_masks().cpu().numpy()[mg].astype(np.float32),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def ppo_update_record(env, n, rank, world, T, cdist):
@@ -290,6 +309,8 @@ def main():
                     help="W > 0: deferred loop, tier-2 longest road + re-deals once per W passes; 0: lock-step loop")
     ap.add_argument("--no-lockstep", action="store_true", help="skip the lock-step measurement of a deferred run")
     ap.add_argument("--preroll", type=int, default=PREROLL_PASSES, help="untimed passes before --warmup (mixes the games' ages)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write what they computed (game states, next masks, decision counters) as DIR/<name>.npy")
     ap.add_argument("--ppo-steps", type=int, default=200,
                     help="T of the `ppo_update` sub-record (three rollouts + PPO updates on the same games, the third one reported; "
                          "200 = the reference's num_steps, RL/ppo/arguments.py:54-56); 0: skip")
@@ -322,40 +343,39 @@ def main():
 
     # ---- pre-roll (untimed, independent of --warmup): all games start a game at pass 0, and the opening phase (initial
     # placement: every road goes through the longest-road slow path) is not the steady state.  Several game lengths of
-    # deferred passes spread the games' ages; its duration also sizes the timed region.
+    # deferred passes spread the games' ages.
     W = args.window if args.window > 0 else 32
     stage("pre-roll")
     cdist.barrier()
-    t0 = time.perf_counter()
     env.random_rollout_deferred(max(args.preroll, 64), W)
     cdist.barrier()
-    pre_pass_s = cdist.max_over_ranks((time.perf_counter() - t0) / max(args.preroll, 64))
     step_idx = 1 << 20                                        # lock-step passes index the policy stream by a global step number
     stage("timed region")
 
     if args.window > 0:
-        reps = _reps_for(pre_pass_s, args.steps)
         env.random_rollout_deferred(args.warmup, args.window)
         c0 = int(env.policy_counters().sum())
         cdist.barrier()
         t0 = time.perf_counter()
-        env.random_rollout_deferred(args.steps * reps, args.window)      # reps x EXACTLY --steps passes, one timed region
+        env.random_rollout_deferred(args.steps, args.window)             # EXACTLY --steps passes, one timed region
         cdist.barrier()
         dt = cdist.max_over_ranks(time.perf_counter() - t0)     # max over ranks
         my_steps = int(env.policy_counters().sum()) - c0        # decisions actually executed by this rank's games
         env_steps = cdist.sum_over_ranks(my_steps)
     else:
-        reps = _reps_for(pre_pass_s * 4.0, args.steps)          # a lock-step pass is ~4 deferred passes long
         env.random_rollout(step_idx, args.warmup); step_idx += args.warmup
         cdist.barrier()
         t0 = time.perf_counter()
-        env.random_rollout(step_idx, args.steps * reps); step_idx += args.steps * reps
+        env.random_rollout(step_idx, args.steps); step_idx += args.steps
         cdist.barrier()
         dt = cdist.max_over_ranks(time.perf_counter() - t0)     # max over ranks
-        my_steps = n * args.steps * reps
+        my_steps = n * args.steps
         env_steps = world * my_steps
-    timed_passes = args.steps * reps
+    timed_passes = args.steps
     bad = env.invalid_action_count()
+    if args.dump_outputs:
+        stage("dump outputs")
+        dump_outputs(env, args.dump_outputs, rank)
     PARTIAL.update(value=env_steps / dt, ms_per_step=dt / timed_passes * 1e3, timed_s=dt, timed_passes=timed_passes, higher_is_better=True,
                    scaling="weak", env_steps_executed=env_steps, invalid_actions=bad, status="timed region done; later stages incomplete")
     stage("device identities (all_gather_object)")
@@ -365,16 +385,15 @@ def main():
 
     lockstep = None
     if args.window > 0 and not args.no_lockstep:
-        # the same games, continued in lock-step (every game steps in every pass): same rule for the timed region
-        ls_reps = _reps_for(pre_pass_s * 4.0, args.steps)
+        # the same games, continued in lock-step (every game steps in every pass): --steps passes as well
         env.random_rollout(step_idx, 32); step_idx += 32
         cdist.barrier()
         t0 = time.perf_counter()
-        env.random_rollout(step_idx, args.steps * ls_reps); step_idx += args.steps * ls_reps
+        env.random_rollout(step_idx, args.steps); step_idx += args.steps
         cdist.barrier()
         ls_dt = cdist.max_over_ranks(time.perf_counter() - t0)
-        ls_passes = args.steps * ls_reps
-        lockstep = {"value": world * n * ls_passes / ls_dt, "unit": "env-steps/s", "steps": args.steps, "reps": ls_reps,
+        ls_passes = args.steps
+        lockstep = {"value": world * n * ls_passes / ls_dt, "unit": "env-steps/s", "steps": args.steps,
                     "timed_s": ls_dt, "ms_per_step": ls_dt / ls_passes * 1e3}
 
     # The same games through the boundary's step entry points with CALLER-SUPPLIED actions (what a collector or a search calls:
@@ -494,7 +513,7 @@ def main():
         value = env_steps / dt
         out = {
             "metric": "Catan env-steps/sec at 65k parallel games", "value": value, "unit": "env-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "reps": reps, "timed_passes": timed_passes,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "timed_passes": timed_passes,
             "timed_s": dt, "preroll_passes": max(args.preroll, 64), "ms_per_step": dt / timed_passes * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/u32 (integer bitboards)",
             "data": "synthetic (random-seed boards, uniform-random legal policy on device)",
@@ -506,7 +525,7 @@ def main():
                        "auto_reset": True, "parallelism": f"games sharded over {world} GPU(s), no collective",
                        "schedule": (f"deferred, window {args.window}, {'fused-sampling loop (one kernel per pass)' if env.deferred_fused else 'sampler + k_step per pass'}: slow-path games sit out; value = executed env steps / time"
                                     if args.window > 0 else "lock-step: every game steps in every pass"),
-                       "timed_region": f"{reps} x --steps passes in one region (>= {MIN_TIMED_S} s), after {max(args.preroll, 64)} "
+                       "timed_region": f"--steps passes in one region, after {max(args.preroll, 64)} "
                                        f"untimed pre-roll passes + --warmup"},
             "env_steps_executed": env_steps, "active_fraction": env_steps / (world * n * timed_passes),
             "invalid_actions": bad,

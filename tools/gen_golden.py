@@ -10,6 +10,7 @@
                       actions + crc32 of the state at every step (config 1 known-answer test for the oracle MT mode)
   longest_road.npz    (edge_owner, corner_owner, player) -> Game.get_longest_path, harvested from play + adversarial
   gae_ppo.npz         BatchProcessor GAE / PPO loss values computed with the reference's torch code
+  ref_checks.npz      the reference's side of several parity checks (gen_ref_checks)
   validate_cases.npz  validate mode (Game.validate_action): states x probe actions -> the reference's accept / reject and,
                       for accepted ones, its state crc / masks / rewards / done afterwards (incl. actions outside the masks)
 """
@@ -834,6 +835,144 @@ def gen_validate_cases(seed=61, n_states=720, every=31):
                 out_of_mask_by_type={int(t): int(((ca[:, 0] == t) & oom).sum()) for t in range(13) if ((ca[:, 0] == t) & oom).any()})
 
 
+def gen_ref_checks():
+    """ref_checks.npz: what the reference returned in the checks that used to import it at test time.
+      eval_*      EvaluationManager.run_evaluation_game (evaluation_manager.py) with a scripted uniform-random legal policy keyed by
+                  (game, decision number) on the philox game streams: seat orders and (winner, policy-0 VPs, game length, policy-0
+                  decisions) of 4 games (tests/test_evaluation_cpu.py)
+      bptt_*      BatchProcessor.generator_lstm (process_batch.py:203-293) on a tagged storage: every field of every minibatch
+      vre_*       compute_advantages_alt (process_batch.py:112-128) with an LSTM stand-in net: its inputs, the rows it evaluated and
+                  the values it stored (tests/test_lstm_bptt_cpu.py)
+      sd_*        the names and shapes of build_agent_model().state_dict(), the key set a strict load_state_dict checks
+                  (tests/test_policy.py)"""
+    import types
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib
+    out = {}
+    # ---------------- evaluation episodes
+    from RL.ppo.evaluation_manager import EvaluationManager
+    import ctypes as C
+    seed, n = 31, 4
+
+    def scripted(L, env_ptr, env_id, step, masks_flat):
+        m = np.ascontiguousarray(masks_flat, dtype=np.float32)
+        a = np.zeros(18, dtype=np.int32)
+        L.orc_sample_action(env_ptr, seed + 99, env_id, int(step), m.ctypes.data_as(C.POINTER(C.c_float)), a.ctypes.data_as(C.POINTER(C.c_int32)))
+        return a
+
+    class EnvAdapter(object):
+        def __init__(self, env_id):
+            self.r = rh.RefEnv(seed, env_id)
+            self.env_id, self.steps = env_id, 0
+            self.mirror = oracle_lib.OracleEnv(seed, env_id)        # supplies the scripted policy with its hand-dependent draws
+
+        @property
+        def game(self): return self.r.env.game
+
+        @property
+        def winner(self): return self.r.env.winner
+
+        @property
+        def curr_vps(self): return self.r.env.curr_vps
+
+        def reset(self):
+            self.mirror.reset()
+            return self.r.reset()
+
+        def get_action_masks(self):
+            return self.r.env.get_action_masks()
+
+        def step(self, a):
+            flat = np.concatenate([np.asarray(h).reshape(-1) for h in a]).astype(np.int32)
+            with rh.patched_rng(self.r.stream):
+                res = self.r.env.step(a)
+            self.mirror.step(flat)
+            self.steps += 1
+            return res
+
+    class FakePolicy(object):
+        lstm_size = 4
+        dummy_param = torch.empty(1)
+
+        def __init__(self, mgr): self.mgr = mgr
+        def eval(self): pass
+        def obs_to_torch(self, obs): return obs
+        def act_masks_to_torch(self, masks): return masks
+        def torch_act_to_np(self, a): return a
+
+        def act(self, obs, hs, tm, masks, deterministic=False):
+            ad = self.mgr.env
+            a = scripted(ad.mirror.L, ad.mirror.p, ad.env_id, ad.steps, rh.masks_flat(masks))
+            return None, rh.action_to_heads(a), None, hs
+
+    mgr = EvaluationManager.__new__(EvaluationManager)
+    mgr.policies = [FakePolicy(mgr) for _ in range(4)]
+    mgr.device = torch.device("cpu")
+    want, orders = [], []
+    random.seed(77)
+    for g in range(n):
+        mgr.env = EnvAdapter(g)
+        want.append([int(x) for x in mgr.run_evaluation_game()])
+        orders.append([int(p) for p in mgr.order])
+        assert np.array_equal(mgr.env.r.state_blob(), mgr.env.mirror.export())
+    out.update(eval_seed=np.int64(seed), eval_orders=np.array(orders, dtype=np.int64), eval_want=np.array(want, dtype=np.int64))
+    # ---------------- truncated-BPTT minibatches
+    from RL.ppo.process_batch import BatchProcessor
+    T, N, L, nmb, H = 20, 6, 5, 4, 3
+    args = types.SimpleNamespace(num_steps=T, num_processes=N, num_envs_per_process=1, gamma=0.99, gae_lambda=0.95)
+    bp = BatchProcessor(args, H, obs_keys=["a", "b"], obs_type=["normal", "normal"], num_action_heads=3,
+                        type_conditional_masks=[1], device="cpu")
+    gen = torch.Generator().manual_seed(0)
+    tag = (torch.arange(T + 1)[:, None] * 100 + torch.arange(N)[None, :]).float()          # value = 100 t + game
+    bp.obs_dict = {"a": tag[:, :, None] + torch.tensor([0.0, 0.25]), "b": tag[:, :, None] * 2}
+    bp.hidden_states = (tag[:, :, None] + torch.tensor([0.1, 0.2, 0.3]), -tag[:, :, None] - torch.tensor([0.1, 0.2, 0.3]))
+    bp.actions = [tag[:T, :, None].long() + i for i in range(3)]
+    bp.action_masks = [tag[:T, :, None] + 0.5, torch.stack([tag[:T, :, None] + 1, tag[:T, :, None] + 2]), tag[:T, :, None] + 3]
+    bp.values = tag[:, :, None] + 7; bp.returns = tag[:T, :, None] + 8
+    bp.masks = (torch.rand(T + 1, N, 1, generator=gen) > 0.2).float()
+    bp.action_log_probs = tag[:T, :, None] + 9; bp.advantages = tag[:T, :, None] + 10
+    np.random.seed(5)
+    batches = list(bp.generator_lstm(nmb, T * N, L))
+    out["bptt_masks"] = bp.masks.numpy()
+    fields = {"obs_a": lambda b: b[0]["a"], "obs_b": lambda b: b[0]["b"], "hid0": lambda b: b[1][0], "hid1": lambda b: b[1][1],
+              "act0": lambda b: b[2][0], "act1": lambda b: b[2][1], "act2": lambda b: b[2][2], "amask0": lambda b: b[3][0],
+              "amask1": lambda b: b[3][1], "vpred": lambda b: b[4], "ret": lambda b: b[5], "msk": lambda b: b[6],
+              "oldlp": lambda b: b[7], "adv": lambda b: b[8]}
+    for k, f in fields.items():
+        out["bptt_" + k] = np.stack([f(b).numpy() for b in batches])
+    # ---------------- the LSTM value re-evaluation rule
+    T, N, H = 4, 3, 2
+    args = types.SimpleNamespace(num_steps=T, num_processes=N, num_envs_per_process=1, gamma=0.9, gae_lambda=0.8)
+    bp = BatchProcessor(args, H, obs_keys=["a"], obs_type=["normal"], device="cpu")
+    gen = torch.Generator().manual_seed(1)
+    bp.obs_dict = {"a": torch.randn(T + 1, N, 2, generator=gen)}
+    bp.hidden_states = (torch.randn(T + 1, N, H, generator=gen), torch.randn(T + 1, N, H, generator=gen))
+    bp.masks = (torch.rand(T + 1, N, 1, generator=gen) > 0.3).float()
+    bp.rewards = torch.randn(T, N, 1, generator=gen)
+    seen = []
+
+    class Net(object):
+        include_lstm, use_value_normalisation = True, False
+        def get_value(self, obs, hidden, masks):
+            seen.append((obs["a"].clone(), hidden[0].clone(), hidden[1].clone(), masks.clone()))
+            return (obs["a"].sum(1, keepdim=True) + (hidden[0] * masks).sum(1, keepdim=True))
+    bp.compute_advantages_alt(Net(), max_processes_at_once=2)
+    out.update(vre_obs=bp.obs_dict["a"].numpy(), vre_h=bp.hidden_states[0].numpy(), vre_c=bp.hidden_states[1].numpy(),
+               vre_masks=bp.masks.numpy(), vre_values=bp.values.numpy(),
+               vre_call_rows=np.array([s[0].shape[0] for s in seen], dtype=np.int64),
+               vre_call_obs=np.concatenate([s[0].numpy() for s in seen]), vre_call_h=np.concatenate([s[1].numpy() for s in seen]),
+               vre_call_c=np.concatenate([s[2].numpy() for s in seen]), vre_call_masks=np.concatenate([s[3].numpy() for s in seen]))
+    # ---------------- the reference net's state-dict layout
+    from RL.models.build_agent_model import build_agent_model
+    sd = build_agent_model().state_dict()
+    names = sorted(sd)
+    out["sd_names"] = np.array(names)
+    out["sd_shapes"] = np.array([list(sd[k].shape) + [-1] * (4 - sd[k].dim()) for k in names], dtype=np.int64)
+    np.savez_compressed(os.path.join(OUT, "ref_checks.npz"), **out)
+    return {k: v.shape for k, v in out.items()}
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "rollout":
         print("rollout_small (games complete, pre-advance, first-game lengths):", gen_rollout_small()); sys.exit(0)
@@ -856,6 +995,8 @@ if __name__ == "__main__":
         gen_gae_ppo(); print("gae/ppo"); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "validate":
         print("validate_cases", gen_validate_cases()); sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "ref_checks":
+        print("ref_checks", gen_ref_checks()); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "league":
         gen_league(); print("league"); sys.exit(0)
     gen_topology(); print("topology")
@@ -875,4 +1016,5 @@ if __name__ == "__main__":
     print("policy_small", gen_policy_small())
     print("forward_search", gen_forward_search())
     print("validate_cases", gen_validate_cases())
+    print("ref_checks", gen_ref_checks())
     os.system(f"ls -la {OUT}; du -sh {OUT}")
