@@ -89,6 +89,31 @@ int catan_mt19937_set_state(catan_env_t* env, int32_t which, const uint32_t* key
 /* Board.reset alone (game/components/board.py:67-100): takes its draws; the game must be reset afterwards (see above). */
 int catan_reset_board_only(catan_env_t* env, catan_stream_t stream);
 
+/* Board layouts: the three knobs of Board.__init__ (game/components/board.py:23-47, Game(board_config=...) game/game.py:16-17), applied
+ * as Board.reset applies them (:67-100):
+ *   has_fixed_terrain:  terrain[t] is tile t's terrain (Desert 0, Hills 1, Forest 2, Mountains 3, Pastures 4, Fields 5 - the reference's
+ *                       Terrain values, as in the blob's tile_res); no draws.  Otherwise the terrain is shuffled.
+ *   has_fixed_numbers:  numbers[i] is the token of the i-th non-desert tile along NUMBER_PLACEMENT_INDS; no shuffle, no 6/8 check.
+ *   otherwise:          randomise_number_placement != 0: DEFAULT_NUMBER_ORDER shuffled until no two 6/8 tiles touch (the default);
+ *                       0: DEFAULT_NUMBER_ORDER as it stands, no draws, no check.
+ * Harbours, player order and the development deck are drawn as always.  The multisets must be the standard ones (TERRAIN_TO_PLACE,
+ * DEFAULT_NUMBER_ORDER): the check the reference's constructor means to make (its np.array_equal call cannot run). */
+typedef struct {
+    int32_t randomise_number_placement;
+    int32_t has_fixed_terrain;
+    int32_t has_fixed_numbers;
+    int8_t terrain[19];
+    int8_t numbers[18];
+    int8_t reserved_[7];                  /* keeps sizeof a multiple of 8; set to 0 */
+} catan_board_cfg_t;
+/* Installs a table of n_cfgs <= 16 layouts (cfgs: host memory) and each game's entry (game_cfg: device uint8[n], NULL = entry 0 for every
+ * game).  Takes effect at each game's next deal (catan_reset, catan_reset_board_only, the auto-reset of catan_step, the re-deals of the
+ * deferred calls and rollouts); games in progress are untouched.  n_cfgs = 0 removes the table: every deal is fully random again, draw for
+ * draw as on a handle that never had one.  CATAN_EINVAL (nothing installed) for a bad multiset, n_cfgs > 16, any game_cfg[g] >= n_cfgs
+ * (checked on the device: the call synchronises its stream once) or an open deferred sequence.  Device memory while a table is installed:
+ * n bytes (the handle's copy of game_cfg, n rounded up to a multiple of 256) plus 56 bytes per layout. */
+int catan_set_board_configs(catan_env_t* env, const catan_board_cfg_t* cfgs, int32_t n_cfgs, const uint8_t* game_cfg, catan_stream_t stream);
+
 /* EnvWrapper.step(action): env/wrapper.py:36-50 (translate + apply + done/reward); then, per cfg, auto-reset of
  * (a game whose action type is negative is left untouched: explicit no-op, reward 0, done 0)
  * finished games; then the next legal-action masks are refreshed (kept packed inside the handle). */
@@ -219,10 +244,6 @@ int catan_obs_rows_of(catan_env_t* env, int32_t bf16, void* dense_f, int32_t* de
                       int8_t* rows_lens, const int64_t* t_idx, const uint8_t* sel, const int32_t* games, int64_t n_rows, catan_stream_t stream);
 int catan_masks_of(catan_env_t* env, float* out_masks, const int32_t* games, int64_t n_rows, catan_stream_t stream);
 
-/* Game.get_longest_path(player): game/game.py:843-862 for players[i] (PlayerId) in game i -> out[i].  Diagnostic/test
- * entry; inside catan_step the same search runs as part of update_longest_road. */
-int catan_longest_path(catan_env_t* env, const int32_t* players, int32_t* out, catan_stream_t stream);
-
 /* BatchProcessor.compute_advantages_alt: RL/ppo/process_batch.py:134-141.  rewards [T][N], values [T+1][N]
  * (denormalised), masks [T+1][N] -> returns [T][N], adv_raw [T][N] = returns - values[:-1], and
  * stats3 (device double[3]) = (sum, sum of squares, count) of adv_raw for the global normalisation.
@@ -257,7 +278,8 @@ int64_t catan_inconsistent_deal_count(catan_env_t* env, catan_stream_t stream);
 /* Not part of the drop-in boundary, declared in their own headers (same library):
  *   catan_hip_nn.h      the policy net's hand-written kernels (RL/models: attention, LayerNorm, tall-skinny linears, the
  *                       tile encoder, the action heads, the dev-card modules, the LSTM cell, the masked categorical)
- *   catan_hip_tuning.h  scheduling knobs, counters and profilers of the env kernels (benchmarks and diagnostics only) */
+ *   catan_hip_tuning.h  scheduling knobs, counters and profilers of the env kernels (benchmarks and diagnostics only), and
+ *                       catan_longest_path, the diagnostic entry to the longest-road search */
 
 
 #ifdef __cplusplus

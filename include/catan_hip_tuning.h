@@ -23,6 +23,9 @@ int catan_set_lr_budgets(catan_env_t* env, int32_t lockstep, int32_t deferred);
 int catan_slow_path_counts(catan_env_t* env, catan_stream_t stream, uint64_t* out3);
 /* tier-2 longest-road search: iterations per bulk-synchronous round (work is re-shared between rounds): lock-step / deferred */
 int catan_set_lr_rounds(catan_env_t* env, int32_t lockstep, int32_t deferred);
+/* Game.get_longest_path(player): game/game.py:843-862 for players[i] (PlayerId) in game i -> out[i].  Diagnostic/test
+ * entry; inside catan_step the same search runs as part of update_longest_road. */
+int catan_longest_path(catan_env_t* env, const int32_t* players, int32_t* out, catan_stream_t stream);
 
 /* the rollout loops with a hipEvent around every kernel launch (recorded on the stream the kernel runs on); window <= 0: the
  * lock-step loop (step_idx0 as in catan_random_rollout), window > 0: the deferred loop (step_idx0 ignored).  kernel_ms is a HOST

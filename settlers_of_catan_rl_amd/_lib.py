@@ -28,6 +28,12 @@ class CatanCfg(C.Structure):
                 ("max_actions_per_turn", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class CatanBoardCfg(C.Structure):
+    """catan_board_cfg_t (include/catan_hip.h): one board layout"""
+    _fields_ = [("randomise_number_placement", C.c_int32), ("has_fixed_terrain", C.c_int32), ("has_fixed_numbers", C.c_int32),
+                ("terrain", C.c_int8 * 19), ("numbers", C.c_int8 * 18), ("reserved_", C.c_int8 * 7)]
+
+
 def _sources():
     out = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h", ".inc"))]
     inc = os.path.join(os.path.dirname(PKG_DIR), "include")
@@ -297,7 +303,11 @@ _SIGS = {
     "catan_linear_wgrad_supported": (C.c_int, [C.c_int64, C.c_int, C.c_int]),
     "catan_linear_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, _vp]),
     "catan_linear_wgrad_grouped": (C.c_int, [C.POINTER(CatanWgradProblem), C.c_int32, _vp]),
+    "catan_set_board_configs": (C.c_int, [_vp, C.POINTER(CatanBoardCfg), C.c_int32, _vp, _vp]),
 }
+# bound only where the library exports them: the same callers also load oracle/libcatan_cpu.so, which implements the env ABI
+# without these
+_OPTIONAL = {"catan_set_board_configs"}
 
 
 def declared_symbols():
@@ -316,6 +326,8 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in _SIGS.items():
+            if name in _OPTIONAL and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         have, want = L.catan_build_hash().decode(), source_hash()

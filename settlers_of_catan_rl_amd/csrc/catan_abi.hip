@@ -1,6 +1,7 @@
 // catan_abi.hip - host side of libcatan_hip.so: handle, launches, C ABI (include/catan_hip.h).
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -74,7 +75,12 @@ struct catan_env {
     int d_window;         // its window length
     hipStream_t d_stream; // ... and the caller's stream (one stream per sequence)
     MtPair* mt_dev;       // RNG contract (A): the handle's two MT19937 generators on the device (catan_seed_mt19937), else NULL
+    BoardCfg* bcfg_dev;   // catan_set_board_configs: the layout table and the games' indices into it (ctx.bcfg / ctx.bcfg_idx), else NULL
+    u8* bcfg_idx_dev;
 };
+static_assert(sizeof(BoardCfg) == sizeof(catan_board_cfg_t) && sizeof(catan_board_cfg_t) == 56 &&
+              offsetof(BoardCfg, terrain) == offsetof(catan_board_cfg_t, terrain) &&
+              offsetof(BoardCfg, numbers) == offsetof(catan_board_cfg_t, numbers), "board layout: device and C ABI layouts differ");
 
 // games per k_step wave (catan_set_step_wave_games).  32 since the end of round 5: two waves per SIMD, so that one wave's gather overlaps the other's
 // rules code - 41.4 -> 40.9 us per pass, lock-step 180.8 -> 178 us (profiles/r05_s5_pass_experiments.txt, run 20; 16: 43.2 us).  In round 3 the
@@ -501,6 +507,8 @@ void catan_destroy(catan_env_t* e) {
     if (e->pend.lists) hipFree(e->pend.lists);
     if (e->pend.bctr) hipFree(e->pend.bctr);
     if (e->mt_dev) hipFree(e->mt_dev);
+    if (e->bcfg_dev) hipFree(e->bcfg_dev);
+    if (e->bcfg_idx_dev) hipFree(e->bcfg_idx_dev);
     if (e->side) hipStreamDestroy(e->side);
     if (e->ev_fork) hipEventDestroy(e->ev_fork);
     if (e->ev_join) hipEventDestroy(e->ev_join);
@@ -598,6 +606,72 @@ int catan_seed_mt19937(catan_env_t* e, uint32_t numpy_seed, uint32_t python_seed
 int catan_mt19937_set_state(catan_env_t* e, int32_t which, const uint32_t* key624, int32_t pos, catan_stream_t stream) {
     if (!e || !key624 || (which != 0 && which != 1) || pos < 0 || pos > 624) return fail(CATAN_EINVAL, "catan_mt19937_set_state: bad arguments");
     return mt_install(e, which, key624, pos, S(stream));
+}
+
+// ---- board layouts (include/catan_hip.h)
+static const char* board_cfg_error(const catan_board_cfg_t& c) {
+    if (c.has_fixed_terrain) {
+        static const int want[6] = { 1, 3, 4, 3, 4, 4 };       // TERRAIN_TO_PLACE: Desert, Hills, Forest, Mountains, Pastures, Fields
+        int cnt[6] = { 0, 0, 0, 0, 0, 0 };
+        for (int t = 0; t < 19; t++) {
+            if (c.terrain[t] < 0 || c.terrain[t] > 5) return "a terrain value outside 0..5";
+            cnt[c.terrain[t]]++;
+        }
+        for (int k = 0; k < 6; k++) if (cnt[k] != want[k]) return "the fixed terrain is not the multiset of TERRAIN_TO_PLACE";
+    }
+    if (c.has_fixed_numbers) {
+        static const int want[13] = { 0, 0, 1, 2, 2, 2, 2, 0, 2, 2, 2, 2, 1 };   // DEFAULT_NUMBER_ORDER: one 2 and one 12, two of 3..6 and 8..11
+        int cnt[13] = { 0 };
+        for (int i = 0; i < 18; i++) {
+            if (c.numbers[i] < 2 || c.numbers[i] > 12) return "a number token outside 2..12";
+            cnt[c.numbers[i]]++;
+        }
+        for (int k = 0; k < 13; k++) if (cnt[k] != want[k]) return "the fixed number order is not the multiset of DEFAULT_NUMBER_ORDER";
+    }
+    return nullptr;
+}
+int catan_set_board_configs(catan_env_t* e, const catan_board_cfg_t* cfgs, int32_t n_cfgs, const uint8_t* game_cfg, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_set_board_configs: null handle");
+    NOT_DEFERRED(e, "catan_set_board_configs");
+    if (n_cfgs < 0 || n_cfgs > MAX_BOARD_CFGS) return fail(CATAN_EINVAL, "catan_set_board_configs: n_cfgs must be 0..16");
+    if (n_cfgs > 0 && !cfgs) return fail(CATAN_EINVAL, "catan_set_board_configs: null cfgs");
+    for (int i = 0; i < n_cfgs; i++)
+        if (const char* why = board_cfg_error(cfgs[i])) return fail(CATAN_EINVAL, "catan_set_board_configs: layout " + std::to_string(i) + ": " + why);
+    const hipStream_t st = S(stream);
+    // the old table may still be read by re-deals in flight on any of the handle's streams
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(e->side));
+    HIPCHK(hipStreamSynchronize(e->fstream[0]));
+    HIPCHK(hipStreamSynchronize(e->sstream));
+    BoardCfg* tab = nullptr;
+    u8* idx = nullptr;
+    if (n_cfgs > 0) {
+        u32* bad = nullptr;
+        hipError_t rc = hipMalloc((void**)&tab, (size_t)n_cfgs * sizeof(BoardCfg));
+        if (rc == hipSuccess) rc = hipMalloc((void**)&idx, (size_t)e->N);
+        if (rc == hipSuccess) rc = hipMalloc((void**)&bad, sizeof(u32));
+        if (rc == hipSuccess) rc = hipMemcpyAsync(tab, cfgs, (size_t)n_cfgs * sizeof(BoardCfg), hipMemcpyHostToDevice, st);
+        if (rc == hipSuccess) rc = hipMemsetAsync(bad, 0, sizeof(u32), st);
+        if (rc == hipSuccess) {
+            hipLaunchKernelGGL(k_board_cfg_index, dim3(blocks(e->N, BLOCK)), dim3(BLOCK), 0, st, (long)e->n, (long)e->N, game_cfg, (int)n_cfgs, idx, bad);
+            rc = hipGetLastError();
+        }
+        u32 nbad = 0;
+        if (rc == hipSuccess) rc = hipMemcpyAsync(&nbad, bad, sizeof(u32), hipMemcpyDeviceToHost, st);
+        if (rc == hipSuccess) rc = hipStreamSynchronize(st);
+        if (bad) hipFree(bad);
+        if (rc != hipSuccess || nbad != 0) {
+            if (tab) hipFree(tab);
+            if (idx) hipFree(idx);
+            if (rc != hipSuccess) return fail(CATAN_EHIP, std::string("catan_set_board_configs: ") + hipGetErrorString(rc));
+            return fail(CATAN_EINVAL, "catan_set_board_configs: " + std::to_string(nbad) + " game_cfg entries >= n_cfgs");
+        }
+    }
+    if (e->bcfg_dev) hipFree(e->bcfg_dev);
+    if (e->bcfg_idx_dev) hipFree(e->bcfg_idx_dev);
+    e->bcfg_dev = tab; e->bcfg_idx_dev = idx;
+    e->ctx.bcfg = tab; e->ctx.bcfg_idx = idx;
+    return CATAN_OK;
 }
 
 static StepCfg step_cfg(const catan_env_t* e) {

@@ -49,6 +49,17 @@ constexpr u64 ALL54 = (1ull << 54) - 1;
 constexpr int MT_RING = 8192, MT_AHEAD = 6144, MT_AHEAD_PY = 1024;
 struct MtGen { u32 mt[624]; u32 idx; u32 produced; u32 ring[MT_RING]; };
 struct MtPair { MtGen np, py; u32 cons_py; };
+// Board layouts (catan_set_board_configs): the device copy of catan_board_cfg_t (include/catan_hip.h; the layouts are
+// static_assert-ed equal in catan_abi.hip).  Board.__init__'s three knobs, game/components/board.py:23-47.
+struct BoardCfg {
+    int32_t randomise;          // randomise_number_placement
+    int32_t fixed_terrain;      // terrain[] holds fixed_terrain_placements (Terrain values, tile order)
+    int32_t fixed_numbers;      // numbers[] holds fixed_number_order (NUMBER_PLACEMENT_INDS order, desert skipped)
+    int8_t terrain[19];
+    int8_t numbers[18];
+    int8_t pad_[7];
+};
+constexpr int MAX_BOARD_CFGS = 16;
 struct Ctx {          // launch-invariant handle fields
     u32* R;           // game records, REC words each
     long N;           // padded number of games (row pitch)
@@ -56,6 +67,8 @@ struct Ctx {          // launch-invariant handle fields
     u32 key0, key1;   // philox key = seed
     u64 env_id0;      // global id of game 0 (multi-GPU shards keep their global ids)
     MtPair* mt;       // contract (A): the handle's two MT19937 generators (n == 1), or null = contract (B), per-game Philox streams
+    const BoardCfg* bcfg;   // board layouts (<= MAX_BOARD_CFGS entries), or null = every deal fully random
+    const u8* bcfg_idx;     // [N] layout of each game (read only when bcfg != null)
 };
 
 // Derived helpers shared by the two state views (CRTP).
@@ -898,17 +911,30 @@ DEVI void shuffle_bytes(u8* a, int n, RngBuf& rng) {     // np.random.shuffle on
 // Same draws, same order, same result as the serial loop (which remains the fall-back when a shuffle needs more than
 // TOK_DRAWS words or the pre-generated words run out).
 DEVI u32 fy_mask(int i) { return 0xFFFFFFFFu >> __clz((u32)i); }
+// bc: the game's board layout, or null (fully random, the default).  A fixed terrain takes no draws (board.py:68-69); fixed
+// numbers replace DEFAULT_NUMBER_ORDER (:74-75) - whether the tokens are then shuffled at all is the caller's (tokens_fixed).
 template <class S>
-DEVI void reset_part1(const S& s, RngBuf& rng, ResetScratch& sc, int hot_rows) {       // lane 0
+DEVI void reset_part1(const S& s, RngBuf& rng, ResetScratch& sc, int hot_rows, const BoardCfg* bc = nullptr) {       // lane 0
     u8* arr = sc.arr; u8* terr = sc.terr;
     for (int r = 0; r < hot_rows; r++) if (r != W_RNG) s.sw(r, 0);
-    for (int i = 0; i < 19; i++) terr[i] = (u8)(i == 0 ? 0 : (i < 4 ? 1 : (i < 8 ? 5 : (i < 12 ? 2 : (i < 15 ? 3 : 4)))));
-    shuffle_bytes(terr, 19, rng);                              // board.py:72
-    // board.py:25: 5 2 6 3 8 10 9 12 11 4 8 10 9 4 5 6 3 11, packed as nibbles (no constant-memory table)
-    for (int i = 0; i < 16; i++) arr[i] = (u8)((0x6549A84BC9A83625ull >> (4 * i)) & 15);       // entry i in bits 4i..4i+3
-    arr[16] = 3; arr[17] = 11;
+    if (bc != nullptr && bc->fixed_terrain) {
+        for (int i = 0; i < 19; i++) terr[i] = (u8)bc->terrain[i];
+    } else {
+        for (int i = 0; i < 19; i++) terr[i] = (u8)(i == 0 ? 0 : (i < 4 ? 1 : (i < 8 ? 5 : (i < 12 ? 2 : (i < 15 ? 3 : 4)))));
+        shuffle_bytes(terr, 19, rng);                          // board.py:72
+    }
+    if (bc != nullptr && bc->fixed_numbers) {
+        for (int i = 0; i < 18; i++) arr[i] = (u8)bc->numbers[i];
+    } else {
+        // board.py:25: 5 2 6 3 8 10 9 12 11 4 8 10 9 4 5 6 3 11, packed as nibbles (no constant-memory table)
+        for (int i = 0; i < 16; i++) arr[i] = (u8)((0x6549A84BC9A83625ull >> (4 * i)) & 15);   // entry i in bits 4i..4i+3
+        arr[16] = 3; arr[17] = 11;
+    }
     sc.tok_state[0] = (int)(rng.slow.draws - rng.base);        // stream offset of the first token shuffle
 }
+// board.py:74-81: fixed numbers are placed as given, and so is DEFAULT_NUMBER_ORDER without randomise_number_placement - no
+// shuffle, no 6/8 check (two touching reds are the caller's choice)
+DEVI bool tokens_fixed(const BoardCfg* bc) { return bc != nullptr && (bc->fixed_numbers || !bc->randomise); }
 // all 64 lanes; returns (on every lane) whether the board is complete; sc.tok_state[0] = stream offset behind the loop
 DEVI bool reset_tokens_parallel(ResetScratch& sc, int lane) {
     // per lane = tile t: its index in the spiral placement order, its neighbours, its terrain
@@ -2863,9 +2889,11 @@ DEVI void wave_reset_game(const Ctx& c, long e, u32* rec, ResetScratch& sc, int 
     RngBuf rb;
     rb.buf = sc.rnd; rb.base = blk0 * 4; rb.avail = RND_WORDS; rb.slow = mine;
     const long long t0 = prof ? wall_clock64() : 0;
-    if (lane == 0) reset_part1(s, rb, sc, ROWS_HOT);
+    // the game's layout: wave-uniform (one game per wave); without a table (c.bcfg == null, the default) nothing more is read
+    const BoardCfg* bc = c.bcfg != nullptr ? c.bcfg + c.bcfg_idx[e] : nullptr;
+    if (lane == 0) reset_part1(s, rb, sc, ROWS_HOT, bc);
     __builtin_amdgcn_wave_barrier();
-    const bool tokens_done = reset_tokens_parallel(sc, lane);
+    const bool tokens_done = tokens_fixed(bc) || reset_tokens_parallel(sc, lane);
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
         reset_part2(s, rb, sc, tokens_done, board_only);
@@ -2938,6 +2966,15 @@ __global__ __launch_bounds__(64) void k_reset(Ctx c, const u8* __restrict__ sel,
         if (sel != nullptr && (e >= c.n || sel[e] == 0)) continue;
         wave_reset_game(c, e, rec, sc, threadIdx.x, nullptr, Limits{ -1, -1 }, nullptr, nullptr, nullptr, nullptr, board_only != 0);
     }
+}
+// catan_set_board_configs: the handle's copy of each game's layout index (padding games: entry 0); bad counts indices >= n_cfgs
+__global__ __launch_bounds__(BLOCK) void k_board_cfg_index(long n, long N, const u8* __restrict__ src, int n_cfgs, u8* __restrict__ dst,
+                                                           u32* __restrict__ bad) {
+    const long g = (long)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= N) return;
+    const u8 v = (src != nullptr && g < n) ? src[g] : (u8)0;
+    if ((int)v >= n_cfgs) atomicAdd(bad, 1u);
+    dst[g] = v;
 }
 // Contract (A): tops the two generators' output rings up to MT_AHEAD / MT_AHEAD_PY draws beyond the consumers' positions (the game's W_RNG,
 // cons_py).  One lane: MT19937 is serial, and a handle under this contract holds ONE game (a step draws 0-3 words, a re-deal ~250).

@@ -23,9 +23,25 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def board_cfg_struct(cfg):
+    """a board layout dict (spec.normalise_board_config) -> catan_board_cfg_t"""
+    randomise, terrain, numbers = spec.normalise_board_config(cfg)
+    c = _lib.CatanBoardCfg()
+    c.randomise_number_placement = int(randomise)
+    c.has_fixed_terrain, c.has_fixed_numbers = int(terrain is not None), int(numbers is not None)
+    for i, v in enumerate(terrain or []):
+        c.terrain[i] = v
+    for i, v in enumerate(numbers or []):
+        c.numbers[i] = v
+    return c
+
+
 class VecCatanEnv(object):
     def __init__(self, num_envs, seed=0, env_id0=0, device=None, max_proposed_trades_per_turn=4, win_reward=500.0,
-                 dense_reward=False, validate_actions=True, auto_reset=True, max_actions_per_turn=None):
+                 dense_reward=False, validate_actions=True, auto_reset=True, max_actions_per_turn=None, board_config=None,
+                 board_config_index=None):
+        """board_config / board_config_index: board layouts, as `set_board_config` takes them; the games are then dealt with them
+        from the start of their streams (as the reference's Game(board_config=...) deals its first board)."""
         if not torch.cuda.is_available():
             raise _lib.CatanHipError("VecCatanEnv needs a HIP device (no CPU fallback)")
         self.L = _lib.lib()
@@ -51,6 +67,40 @@ class VecCatanEnv(object):
         self.reward = torch.zeros((self.n, 4), dtype=torch.float32, device=self.device)
         self.done = torch.zeros((self.n,), dtype=torch.uint8, device=self.device)
         self.reward64 = None
+        if board_config is not None:
+            self.set_board_config(board_config, board_config_index)
+            # catan_create dealt random boards: deal again from draw 0 of every game's stream, now with the layouts
+            with torch.cuda.device(self.device):
+                blobs = self.export_state()
+                spec.state_field(blobs, "rng_draws").zero_()
+                self.import_state(blobs)
+                del blobs
+                self.reset()
+        elif board_config_index is not None:
+            raise ValueError("board_config_index without board_config")
+
+    def set_board_config(self, config_or_list, index=None):
+        """Board layouts (include/catan_hip.h catan_set_board_configs): one layout or a list of up to 16, each a dict with the
+        keyword names of the reference's Board (randomise_number_placement, fixed_terrain_placements - names or Terrain values -,
+        fixed_number_order); index: each game's entry (n values, None = entry 0 for all).  They apply from each game's next deal;
+        None or [] removes the table (fully random deals, as before)."""
+        cfgs = [] if config_or_list is None else ([config_or_list] if isinstance(config_or_list, dict) else list(config_or_list))
+        if len(cfgs) > spec.MAX_BOARD_CONFIGS:
+            raise ValueError(f"at most {spec.MAX_BOARD_CONFIGS} board layouts per env, got {len(cfgs)}")
+        arr = (_lib.CatanBoardCfg * max(1, len(cfgs)))(*[board_cfg_struct(c) for c in cfgs])
+        idx = None
+        if index is not None:
+            if not cfgs:
+                raise ValueError("a board config index without board configs")
+            idx = torch.as_tensor(index, device=self.device)
+            if idx.shape != (self.n,):
+                raise ValueError(f"board config index: one entry per game ({self.n}), got shape {tuple(idx.shape)}")
+            if bool(((idx < 0) | (idx >= len(cfgs))).any()):
+                raise ValueError(f"board config index: entries must be in 0..{len(cfgs) - 1}")
+            idx = idx.to(torch.uint8).contiguous()
+        if not hasattr(self.L, "catan_set_board_configs"):
+            raise _lib.CatanHipError("the loaded library has no catan_set_board_configs")
+        _lib.check(self.L.catan_set_board_configs(self.h, arr, len(cfgs), _ptr(idx), _stream()))
 
     def set_step_wave_games(self, games):
         """scheduling knob of k_step: 64 / 32 / 16 games per wave (results do not depend on it)"""
@@ -342,19 +392,20 @@ class EnvWrapper(object):
     """Single-game view with the reference EnvWrapper signatures (env/wrapper.py:11-50)."""
 
     def __init__(self, interactive=False, max_actions_per_turn=None, max_proposed_trades_per_turn=4, validate_actions=True,
-                 debug_mode=False, win_reward=500, dense_reward=False, policies=None, seed=0, env_id=0, rng="philox"):
+                 debug_mode=False, win_reward=500, dense_reward=False, policies=None, seed=0, env_id=0, rng="philox", board_config=None):
         """The reference's keyword arguments in the reference's order (env/wrapper.py:12-13) plus the game's Philox stream
         (seed, env_id).  Anything else is a TypeError, as with the reference; `interactive` / `debug_mode` / `policies` drive
         the reference's pygame display and its text log (game/game.py:30-37), which are out of scope: only their defaults.
         rng="mt19937": RNG contract (A) - the game draws from copies of THIS PROCESS's np.random / random generators as they are now
         (`np.random.seed(s); random.seed(s); env = EnvWrapper(rng="mt19937")` replays the unpatched reference draw for draw,
-        tests/test_gpu_golden.py::test_mt19937_known_answer_on_the_hip_path); the constructor takes the draws of Board() and Game()."""
+        tests/test_gpu_golden.py::test_mt19937_known_answer_on_the_hip_path); the constructor takes the draws of Board() and Game().
+        board_config: Game(board_config=...)'s layout (game/game.py:16-17; VecCatanEnv.set_board_config), an extension keyword."""
         if interactive or debug_mode or policies is not None:
             raise NotImplementedError("EnvWrapper(interactive / debug_mode / policies): the reference's display and text log "
                                       "are not part of the batched HIP path")
         self.vec = VecCatanEnv(1, seed=seed, env_id0=env_id, max_proposed_trades_per_turn=max_proposed_trades_per_turn,
                                win_reward=win_reward, dense_reward=dense_reward, validate_actions=validate_actions,
-                               auto_reset=False, max_actions_per_turn=max_actions_per_turn)
+                               auto_reset=False, max_actions_per_turn=max_actions_per_turn, board_config=board_config)
         self.max_actions_per_turn = float("inf") if max_actions_per_turn is None else max_actions_per_turn
         self.max_proposed_trades_per_turn = max_proposed_trades_per_turn
         self.win_reward, self.dense_reward = win_reward, dense_reward

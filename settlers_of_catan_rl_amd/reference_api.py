@@ -750,9 +750,12 @@ class SubProcEvaluationManager(object):
     batched env; results come back in the per-process tuples `(winners, game_lengths, victory_points, policy_steps)`."""
 
     def __init__(self, evaluation_manager_fns, start_method=None, *, device=_UNSET, seed=_UNSET, env_factory=_UNSET, make_policy=_UNSET,
-                 autocast_dtype=_UNSET):
+                 autocast_dtype=_UNSET, env_kwargs=_UNSET):
         device, seed, env_factory = _default("device", device), _default("seed", seed), _default("eval_env_factory", env_factory)
         make_policy, autocast_dtype = _default("make_policy", make_policy), _default("autocast_dtype", autocast_dtype)
+        # of env_kwargs only the board layout reaches the evaluation games: they keep the default rules, as the reference's
+        # evaluation workers build EnvWrapper() with its defaults
+        self._board_config = (_default("env_kwargs", env_kwargs) or {}).get("board_config")
         self.processes = [_ProcessStub() for _ in evaluation_manager_fns]
         self.waiting, self.closed = False, False
         self._device, self._seed, self._env_factory = device, seed, env_factory
@@ -781,7 +784,8 @@ class SubProcEvaluationManager(object):
         n = eps * len(self.processes)
         if self._env_factory is None:
             from .env import VecCatanEnv
-            env = VecCatanEnv(n, seed=self._seed + 7919 * (self._calls + 1), auto_reset=False, device=self._device)
+            env = VecCatanEnv(n, seed=self._seed + 7919 * (self._calls + 1), auto_reset=False, device=self._device,
+                              board_config=self._board_config)
         else:
             env = self._env_factory(n)
         self._calls += 1

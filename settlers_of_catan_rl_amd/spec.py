@@ -120,3 +120,65 @@ def describe_state_diff(a, b, limit=12):
             if len(out) >= limit:
                 break
     return "\n".join(out)
+
+
+# ---------------------------------------------------------------- board layouts (reference game/components/board.py:23-47)
+# A layout is a dict with the keyword names of the reference's Board(...) / Game(board_config=...): randomise_number_placement,
+# fixed_terrain_placements (19 terrains in tile order), fixed_number_order (18 tokens along NUMBER_PLACEMENT_INDS, desert skipped).
+TERRAIN_NAMES = ["Desert", "Hills", "Forest", "Mountains", "Pastures", "Fields"]        # the reference's Terrain values 0..5
+TERRAIN_TO_PLACE = [0] + [1] * 3 + [5] * 4 + [2] * 4 + [3] * 3 + [4] * 4
+DEFAULT_NUMBER_ORDER = [5, 2, 6, 3, 8, 10, 9, 12, 11, 4, 8, 10, 9, 4, 5, 6, 3, 11]
+NUMBER_PLACEMENT_INDS = [0, 3, 7, 12, 16, 17, 18, 15, 11, 6, 2, 1, 4, 8, 13, 14, 10, 5, 9]
+BOARD_CONFIG_KEYS = ("randomise_number_placement", "fixed_terrain_placements", "fixed_number_order")
+MAX_BOARD_CONFIGS = 16
+
+
+def terrain_code(t):
+    """A terrain as its Terrain value: the value itself, the reference's Terrain member, or its name ("Hills", "hills")."""
+    if isinstance(t, str):
+        name = t.split(".")[-1].strip().lower()
+        for code, n in enumerate(TERRAIN_NAMES):
+            if n.lower() == name:
+                return code
+        raise ValueError(f"unknown terrain name {t!r} (one of {TERRAIN_NAMES})")
+    if isinstance(t, bool) or not hasattr(t, "__index__"):
+        raise ValueError(f"a terrain is a name or a Terrain value 0..5, not {t!r}")
+    code = int(t)
+    if not 0 <= code <= 5:
+        raise ValueError(f"terrain value {code} outside 0..5 ({TERRAIN_NAMES})")
+    return code
+
+
+def normalise_board_config(cfg):
+    """-> (randomise_number_placement: bool, terrain: list of 19 Terrain values or None, numbers: list of 18 or None).  None or {}
+    is the reference's default Board().  Raises ValueError for unknown keys and for multisets other than TERRAIN_TO_PLACE /
+    DEFAULT_NUMBER_ORDER (the check the reference's constructor means to make, board.py:37-42)."""
+    cfg = {} if cfg is None else cfg
+    if not isinstance(cfg, dict):
+        raise ValueError(f"a board config is a dict with the keys {BOARD_CONFIG_KEYS}, not {type(cfg).__name__}")
+    unknown = set(cfg) - set(BOARD_CONFIG_KEYS)
+    if unknown:
+        raise ValueError(f"unknown board config keys {sorted(unknown)} (Board's keywords: {BOARD_CONFIG_KEYS})")
+    randomise = bool(cfg.get("randomise_number_placement", True))
+    terrain = cfg.get("fixed_terrain_placements")
+    if terrain is not None:
+        terrain = [terrain_code(t) for t in terrain]
+        if len(terrain) != N_TILES or sorted(terrain) != sorted(TERRAIN_TO_PLACE):
+            raise ValueError(f"fixed_terrain_placements must be 19 terrains with the counts of TERRAIN_TO_PLACE "
+                             f"(1 desert, 3 hills, 4 forest, 3 mountains, 4 pastures, 4 fields), got {terrain}")
+    numbers = cfg.get("fixed_number_order")
+    if numbers is not None:
+        numbers = [int(v) for v in numbers]
+        if sorted(numbers) != sorted(DEFAULT_NUMBER_ORDER):
+            raise ValueError(f"fixed_number_order must be a permutation of DEFAULT_NUMBER_ORDER {DEFAULT_NUMBER_ORDER}, got {numbers}")
+    return randomise, terrain, numbers
+
+
+def board_config_from_state(blob):
+    """The layout of an exported game (a state blob): its terrain in tile order and its tokens in placement order, read from
+    tile_res / tile_val - `env.set_board_config(spec.board_config_from_state(blob))` deals that board from then on."""
+    res = [int(v) for v in state_field(blob, "tile_res")]
+    val = [int(v) for v in state_field(blob, "tile_val")]
+    return {"randomise_number_placement": True, "fixed_terrain_placements": res,
+            "fixed_number_order": [val[t] for t in NUMBER_PLACEMENT_INDS if res[t] != 0]}
+
