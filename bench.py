@@ -10,15 +10,18 @@ legal-action masks, all inputs resident in HBM.  Two schedules of the same kerne
                            still follows its own lock-step trajectory bit for bit (tests/test_gpu_env_parity.py).
                            `value` counts the env steps actually executed (sum of the per-game decision counters).
   --window 0               lock-step loop, catan_random_rollout: every game steps in every pass (the per-step API
-                           schedule); also measured briefly in every default run and reported as `lockstep`.
+                           schedule); also measured briefly in every --full run and reported as `lockstep`.
 
     python bench.py --gpus 1 --steps 4096 --warmup 256
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` (dominant kernel of the timed loop, HIP events on the
-stream it is launched on) and `cpu_baseline` (the CPU oracle - a port of the reference algorithm - timed on this box's
-host cores).  Games shard across ranks by global game id with no data-path collective ("weak": 65 536 games per GPU).
+Prints ONE JSON line on rank 0 (driver contract).  A plain run does only what that line's headline needs: set-up, the
+untimed pre-roll, --warmup, the --steps timed passes, --dump-outputs if given, the line.  --full adds everything else the
+benchmark measures, after the timed region: `lockstep`, `step_api`, `roofline` (dominant kernel of the timed loop, HIP
+events on the stream it is launched on, with live PMC traffic), `ppo_update` with `roofline_learner`, and `cpu_baseline`
+(the CPU oracle - a port of the reference algorithm - timed on the host's cores).  Games shard across ranks by global
+game id with no data-path collective ("weak": 65 536 games per GPU).
 """
 import argparse
 import json
@@ -302,6 +305,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=256)
     ap.add_argument("--envs", type=int, default=65536, help="games per GPU")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure lockstep, step_api, roofline, ppo_update and cpu_baseline (minutes); "
+                         "--no-cpu-baseline, --no-live-pmc, --no-lockstep and --ppo-steps only trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true", help="skip the two rocprofv3 --pmc passes that measure roofline.traffic (N = 1)")
     ap.add_argument("--no-validate", action="store_true", help="skip the mask-bit legality check in k_step")
@@ -381,10 +387,11 @@ def main():
     stage("device identities (all_gather_object)")
     devices = cdist.device_identities()                       # (a collective: every rank calls it)
     PARTIAL["ranks"] = devices
+    # ---- everything below the headline: --full only
     stage("lock-step / step_api measurements")
 
     lockstep = None
-    if args.window > 0 and not args.no_lockstep:
+    if args.full and args.window > 0 and not args.no_lockstep:
         # the same games, continued in lock-step (every game steps in every pass): --steps passes as well
         env.random_rollout(step_idx, 32); step_idx += 32
         cdist.barrier()
@@ -400,7 +407,7 @@ def main():
     # include/catan_hip.h catan_step / catan_step_deferred; the value above is the library's own loop around the same kernels).
     # The policy stub is the library's sampler writing into a caller-owned buffer: one more launch per pass, no host read.
     step_api = None
-    if args.window > 0 and not args.no_lockstep:
+    if args.full and args.window > 0 and not args.no_lockstep:
         acts = torch.empty((n, 18), dtype=torch.int32, device="cuda")
         api_passes = max(1024, args.steps // 2)
         def api_loop(deferred, passes, base):
@@ -437,7 +444,7 @@ def main():
 
     out = None
     kms = None
-    if rank == 0:
+    if args.full and rank == 0:
         # per-kernel durations: HIP events on the stream each kernel is launched on, a separate short pass right after
         prof_steps = 512
         sp0 = env.slow_path_counts()
@@ -445,71 +452,73 @@ def main():
         sp1 = env.slow_path_counts()
     step_idx += 512
     ppo = None
-    if args.ppo_steps > 0:
+    if args.full and args.ppo_steps > 0:
         stage("ppo_update (3 rollouts + PPO updates with the gradient all-reduce)")
         ppo = ppo_update_record(env, n, rank, world, args.ppo_steps, cdist)
     stage("assembling the line")
     if ppo is not None and rank != 0:
         ppo.pop("roofline_learner", None)
     if rank == 0:
-        slow_launches = prof_steps if args.window <= 0 else -(-prof_steps // args.window)
-        launches = {k: (slow_launches if k in ("k_lr_heavy", "k_reset_list") else prof_steps) for k in kms}
-        per_launch_us = {k: v * 1e3 / launches[k] for k, v in kms.items() if k in ALGO_BYTES}
-        fused_loop = args.window > 0 and env.deferred_fused   # ONE kernel per pass: k_step<G, true> samples the next action itself
-        fast_path = ("k_step",) if fused_loop else FAST_PATH
-        if fused_loop:
-            per_launch_us.pop("k_sample_random", None)        # (no such kernel in this loop: the slot holds the gap between two event records)
-        algo = dict(ALGO_BYTES, k_step=ALGO_BYTES["k_step_fused"]) if fused_loop else ALGO_BYTES
-        dom = max(fast_path, key=per_launch_us.get)
-        active = my_steps / (n * timed_passes)                # games that take a step in a pass (the others are busy)
-        achieved = algo[dom] * n * active / (per_launch_us[dom] * 1e-6) / 1e9
-        fast_us = sum(per_launch_us[k] for k in fast_path)
-        traffic, traffic_src = None, None
-        if world == 1 and n == 65536 and not args.no_live_pmc:     # (the counter workload runs the BASELINE size)
-            traffic, traffic_src = live_pmc_traffic(dom)
-            if traffic is None:
-                traffic_src = f"live counter passes unavailable ({traffic_src}); "
-        if traffic is None and os.path.exists(PMC_SUMMARY):
-            live_note = traffic_src or ""
-            with open(PMC_SUMMARY) as f:
-                pm = json.load(f)
-            k = pm.get("kernels", {}).get(dom, {})
-            traffic = k.get("hbm_bytes_per_launch")
-            traffic_src = live_note + (f"steady-state PMC of the same kernel, NOT collected in this run: "
-                           f"{os.path.relpath(PMC_SUMMARY, ROOT)}, separate --pmc FETCH_SIZE / WRITE_SIZE passes, calibrated, "
-                           f"65 536 games after the same pre-roll")
-        per_step_bytes = sum(algo[k] for k in fast_path)
-        roofline = {
-            "bound": "hbm", "kernel": dom + ("<G, SAMPLE> (fused-sampling step)" if fused_loop else ""), "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-            "algorithmic_bytes_per_game": algo[dom],
-            "algorithmic_bytes_per_launch": algo[dom] * n * active,
-            "avg_launch_us": per_launch_us[dom],
-            "all_kernels_avg_launch_us": per_launch_us,
-            "fast_path_algorithmic_bytes_per_game": per_step_bytes,
-            "fast_path_achieved_gbs": per_step_bytes * n * active / (fast_us * 1e-6) / 1e9,
-            # whole schedules, end to end: algorithmic bytes of one env step x executed steps / wall time
-            "end_to_end": {"algorithmic_bytes_per_env_step": per_step_bytes,
-                           "timed_schedule_gbs": per_step_bytes * env_steps / world / dt / 1e9,
-                           "timed_schedule_frac": per_step_bytes * env_steps / world / dt / 1e9 / HBM_PEAK_GBS},
-            "note": "integer/byte rules engine at one or two waves per SIMD: latency- and divergence-bound, far below the HBM "
-                    "roofline by nature (SURVEY.md 8(d)); frac is reported for the dominant kernel of the timed loop; "
-                    "the slow-path kernels (k_lr_*, k_reset_list) are latency-bound path searches / re-deals (LDS + ALU, "
-                    "a few MB per launch) and run on side streams in the deferred loop",
-        }
-        t1_req, t2_req, t1_launches = (b - a for a, b in zip(sp0, sp1))
-        lr_us = per_launch_us["k_lr_finish"]
-        roofline["slow_path"] = {
-            "bound": "latency (path search in LDS / registers; not an HBM- or MFMA-bound kernel)",
-            "tier1_requests_per_launch": t1_req / max(1, t1_launches), "tier2_requests_per_launch": t2_req / max(1, slow_launches),
-            "algorithmic_bytes_per_request": LR_REQUEST_BYTES, "k_lr_finish_avg_launch_us": lr_us,
-            "k_lr_finish_achieved_gbs": LR_REQUEST_BYTES * t1_req / max(1, t1_launches) / (lr_us * 1e-6) / 1e9 if lr_us > 0 else None,
-            "k_lr_heavy_avg_launch_us": per_launch_us["k_lr_heavy"],
-            "note": "while a player's cached longest path is exact, a new road only searches the paths THROUGH the new edge "
-                    "(DESIGN.md 4.2); requests that exceed the tier-1 iteration budget go to tier 2"}
-        if lockstep is not None:
-            g = per_step_bytes * n / (lockstep["ms_per_step"] * 1e-3) / 1e9
-            roofline["end_to_end"].update(lockstep_gbs=g, lockstep_frac=g / HBM_PEAK_GBS)
+        roofline = None
+        if kms is not None:
+            slow_launches = prof_steps if args.window <= 0 else -(-prof_steps // args.window)
+            launches = {k: (slow_launches if k in ("k_lr_heavy", "k_reset_list") else prof_steps) for k in kms}
+            per_launch_us = {k: v * 1e3 / launches[k] for k, v in kms.items() if k in ALGO_BYTES}
+            fused_loop = args.window > 0 and env.deferred_fused   # ONE kernel per pass: k_step<G, true> samples the next action itself
+            fast_path = ("k_step",) if fused_loop else FAST_PATH
+            if fused_loop:
+                per_launch_us.pop("k_sample_random", None)        # (no such kernel in this loop: the slot holds the gap between two event records)
+            algo = dict(ALGO_BYTES, k_step=ALGO_BYTES["k_step_fused"]) if fused_loop else ALGO_BYTES
+            dom = max(fast_path, key=per_launch_us.get)
+            active = my_steps / (n * timed_passes)                # games that take a step in a pass (the others are busy)
+            achieved = algo[dom] * n * active / (per_launch_us[dom] * 1e-6) / 1e9
+            fast_us = sum(per_launch_us[k] for k in fast_path)
+            traffic, traffic_src = None, None
+            if world == 1 and n == 65536 and not args.no_live_pmc:     # (the counter workload runs the BASELINE size)
+                traffic, traffic_src = live_pmc_traffic(dom)
+                if traffic is None:
+                    traffic_src = f"live counter passes unavailable ({traffic_src}); "
+            if traffic is None and os.path.exists(PMC_SUMMARY):
+                live_note = traffic_src or ""
+                with open(PMC_SUMMARY) as f:
+                    pm = json.load(f)
+                k = pm.get("kernels", {}).get(dom, {})
+                traffic = k.get("hbm_bytes_per_launch")
+                traffic_src = live_note + (f"steady-state PMC of the same kernel, NOT collected in this run: "
+                               f"{os.path.relpath(PMC_SUMMARY, ROOT)}, separate --pmc FETCH_SIZE / WRITE_SIZE passes, calibrated, "
+                               f"65 536 games after the same pre-roll")
+            per_step_bytes = sum(algo[k] for k in fast_path)
+            roofline = {
+                "bound": "hbm", "kernel": dom + ("<G, SAMPLE> (fused-sampling step)" if fused_loop else ""), "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                "algorithmic_bytes_per_game": algo[dom],
+                "algorithmic_bytes_per_launch": algo[dom] * n * active,
+                "avg_launch_us": per_launch_us[dom],
+                "all_kernels_avg_launch_us": per_launch_us,
+                "fast_path_algorithmic_bytes_per_game": per_step_bytes,
+                "fast_path_achieved_gbs": per_step_bytes * n * active / (fast_us * 1e-6) / 1e9,
+                # whole schedules, end to end: algorithmic bytes of one env step x executed steps / wall time
+                "end_to_end": {"algorithmic_bytes_per_env_step": per_step_bytes,
+                               "timed_schedule_gbs": per_step_bytes * env_steps / world / dt / 1e9,
+                               "timed_schedule_frac": per_step_bytes * env_steps / world / dt / 1e9 / HBM_PEAK_GBS},
+                "note": "integer/byte rules engine at one or two waves per SIMD: latency- and divergence-bound, far below the HBM "
+                        "roofline by nature (SURVEY.md 8(d)); frac is reported for the dominant kernel of the timed loop; "
+                        "the slow-path kernels (k_lr_*, k_reset_list) are latency-bound path searches / re-deals (LDS + ALU, "
+                        "a few MB per launch) and run on side streams in the deferred loop",
+            }
+            t1_req, t2_req, t1_launches = (b - a for a, b in zip(sp0, sp1))
+            lr_us = per_launch_us["k_lr_finish"]
+            roofline["slow_path"] = {
+                "bound": "latency (path search in LDS / registers; not an HBM- or MFMA-bound kernel)",
+                "tier1_requests_per_launch": t1_req / max(1, t1_launches), "tier2_requests_per_launch": t2_req / max(1, slow_launches),
+                "algorithmic_bytes_per_request": LR_REQUEST_BYTES, "k_lr_finish_avg_launch_us": lr_us,
+                "k_lr_finish_achieved_gbs": LR_REQUEST_BYTES * t1_req / max(1, t1_launches) / (lr_us * 1e-6) / 1e9 if lr_us > 0 else None,
+                "k_lr_heavy_avg_launch_us": per_launch_us["k_lr_heavy"],
+                "note": "while a player's cached longest path is exact, a new road only searches the paths THROUGH the new edge "
+                        "(DESIGN.md 4.2); requests that exceed the tier-1 iteration budget go to tier 2"}
+            if lockstep is not None:
+                g = per_step_bytes * n / (lockstep["ms_per_step"] * 1e-3) / 1e9
+                roofline["end_to_end"].update(lockstep_gbs=g, lockstep_frac=g / HBM_PEAK_GBS)
         value = env_steps / dt
         out = {
             "metric": "Catan env-steps/sec at 65k parallel games", "value": value, "unit": "env-steps/s",
@@ -519,7 +528,7 @@ def main():
             "data": "synthetic (random-seed boards, uniform-random legal policy on device)",
             "config": {"workload": ("configs[1]: 65 536 parallel envs per GPU, random policy, step+mask only, bit-exact vs CPU oracle" if world == 1 else
                                     f"configs[3]: {world * n} envs sharded across {world} x MI355X ({n} per GPU, global game ids), PPO with one flat "
-                                    f"gradient all-reduce per optimiser step (`ppo_update`); `value` = configs[1]'s random-policy step+mask rate "
+                                    f"gradient all-reduce per optimiser step (`ppo_update`, --full); `value` = configs[1]'s random-policy step+mask rate "
                                     f"summed over the {world} shards"),
                        "games_per_gpu": n, "games_total": world * n, "validate_actions": not args.no_validate,
                        "auto_reset": True, "parallelism": f"games sharded over {world} GPU(s), no collective",
@@ -532,8 +541,9 @@ def main():
             # who ran: one record per rank (all-gathered), the collective backend the learner's all-reduce uses
             "world": world, "backend": (torch.distributed.get_backend() if world > 1 else None), "ranks": devices,
             "distinct_devices": len({(d["host"], d["uuid"] or d["pci_bus_id"] or d["device"]) for d in devices}),
-            "roofline": roofline,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if lockstep is not None:
             out["lockstep"] = lockstep
         if step_api is not None:
@@ -541,7 +551,7 @@ def main():
         if ppo is not None:
             out["roofline_learner"] = ppo.pop("roofline_learner", None)
             out["ppo_update"] = ppo
-        if not args.no_cpu_baseline and world == 1:         # (rank 0 at N = 1 only: with N ranks on the node the host cores are shared)
+        if args.full and not args.no_cpu_baseline and world == 1:   # (rank 0 at N = 1 only: with N ranks on the node the host cores are shared)
             out["cpu_baseline"] = cpu_baseline()
             out["gpu_over_cpu_all_cores"] = value / out["cpu_baseline"]["value"]
     if rank == 0:

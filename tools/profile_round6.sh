@@ -11,9 +11,9 @@ run() { name=$1; shift; ( "$@" ) > $OUT/$name.txt 2> $OUT/$name.err.full; rc=$?;
 run gpu_tests timeout 2400 python -m pytest tests -q -m gpu
 run smoke timeout 600 python -c "import __graft_entry__ as g; g.smoke()"
 cd /tmp
-run bench_default timeout 1200 python $REPO/bench.py
-run bench_driver_args_env_only timeout 300 python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --ppo-steps 0 --no-live-pmc
-run bench_under_rocprof timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $REPO/bench.py --no-cpu-baseline --no-live-pmc --ppo-steps 0
+run bench_default timeout 1200 python $REPO/bench.py --full
+run bench_driver_args_env_only timeout 300 python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --ppo-steps 0 --no-live-pmc
+run bench_under_rocprof timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $REPO/bench.py --full --no-cpu-baseline --no-live-pmc --ppo-steps 0
 find $OUT/stats -name "*kernel_stats.csv" -exec cp {} $OUT/bench_default_kernel_stats.csv \;
 run pmc_fetch timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- python $REPO/tools/pmc_workload.py
 run pmc_write timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o pmc -- python $REPO/tools/pmc_workload.py
