@@ -74,16 +74,17 @@ int catan_linear_wgrad_big(const void* x, const void* dy, float* dw, int64_t dw_
 /* The optimiser step of PPO.update - `nn.utils.clip_grad_norm_(parameters, max_grad_norm)` then `optim.Adam.step()` (RL/ppo/ppo.py:23,
  * 67-68) - over all parameters in two launches (sum of squared gradients per chunk; norm, clip coefficient and Adam update per chunk).
  * tensors: n_tensors rows {p, m, v} ON THE DEVICE (fp32, 16-byte aligned); chunks: n_chunks rows ON THE DEVICE, chunk i = elements
- * [offset, offset + count) of tensor `tensor`, count <= catan_adam_chunk_elements(), offset a multiple of 4; grads: n_tensors device
- * pointers ON THE DEVICE (this step's gradient of every tensor; null = the tensor takes no step, as torch skips a parameter without
- * gradient); partial: n_chunks doubles of scratch.  max_norm <= 0: no clipping.  bias_correction1 = 1 - beta1^t, bias_correction2_sqrt
- * = sqrt(1 - beta2^t) for the step number t (computed by the caller in double, as torch does on the host).  norm_out (may be null):
- * the total gradient norm before clipping.  Deterministic: the partial sums are added in index order. */
+ * [offset, offset + count) of tensor `tensor`, count <= catan_adam_chunk_elements(), offset a multiple of 4; grads: a row ON THE DEVICE of
+ * n_tensors device pointers (this step's gradient of every tensor; null = the tensor takes no step, as torch skips a parameter without
+ * gradient - or, with none_is_zero, the step of a zero gradient) followed by n_tensors pairs of floats (bias_correction1 = 1 - beta1^t,
+ * bias_correction2_sqrt = sqrt(1 - beta2^t) for the tensor's own step number t, computed by the caller in double as torch does on the
+ * host); partial: n_chunks doubles of scratch.  max_norm <= 0: no clipping.  norm_out (may be null): the total gradient norm before
+ * clipping.  Deterministic: the partial sums are added in index order. */
 typedef struct catan_adam_tensor { float* p; float* m; float* v; } catan_adam_tensor_t;
 typedef struct catan_adam_chunk { int32_t tensor; int32_t count; int64_t offset; } catan_adam_chunk_t;
 int32_t catan_adam_chunk_elements(void);
-int catan_adam_step(const void* tensors, const void* chunks, int32_t n_chunks, const void* grads, void* partial, float max_norm, float lr, float beta1,
-                    float beta2, float eps, float bias_correction1, float bias_correction2_sqrt, float* norm_out, catan_stream_t stream);
+int catan_adam_step(const void* tensors, const void* chunks, int32_t n_chunks, const void* grads, int32_t n_tensors, int32_t none_is_zero, void* partial,
+                    float max_norm, float lr, float beta1, float beta2, float eps, float* norm_out, catan_stream_t stream);
 
 /* catan_qkv_bwd_dx AND the QKV product's weight gradient in one pass (k_qkv_bwd_w): additionally n [rows][64] = LayerNorm 1's output,
  * or n = NULL and ln_b = the LayerNorm's bias (n recomputed from x, as catan_ffn_bwd); dw float [192][64] and db [192] are

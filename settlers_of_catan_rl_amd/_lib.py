@@ -226,7 +226,7 @@ _SIGS = {
     "catan_wgrad_big_workspace_floats": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "catan_linear_wgrad_big": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp]),
     "catan_adam_chunk_elements": (C.c_int32, []),
-    "catan_adam_step": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
+    "catan_adam_step": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
     "catan_gather_rows": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int64, _vp]),
     "catan_expand_rows": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "catan_segment_sum_rows": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),

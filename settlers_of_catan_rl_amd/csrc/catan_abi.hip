@@ -1734,12 +1734,12 @@ int catan_linear_wgrad_big(const void* x, const void* dy, float* dw, int64_t dw_
     return CATAN_OK;
 }
 int32_t catan_adam_chunk_elements(void) { return OPT_CHUNK; }
-int catan_adam_step(const void* tensors, const void* chunks, int32_t n_chunks, const void* grads, void* partial, float max_norm, float lr, float beta1,
-                    float beta2, float eps, float bias_correction1, float bias_correction2_sqrt, float* norm_out, catan_stream_t stream) {
+int catan_adam_step(const void* tensors, const void* chunks, int32_t n_chunks, const void* grads, int32_t n_tensors, int32_t none_is_zero, void* partial,
+                    float max_norm, float lr, float beta1, float beta2, float eps, float* norm_out, catan_stream_t stream) {
     static_assert(sizeof(AdamTensor) == sizeof(catan_adam_tensor_t) && sizeof(AdamChunk) == sizeof(catan_adam_chunk_t), "the header's structs are the kernels'");
-    if (!tensors || !chunks || !grads || !partial || n_chunks <= 0 || !(bias_correction1 > 0.f) || !(bias_correction2_sqrt > 0.f))
+    if (!tensors || !chunks || !grads || !partial || n_chunks <= 0 || n_tensors <= 0)
         return fail(CATAN_EINVAL, "catan_adam_step: bad arguments");
-    AdamHyper h = { max_norm, lr, beta1, beta2, eps, bias_correction1, bias_correction2_sqrt, max_norm > 0.f ? 1 : 0 };
+    AdamHyper h = { max_norm, lr, beta1, beta2, eps, max_norm > 0.f ? 1 : 0, none_is_zero ? 1 : 0, (int)n_tensors };
     hipLaunchKernelGGL(k_grad_sumsq, dim3((unsigned)n_chunks), dim3(OPT_BLOCK), 0, S(stream), (const AdamChunk*)chunks, (const float* const*)grads, (double*)partial);
     hipLaunchKernelGGL(k_adam_step, dim3((unsigned)n_chunks), dim3(OPT_BLOCK), 0, S(stream), (const AdamTensor*)tensors, (const AdamChunk*)chunks, (int)n_chunks,
                        (const float* const*)grads, (const double*)partial, h, norm_out);

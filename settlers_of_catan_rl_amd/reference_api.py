@@ -697,7 +697,8 @@ class PPO(object):
         self.max_grad_norm, self.recompute_returns = args.max_grad_norm, getattr(args, "recompute_returns", True)
         self.gamma, self.gae_lambda = args.gamma, args.gae_lambda
         from .optim import FusedAdam
-        self.optimiser = FusedAdam(actor_critic.parameters(), lr=args.lr, eps=args.eps)         # ppo.py:23 (Adam; the clip of :67 rides in its step)
+        # ppo.py:23 (Adam; the clip of :67 rides in its step; a parameter without a gradient steps on zeros, as the reference's heads give it)
+        self.optimiser = FusedAdam(actor_critic.parameters(), lr=args.lr, eps=args.eps, none_grad_is_zero=True)
         self.bucket = cdist.GradBucket(actor_critic.parameters(), assign_when_single_rank=True)     # persistent flat gradient buffer (one all-reduce per step)
         self.timings = {}
 

@@ -71,7 +71,9 @@ class PPOTrainer(object):
             from . import nn_kernels
             nn_kernels.use_tuned_gemms()           # library GEMMs: tuned solution per shape (tunableop_gfx950.csv)
         from .optim import FusedAdam
-        self.optimiser = FusedAdam(policy.parameters(), lr=self.cfg.lr, eps=self.cfg.eps)           # ppo.py:23 (+ the clip of :67 in its step)
+        # ppo.py:23 (+ the clip of :67 in its step).  A parameter left without a gradient (a head no row of the minibatch uses, under
+        # the compact heads; the single-rank GradBucket leaves it None) steps as on a zero gradient: the reference's heads give it zeros
+        self.optimiser = FusedAdam(policy.parameters(), lr=self.cfg.lr, eps=self.cfg.eps, none_grad_is_zero=True)
         # gradients live in one persistent flat buffer with a fixed layout (dist.GradBucket): the all-reduce of a step is one
         # collective on that buffer, and zeroing the gradients is one memset
         self.bucket = cdist.GradBucket(policy.parameters(), assign_when_single_rank=True)

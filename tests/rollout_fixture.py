@@ -88,10 +88,11 @@ def pre_advance(env, pre_len, pre_actions):
         assert not bool(done.any())
 
 
-def check_rollout_fixture(make_env, collector_kwargs=None):
+def check_rollout_fixture(make_env, collector_kwargs=None, on_rollout=None):
     """make_env(n, seed) -> freshly created batched env with auto-reset.  Drives `reference_api.SubProcGameManager` +
     `BatchProcessor` over it and compares every rollout with the tensors of the reference's GamesAndPoliciesManager +
-    BatchProcessor (verbatim layouts).  Returns (manager, batch processor, last rollouts handle)."""
+    BatchProcessor (verbatim layouts); on_rollout(r, batch processor, rollouts handle), if given, sees every rollout after its
+    checks.  Returns (manager, batch processor, last rollouts handle)."""
     import types
     from settlers_of_catan_rl_amd import reference_api as ra
     g = gu.load("rollout_small.npz")
@@ -128,6 +129,8 @@ def check_rollout_fixture(make_env, collector_kwargs=None):
         blobs = env.export_state().cpu().numpy()
         assert [gu.crc(b) for b in blobs] == [int(c) for c in g[f"r{r}_state_crc"]], r
         ends += int((g[f"r{r}_masks"] == 0).sum())
+        if on_rollout is not None:
+            on_rollout(r, bp, ro)
     assert ends >= 3                                       # the fixture covers game ends and the carry-over behind them
     check_generator_lstm(g, bp, T, n)
     return mgr, bp, ro

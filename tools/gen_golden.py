@@ -10,6 +10,8 @@
                       actions + crc32 of the state at every step (config 1 known-answer test for the oracle MT mode)
   longest_road.npz    (edge_owner, corner_owner, player) -> Game.get_longest_path, harvested from play + adversarial
   gae_ppo.npz         BatchProcessor GAE / PPO loss values computed with the reference's torch code
+  ppo_update.npz      two whole PPO.update calls of the reference (fp32 and fp64) on the fixture net: per optimiser step the
+                      losses, the pre-clip norm, every parameter's gradient and theta_k - theta_0 (norms, hashed projections)
   ref_checks.npz      the reference's side of several parity checks (gen_ref_checks)
   validate_cases.npz  validate mode (Game.validate_action): states x probe actions -> the reference's accept / reject and,
                       for accepted ones, its state crc / masks / rewards / done afterwards (incl. actions outside the masks)
@@ -626,6 +628,186 @@ def gen_policy_small(n_games=40, lstm_T=5, lstm_B=8):
             "bytes": os.path.getsize(os.path.join(OUT, "policy_small.npz"))}
 
 
+PPO_UPDATE_ARGS = dict(clip_param=0.2, ppo_epoch=2, num_mini_batch=4, value_loss_coef=1.0, entropy_coef_start=0.04, max_grad_norm=0.5,
+                       recompute_returns=True, gamma=0.999, gae_lambda=0.95, lr=3e-4, eps=1e-5, truncated_seq_len=10)
+PPO_UPDATE_LRS = (3e-4, 2e-4)          # the second update runs at a lower learning rate (train_loop's linear decay writes param_groups)
+
+
+def _ref_batch_processor(g, r, dtype):
+    """the reference's BatchProcessor holding rollout r of rollout_small.npz (the attributes its process_rollouts wrote, verbatim)"""
+    import types
+    import torch
+    from RL.ppo.process_batch import BatchProcessor, OBS_KEYS
+    T, n = int(g["T"]), int(g["n_envs"])
+    args = types.SimpleNamespace(num_steps=T, num_processes=1, num_envs_per_process=n, gamma=0.999, gae_lambda=0.95)
+    bp = BatchProcessor(args, lstm_dim=256, device="cpu")
+    bp.obs_dict = {}
+    for k in OBS_KEYS:
+        v = g[f"r{r}_obs_{k}"]
+        bp.obs_dict[k] = torch.from_numpy(v.astype(np.int64)) if v.dtype == np.int8 else torch.from_numpy(v.astype(np.float32)).to(dtype)
+    bp.hidden_states = (torch.zeros(T + 1, n, 256, dtype=dtype), torch.zeros(T + 1, n, 256, dtype=dtype))
+    bp.rewards = torch.from_numpy(g[f"r{r}_rewards"]).to(dtype)
+    bp.masks = torch.from_numpy(g[f"r{r}_masks"]).to(dtype)
+    bp.action_log_probs = torch.from_numpy(g[f"r{r}_action_log_probs"]).to(dtype)
+    bp.actions = [torch.from_numpy(g[f"r{r}_actions_{i}"].astype(np.int64)) for i in range(12)]
+    bp.action_masks = [torch.from_numpy(g[f"r{r}_action_masks_{i}"].astype(np.float32)).to(dtype) for i in range(12)]
+    return bp
+
+
+def gen_ppo_update(seed=51):
+    """VERDICT r6 / the whole-update pin: the reference's OWN `PPO.update` (RL/ppo/ppo.py:25-79: its BatchProcessor's
+    compute_advantages_alt and generator_standard, clip_grad_norm_, torch.optim.Adam) on the net `build_agent_model()` with the
+    deterministic weights of tests/policy_fixture.py (salt "ppo:", stored as crc32s only), two updates in a row with one optimiser
+    (the second at a lower learning rate) on rollouts r0 and r1 of rollout_small.npz (T = 12 x N = 4 = 48 rows, 2 epochs x 4
+    minibatches of 12 rows: several action heads have no row in a minibatch).
+      - old log-probs: the fixture net's own log-probs of the stored actions + deterministic offsets in about +-0.4 (stored), so
+        that the ratios leave [1 - clip, 1 + clip] on both sides in some rows;
+      - the samplers' permutations are drawn here (numpy, seeded) and handed to SubsetRandomSampler through torch.randperm;
+      - per optimiser step k: the losses ppo.py:77-79 reads (.item() calls of ppo.py), the pre-clip total gradient norm, and per
+        parameter whether its gradient is None, whether the step moved it, the gradient's norm and hashed projection
+        (policy_fixture.projection), and the norm and projection of theta_k - theta_0.
+    Twice: in fp32, and in fp64 (torch's default dtype set to float64 and the net `.double()`: the reference's code then computes
+    in fp64 throughout, the BatchProcessor's own torch.zeros included), so that the tests can take their tolerances from the
+    reference's own fp32 noise."""
+    import torch
+    import torch.nn.utils
+    import types
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import golden_util as gu
+    import policy_fixture as pf
+    import RL.models.build_agent_model as bam
+    from RL.ppo.ppo import PPO
+    g = gu.load("rollout_small.npz")
+    T, n = int(g["T"]), int(g["n_envs"])
+    rows = T * n
+    nmb, epochs, n_upd = PPO_UPDATE_ARGS["num_mini_batch"], PPO_UPDATE_ARGS["ppo_epoch"], len(PPO_UPDATE_LRS)
+    rng = np.random.default_rng(seed)
+    perms = np.stack([rng.permutation(rows) for _ in range(n_upd * epochs)]).astype(np.int64)          # [update * epoch, rows]
+    offsets = (rng.integers(-400, 401, size=(n_upd, T, n)) / 1000.0).astype(np.float32)
+    out = {"rollouts": np.array([0, 1], dtype=np.int32), "perms": perms, "lrs": np.array(PPO_UPDATE_LRS),
+           "seed": seed}
+    for k, v in PPO_UPDATE_ARGS.items():
+        out["arg_" + k] = v
+
+    def build(dtype):
+        torch.manual_seed(0)
+        ref = bam.build_agent_model()
+        sd = ref.state_dict()
+        shapes = {k: tuple(v.shape) for k, v in sd.items() if v.numel() > 0 and not k.startswith("value_normaliser.")}
+        new = pf.fixture_state_dict(shapes, "ppo:")
+        full = dict(sd); full.update(new)
+        ref.load_state_dict(full, strict=True)
+        names = sorted(shapes)
+        return ref.to(dtype), names, np.array([pf.tensor_crc(new[k]) for k in names], dtype=np.uint32)
+
+    # the actions: the stored ones, except that the fixture's scripted decisions left the two trade heads' columns at 0 in rows
+    # whose action type does not use them, and 0 ("stop") is not a legal FIRST resource of those heads when the player holds
+    # resources: the reference evaluates every head on every row and multiplies the masked log-prob by 0, so -inf * 0 = NaN
+    # (the reference's own sampler never produces such a row).  Those first entries are replaced by the first legal resource
+    # (under the mask RecurrentResourceActionHead.forward forms), the rest by 0.  Then the old log-probs: the fixture net's
+    # (fp32) log-probs of those actions at theta_0, + the offsets
+    ref, names, crcs = build(torch.float32)
+    out["param_names"] = np.array(names); out["param_crc"] = crcs
+    for u, r in enumerate(out["rollouts"]):
+        bp = _ref_batch_processor(g, int(r), torch.float32)
+        obs = {k: v[:-1].reshape((rows,) + tuple(v.shape[2:])) for k, v in bp.obs_dict.items()}
+        acts = [a.reshape(rows, -1).clone() for a in bp.actions]
+        res = obs["current_resources"]
+        for hi in (7, 8):
+            head = ref.action_head_module.action_heads[hi]
+            mask = (res > 0).float() if head.mask_based_on_curr_res else torch.ones_like(res)
+            mask[:, 0] = (res.sum(-1) == 0).float()
+            bad = mask.gather(1, acts[hi][:, :1]).view(-1) == 0
+            acts[hi][bad] = 0
+            acts[hi][bad, 0] = mask[bad].argmax(1)
+        masks = [m.reshape(m.shape[0], rows, *m.shape[3:]) if i in (1, 6, 9) else m.reshape(rows, *m.shape[2:]) for i, m in enumerate(bp.action_masks)]
+        with torch.no_grad():
+            _, lp, _, _ = ref.evaluate_actions(obs, None, bp.masks[:-1].reshape(rows, 1), acts, masks)
+        assert bool(torch.isfinite(lp).all()), lp
+        out[f"u{u}_actions"] = torch.cat(acts, 1).reshape(T, n, -1).numpy().astype(np.int8)
+        out[f"u{u}_old_log_probs"] = (lp.reshape(T, n).numpy() + offsets[u]).astype(np.float32)
+
+    for tag, dtype in (("f32", torch.float32), ("f64", torch.float64)):
+        old_default = torch.get_default_dtype()
+        torch.set_default_dtype(dtype)
+        try:
+            ref, names, _ = build(dtype)
+            prm = dict(ref.named_parameters())
+            theta0 = {k: prm[k].detach().clone() for k in names}
+            agent = PPO(ref, types.SimpleNamespace(**PPO_UPDATE_ARGS))
+            rec = {k: [] for k in ("norm", "g_none", "moved", "g_norm", "g_proj", "d_norm", "d_proj")}
+            items = []
+            clip0, randperm0, item0 = torch.nn.utils.clip_grad_norm_, torch.randperm, torch.Tensor.item
+            perm_iter = iter(perms)
+
+            def clip(params, max_norm, *a, **kw):
+                rec["g_none"].append([prm[k].grad is None for k in names])
+                rec["g_norm"].append([float(prm[k].grad.double().norm()) if prm[k].grad is not None else 0.0 for k in names])
+                rec["g_proj"].append([pf.projection(k, prm[k].grad) if prm[k].grad is not None else 0.0 for k in names])
+                total = clip0(params, max_norm, *a, **kw)
+                rec["norm"].append(float(total))
+                return total
+
+            def randperm(m, *a, **kw):
+                p = next(perm_iter)
+                assert m == len(p)
+                return torch.from_numpy(p.copy())
+
+            def item(t):
+                v = item0(t)
+                if sys._getframe(1).f_code.co_filename.endswith(os.path.join("ppo", "ppo.py")):
+                    items.append(v)
+                return v
+
+            step0 = agent.optimiser.step
+
+            def step(*a, **kw):
+                before = {k: prm[k].detach().clone() for k in names}
+                r_ = step0(*a, **kw)
+                with torch.no_grad():
+                    rec["moved"].append([not torch.equal(before[k], prm[k]) for k in names])
+                    d = {k: prm[k].detach() - theta0[k] for k in names}
+                rec["d_norm"].append([float(d[k].double().norm()) for k in names])
+                rec["d_proj"].append([pf.projection(k, d[k]) for k in names])
+                return r_
+            agent.optimiser.step = step
+            torch.nn.utils.clip_grad_norm_, torch.randperm, torch.Tensor.item = clip, randperm, item
+            try:
+                returned = []
+                for u, r in enumerate(out["rollouts"]):
+                    for grp in agent.optimiser.param_groups:
+                        grp["lr"] = PPO_UPDATE_LRS[u]
+                    bp = _ref_batch_processor(g, int(r), dtype)
+                    bp.action_log_probs = torch.from_numpy(out[f"u{u}_old_log_probs"]).to(dtype)[:, :, None]
+                    a = torch.from_numpy(out[f"u{u}_actions"].astype(np.int64))
+                    bp.actions = [a[:, :, off:off + ln] for off, ln in spec.ACTION_HEAD_SLICES]
+                    returned.append(agent.update(bp))
+            finally:
+                torch.nn.utils.clip_grad_norm_, torch.randperm, torch.Tensor.item = clip0, randperm0, item0
+        finally:
+            torch.set_default_dtype(old_default)
+        n_steps = n_upd * epochs * nmb
+        assert len(items) == 3 * n_steps and len(rec["norm"]) == n_steps, (len(items), len(rec["norm"]))
+        # ppo.py:77-79 reads value_loss, action_loss, entropy (in that order) and multiplies the first and the last by their coefficients:
+        # stored as (value loss x value_loss_coef, action loss, entropy x entropy_coef), the terms update() averages
+        coefs = np.array([PPO_UPDATE_ARGS["value_loss_coef"], 1.0, PPO_UPDATE_ARGS["entropy_coef_start"]])
+        out[f"{tag}_step_losses"] = np.array(items, dtype=np.float64).reshape(n_steps, 3) * coefs
+        out[f"{tag}_update_losses"] = np.array(returned, dtype=np.float64)
+        out[f"{tag}_grad_norm_total"] = np.array(rec["norm"], dtype=np.float64)
+        out[f"{tag}_grad_none"] = np.packbits(np.array(rec["g_none"], dtype=np.uint8), axis=1, bitorder="little")
+        out[f"{tag}_moved"] = np.packbits(np.array(rec["moved"], dtype=np.uint8), axis=1, bitorder="little")
+        for k in ("g_norm", "g_proj", "d_norm", "d_proj"):
+            out[f"{tag}_{k}"] = np.array(rec[k], dtype=np.float64)
+    np.savez_compressed(os.path.join(OUT, "ppo_update.npz"), **out)
+    f32, f64 = out["f32_d_proj"], out["f64_d_proj"]
+    scale = np.maximum(out["f64_d_norm"], 1e-3 * out["f64_d_norm"].max(1, keepdims=True))
+    return {"bytes": os.path.getsize(os.path.join(OUT, "ppo_update.npz")), "params": len(names),
+            "grad_none_f32": int(np.unpackbits(out["f32_grad_none"], axis=1, bitorder="little")[:, :len(names)].sum()),
+            "fp32_vs_fp64_dtheta_proj_rel": float((np.abs(f32 - f64) / scale).max()),
+            "fp32_vs_fp64_loss_abs": float(np.abs(out["f32_step_losses"] - out["f64_step_losses"]).max()),
+            "fp32_vs_fp64_norm_rel": float((np.abs(out["f32_grad_norm_total"] - out["f64_grad_norm_total"]) / out["f64_grad_norm_total"]).max())}
+
+
 def gen_forward_search(n_ucb_roots=3):
     """the reference's forward-search HOST logic and simulator, as data.
       prop_*   `default_sample_actions` (sample_actions_fn.py:55-329) root by root with the reference net (fixture weights,
@@ -991,6 +1173,8 @@ if __name__ == "__main__":
         print("forward_search", gen_forward_search()); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "policy":
         print("policy_small", gen_policy_small()); sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "ppo_update":
+        print("ppo_update", gen_ppo_update()); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "gae_ppo":
         gen_gae_ppo(); print("gae/ppo"); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "validate":
