@@ -270,6 +270,21 @@ int32_t catan_head_state_floats(void);
 int catan_head_chain(const void* pre, int64_t pre_ld, const void* wts, const float* vec, float eps, int32_t head_id, int32_t step, float* state,
                      const float* maskmat, const float* cur_res, const float* trade, const float* custom, const int64_t* forced, const float* u,
                      int64_t* actions, float* logp_out, int64_t B, catan_stream_t stream);
+/* Per-row statistics of a pass, opt-in; actions and log-probs are the same bits with or without them.
+ * catan_head_fwd_entropy: catan_head_fwd that also writes the entropy -sum p log p (p > 0) of each row's masked distribution to
+ * entropy (float [B], not NULL).
+ * catan_head_chain_ex: catan_head_chain with flags; CATAN_HEAD_STATS makes the eighteen calls also fill state columns 26..31 (the
+ * caller zeroes `state` as before): [26] the row's entropy, sum over the evaluations of the head's log-prob mask x entropy (the
+ * trade lists' steps behind a "stop" count 0; a forced type takes none); [27] scratch; [28] the type's probability (1 for a forced
+ * type), [29] its number of legal types (0 for a forced type), [30] / [31] the probability and the number of legal columns of
+ * the type's specific head (type 0 / 2 -> head 1, 1 -> 2, 8 -> 3, 4 -> 4, 11 -> 6; 0 / 0 for other types). */
+#define CATAN_HEAD_STATS 1
+int catan_head_fwd_entropy(const void* pre, int64_t pre_ld, const float* cond, int64_t cond_ld, int32_t ncond, const void* wts, const float* vec, float eps,
+                           int32_t K, const float* mask, int64_t mask_ld, const float* u, int64_t* action, float* logp, float* entropy, int64_t B,
+                           catan_stream_t stream);
+int catan_head_chain_ex(const void* pre, int64_t pre_ld, const void* wts, const float* vec, float eps, int32_t head_id, int32_t step, float* state,
+                        const float* maskmat, const float* cur_res, const float* trade, const float* custom, const int64_t* forced, const float* u,
+                        int64_t* actions, float* logp_out, int32_t flags, int64_t B, catan_stream_t stream);
 
 /* The dev-card list modules of the policy net (RL/models/player_modules.py:55-69: embedding(6 x 16) -> 4-head attention with
  * key mask -> out projection -> LayerNorm(16) -> zero the padding -> sum over the list), one fused kernel, evaluated per card

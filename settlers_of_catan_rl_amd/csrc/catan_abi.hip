@@ -258,21 +258,23 @@ static int wgrad_launch_grouped_dispatch(bool tr, int otw, int itc, const WgBatc
     return fail(CATAN_EINVAL, "catan_linear_wgrad_grouped: no kernel for this tile shape");
 }
 
-template <int RT, int WAVES>
+template <int RT, int WAVES, bool STATS>
 static int head_launch_cfg(const HeadArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)((a.B + WAVES * RT * 16 - 1) / (WAVES * RT * 16))), block(WAVES * 64);
     switch ((a.K + 15) / 16) {
-    case 1: hipLaunchKernelGGL((k_head_fwd<1, RT, WAVES>), grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_head_fwd<2, RT, WAVES>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_head_fwd<3, RT, WAVES>), grid, block, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_head_fwd<4, RT, WAVES>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((k_head_fwd<5, RT, WAVES>), grid, block, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((k_head_fwd<1, RT, WAVES, STATS>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_head_fwd<2, RT, WAVES, STATS>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_head_fwd<3, RT, WAVES, STATS>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((k_head_fwd<4, RT, WAVES, STATS>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_head_fwd<5, RT, WAVES, STATS>), grid, block, 0, st, a); break;
     }
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
-static int head_launch(const HeadArgs& a, hipStream_t st) {
-    return a.B <= HD_NARROW_MAX_ROWS ? head_launch_cfg<HD_RT_NARROW, HD_WAVES_NARROW>(a, st) : head_launch_cfg<HD_RT_WIDE, HD_WAVES_WIDE>(a, st);
+static int head_launch(const HeadArgs& a, hipStream_t st, bool stats = false) {
+    if (stats)
+        return a.B <= HD_NARROW_MAX_ROWS ? head_launch_cfg<HD_RT_NARROW, HD_WAVES_NARROW, true>(a, st) : head_launch_cfg<HD_RT_WIDE, HD_WAVES_WIDE, true>(a, st);
+    return a.B <= HD_NARROW_MAX_ROWS ? head_launch_cfg<HD_RT_NARROW, HD_WAVES_NARROW, false>(a, st) : head_launch_cfg<HD_RT_WIDE, HD_WAVES_WIDE, false>(a, st);
 }
 
 template <int KS>
@@ -1830,36 +1832,60 @@ int catan_qkv_bwd(const void* dqkv, const void* x, const void* dres, const void*
 }
 int32_t catan_head_weight_elems(void) { return HD_WELEMS; }
 int32_t catan_head_vec_elems(void) { return HD_VELEMS; }
-int catan_head_fwd(const void* pre, int64_t pre_ld, const float* cond, int64_t cond_ld, int32_t ncond, const void* wts, const float* vec, float eps,
-                   int32_t K, const float* mask, int64_t mask_ld, const float* u, int64_t* action, float* logp, int64_t B, catan_stream_t stream) {
+static int head_fwd(const char* fn, const void* pre, int64_t pre_ld, const float* cond, int64_t cond_ld, int32_t ncond, const void* wts, const float* vec,
+                    float eps, int32_t K, const float* mask, int64_t mask_ld, const float* u, int64_t* action, float* logp, float* entropy, int64_t B,
+                    catan_stream_t stream) {
     if (!pre || !wts || !vec || !mask || !action || !logp || B <= 0 || K < 1 || K > HD_KP || ncond < 0 || ncond > HD_NCP || (ncond > 0 && !cond) ||
         pre_ld % 8 != 0 || ((uintptr_t)pre & 15) != 0)
-        return fail(CATAN_EINVAL, "catan_head_fwd: bad arguments (K <= 80, ncond <= 32, pre 16-byte aligned with a row pitch that is a multiple of 8)");
+        return fail(CATAN_EINVAL, std::string(fn) + ": bad arguments (K <= 80, ncond <= 32, pre 16-byte aligned with a row pitch that is a multiple of 8)");
     HeadArgs a;
     a.pre = (const unsigned short*)pre; a.pre_ld = pre_ld; a.cond = cond; a.cond_ld = cond_ld; a.ncond = ncond;
     a.wts = (const unsigned short*)wts; a.vec = vec; a.eps = eps; a.K = K; a.mask = mask; a.mask_ld = mask_ld; a.u = u;
-    a.action = (long long*)action; a.logp = logp; a.B = B;
+    a.action = (long long*)action; a.logp = logp; a.B = B; a.ent = entropy;
     a.state = nullptr; a.head_id = 0; a.step = 0; a.maskmat = nullptr; a.cur_res = nullptr; a.trade = nullptr; a.custom = nullptr;
     a.forced = nullptr; a.actions = nullptr; a.logp_out = nullptr;
-    return head_launch(a, S(stream));
+    return head_launch(a, S(stream), entropy != nullptr);
+}
+int catan_head_fwd(const void* pre, int64_t pre_ld, const float* cond, int64_t cond_ld, int32_t ncond, const void* wts, const float* vec, float eps,
+                   int32_t K, const float* mask, int64_t mask_ld, const float* u, int64_t* action, float* logp, int64_t B, catan_stream_t stream) {
+    return head_fwd("catan_head_fwd", pre, pre_ld, cond, cond_ld, ncond, wts, vec, eps, K, mask, mask_ld, u, action, logp, nullptr, B, stream);
+}
+int catan_head_fwd_entropy(const void* pre, int64_t pre_ld, const float* cond, int64_t cond_ld, int32_t ncond, const void* wts, const float* vec, float eps,
+                           int32_t K, const float* mask, int64_t mask_ld, const float* u, int64_t* action, float* logp, float* entropy, int64_t B,
+                           catan_stream_t stream) {
+    if (!entropy) return fail(CATAN_EINVAL, "catan_head_fwd_entropy: bad arguments (entropy is NULL)");
+    return head_fwd("catan_head_fwd_entropy", pre, pre_ld, cond, cond_ld, ncond, wts, vec, eps, K, mask, mask_ld, u, action, logp, entropy, B, stream);
 }
 
 int32_t catan_head_state_floats(void) { return HD_STATE; }
-int catan_head_chain(const void* pre, int64_t pre_ld, const void* wts, const float* vec, float eps, int32_t head_id, int32_t step, float* state,
-                     const float* maskmat, const float* cur_res, const float* trade, const float* custom, const int64_t* forced, const float* u,
-                     int64_t* actions, float* logp_out, int64_t B, catan_stream_t stream) {
+static int head_chain(const char* fn, const void* pre, int64_t pre_ld, const void* wts, const float* vec, float eps, int32_t head_id, int32_t step,
+                      float* state, const float* maskmat, const float* cur_res, const float* trade, const float* custom, const int64_t* forced,
+                      const float* u, int64_t* actions, float* logp_out, bool stats, int64_t B, catan_stream_t stream) {
     static const int KS[12] = { 13, 54, 73, 19, 5, 2, 3, 6, 6, 5, 5, 5 }, NC[12] = { 0, 2, 0, 0, 0, 32, 2, 6, 12, 4, 9, 0 };
     if (!pre || !wts || !vec || !state || !maskmat || !cur_res || !actions || !logp_out || B <= 0 || head_id < 0 || head_id > 11 || step < 0 || step > 3 ||
         ((head_id != 7 && head_id != 8) && step != 0) || (head_id == 5 && (!trade || !custom)) || pre_ld % 8 != 0 || ((uintptr_t)pre & 15) != 0 ||
         ((uintptr_t)state & 15) != 0)
-        return fail(CATAN_EINVAL, "catan_head_chain: bad arguments");
+        return fail(CATAN_EINVAL, std::string(fn) + ": bad arguments");
     HeadArgs a;
     a.pre = (const unsigned short*)pre; a.pre_ld = pre_ld; a.cond = nullptr; a.cond_ld = 0; a.ncond = NC[head_id];
     a.wts = (const unsigned short*)wts; a.vec = vec; a.eps = eps; a.K = KS[head_id]; a.mask = nullptr; a.mask_ld = 0; a.u = u;
-    a.action = nullptr; a.logp = nullptr; a.B = B;
+    a.action = nullptr; a.logp = nullptr; a.B = B; a.ent = nullptr;
     a.state = state; a.head_id = head_id; a.step = step; a.maskmat = maskmat; a.cur_res = cur_res; a.trade = trade; a.custom = custom;
     a.forced = (const long long*)forced; a.actions = (long long*)actions; a.logp_out = logp_out;
-    return head_launch(a, S(stream));
+    return head_launch(a, S(stream), stats);
+}
+int catan_head_chain(const void* pre, int64_t pre_ld, const void* wts, const float* vec, float eps, int32_t head_id, int32_t step, float* state,
+                     const float* maskmat, const float* cur_res, const float* trade, const float* custom, const int64_t* forced, const float* u,
+                     int64_t* actions, float* logp_out, int64_t B, catan_stream_t stream) {
+    return head_chain("catan_head_chain", pre, pre_ld, wts, vec, eps, head_id, step, state, maskmat, cur_res, trade, custom, forced, u, actions, logp_out,
+                      false, B, stream);
+}
+int catan_head_chain_ex(const void* pre, int64_t pre_ld, const void* wts, const float* vec, float eps, int32_t head_id, int32_t step, float* state,
+                        const float* maskmat, const float* cur_res, const float* trade, const float* custom, const int64_t* forced, const float* u,
+                        int64_t* actions, float* logp_out, int32_t flags, int64_t B, catan_stream_t stream) {
+    if ((flags & ~CATAN_HEAD_STATS) != 0) return fail(CATAN_EINVAL, "catan_head_chain_ex: bad arguments (unknown flags)");
+    return head_chain("catan_head_chain_ex", pre, pre_ld, wts, vec, eps, head_id, step, state, maskmat, cur_res, trade, custom, forced, u, actions, logp_out,
+                      (flags & CATAN_HEAD_STATS) != 0, B, stream);
 }
 
 int catan_randomise_uncertainty(catan_env_t* e, const int32_t* controlling_player, catan_stream_t stream) {

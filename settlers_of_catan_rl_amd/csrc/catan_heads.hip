@@ -45,6 +45,7 @@ struct HeadArgs {
     const float* mask; long mask_ld;             // float [B][K] (a column window of the mask matrix is fine)
     const float* u;                              // uniform per row (inverse-CDF sample) or null (arg-max)
     long long* action; float* logp; long B;
+    float* ent;                                  // per-head mode with statistics (STATS): the row's entropy [B]
     // ---- chained mode (state != null): the autoregressive glue of the twelve heads (which mask row, which conditioning
     // columns, whether the head counts towards the joint log-prob, the trade heads' running hand) happens in the kernel, from a
     // small per-row state that the twenty evaluations of a policy pass hand on to each other; cond / mask / action / logp above
@@ -62,6 +63,10 @@ struct HeadArgs {
 constexpr int HD_STATE = 32;                     // floats per row
 // state slots
 constexpr int HS_TYP = 0, HS_CARD = 1, HS_RA = 2, HS_CNT9 = 3, HS_TOTAL = 4, HS_LPSUM = 5, HS_PREV = 6, HS_FILT7 = 7, HS_OUT = 8, HS_RES = 14, HS_GIVE = 20;
+// written only by the kernels with statistics (STATS): the row's entropy (sum over the evaluations of log_prob_mask x H,
+// action_heads_module.py:154-160,302-328), the running entropy of a trade list, and the record of log_specific_head_probs
+// (:111-142): the type's probability, the number of legal types, the type's specific head's probability and its legal columns
+constexpr int HS_ENT = 26, HS_ENT78 = 27, HS_LOG = 28;
 
 // what a row's evaluation of head `h` needs besides its mask: its conditioning columns (-> cd) and the factor its log-prob enters
 // the joint log-prob with (log_prob_masks, build_agent_model.py:132-147); the trade heads' running hand starts here.  One lane per row.
@@ -152,16 +157,32 @@ DEVI void hd_mask20(const HeadArgs& a, long row, const float* st, int c0, float*
         mk[q] = col < a.K ? p1[col] * (p2 != nullptr ? p2[col] : 1.0f) : 0.0f;
     }
 }
-// after the row's action `act` with log-prob `lp` is known: the action column(s), the joint log-prob, the state for the next heads
-DEVI void hd_commit(const HeadArgs& a, long row, float* st, int act, float lp, float count) {
+// after the row's action `act` with log-prob `lp` is known: the action column(s), the joint log-prob, the state for the next heads.
+// STATS: also the entropy H of this evaluation's distribution and its number of legal columns `nav` go into the statistics slots.
+template <bool STATS>
+DEVI void hd_commit(const HeadArgs& a, long row, float* st, int act, float lp, float count, float H, float nav) {
     long long* out = a.actions + row * 18;
     const int h = a.head_id;
-    auto add = [&](float v) { st[HS_TOTAL] += count != 0.0f ? v * count : 0.0f; };
+    auto add = [&](float v) {
+        st[HS_TOTAL] += count != 0.0f ? v * count : 0.0f;
+        if constexpr (STATS) {
+            st[HS_ENT] += count != 0.0f ? H * count : 0.0f;
+            const int typ = (int)st[HS_TYP];                          // the type's specific head (action_heads_module.py:124-134)
+            const bool spec = (h == 1 && (typ == T_SETTLE || typ == T_CITY)) || (h == 2 && typ == T_ROAD) || (h == 3 && typ == T_ROBBER) ||
+                              (h == 4 && typ == T_PLAYDEV) || (h == 6 && typ == T_STEAL);
+            if (spec) { st[HS_LOG + 2] = __expf(lp); st[HS_LOG + 3] = nav; }
+        }
+    };
     switch (h) {
     case 0: {
         int typ = act; float l = lp;
-        if (a.forced != nullptr && a.forced[row] >= 0) { typ = (int)a.forced[row]; l = 0.0f; }
+        const bool forced = a.forced != nullptr && a.forced[row] >= 0;
+        if (forced) { typ = (int)a.forced[row]; l = 0.0f; }
         st[HS_TYP] = (float)typ; st[HS_TOTAL] = l; out[0] = typ;
+        if constexpr (STATS) {                                         // a forced type takes no type-head entropy (:37-48)
+            st[HS_ENT] = forced ? 0.0f : H;
+            st[HS_LOG] = forced ? 1.0f : __expf(lp); st[HS_LOG + 1] = forced ? 0.0f : nav;
+        }
         return;
     }
     case 1: out[1] = act; add(lp); return;
@@ -179,12 +200,14 @@ DEVI void hd_commit(const HeadArgs& a, long row, float* st, int act, float lp, f
         st[HS_RES + act] = fmaxf(st[HS_RES + act] - 1.0f, 0.0f);
         const float keep = a.step == 0 ? 1.0f : (st[HS_PREV] > 0.0f ? 1.0f : 0.0f);       // a list ends at its first 0 ("stop")
         st[HS_LPSUM] += keep != 0.0f ? lp : 0.0f;
+        if constexpr (STATS) st[HS_ENT78] = (a.step == 0 ? 0.0f : st[HS_ENT78]) + (keep != 0.0f ? H : 0.0f);
         st[HS_PREV] = (float)act;
         st[HS_OUT] = 0.0f;                                                              // column 0 never feeds back
         if (a.step == 3) {
             const float prop = (int)st[HS_TYP] == T_PROPOSE ? 1.0f : 0.0f;
             const float l = prop != 0.0f ? st[HS_LPSUM] : 0.0f;
             st[HS_TOTAL] += l;
+            if constexpr (STATS) st[HS_ENT] += prop != 0.0f ? st[HS_ENT78] : 0.0f;
             if (h == 7) {
                 st[HS_FILT7] = l == 0.0f ? 1.0f : 0.0f;                                 // action_heads_module.py:175
                 for (int k = 0; k < 6; k++) st[HS_GIVE + k] = st[HS_OUT + k];
@@ -211,7 +234,9 @@ struct HeadShared {
     __attribute__((aligned(16))) float sState[WAVES][RT][16][HD_STATE];   // the rows' chained state (LDS: ordered within the wave)
 };
 // One head evaluation of a workgroup's 256 rows.
-template <int KT, int RT, int WAVES>
+// STATS: the per-row statistics besides the action (chained: the HS_ENT .. HS_LOG slots; per-head: `ent`); without, the
+// instantiation is the plain kernel, so actions and log-probs are the same bits either way
+template <int KT, int RT, int WAVES, bool STATS>
 DEVI void hd_eval(const HeadArgs& a, HeadShared<RT, WAVES>& sh) {
     constexpr int HD_RT = RT, HD_WAVES = WAVES, HD_THREADS = WAVES * 64, HD_ROWS = WAVES * RT * 16;
     auto& sW2 = sh.sW2; auto& sW3 = sh.sW3; auto& sW1 = sh.sW1; auto& sV = sh.sV; auto& sLg = sh.sLg; auto& sCond = sh.sCond; auto& sCnt = sh.sCnt;
@@ -435,6 +460,19 @@ DEVI void hd_eval(const HeadArgs& a, HeadShared<RT, WAVES>& sh) {
             float incl = mine;
             { const float v1 = __shfl_up(incl, 1); if (part >= 1) incl += v1; }
             { const float v2 = __shfl_up(incl, 2); if (part >= 2) incl += v2; }
+            float H = 0.0f, nav = 0.0f;                                 // STATS: -sum p log p over p > 0 (distributions.py:18-20), legal columns
+            if constexpr (STATS) {
+                float plp = 0.0f;
+#pragma unroll
+                for (int q = 0; q < 20; q++) if ((valid >> q) & 1u) {
+                    const float p = __expf(z[q] - lse);
+                    plp += p > 0.0f ? p * (z[q] - lse) : 0.0f;
+                }
+                plp += __shfl_xor(plp, 1); plp += __shfl_xor(plp, 2);
+                int nv = __popc(valid);
+                nv += __shfl_xor(nv, 1); nv += __shfl_xor(nv, 2);
+                H = -plp; nav = (float)nv;
+            }
             float cdf = incl - mine;
             int pick = 0x7fff, last = -1;
 #pragma unroll
@@ -454,8 +492,11 @@ DEVI void hd_eval(const HeadArgs& a, HeadShared<RT, WAVES>& sh) {
             const u32 vb = __shfl(valid, (lane & ~3) | (act / 20));
             if (part == 0 && row0 + rr < a.B) {
                 const float lpa = (((vb >> (act % 20)) & 1u) ? te_bf(lg[rr * HD_LG + act]) : -INFINITY) - lse;
-                if (chained) hd_commit(a, grow, sState[wave][tt][rr], act, lpa, sCnt[wave][tt][rr]);
-                else { a.action[grow] = act; a.logp[grow] = lpa; }
+                if (chained) hd_commit<STATS>(a, grow, sState[wave][tt][rr], act, lpa, sCnt[wave][tt][rr], H, nav);
+                else {
+                    a.action[grow] = act; a.logp[grow] = lpa;
+                    if constexpr (STATS) a.ent[grow] = H;
+                }
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -467,9 +508,9 @@ DEVI void hd_eval(const HeadArgs& a, HeadShared<RT, WAVES>& sh) {
     }
 }
 
-template <int KT, int RT, int WAVES>
+template <int KT, int RT, int WAVES, bool STATS>
 __global__ __launch_bounds__(WAVES * 64) void k_head_fwd(HeadArgs a) {
     __shared__ HeadShared<RT, WAVES> sh;
-    hd_eval<KT, RT, WAVES>(a, sh);
+    hd_eval<KT, RT, WAVES, STATS>(a, sh);
 }
 }  // namespace catan

@@ -28,13 +28,31 @@ def sample_orders(n_games, rng=None):
     return out
 
 
+def _stats_of(res, rows, dev):
+    """act_fn's return value -> (actions, extras): a tensor of actions, or a dict with "actions" and any of "entropy",
+    "value", "logp" ([rows]) and "head_log" ([rows, 4]); missing statistics are zeros"""
+    if torch.is_tensor(res):
+        res = {"actions": res}
+    z = torch.zeros(rows, dtype=torch.float32, device=dev)
+    ex = {k: (torch.as_tensor(res[k], device=dev).float().reshape(rows) if k in res else z) for k in ("entropy", "value", "logp")}
+    ex["head_log"] = torch.as_tensor(res["head_log"], device=dev).float().reshape(rows, 4) if "head_log" in res else torch.zeros((rows, 4), device=dev)
+    return res["actions"], ex
+
+
 @torch.no_grad()
 def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=False, generator=None, autocast_dtype=None,
-                            act_fn=None):
-    """env: freshly reset games, auto_reset off.  nets: 4 policies (entries may be the same object; equal objects share a
-    forward).  orders int [n,4].  max_steps: the offline evaluator's draw cap (2 500; None = play to the end).
-    act_fn(net, idx, f, lists, lens, masks) -> actions [len(idx),18]: replaces net.act on the rows idx (test hook).
-    -> dict of numpy arrays: winner (policy index, -1 = draw), victory_points (of policy 0), game_steps, policy_decisions."""
+                            act_fn=None, assignment=None, stats=False, detailed=False):
+    """env: freshly reset games, auto_reset off.  nets: the policies (entries may be the same object; equal objects share a
+    forward); without `assignment` four of them, policy i = nets[i] in every game.  assignment int [n,4] (optional): game g's
+    policy i is nets[assignment[g][i]] (the offline evaluator's opponents drawn per game).  orders int [n,4].  max_steps: the
+    offline evaluator's draw cap (2 500; None = play to the end).
+    act_fn(net, idx, f, lists, lens, masks) -> actions [len(idx),18], or a dict of "actions" and optionally "entropy", "value",
+    "logp", "head_log" (see _stats_of): replaces net.act on the rows idx (test hook).
+    -> dict of numpy arrays: winner (policy index, -1 = draw), victory_points (of policy 0), game_steps, policy_decisions.
+    stats: also, over policy 0's decisions (evaluation/evaluation_manager.py:44-134), tallied on the device inside the loop:
+    entropy (per game: mean of the decisions' entropies; NaN without decisions), value (mean value), action_types (int [n, 13]
+    counts), type_log_probs (per game: the list of (action type, joint log-prob) tuples); detailed: also head_logs (per game:
+    the log_specific_action_output tuples of all its decisions, reference_api.head_log_tuples)."""
     n, dev = env.n, env.device
     orders_t = torch.as_tensor(orders, device=dev).long()
     policy_of_pid = torch.empty((n, 4), dtype=torch.long, device=dev)
@@ -47,7 +65,19 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
     for net in nets:
         if not any(net is d for d in distinct):
             distinct.append(net)
-    net_of_policy = torch.tensor([[i for i, d in enumerate(distinct) if d is net][0] for net in nets], device=dev)
+    distinct_of = [[i for i, d in enumerate(distinct) if d is net][0] for net in nets]
+    if assignment is None:
+        assert len(nets) == 4
+        assignment = np.broadcast_to(np.arange(4), (n, 4))
+    assignment = np.asarray(assignment, dtype=np.int64)
+    net_of = np.asarray(distinct_of, dtype=np.int64)[assignment]                 # [n, 4]: distinct net of game g's policy i
+    net_of_policy = torch.as_tensor(net_of, device=dev)
+    stats = stats or detailed
+    stats_nets = set(int(k) for k in np.unique(net_of[:, 0])) if stats else set()  # the nets that play policy 0 somewhere
+    if stats:
+        ent_sum = torch.zeros(n, dtype=torch.float64, device=dev); val_sum = torch.zeros(n, dtype=torch.float64, device=dev)
+        type_counts = torch.zeros((n, 13), dtype=torch.long, device=dev)
+        trace_typ, trace_lp, trace_rec, trace_act = [], [], [], []
     ar = torch.arange(n, device=dev)
     steps = torch.zeros(n, dtype=torch.long, device=dev)
     decisions = torch.zeros(n, dtype=torch.long, device=dev)
@@ -63,16 +93,24 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
         f, lists, lens = env.get_obs()
         masks = env.get_action_masks()
         actions = torch.zeros((n, spec.ACTION_WORDS), dtype=torch.int64, device=dev)
-        net_id = net_of_policy[pol]
+        net_id = net_of_policy[ar, pol]
+        if stats:
+            ent_p = torch.zeros(n, device=dev); val_p = torch.zeros(n, device=dev); lp_p = torch.zeros(n, device=dev)
+            rec_p = torch.zeros((n, 4), device=dev)
         for k, net in enumerate(distinct):
             idx = ((net_id == k) & running).nonzero(as_tuple=True)[0]
             if idx.numel() == 0:
                 continue
             args = (f[idx], lists[idx], lens[idx].long(), masks[idx])
+            want = k in stats_nets
             if act_fn is not None:
-                actions[idx] = act_fn(net, idx, *args)
+                actions[idx], ex = _stats_of(act_fn(net, idx, *args), idx.numel(), dev)
+                if want:
+                    ent_p[idx], val_p[idx], lp_p[idx], rec_p[idx] = ex["entropy"], ex["value"], ex["logp"], ex["head_log"]
                 continue
             kw = {"deterministic": deterministic, "generator": generator}
+            if want:
+                kw.update(return_entropy=True, return_head_log=detailed)
             rec = getattr(net, "include_lstm", False)
             if rec:
                 L, seat = int(net.lstm_size), deciding[idx] - 1
@@ -85,6 +123,20 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
             actions[idx] = res[1]
             if rec:
                 hid[0, idx, seat, :L], hid[1, idx, seat, :L] = res[3][0].float(), res[3][1].float()
+            if want:
+                j = 4 if rec else 3
+                ent_p[idx], val_p[idx], lp_p[idx] = res[j].float(), res[0].float().reshape(-1), res[2].float().reshape(-1)
+                if detailed:
+                    rec_p[idx] = res[j + 1].float()
+        if stats:                                        # policy 0's decisions of this pass, on the device
+            p0 = running & (pol == 0)
+            ent_sum += torch.where(p0, ent_p, torch.zeros_like(ent_p)).double()
+            val_sum += torch.where(p0, val_p, torch.zeros_like(val_p)).double()
+            type_counts.index_put_((ar, actions[:, 0].clamp(0, 12)), p0.long(), accumulate=True)
+            trace_typ.append(torch.where(p0, actions[:, 0], torch.full_like(actions[:, 0], -1)).to(torch.int8))
+            trace_lp.append(lp_p)
+            if detailed:
+                trace_rec.append(rec_p); trace_act.append(actions[:, :7].to(torch.int8))
         a_env = actions.to(torch.int32)
         a_env[:, 0] = torch.where(running, a_env[:, 0], torch.full_like(a_env[:, 0], -1))
         _, done = env.step(a_env)
@@ -101,8 +153,32 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
     winner_pid = blob[:, off_w].long()
     winner = torch.where(draw, torch.full_like(winner_pid, -1), policy_of_pid[ar, (winner_pid - 1).clamp(min=0)])
     vps = blob[:, off_v:off_v + 4].long()[ar, orders_t[:, 0] - 1]             # env.curr_vps[self.order[0]]
-    return {"winner": winner.cpu().numpy(), "victory_points": vps.cpu().numpy(), "game_steps": steps.cpu().numpy(),
-            "policy_decisions": decisions.cpu().numpy()}
+    out = {"winner": winner.cpu().numpy(), "victory_points": vps.cpu().numpy(), "game_steps": steps.cpu().numpy(),
+           "policy_decisions": decisions.cpu().numpy()}
+    if stats:
+        out.update(_stats_result(decisions, ent_sum, val_sum, type_counts, trace_typ, trace_lp, trace_rec, trace_act, detailed))
+    return out
+
+
+def _stats_result(decisions, ent_sum, val_sum, type_counts, trace_typ, trace_lp, trace_rec, trace_act, detailed):
+    """the device tallies -> the per-game statistics (one copy to the host at the end)"""
+    dec = decisions.double()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ent = (ent_sum / dec).cpu().numpy(); val = (val_sum / dec).cpu().numpy()
+    typ = torch.stack(trace_typ, 1).cpu().numpy()                               # [n, passes], -1: not a policy-0 decision
+    lp = torch.stack(trace_lp, 1).cpu().numpy()
+    n = typ.shape[0]
+    g, p = np.nonzero(typ >= 0)                                                 # row-major: per game in pass order
+    bounds = np.searchsorted(g, np.arange(n + 1))
+    t_all, l_all = typ[g, p].tolist(), lp[g, p]
+    tuples = [[(t_all[i], l_all[i]) for i in range(bounds[k], bounds[k + 1])] for k in range(n)]
+    out = {"entropy": ent, "value": val, "action_types": type_counts.cpu().numpy(), "type_log_probs": tuples}
+    if detailed:
+        from .reference_api import head_log_tuples_np
+        rec = torch.stack(trace_rec, 1).cpu().numpy()[g, p]
+        act = torch.stack(trace_act, 1).cpu().numpy()[g, p]
+        out["head_logs"] = [[t for i in range(bounds[k], bounds[k + 1]) for t in head_log_tuples_np(rec[i], act[i])] for k in range(n)]
+    return out
 
 
 def run_evaluation_protocol(make_env, central_policy, opponent_policy, num_eval_episodes, update_num=0, rng=None, **kw):

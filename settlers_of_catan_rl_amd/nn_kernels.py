@@ -1276,10 +1276,10 @@ fused_heads_enabled = True
 chained_heads_enabled = True       # the heads' glue inside the fused kernels (heads_chain); off: one kernel per head + torch glue
 
 
-def head_sample(head, trunk_dim, pre, cond, mask, deterministic=False, generator=None):
+def head_sample(head, trunk_dim, pre, cond, mask, deterministic=False, generator=None, with_entropy=False):
     """One head evaluation as one kernel (catan_head_fwd).  pre: bf16 [B, 128] view of the shared trunk product (row pitch =
     stride(0)); cond: [B, e] conditioning columns or None; mask float [B, K] (a column window is fine).
-    -> (action int64 [B], log-prob [B])."""
+    -> (action int64 [B], log-prob [B]); with_entropy: (action, log-prob, entropy [B]) from catan_head_fwd_entropy."""
     wts, vec = head_pack(head, trunk_dim)
     B = pre.shape[0]
     K = head.distribution.linear.weight.shape[0]
@@ -1297,6 +1297,12 @@ def head_sample(head, trunk_dim, pre, cond, mask, deterministic=False, generator
     assert ncond == head.mlp_1.weight.shape[1] - trunk_dim and mask.shape[1] == K
     action = torch.empty(B, dtype=torch.int64, device=pre.device)
     logp = torch.empty(B, dtype=torch.float32, device=pre.device)
+    if with_entropy:
+        ent = torch.empty(B, dtype=torch.float32, device=pre.device)
+        _lib.check(_lib.lib().catan_head_fwd_entropy(_ptr(pre), pre.stride(0), _ptr(cond), cond.stride(0) if cond is not None else 0, ncond, _ptr(wts),
+                                                     _ptr(vec), float(head.norm.eps), K, _ptr(mask), mask.stride(0), _ptr(u), _ptr(action), _ptr(logp),
+                                                     _ptr(ent), B, _stream()))
+        return action, logp, ent
     _lib.check(_lib.lib().catan_head_fwd(_ptr(pre), pre.stride(0), _ptr(cond), cond.stride(0) if cond is not None else 0, ncond, _ptr(wts), _ptr(vec),
                                          float(head.norm.eps), K, _ptr(mask), mask.stride(0), _ptr(u), _ptr(action), _ptr(logp), B, _stream()))
     return action, logp
@@ -1325,10 +1331,16 @@ def head5_custom_pack(head):
     return pack
 
 
-def heads_chain(heads, trunk_dim, pre_all, masks, cur_res, trade, deterministic=False, generator=None, forced_type=None):
+HEAD_STATS_SLOT = 26        # include/catan_hip_nn.h catan_head_chain_ex: entropy [26], scratch [27], log record [28:32]
+CATAN_HEAD_STATS = 1        # catan_head_chain_ex flag (include/catan_hip_nn.h)
+
+
+def heads_chain(heads, trunk_dim, pre_all, masks, cur_res, trade, deterministic=False, generator=None, forced_type=None, stats=False):
     """All twelve heads of an inference pass - eighteen head evaluations - as eighteen launches of the fused head kernel in its
     chained mode (catan_head_chain): the glue between them (type-conditional mask rows, conditioning columns, log-prob masks,
-    the trade heads' lists) runs inside the kernels on a per-row state.  -> (actions int64 [B, 18], joint log-prob [B])"""
+    the trade heads' lists) runs inside the kernels on a per-row state.  -> (actions int64 [B, 18], joint log-prob [B]).
+    stats: the kernels with statistics (catan_head_chain_ex, same actions and log-probs) -> (actions, log-prob, entropy [B],
+    log record [B, 4] = type probability, legal types, the type's specific head's probability, its legal columns)."""
     L = _lib.lib()
     B, dev = pre_all.shape[0], pre_all.device
     masks = masks if (masks.dtype == torch.float32 and masks.is_contiguous()) else masks.float().contiguous()
@@ -1349,9 +1361,15 @@ def heads_chain(heads, trunk_dim, pre_all, masks, cur_res, trade, deterministic=
     for k, (h, step) in enumerate(HEAD_CHAIN_ORDER):
         wts, vec = head_pack(heads[h], trunk_dim)
         pre = pre_all[:, 128 * h:128 * (h + 1)]
-        _lib.check(L.catan_head_chain(_ptr(pre), pre_all.stride(0), _ptr(wts), _ptr(vec), float(heads[h].norm.eps), h, step, _ptr(state), _ptr(masks),
-                                      _ptr(cur_res), _ptr(trade), _ptr(custom) if h == 5 else None, _ptr(forced) if h == 0 else None,
-                                      None if us is None else _ptr(us[k]), _ptr(actions), _ptr(logp), B, st))
+        args = (_ptr(pre), pre_all.stride(0), _ptr(wts), _ptr(vec), float(heads[h].norm.eps), h, step, _ptr(state), _ptr(masks),
+                _ptr(cur_res), _ptr(trade), _ptr(custom) if h == 5 else None, _ptr(forced) if h == 0 else None,
+                None if us is None else _ptr(us[k]), _ptr(actions), _ptr(logp))
+        if stats:
+            _lib.check(L.catan_head_chain_ex(*args, CATAN_HEAD_STATS, B, st))
+        else:
+            _lib.check(L.catan_head_chain(*args, B, st))
+    if stats:
+        return actions, logp, state[:, HEAD_STATS_SLOT], state[:, HEAD_STATS_SLOT + 2:HEAD_STATS_SLOT + 6]
     return actions, logp
 
 

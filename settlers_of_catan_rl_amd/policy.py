@@ -579,6 +579,10 @@ GROUPED_WGRAD = True        # (A/B switch, tools/ab_step_switches.py)
 RECURRENT_BATCHED = True    # (A/B switch) the trade heads' four steps as one pass when the actions are given
 
 
+# the type -> specific head pairs of log_specific_head_probs (action_heads_module.py:124-134)
+HEAD_LOG_SPECIFIC = ((1, (T_SETTLE, T_CITY)), (2, (T_ROAD,)), (3, (T_ROBBER,)), (4, (T_PLAYDEV,)), (6, (T_STEAL,)))
+
+
 class _ActionHeads(nn.Module):
     def __init__(self, D=512):
         super().__init__()
@@ -766,9 +770,10 @@ class _ActionHeads(nn.Module):
         logp = logp0.index_add(0, all_rows, torch.cat([lp for _, lp in lps]))
         return actions.clone(), logp, torch.cat([e0] + ents).sum() / B
 
-    def _recurrent(self, head, pre, fixed, cur_res, from_hand, acts, deterministic, generator):
+    def _recurrent(self, head, pre, fixed, cur_res, from_hand, acts, deterministic, generator, stats=False):
         """RecurrentResourceActionHead.forward (action_heads_module.py:258-329) without the final type mask.
-        pre: the head's trunk contribution (constant over the four steps); fixed: conditioning columns before `out` or None."""
+        pre: the head's trunk contribution (constant over the four steps); fixed: conditioning columns before `out` or None.
+        stats: the per-row entropy also while sampling."""
         if acts is not None and RECURRENT_BATCHED:
             return self._recurrent_given(head, pre, fixed, cur_res, from_hand, acts)
         B, x = pre.shape[0], pre
@@ -783,8 +788,8 @@ class _ActionHeads(nn.Module):
         for i in range(4):
             cond = out if fixed is None else torch.cat((fixed, out), -1)
             if fused:
-                a, step_lp = nn_kernels.head_sample(head, self.D, pre, cond, mask, deterministic, generator)
-                ent = None
+                r = nn_kernels.head_sample(head, self.D, pre, cond, mask, deterministic, generator, with_entropy=stats)
+                a, step_lp, ent = r[0], r[1], (r[2] if stats else None)
             else:
                 a, step_lp, ent = _categorical(head.logits(pre, cond), mask,
                                                None if acts is None else acts[:, i], deterministic, generator)
@@ -796,10 +801,10 @@ class _ActionHeads(nn.Module):
             if i > 0:
                 keep = (chosen[-1] > 0).float()
                 step_lp = step_lp * keep
-                if acts is not None:
+                if acts is not None or stats:
                     ent = ent * keep
             logp_sum = logp_sum + step_lp
-            if acts is not None:                        # (sampling discards the entropy)
+            if acts is not None or stats:               # (sampling discards the entropy unless asked for statistics)
                 ent_sum = ent_sum + ent
             chosen.append(a)
             out = torch.cat((torch.zeros_like(out[:, :1]), out[:, 1:]), 1)     # column 0 ("stop") never feeds back; no host constant
@@ -835,11 +840,16 @@ class _ActionHeads(nn.Module):
         out_final = torch.cat((torch.zeros(B, 1, device=pre.device), total[:, 1:]), 1)
         return out_final, acts[:, :4], logp_sum, ent_sum
 
-    def forward(self, main, masks, cur_res, trade, actions=None, deterministic=False, generator=None, forced_type=None, grouping=None, value_fn=None):
+    def forward(self, main, masks, cur_res, trade, actions=None, deterministic=False, generator=None, forced_type=None, grouping=None, value_fn=None,
+                stats=False):
         """main [B,512] (+ lstm_size with the LSTM); masks [B,325]; cur_res [B,6]; trade [B,12]; actions int64 [B,18] or None.
         forced_type int64 [B] or None: rows with a value >= 0 take that action type instead of sampling the type head
         (`condition_on_action_type`, action_heads_module.py:37-48: the type head is skipped, its output is the one-hot).
-        -> actions [B,18], joint log-prob [B], entropy (scalar, action_heads_module.py:159-160,174)."""
+        -> actions [B,18], joint log-prob [B], entropy (scalar, action_heads_module.py:159-160,174).
+        stats (sampling only): -> actions, joint log-prob, entropy per row [B] (its batch mean is the reference's scalar) and the
+        record of log_specific_head_probs (:111-142) per row [B, 4]: the type's probability (1 for a forced type), its number of
+        legal types (0 for a forced type), the probability and the number of legal columns of the type's specific head (0, 0 for
+        types without one: HEAD_LOG_SPECIFIC)."""
         if actions is not None and forced_type is None and self.compact_evaluate and main.shape[0] >= self.compact_min_rows:
             return self._evaluate_compact(main, masks, cur_res, trade, actions, grouping, value_fn)
         if isinstance(masks, PackedActionMasks):
@@ -867,8 +877,12 @@ class _ActionHeads(nn.Module):
         if fused and nn_kernels.chained_heads_enabled:
             # ... and the glue between the evaluations (type-conditional mask rows, conditioning columns, log-prob masks, the
             # trade heads' lists: ~200 small torch launches) runs inside those kernels on a per-row state: eighteen launches
+            if stats:
+                return nn_kernels.heads_chain(H, D, pre_all, m, cur_res, trade, deterministic, generator, forced_type, stats=True)
             acts, lp = nn_kernels.heads_chain(H, D, pre_all, m, cur_res, trade, deterministic, generator, forced_type)
             return acts, lp, 0.0
+        assert not (stats and actions is not None), "stats: sampling only"
+        hlog = {}                                        # stats: head -> (probability of its action, legal columns) per row
 
         def run(i, extra, mask, idx, count, custom=None):
             if fused:
@@ -876,9 +890,15 @@ class _ActionHeads(nn.Module):
                 if custom is not None:
                     cf = _ln(H[i].custom_norm, _lin(custom, H[i].custom_mlp.weight, H[i].custom_mlp.bias), relu=True)
                     cond = cf if extra is None else torch.cat((extra, cf.float()), -1)
-                a, lpa = nn_kernels.head_sample(H[i], D, pre(i), cond, mask, deterministic, generator)
-                return a, lpa * count, 0.0
-            a, lpa, ent = _categorical(H[i].logits(pre(i), extra, custom), mask, given(idx), deterministic, generator)
+                r = nn_kernels.head_sample(H[i], D, pre(i), cond, mask, deterministic, generator, with_entropy=stats)
+                if not stats:
+                    return r[0], r[1] * count, 0.0
+                a, lpa, ent = r
+            else:
+                a, lpa, ent = _categorical(H[i].logits(pre(i), extra, custom), mask, given(idx), deterministic, generator)
+            if stats:
+                hlog[i] = _HEAD_BRANCHES.keep(lpa.exp(), (mask > 0).sum(-1).float())       # (made on a branch's stream, read after the join)
+                return a, lpa * count, count * ent
             return a, lpa * count, ((count * ent).mean() if want_ent else 0.0)
 
         # head 0: action type
@@ -887,6 +907,9 @@ class _ActionHeads(nn.Module):
             forced = forced_type >= 0
             typ = torch.where(forced, forced_type, typ)
             logp = torch.where(forced, torch.zeros_like(logp), logp)
+            if stats:
+                entropy = torch.where(forced, torch.zeros_like(entropy), entropy)
+                hlog[0] = (torch.where(forced, torch.ones_like(hlog[0][0]), hlog[0][0]), torch.where(forced, torch.zeros_like(hlog[0][1]), hlog[0][1]))
         cols[0] = typ
         _is = {}
 
@@ -938,17 +961,28 @@ class _ActionHeads(nn.Module):
             res[10] = br.keep(*run(10, x, m[:, MO[10]:MO[10] + 5], 16, cnt10))
         with br.on(0):       # heads 7 -> 8: the recurrent give / receive resource lists (the longest chain: eight sequential draws)
             prop = is_(T_PROPOSE)
-            give_out, give_a, lp7, e7 = self._recurrent(H[7], pre(7), None, cur_res, True, None if actions is None else actions[:, 7:11], deterministic, generator)
+            give_out, give_a, lp7, e7 = self._recurrent(H[7], pre(7), None, cur_res, True, None if actions is None else actions[:, 7:11], deterministic, generator,
+                                                        stats)
             lp7 = lp7 * prop
             filt7 = (lp7 == 0).float()                                           # action_heads_module.py:175
             _, recv_a, lp8, e8 = self._recurrent(H[8], pre(8), give_out * (1 - filt7)[:, None], cur_res, False,
-                                                 None if actions is None else actions[:, 11:15], deterministic, generator)
+                                                 None if actions is None else actions[:, 11:15], deterministic, generator, stats)
         br.join()
         lps = [logp, lp7, lp8 * prop]
         for i, col in ((1, 1), (2, 2), (3, 3), (4, 4), (5, 5), (6, 6), (9, 15), (10, 16), (11, 17)):
             a, lp, e = res[i]
             cols[col] = a; lps.append(lp); entropy = entropy + e
         logp = torch.stack(lps).sum(0)                   # (one reduction instead of eleven adds)
+        if stats:
+            cols[7] = give_a; cols[11] = recv_a
+            entropy = entropy + (e7 + e8) * prop
+            sp, sn = torch.zeros_like(logp), torch.zeros_like(logp)
+            for h, types in HEAD_LOG_SPECIFIC:
+                sel = is_(types[0]) if len(types) == 1 else is_(types[0]) + is_(types[1])
+                sel = sel > 0
+                sp = torch.where(sel, hlog[h][0], sp); sn = torch.where(sel, hlog[h][1], sn)
+            out = torch.cat((torch.stack([cols[i] for i in range(7)], 1), cols[7], cols[11], torch.stack([cols[15], cols[16], cols[17]], 1)), 1)
+            return out, logp, entropy, torch.stack((hlog[0][0], hlog[0][1], sp, sn), 1)
         cols[7] = give_a; entropy = entropy + ((e7 * prop).mean() if want_ent else 0.0)
         cols[11] = recv_a; entropy = entropy + ((e8 * prop).mean() if want_ent else 0.0)
         out = torch.cat((torch.stack([cols[i] for i in range(7)], 1), cols[7], cols[11], torch.stack([cols[15], cols[16], cols[17]], 1)), 1)
@@ -1054,17 +1088,26 @@ class CatanPolicy(nn.Module):
 
     # ---- reference-shaped API (with include_lstm the new hidden state is returned as a last extra item)
     def act(self, obs_f, lists, lens, masks, deterministic=False, generator=None, condition_on_action_type=None,
-            hidden=None, nonterminal=None):
-        """condition_on_action_type: int64 [B] (entries < 0 = free) or None (RL/models/policy.py:72-82)."""
+            hidden=None, nonterminal=None, return_entropy=False, return_head_log=False):
+        """condition_on_action_type: int64 [B] (entries < 0 = free) or None (RL/models/policy.py:72-82).
+        return_entropy: append the entropy per row [B]; return_head_log: append the log_specific_head_probs record [B, 4]
+        (_ActionHeads.forward's stats).  The actions and log-probs are the same either way."""
         main, hidden = self._main(obs_f, lists, lens, hidden, nonterminal)
         br = _VALUE_BRANCHES.fork(main)          # inference: the value head (three products, two LayerNorms: ~120 us in a row at 65 536 rows) beside the action heads
         with br.on(1):
             value = br.keep(self._value(main))
         cur_res, trade = self._custom(obs_f)
-        actions, logp, _ = self.action_head_module(main, masks.float(), cur_res, trade, None, deterministic, generator,
-                                                   forced_type=condition_on_action_type)
+        stats = return_entropy or return_head_log
+        r = self.action_head_module(main, masks.float(), cur_res, trade, None, deterministic, generator,
+                                    forced_type=condition_on_action_type, stats=stats)
+        actions, logp = r[0], r[1]
         br.join()
-        return (value, actions, logp[:, None], hidden) if self.include_lstm else (value, actions, logp[:, None])
+        out = (value, actions, logp[:, None], hidden) if self.include_lstm else (value, actions, logp[:, None])
+        if return_entropy:
+            out += (r[2],)
+        if return_head_log:
+            out += (r[3],)
+        return out
 
     def evaluate_actions(self, obs_f, lists, lens, masks, actions, hidden=None, nonterminal=None, tile_dedupe=None, grouping=None):
         """grouping: this batch's entry of _ActionHeads.precompute_groupings (the learner computes them for a whole epoch at once)"""

@@ -65,7 +65,10 @@ def install(**defaults):
     `RL.ppo.update_opponent_policies`, `RL.ppo.vec_evaluation`, `RL.ppo.evaluation_manager`,
     `RL.ppo.run_evaluation_protocol`) in `sys.modules`: after `reference_api.install()` the UNMODIFIED
     `RL/robust_train.py` of a reference checkout imports the device pipeline through its own import lines
-    (robust_train.py:13-22).  Everything else of the `RL` package (arguments, utils) stays the reference's."""
+    (robust_train.py:13-22).  Everything else of the `RL` package (arguments, utils) stays the reference's.
+    The offline evaluator's two modules (`evaluation.evaluation_manager`, `evaluation.vec_evaluation`) get
+    `make_offline_evaluation_manager` / `OfflineEvaluationManager` under the reference's names, so that the UNMODIFIED
+    `evaluation/run_evaluations.py` ranks checkpoints on the device."""
     import sys
     import types
     configure(**defaults)
@@ -80,12 +83,23 @@ def install(**defaults):
         "RL.ppo.vec_evaluation": ("SubProcEvaluationManager",),
         "RL.ppo.evaluation_manager": ("make_evaluation_manager",),
         "RL.ppo.run_evaluation_protocol": ("run_evaluation_protocol",),
+        # the offline evaluator (evaluation/run_evaluations.py:8-9)
+        "evaluation.evaluation_manager": (("make_evaluation_manager", "make_offline_evaluation_manager"),),
+        "evaluation.vec_evaluation": (("SubProcEvaluationManager", "OfflineEvaluationManager"),),
     }
+    if "evaluation" not in sys.modules:
+        try:
+            import evaluation  # noqa: F401  (the reference's own package, when its checkout is on sys.path)
+        except ImportError:
+            pkg = types.ModuleType("evaluation")
+            pkg.__path__ = []
+            sys.modules["evaluation"] = pkg
     for name, attrs in table.items():
         mod = types.ModuleType(name)
         mod.__doc__ = f"alias installed by {__name__}.install()"
         for a in attrs:
-            setattr(mod, a, getattr(me, a))
+            alias, own = (a, a) if isinstance(a, str) else a
+            setattr(mod, alias, getattr(me, own))
         sys.modules[name] = mod
     return sorted(table)
 
@@ -209,20 +223,32 @@ class SettlersAgentPolicy(nn.Module):
 
     def act(self, obs_dict, hidden_states, nonterminal_masks, action_masks, deterministic=False, return_entropy=False,
             condition_on_action_type=None, log_specific_action_output=False):
-        if return_entropy or log_specific_action_output:
-            raise NotImplementedError("return_entropy / log_specific_action_output are only used by the reference's GUI")
+        """return_entropy: also the entropy, the batch mean of the per-row values (the reference's sum of per-head means);
+        log_specific_action_output (a single-row call, as the offline evaluator makes it): also the reference's list of
+        (action_type or None, head, prob, n_available, action) tuples (action_heads_module.py:111-142)."""
         f, lists, lens = obs_dict_to_flat(obs_dict)
         cond = None
         if condition_on_action_type is not None:
             cond = torch.as_tensor(condition_on_action_type, device=f.device).reshape(-1).long().expand(f.shape[0])
+        stats = return_entropy or log_specific_action_output
+        if log_specific_action_output and f.shape[0] != 1:
+            raise ValueError("log_specific_action_output: one row per call (as the reference's evaluator makes them)")
         with self._ctx():
             res = self.net.act(f, lists, lens.long(), masks_list_to_flat(action_masks), deterministic=deterministic,
                                generator=self.sample_generator, condition_on_action_type=cond,
+                               return_entropy=stats, return_head_log=log_specific_action_output,
                                **self._hidden_kw(hidden_states, nonterminal_masks))
         a = res[1]
         actions = [[a[:, off + j:off + j + 1] for j in range(ln)] if ln > 1 else a[:, off:off + 1]
                    for off, ln in spec.ACTION_HEAD_SLICES]
-        return res[0], actions, res[2], (res[3] if self.include_lstm else hidden_states)
+        out = (res[0], actions, res[2], (res[3] if self.include_lstm else hidden_states))
+        if not stats:
+            return out
+        k = 4 if self.include_lstm else 3
+        entropy = res[k].float().mean()
+        if log_specific_action_output:
+            return out + (entropy, head_log_tuples(res[k + 1][0], a[0], forced=cond is not None and int(cond[0]) >= 0))
+        return out + (entropy,)
 
     def evaluate_actions(self, obs_dict, hidden_states, nonterminal_masks, actions, action_masks):
         f, lists, lens = obs_dict_to_flat(obs_dict)
@@ -267,6 +293,27 @@ class SettlersAgentPolicy(nn.Module):
 
     def load_state_dict(self, sd, strict=True):
         self.net.load_reference_state_dict(sd)
+
+
+# log_specific_head_probs (action_heads_module.py:124-134): action type -> the head whose probability is logged
+_LOG_SPECIFIC_HEAD = {0: 1, 2: 1, 1: 2, 8: 3, 4: 4, 11: 6}
+
+
+def head_log_tuples(rec, actions, forced=False):
+    """one row's record of CatanPolicy.act(return_head_log=True) ([type prob, legal types, specific head prob, its legal
+    columns]) and flat actions [18] -> the reference's tuples (None, 0, type prob, legal types, type) and, for a type with a
+    specific head, (type, head, prob, n_available, action); a forced type has no type tuple"""
+    return head_log_tuples_np(rec.detach().float().cpu().numpy(), [int(v) for v in actions[:7]], forced)
+
+
+def head_log_tuples_np(r, actions, forced=False):
+    """head_log_tuples on host values: r float [4], actions int [>= 7]"""
+    typ = int(actions[0])
+    out = [] if forced else [(None, 0, np.float32(r[0]), int(round(float(r[1]))), typ)]
+    h = _LOG_SPECIFIC_HEAD.get(typ)
+    if h is not None:
+        out.append((typ, h, np.float32(r[2]), int(round(float(r[3]))), int(actions[h])))
+    return out
 
 
 def build_agent_model(device="cpu", autocast_dtype="auto", include_lstm=False):
@@ -798,6 +845,90 @@ class SubProcEvaluationManager(object):
         for p in range(len(self.processes)):
             sl = slice(p * eps, (p + 1) * eps)
             out.append((list(res["winner"][sl]), list(res["game_steps"][sl]), list(res["victory_points"][sl]), list(res["policy_decisions"][sl])))
+        return out
+
+    def close(self):
+        self.closed = True
+
+
+# ------------------------------------------------------------------------------------------------ offline evaluator
+def make_offline_evaluation_manager():
+    return "offline-evaluation-manager"  # placeholder thunk: OfflineEvaluationManager only counts them
+
+
+OFFLINE_DRAW_CAP = 2500              # evaluation/evaluation_manager.py:119: `if total_game_steps > 2500: DRAW`
+
+
+class OfflineEvaluationManager(object):
+    """evaluation/vec_evaluation.py:86-139 (the offline evaluator's SubProcEvaluationManager, not the in-training one above)
+    over `evaluation.run_evaluation_episodes(stats=True)`: a pool of checkpoints, and per call ALL episodes of all stub
+    "processes" at once on one batched env with the 2 500-step draw cap; policy 0's entropy, value, action types and
+    (type, joint log-prob) tuples are tallied on the device.  Results come back per process in the worker's layout
+    (:81-83): (winners, game_steps, victory_points, policy_decisions, entropies, action_types dict, type log-prob tuple
+    lists, values[, detailed head logs]).  In random mode (opponent_ids None) the games hold one forward per distinct
+    checkpoint in play per env pass."""
+
+    def __init__(self, evaluation_manager_fns, start_method=None, *, device=_UNSET, seed=_UNSET, env_factory=_UNSET, make_policy=_UNSET,
+                 autocast_dtype=_UNSET, env_kwargs=_UNSET, results_dir="../RL/results"):
+        device, seed, env_factory = _default("device", device), _default("seed", seed), _default("eval_env_factory", env_factory)
+        make_policy, autocast_dtype = _default("make_policy", make_policy), _default("autocast_dtype", autocast_dtype)
+        self._board_config = (_default("env_kwargs", env_kwargs) or {}).get("board_config")
+        self.processes = [_ProcessStub() for _ in evaluation_manager_fns]
+        self.waiting, self.closed = False, False
+        self._device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+        self._seed, self._env_factory = seed, env_factory
+        self._make_policy = make_policy or CatanPolicy
+        self._autocast = autocast_dtype
+        self._results_dir = results_dir
+        self._pool = {}
+        self.detailed_logging = False
+        self._calls = 0
+
+    def initialise_policy_pool(self, policy_ids, detailed_logging=False):
+        """vec_evaluation.py:24-31: loads ../RL/results/default_after_update_{id}.pt (relative to the cwd) for every id"""
+        import os
+        for pid in policy_ids:
+            sd = torch.load(os.path.join(self._results_dir, "default_after_update_" + str(pid) + ".pt"), map_location="cpu")
+            net = self._make_policy().to(self._device).eval()
+            net.load_reference_state_dict(sd)
+            self._pool[pid] = net
+        self.detailed_logging = bool(detailed_logging)
+        return [True] * len(self.processes)
+
+    def run_evaluation_episodes(self, num_episodes, player_id, opponent_ids):
+        import random
+        from . import evaluation
+        n = int(num_episodes) * len(self.processes)
+        pool_ids = list(self._pool)
+        if opponent_ids is None:                 # vec_evaluation.py:59-61: three opponents per episode from the whole pool
+            opp = [[random.choice(pool_ids) for _ in range(3)] for _ in range(n)]
+        else:
+            opp = [list(opponent_ids)] * n
+        ids = sorted(set([player_id] + [o for row in opp for o in row]))
+        where = {pid: i for i, pid in enumerate(ids)}
+        assignment = np.array([[where[player_id]] + [where[o] for o in row] for row in opp], dtype=np.int64)
+        if self._env_factory is None:
+            from .env import VecCatanEnv
+            env = VecCatanEnv(n, seed=self._seed + 7919 * (self._calls + 1), auto_reset=False, device=self._device,
+                              board_config=self._board_config)
+        else:
+            env = self._env_factory(n)
+        self._calls += 1
+        ac = self._autocast
+        if ac == "auto":
+            ac = torch.bfloat16 if torch.device(env.device).type == "cuda" else None
+        res = evaluation.run_evaluation_episodes(env, [self._pool[i] for i in ids], evaluation.sample_orders(n), max_steps=OFFLINE_DRAW_CAP,
+                                                 autocast_dtype=ac, assignment=assignment, stats=True, detailed=self.detailed_logging)
+        out = []
+        for p in range(len(self.processes)):
+            sl = slice(p * num_episodes, (p + 1) * num_episodes)
+            counts = res["action_types"][sl].sum(0)
+            types = {int(t): int(c) for t, c in enumerate(counts) if c}
+            row = (list(res["winner"][sl]), list(res["game_steps"][sl]), list(res["victory_points"][sl]), list(res["policy_decisions"][sl]),
+                   list(res["entropy"][sl]), types, res["type_log_probs"][sl], list(res["value"][sl]))
+            if self.detailed_logging:
+                row = row + (res["head_logs"][sl],)
+            out.append(row)
         return out
 
     def close(self):
