@@ -279,7 +279,8 @@ int64_t catan_inconsistent_deal_count(catan_env_t* env, catan_stream_t stream);
  *   catan_hip_nn.h      the policy net's hand-written kernels (RL/models: attention, LayerNorm, tall-skinny linears, the
  *                       tile encoder, the action heads, the dev-card modules, the LSTM cell, the masked categorical)
  *   catan_hip_tuning.h  scheduling knobs, counters and profilers of the env kernels (benchmarks and diagnostics only), and
- *                       catan_longest_path, the diagnostic entry to the longest-road search */
+ *                       catan_longest_path, the diagnostic entry to the longest-road search, and catan_state_fork (search support:
+ *                       games copied from one handle into another on the device, what export -> import does through the blob) */
 
 
 #ifdef __cplusplus

@@ -1,7 +1,7 @@
 /*
  * catan_hip_tuning.h - scheduling knobs, counters and profilers of the env kernels in libcatan_hip.so.  Benchmarks, sweeps and
  * diagnostics only (bench.py, tools): results never depend on any of them, and nothing a reference-side binding needs is
- * declared here (that is catan_hip.h).
+ * declared here (that is catan_hip.h).  One section is no knob: "search support" (catan_state_fork), which the forward search uses.
  */
 #ifndef CATAN_HIP_TUNING_H
 #define CATAN_HIP_TUNING_H
@@ -26,6 +26,23 @@ int catan_set_lr_rounds(catan_env_t* env, int32_t lockstep, int32_t deferred);
 /* Game.get_longest_path(player): game/game.py:843-862 for players[i] (PlayerId) in game i -> out[i].  Diagnostic/test
  * entry; inside catan_step the same search runs as part of update_longest_road. */
 int catan_longest_path(catan_env_t* env, const int32_t* players, int32_t* out, catan_stream_t stream);
+
+/* ---- search support ----
+ * dst game dst_idx[j] (NULL: game j) becomes a copy of src game src_idx[j], j < cnt.  The game stream's draw counter of the copy is the
+ * source's plus draw_offset[j] modulo 2^32 (NULL: unchanged).  The destination's packed masks are valid when the call returns.
+ * Equal BY DEFINITION to catan_state_export(src, src_idx) -> add draw_offset to the blob's rng_draws word -> catan_state_import(dst, dst_idx):
+ * EnvWrapper.save_state() / restore_state(), env/wrapper.py:711-721, between two envs.
+ * src_idx, dst_idx and draw_offset are DEVICE arrays.  A source game may appear any number of times (K simulations of one root: consecutive j
+ * read the same lines).  The SAME destination id twice in one call is undefined: the copies race.  Ids are not validated on the host;
+ * an entry whose source or destination id lies outside its handle copies nothing.
+ * Each handle keeps its own configuration (catan_cfg_t, board-layout table); only the game moves: the 704-byte packed record as it is -
+ * the longest-path cache included, which an import would invalidate and recompute to the same values - and the 44 bytes of packed masks
+ * (recomputed instead when the two handles' max_proposed_trades_per_turn / max_actions_per_turn differ).  The rest of the destination's
+ * side row is left as catan_state_import leaves it.
+ * CATAN_EINVAL, nothing launched: a null handle or src_idx, cnt <= 0, cnt > n of dst with dst_idx NULL, dst == src, handles on different
+ * devices, an open deferred sequence on either handle, a handle under the MT19937 contract on either side. */
+int catan_state_fork(catan_env_t* dst, const catan_env_t* src, const int64_t* src_idx, const int64_t* dst_idx,
+                     const uint32_t* draw_offset, int64_t cnt, catan_stream_t stream);
 
 /* the rollout loops with a hipEvent around every kernel launch (recorded on the stream the kernel runs on); window <= 0: the
  * lock-step loop (step_idx0 as in catan_random_rollout), window > 0: the deferred loop (step_idx0 ignored).  kernel_ms is a HOST

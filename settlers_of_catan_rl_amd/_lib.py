@@ -238,6 +238,7 @@ _SIGS = {
     "catan_sample_random_actions": (C.c_int, [_vp, C.c_uint32, _vp, _vp]),
     "catan_state_export": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
     "catan_state_import": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
+    "catan_state_fork": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "catan_set_reward_annealing": (C.c_int, [_vp, C.c_double]),
     "catan_set_reward_f64_buffer": (C.c_int, [_vp, _vp]),
     "catan_invalid_action_count": (C.c_int64, [_vp, _vp]),

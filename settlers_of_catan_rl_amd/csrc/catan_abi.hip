@@ -930,6 +930,28 @@ int catan_state_import(catan_env_t* e, const int32_t* blob, const int64_t* env_i
     return launch_masks(e, S(stream));
 }
 
+int catan_state_fork(catan_env_t* dst, const catan_env_t* src, const int64_t* src_idx, const int64_t* dst_idx, const uint32_t* draw_offset,
+                     int64_t cnt, catan_stream_t stream) {
+    if (!dst || !src || !src_idx || cnt <= 0 || (!dst_idx && cnt > dst->n)) return fail(CATAN_EINVAL, "catan_state_fork: bad arguments");
+    if (dst == src) return fail(CATAN_EINVAL, "catan_state_fork: the two handles are the same (a fork inside one handle is not supported)");
+    if (dst->device != src->device) return fail(CATAN_EINVAL, "catan_state_fork: the handles live on different devices");
+    NOT_DEFERRED(dst, "catan_state_fork");
+    NOT_DEFERRED(src, "catan_state_fork");
+    NOT_MT(dst, "catan_state_fork");
+    NOT_MT(src, "catan_state_fork");
+    // the packed masks depend on the state and on two limits of the handle's configuration: equal limits -> the source's words are the destination's
+    const Limits ls = limits_of(src), ld = limits_of(dst);
+    const int copy_masks = ls.max_trades == ld.max_trades && ls.max_actions == ld.max_actions;
+    hipLaunchKernelGGL(k_fork, dim3(blocks(cnt * FORK_SLOTS, BLOCK)), dim3(BLOCK), 0, S(stream), dst->ctx, dst->mpk, src->ctx, (const u32*)src->mpk,
+                       (const long*)src_idx, (const long*)dst_idx, (const u32*)draw_offset, (long)cnt, copy_masks);
+    HIPCHK(hipGetLastError());
+    if (!copy_masks) {
+        hipLaunchKernelGGL(k_masks_of_list, dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, S(stream), dst->ctx, dst->mpk, ld, (const long*)dst_idx, (long)cnt);
+        HIPCHK(hipGetLastError());
+    }
+    return CATAN_OK;
+}
+
 int catan_set_reward_f64_buffer(catan_env_t* e, double* reward64) {
     if (!e) return fail(CATAN_EINVAL, "catan_set_reward_f64_buffer: null handle");
     e->reward64 = reward64;

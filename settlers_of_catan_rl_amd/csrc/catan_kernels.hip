@@ -3414,6 +3414,53 @@ __global__ __launch_bounds__(BLOCK) void k_import(Ctx c, const long* __restrict_
     lc.store(s.P);
 }
 
+// ------------------------------------------------------------------------------------------------ fork (search support)
+// catan_state_fork: dst game dst_idx[j] (null: j) becomes a copy of src game src_idx[j]; its draw counter is the source's plus off[j].
+// A plain bandwidth kernel: the record is 44 x 16 B and the packed masks are the first 44 B of the side row, so a copy is FORK_SLOTS = 48
+// lane slots (slot q < 44: chunk q of the record, 44 / 45: mask words 0..3 / 4..7, 46: mask words 8..10, 47: idle) and a wave holds one
+// and a third copies (four games per three waves).  Every load and store of the record is one aligned global_load / global_store_dwordx4;
+// the further copies of a root read lines the first copy brought into L2.  The rest of the destination's side row (the deferred loops'
+// next action, decision counter and shadow tag) stays as it is, which is how k_import + k_masks leave it.
+// With `copy_masks` off (the handles' mask limits differ) the mask words are left to k_masks_of_list below.
+constexpr int FORK_SLOTS = 48, FORK_REC_CHUNKS = REC / 4;
+static_assert(REC % 4 == 0 && FORK_REC_CHUNKS == 44 && W_RNG / 4 == 16 && W_RNG % 4 == 0 && MASK_WORDS == 11 && FORK_REC_CHUNKS + 3 <= FORK_SLOTS &&
+              MPK_STRIDE % 4 == 0 && MASK_WORDS <= ROW_ACT && MASK_WORDS > 8,
+              "k_fork's chunk map follows the record and side-row layouts (16-byte side rows whose words 0 .. MASK_WORDS-1 are the masks)");
+__global__ __launch_bounds__(BLOCK) void k_fork(Ctx d, u32* __restrict__ dmpk, Ctx s, const u32* __restrict__ smpk, const long* __restrict__ sidx,
+                                                const long* __restrict__ didx, const u32* __restrict__ off, long cnt, int copy_masks) {
+    const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+    const long j = i / FORK_SLOTS;
+    const int q = (int)(i - j * FORK_SLOTS);
+    if (j >= cnt) return;
+    const long se = sidx[j], de = didx ? didx[j] : j;
+    if (se < 0 || se >= s.n || de < 0 || de >= d.n) return;          // ids outside either handle copy nothing
+    if (q < FORK_REC_CHUNKS) {
+        const uint4 v = reinterpret_cast<const uint4*>(s.R + se * REC)[q];
+        u32 x = v.x;
+        if (q == W_RNG / 4 && off) x += off[j];                      // modulo 2^32
+        reinterpret_cast<uint4*>(d.R + de * REC)[q] = make_uint4(x, v.y, v.z, v.w);
+    } else if (copy_masks && q < FORK_REC_CHUNKS + 2) {
+        reinterpret_cast<uint4*>(dmpk + de * MPK_STRIDE)[q - FORK_REC_CHUNKS] = reinterpret_cast<const uint4*>(smpk + se * MPK_STRIDE)[q - FORK_REC_CHUNKS];
+    } else if (copy_masks && q == FORK_REC_CHUNKS + 2) {
+        const u32* i3 = smpk + se * MPK_STRIDE + 8;                  // words 8..10; word 11 of the row is not a mask word
+        u32* o3 = dmpk + de * MPK_STRIDE + 8;
+        const u32 a = i3[0], b = i3[1], c = i3[2];
+        o3[0] = a; o3[1] = b; o3[2] = c;
+    }
+}
+// the masks of the games idx[j] (null: j) under this handle's limits: the fork between handles whose limits differ
+__global__ __launch_bounds__(BLOCK) void k_masks_of_list(Ctx c, u32* __restrict__ mpk, Limits lim, const long* __restrict__ idx, long cnt) {
+    const long j = (long)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= cnt) return;
+    const long e = idx ? idx[j] : j;
+    if (e < 0 || e >= c.n) return;
+    St s(c.R, c.N, e);
+    u32 m[MASK_WORDS];
+    compute_masks(s, m, lim);
+#pragma unroll
+    for (int i = 0; i < MASK_WORDS; i++) mpk[e * MPK_STRIDE + i] = m[i];
+}
+
 // test/diagnostic entry: longest path of player players[i] (PlayerId 1..4) in game i, unbudgeted tier-1 search
 __global__ __launch_bounds__(64) void k_longest_path(Ctx c, const i32* __restrict__ players, i32* __restrict__ out) {
     __shared__ LrWave L;

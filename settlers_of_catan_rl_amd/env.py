@@ -37,6 +37,8 @@ def board_cfg_struct(cfg):
 
 
 class VecCatanEnv(object):
+    takes_game_lists = True      # export_state / import_state accept a list of game ids
+
     def __init__(self, num_envs, seed=0, env_id0=0, device=None, max_proposed_trades_per_turn=4, win_reward=500.0,
                  dense_reward=False, validate_actions=True, auto_reset=True, max_actions_per_turn=None, board_config=None,
                  board_config_index=None):
@@ -307,6 +309,23 @@ class VecCatanEnv(object):
             assert idx.numel() == cnt
         bt = b.t().contiguous()
         _lib.check(self.L.catan_state_import(self.h, _ptr(bt), _ptr(idx), cnt, _stream()))
+
+    def fork_from(self, src_env, src_idx, dst_idx=None, draw_offset=None):
+        """catan_state_fork (include/catan_hip_tuning.h): this env's game dst_idx[j] (None: game j) becomes a copy of src_env's game
+        src_idx[j]; draw_offset[j] (None: 0) is added to the copy's draw counter modulo 2^32.  What export_state -> an edit of the
+        rng_draws word -> import_state does, without the blobs.  The same destination id twice is undefined."""
+        si = torch.as_tensor(src_idx, dtype=torch.int64, device=self.device).contiguous()
+        cnt = si.numel()
+        di = off = None
+        if dst_idx is not None:
+            di = torch.as_tensor(dst_idx, dtype=torch.int64, device=self.device).contiguous()
+            assert di.numel() == cnt
+        if draw_offset is not None:
+            off = torch.as_tensor(draw_offset, device=self.device)
+            assert off.numel() == cnt
+            off = off.long() & 0xFFFFFFFF                                      # the low 32 bits, as the kernel reads them (uint32)
+            off = torch.where(off >= 2 ** 31, off - 2 ** 32, off).to(torch.int32).contiguous()
+        _lib.check(self.L.catan_state_fork(self.h, src_env.h, _ptr(si), _ptr(di), _ptr(off), cnt, _stream()))
 
     def get_obs(self, out=None):
         from . import obs as _obs

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import spec
+from .forward_search import export_games
 
 PLAYER_IDS = [2, 4, 3, 1]            # [Blue, Red, Orange, White] - the list the reference shuffles (evaluation_manager.py:27)
 
@@ -41,7 +42,7 @@ def _stats_of(res, rows, dev):
 
 @torch.no_grad()
 def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=False, generator=None, autocast_dtype=None,
-                            act_fn=None, assignment=None, stats=False, detailed=False):
+                            act_fn=None, assignment=None, stats=False, detailed=False, searchers=None):
     """env: freshly reset games, auto_reset off.  nets: the policies (entries may be the same object; equal objects share a
     forward); without `assignment` four of them, policy i = nets[i] in every game.  assignment int [n,4] (optional): game g's
     policy i is nets[assignment[g][i]] (the offline evaluator's opponents drawn per game).  orders int [n,4].  max_steps: the
@@ -52,7 +53,14 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
     stats: also, over policy 0's decisions (evaluation/evaluation_manager.py:44-134), tallied on the device inside the loop:
     entropy (per game: mean of the decisions' entropies; NaN without decisions), value (mean value), action_types (int [n, 13]
     counts), type_log_probs (per game: the list of (action type, joint log-prob) tuples); detailed: also head_logs (per game:
-    the log_specific_action_output tuples of all its decisions, reference_api.head_log_tuples)."""
+    the log_specific_action_output tuples of all its decisions, reference_api.head_log_tuples).
+    searchers {policy index: forward_search.ForwardSearch (n_roots >= n)}: that policy's decisions are searched
+    (evaluation/evaluation_manager.py:83-96).  In every pass the running games it decides are collected on the device and decided
+    by `searcher.act(env, games=idx, initial_settlement=flag, ...)`; `initial_settlement` is true when the deciding player has placed
+    no initial settlement, or one settlement and one road (:85-88).  A searched decision of policy 0 counts as a decision and its
+    action type is tallied; its entropy, log-prob and value are 0.0 (:94-96).  LSTM nets: the planner gets all four seats' states of
+    its games and returns its own next state (:90-93,108); `searcher.zero_opponent_hidden_states` and `searcher.max_thinking_time`
+    (attributes, optional) are passed on."""
     n, dev = env.n, env.device
     orders_t = torch.as_tensor(orders, device=dev).long()
     policy_of_pid = torch.empty((n, 4), dtype=torch.long, device=dev)
@@ -86,7 +94,10 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
     # LSTM policies: one (h, c) per seat, zero at the start of the game (evaluation_manager.py:20-26,50-59); a net without
     # an LSTM ignores its seats' entries.  The terminal mask stays 1: a finished evaluation game takes no further step.
     sizes = [int(net.lstm_size) for net in distinct if getattr(net, "include_lstm", False)]
+    searchers = {int(k): v for k, v in (searchers or {}).items()}
+    sizes += [int(sr.policy.lstm_size) for sr in searchers.values() if getattr(getattr(sr, "policy", None), "include_lstm", False)]
     hid = torch.zeros((2, n, 4, max(sizes)), dtype=torch.float32, device=dev) if sizes else None
+    off_is, _ = spec.STATE_OFFSETS["init_settlements"]; off_ir, _ = spec.STATE_OFFSETS["init_roads"]
     while bool(running.any()):
         deciding = env.deciding_player().long()
         pol = policy_of_pid[ar, deciding - 1]
@@ -97,8 +108,40 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
         if stats:
             ent_p = torch.zeros(n, device=dev); val_p = torch.zeros(n, device=dev); lp_p = torch.zeros(n, device=dev)
             rec_p = torch.zeros((n, 4), device=dev)
+        searched = torch.zeros(n, dtype=torch.bool, device=dev)
+        for p, sr in searchers.items():
+            idx = (running & (pol == p)).nonzero(as_tuple=True)[0]
+            if idx.numel() == 0:
+                continue
+            searched[idx] = True
+            seat = deciding[idx] - 1
+            blob = export_games(env, idx)        # (the whole 2 944-byte blob for two of its words per game: small beside a search)
+            ar_i = torch.arange(idx.numel(), device=dev)
+            n_set, n_road = blob[ar_i, off_is + seat], blob[ar_i, off_ir + seat]
+            flag = (n_set == 0) | ((n_set == 1) & (n_road == 1))                      # evaluation_manager.py:85-88
+            kw = {"games": idx, "initial_settlement": flag.cpu().numpy(), "deterministic": deterministic}
+            if getattr(sr, "max_thinking_time", None) is not None:
+                kw["max_thinking_time"] = sr.max_thinking_time
+            rec = bool(getattr(getattr(sr, "policy", None), "include_lstm", False))
+            if rec:
+                L = int(sr.policy.lstm_size)
+                zero = bool(getattr(sr, "zero_opponent_hidden_states", False))
+                kw.update(hidden=hid[:, idx, :, :L].clone(), zero_opponent_hidden_states=zero)
+                if zero:
+                    # The reference planner writes the zeros into the dict it was handed (policy.py:81-86), and that dict is the
+                    # manager's own current_hidden_states: the opponents' REAL states are wiped at every searched decision,
+                    # single-proposal decisions included (the zeroing precedes the shortcut at policy.py:89).  The planner's own
+                    # row is replaced by its next state below.
+                    own = torch.zeros((idx.numel(), 4), dtype=torch.bool, device=dev)
+                    own[ar_i, seat] = True
+                    hid[:, idx] = hid[:, idx] * own[None, :, :, None]
+            chosen, info = sr.act(env, **kw)
+            actions[idx] = torch.as_tensor(chosen, device=dev).long()
+            if rec:
+                nh = info["next_hidden"].to(dev).float()                              # [2, r, L] (:108)
+                hid[0, idx, seat, :L], hid[1, idx, seat, :L] = nh[0], nh[1]
         for k, net in enumerate(distinct):
-            idx = ((net_id == k) & running).nonzero(as_tuple=True)[0]
+            idx = ((net_id == k) & running & ~searched).nonzero(as_tuple=True)[0]
             if idx.numel() == 0:
                 continue
             args = (f[idx], lists[idx], lens[idx].long(), masks[idx])
@@ -197,3 +240,26 @@ def run_evaluation_protocol(make_env, central_policy, opponent_policy, num_eval_
                                                                num_eval_episodes, r["avg_game_length"], r["avg_policy_decisions"],
                                                                r["avg_victory_points"])
     return log, summary
+
+
+def run_forward_search_evaluation(planner, other_policies, num_games, make_env=None, make_sim_env=None, seed=10, deterministic=False,
+                                  out_file="forward_policy_evaluation.pt", max_steps=2500, autocast_dtype=None):
+    """evaluation/run_forward_search_evaluation.py: policy 0 is the planner (`reference_api.ForwardSearchPolicy`), the other
+    three seats are the nets `other_policies`; all num_games games run at once.  make_env(n) -> n freshly reset games without
+    auto-reset (default: VecCatanEnv on the planner's device).  Prints the fraction of games the planner won and saves the
+    reference's tuple (winners, game steps, victory points, planner decisions, sorted action-type counts) to out_file
+    (None: not saved).  -> the dict of run_evaluation_episodes(stats=True)."""
+    if make_env is None:
+        from .env import VecCatanEnv
+        make_env = lambda n: VecCatanEnv(n, seed=seed, auto_reset=False, device=planner._device)  # noqa: E731
+    env = make_env(num_games)
+    searcher = planner.make_searcher(num_games, make_sim_env)
+    res = run_evaluation_episodes(env, [planner.base_policy] + list(other_policies), sample_orders(num_games, _py_random.Random(seed)),
+                                  max_steps=max_steps, deterministic=deterministic, autocast_dtype=autocast_dtype, stats=True,
+                                  searchers={0: searcher})
+    print("{} games finished. Fraction of games won by forward search: {}".format(num_games, float(np.mean(res["winner"] == 0))))
+    if out_file is not None:
+        counts = res["action_types"].sum(0)
+        torch.save(([int(w) for w in res["winner"]], [int(x) for x in res["game_steps"]], [int(x) for x in res["victory_points"]],
+                    [int(x) for x in res["policy_decisions"]], sorted((int(t), int(c)) for t, c in enumerate(counts) if c)), out_file)
+    return res

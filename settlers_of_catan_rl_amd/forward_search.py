@@ -19,7 +19,8 @@ Here R root games are searched at once.  Every piece keeps the reference's arith
                          budget (the reference's own "deterministic testing" variant, policy.py:112) or the reference's
                          wall-clock budget per root (`max_thinking_time`, policy.py:91,111); LSTM policies carry every
                          seat's (h, c) through proposals and simulations (policy.py:72-106, worker.py:61-95).
-State broadcast = catan_state_export / catan_state_import; every simulation gets its own Philox substream.
+State broadcast = catan_state_fork (records copied on the device) or catan_state_export / catan_state_import; every simulation
+gets its own Philox substream.
 """
 import math
 import random as _py_random
@@ -34,6 +35,9 @@ PRIORITIES = [["settlement", "city", "move_robber", "steal", "discard"], ["road"
 TYPE_TO_IND = {"settlement": 0, "road": 1, "city": 2, "buy_dev": 3, "play_dev": 4, "exchange_res": 5, "prop_trade": 6,
                "respond_trade": 7, "move_robber": 8, "roll_dice": 9, "end_turn": 10, "steal": 11, "discard": 12}
 MO = spec.MASK_OFFSETS
+# "fork" may become the default only once tools/bench_state_fork.py has shown catan_state_fork not slower than the per-round blob
+# path on an MI355X (profiles/state_fork_bench.txt); that file does not exist yet, so the default is the path that was there before
+DEFAULT_STATE_BROADCAST = "blob"
 
 
 # ---------------------------------------------------------------------------------------------------- worker.gae
@@ -65,6 +69,7 @@ def gae_estimate(values, n_values, rewards, n_rewards, gamma, done, gae_lambda=0
 # ---------------------------------------------------------------------------------------------------- UCB bookkeeping
 class UCBStats(object):
     """policy.py:151-177 + utils.MovingAvgCalculator for R roots; root i has n_actions[i] proposed actions."""
+    PERSISTENT = ("window", "num_added", "avg", "var", "last_std")      # the moving average: what outlives a decision
 
     def __init__(self, n_roots, max_actions, window=500):
         R, A = n_roots, max_actions
@@ -80,6 +85,27 @@ class UCBStats(object):
         self.finished = np.zeros(self.R, dtype=np.int64)
         self.finished_each = np.zeros((self.R, self.A)); self.started_each = np.zeros((self.R, self.A))
         self.exploit = np.zeros((self.R, self.A))
+
+    def grow(self, n_roots):
+        """rows for roots up to n_roots - 1 (new ones start with an empty window)"""
+        if n_roots <= self.R:
+            return
+        new = UCBStats(n_roots - self.R, self.A, self.window_size)
+        for k in self.PERSISTENT:
+            setattr(self, k, np.concatenate((getattr(self, k), getattr(new, k))))
+        self.R = n_roots
+        self.new_decision(np.zeros(n_roots, dtype=np.int64))
+
+    def take(self, rows):
+        """-> the bookkeeping of the roots `rows` alone (copies), for one decision of theirs; `put` stores their moving averages back"""
+        sub = UCBStats(len(rows), self.A, self.window_size)
+        for k in self.PERSISTENT:
+            setattr(sub, k, getattr(self, k)[rows].copy())
+        return sub
+
+    def put(self, rows, sub):
+        for k in self.PERSISTENT:
+            getattr(self, k)[rows] = getattr(sub, k)
 
     def select(self, explore=True):
         """_select_action for every root (first best index wins ties, `score > best_score`)."""
@@ -210,8 +236,9 @@ class GraphedAct(object):
 # ---------------------------------------------------------------------------------------------------- simulations
 @torch.no_grad()
 def simulate(env, policy, ctrl, init_actions, max_depth=20, gamma=0.999, deterministic=False, generator=None, autocast_dtype=None,
-             graphed=None, hidden=None, init_hidden=None):
-    """run_simulation_forward (worker.py:61-114) for all env.n simulations in lock-step.  env: dense-reward, no auto-reset,
+             graphed=None, hidden=None, init_hidden=None, idle=None):
+    """run_simulation_forward (worker.py:61-114) for all env.n simulations in lock-step.  idle (bool [n], optional): rows that hold no
+    simulation - they take no step (action type -1 throughout), are in no policy pass, and their entry of the result means nothing.  env: dense-reward, no auto-reset,
     already holding the (randomised) start states; ctrl int [n] PlayerId of the searching player; init_actions [n,18].
     LSTM policies (`include_lstm`): hidden [2, n, 4, L] = every seat's (h, c) at the start state (`curr_hidden_states`),
     init_hidden [2, n, L] = the searching seat's state after it took the initial action (`init_player_hs`, worker.py:73); each
@@ -229,8 +256,15 @@ def simulate(env, policy, ctrl, init_actions, max_depth=20, gamma=0.999, determi
         buf[ar, c] = torch.where(sel, x.double(), buf[ar, c])
         cnt += sel.long()
 
-    reward, done = env.step(torch.as_tensor(init_actions, device=dev).to(torch.int32))      # worker.py:71
+    a0 = torch.as_tensor(init_actions, device=dev).to(torch.int32)
+    if idle is not None:
+        idle = torch.as_tensor(idle, device=dev).bool()
+        a0 = a0.clone()
+        a0[:, 0] = torch.where(idle, torch.full_like(a0[:, 0], -1), a0[:, 0])
+    reward, done = env.step(a0)                                                             # worker.py:71
     reward = reward.clone(); first_done = done.bool().clone()
+    if idle is not None:
+        first_done |= idle                                                                  # nothing to estimate for them
     push(rewards, n_rew, torch.ones(n, dtype=torch.bool, device=dev), reward[ar, ctrl - 1])
     agent_actions = torch.ones(n, dtype=torch.long, device=dev)
     active = ~first_done                                                                    # `if done: return actual_rewards[0]`
@@ -337,9 +371,10 @@ def _update_action_masks(action, m):
 @torch.no_grad()
 def propose_actions(policy, f, lists, lens, masks, max_actions=10, initial_settlement_phase=None,
                     consider_all_initial_settlements=False, rngs=None, deterministic=False, generator=None, autocast_dtype=None,
-                    hidden=None, return_hidden=False):
-    """default_sample_actions (sample_actions_fn.py:55-328, with dont_propose_devcards = dont_propose_trades = False) for R
-    roots.  f/lists/lens/masks: the roots' observations and masks (device tensors); rngs: one `random.Random` per root for
+                    hidden=None, return_hidden=False, dont_propose_devcards=False, dont_propose_trades=False):
+    """default_sample_actions (sample_actions_fn.py:55-328) for R roots.  dont_propose_devcards: no BuyDevelopmentCard proposal,
+    and where PlayDevelopmentCard is legal the previous proposal is listed a second time instead (:130,144-159: the reference's
+    append sits outside its `if`); dont_propose_trades: no ProposeTrade proposal (:178).  f/lists/lens/masks: the roots' observations and masks (device tensors); rngs: one `random.Random` per root for
     the procedure's random.choice calls.  hidden (LSTM policies): (h, c) [R, L] each, the deciding seat's state; every proposal
     is sampled from it, and the state after the decision - the same for all proposals of a root, the LSTM step precedes the
     action heads - is returned with return_hidden (`player_next_hidden_states`, sample_actions_fn.py).
@@ -417,6 +452,16 @@ def propose_actions(policy, f, lists, lens, masks, max_actions=10, initial_settl
         rows = np.flatnonzero(type_masks[:, t] == 1)
         if rows.size == 0:
             continue
+        if (dont_propose_devcards and t == 3) or (dont_propose_trades and t == 6):      # :130, :178 - no proposal, nothing counted
+            continue
+        if dont_propose_devcards and t == 4:
+            # :144-159: only the sampling is inside the `if`; the append below it runs again on the PREVIOUS proposal (a settlement,
+            # road or city: its second mask update changes nothing).  A root with no earlier proposal raises UnboundLocalError in the
+            # reference; here it gets no entry.
+            rows = rows[n_prop[rows] > 0]
+            if rows.size:
+                append(rows, props[rows, n_prop[rows] - 1])
+            continue
         if t in REFINABLE:
             c = counts_for(t, rows).astype(np.float64)
             avail[rows, t] = c
@@ -487,69 +532,143 @@ def propose_actions(policy, f, lists, lens, masks, max_actions=10, initial_settl
 
 # ---------------------------------------------------------------------------------------------------- the planner
 class ForwardSearch(object):
-    """ForwardSearchPolicy.act (policy.py:72-149) for all games of `root_env` at once, each searched by its deciding
-    player.  make_sim_env(n) -> an env of n games with dense rewards and no auto-reset (VecCatanEnv on the GPU)."""
+    """ForwardSearchPolicy.act (policy.py:72-149) for all games of `root_env` at once - or for a sub-list of them (`games`) -,
+    each searched by its deciding player.  make_sim_env(n) -> an env of n games with dense rewards and no auto-reset
+    (VecCatanEnv on the GPU).
+
+    state_broadcast: how a round's simulations get their start states.  "fork": catan_state_fork copies the packed records from
+    the root env into the simulation env on the device (env.fork_from); "blob": catan_state_export once per decision, one blob per
+    simulation, an edit of the draw-counter word and catan_state_import per round.  Both start every simulation from the same
+    state with the same substream (draw counter = the root's + (1 + round * K + k) << 22), so they give identical simulations;
+    an env without `fork_from` (the CPU test envs) always takes the blob path.
+
+    What is kept PER GAME ID of the root env, so that it follows a game from one decision to the next whichever games are searched
+    beside it: the Python `Random` of the proposals (`rngs`), the UCB counters and the value moving average (`stats`).
+    One difference from the reference cannot be removed: the reference plays its evaluation games one after the other with ONE
+    planner object, so `value_moving_average` (policy.py:47) carries over from game to game.  Here every game has a window of
+    its own that starts empty, which is what the reference's first game sees.
+    Simulation rows are handed out in ascending order of the game ids (rows j*K .. j*K+K-1 belong to the j-th smallest id), so the
+    order in which `games` lists them changes nothing.  The dice of a simulation come from the simulation env's stream of its row:
+    a game searched beside a different set of games may sit in another row and then sees other dice (the proposals, the UCB
+    bookkeeping and the moving average do not move).  This departs from "the result for a game does not depend on which other
+    games are searched beside it" and from "rows j*K .. belong to games[j]": the env's Philox streams are keyed by the handle's seed
+    and the row, so only a per-game stream id in the simulation env would remove it."""
 
     def __init__(self, policy, make_sim_env, n_roots, max_init_actions=10, max_depth=20, gamma=0.999, sims_per_root=64,
-                 sims_per_round=16, consider_all_moves_for_opening_placement=False, seed=0, autocast_dtype=None, use_graphs=False):
+                 sims_per_round=16, consider_all_moves_for_opening_placement=False, seed=0, autocast_dtype=None, use_graphs=False,
+                 state_broadcast=DEFAULT_STATE_BROADCAST, dont_propose_devcards=False, dont_propose_trades=False):
         assert sims_per_root % sims_per_round == 0
+        assert state_broadcast in ("fork", "blob"), state_broadcast
         if autocast_dtype is not None and hasattr(policy, "inference_copy") and getattr(policy, "_inference_dtype", None) is None:
             policy = policy.inference_copy(autocast_dtype)      # weights in the autocast dtype: no per-call casts
         self.policy, self.R = policy, n_roots
         self.max_init_actions, self.max_depth, self.gamma = max_init_actions, max_depth, gamma
         self.S, self.K = sims_per_root, sims_per_round
         self.consider_all = consider_all_moves_for_opening_placement
+        self.dont_propose_devcards, self.dont_propose_trades = bool(dont_propose_devcards), bool(dont_propose_trades)
+        self.state_broadcast = state_broadcast
         self.sim_env = make_sim_env(n_roots * sims_per_round)
         self.stats = UCBStats(n_roots, 54 if consider_all_moves_for_opening_placement else max_init_actions)
-        self.rngs = [_py_random.Random(seed * 1000003 + i) for i in range(n_roots)]
+        self.seed = seed
+        self.rngs = [_py_random.Random(seed * 1000003 + i) for i in range(n_roots)]       # indexed by game id (grown on demand)
         self.gen = None
         self.autocast_dtype = autocast_dtype
-        if torch.cuda.is_available() and next(policy.parameters()).is_cuda:
+        params = getattr(policy, "parameters", None)
+        if torch.cuda.is_available() and params is not None and next(params()).is_cuda:
             from . import nn_kernels
             nn_kernels.use_tuned_gemms()
         self.graphed = GraphedAct(policy, buckets=(512, 4096, 16384, 32768, 49152, 65536), autocast_dtype=autocast_dtype) if use_graphs else None
         self.sims_run = 0
         self._rng_word = spec.STATE_OFFSETS["rng_draws"][0]
 
+    def _per_game(self, n_games):
+        """the per-game-id state covers game ids 0 .. n_games-1"""
+        while len(self.rngs) < n_games:
+            self.rngs.append(_py_random.Random(self.seed * 1000003 + len(self.rngs)))
+        self.stats.grow(n_games)
+
     @torch.no_grad()
     def act(self, root_env, initial_settlement=None, deterministic=False, hidden=None, zero_opponent_hidden_states=False,
-            max_thinking_time=None):
+            max_thinking_time=None, games=None):
         """-> (actions int64 numpy [R,18], info dict).  Roots with a single proposal skip the search (policy.py:88-89).
+        games (device int64 [r], r <= n_roots, distinct ids into root_env, which may then hold more than n_roots games): only these
+        games are searched; every per-root argument (initial_settlement, hidden) and every returned array then has r rows, in the
+        order of `games`.  Simulation rows beyond r*K idle.
         LSTM policies: hidden [2, R, 4, L] = the (h, c) of every seat of every root (`curr_hidden_states`, policy.py:72; zeros if
         omitted); proposals and simulations run from them as the reference's do (:73-86, worker.py:61-95), and
         info["next_hidden"] [2, R, L] is the searching seat's state after its decision (`player_next_hidden_states`).
         max_thinking_time (seconds; None = the fixed budget of `sims_per_root`): the reference's wall-clock budget
         (policy.py:91,112-138): root r thinks for max_thinking_time * n_proposed[r] / max_init_actions; rounds of K simulations
         per root are run until the longest of those budgets is spent, and a root stops taking results once its own is."""
-        R, K = self.R, self.K
-        assert root_env.n == R
+        K = self.K
+        dev = root_env.device
+        if games is None:
+            assert root_env.n == self.R
+            R = self.R
+            ids = np.arange(R)
+            pos = None
+            gsel = None
+        else:
+            g_host = torch.as_tensor(games).cpu().numpy().astype(np.int64).reshape(-1)
+            R = int(g_host.size)
+            assert 0 < R <= self.R and np.unique(g_host).size == R and g_host.min() >= 0 and g_host.max() < root_env.n
+            order = np.argsort(g_host, kind="stable")
+            ids = g_host[order]                                                     # ascending game ids: the order of the simulation rows
+            pos = np.empty(R, dtype=np.int64); pos[order] = np.arange(R)            # row of games[j] in that order
+            gsel = torch.from_numpy(ids).to(dev)
+            order_t = torch.from_numpy(order).to(dev)
+            if initial_settlement is not None:
+                initial_settlement = np.asarray(torch.as_tensor(initial_settlement).cpu().numpy() if torch.is_tensor(initial_settlement)
+                                                else initial_settlement, dtype=bool)[order]
+            if hidden is not None:
+                hidden = hidden.to(dev)[:, order_t]
+        self._per_game(int(ids.max()) + 1)
+        stats = self.stats if games is None else self.stats.take(ids)
+        rngs = self.rngs if games is None else [self.rngs[g] for g in ids]
+        n_sim = self.sim_env.n
+        live_rows = R * K
         ctrl = root_env.deciding_player().long()
         f, lists, lens = root_env.get_obs()
         masks = root_env.get_action_masks()
+        if gsel is not None:
+            ctrl, f, lists, lens, masks = ctrl[gsel], f[gsel], lists[gsel], lens[gsel], masks[gsel]
         rec = bool(getattr(self.policy, "include_lstm", False))
         hid_sim = init_sim = next_hidden = None
         if rec:
             Lh = int(self.policy.lstm_size)
-            hidden = torch.zeros((2, R, 4, Lh), device=root_env.device) if hidden is None else hidden.to(root_env.device).float()
-            ar_r = torch.arange(R, device=root_env.device)
+            hidden = torch.zeros((2, R, 4, Lh), device=dev) if hidden is None else hidden.to(dev).float()
+            ar_r = torch.arange(R, device=dev)
             own = (hidden[0, ar_r, ctrl - 1], hidden[1, ar_r, ctrl - 1])
         props, counts, nh = propose_actions(self.policy, f, lists, lens, masks, self.max_init_actions, initial_settlement, self.consider_all,
-                                            self.rngs, deterministic, self.gen, self.autocast_dtype, hidden=own if rec else None, return_hidden=True)
+                                            rngs, deterministic, self.gen, self.autocast_dtype, hidden=own if rec else None, return_hidden=True,
+                                            dont_propose_devcards=self.dont_propose_devcards, dont_propose_trades=self.dont_propose_trades)
+        pad = n_sim - live_rows                                                     # idle simulation rows
         if rec:
             next_hidden = torch.stack(nh)                                           # [2, R, L]
             if zero_opponent_hidden_states:                                         # policy.py:81-86
-                keep = torch.zeros((R, 4), dtype=torch.bool, device=root_env.device)
+                keep = torch.zeros((R, 4), dtype=torch.bool, device=dev)
                 keep[ar_r, ctrl - 1] = True
                 hidden = hidden * keep[None, :, :, None]
             hid_sim = hidden.repeat_interleave(K, dim=1)
             init_sim = next_hidden.repeat_interleave(K, dim=1)
-        self.stats.new_decision(counts)
-        blobs = root_env.export_state()                                             # [R, 736] int32 (state broadcast)
-        blobs = blobs.repeat_interleave(K, dim=0).clone()
+            if pad:
+                hid_sim = torch.cat((hid_sim, hid_sim.new_zeros((2, pad, 4, Lh))), 1)
+                init_sim = torch.cat((init_sim, init_sim.new_zeros((2, pad, Lh))), 1)
+        stats.new_decision(counts)
+        use_fork = self.state_broadcast == "fork" and hasattr(self.sim_env, "fork_from") and hasattr(root_env, "fork_from")
+        ar_sim = torch.arange(live_rows, device=dev)
+        if use_fork:
+            src_rows = (ar_sim // K) if gsel is None else gsel.repeat_interleave(K)
+        else:
+            blobs = export_games(root_env, gsel)                                   # [R, 736] int32 (state broadcast)
+            blobs = blobs.repeat_interleave(K, dim=0).clone()
+            base_draws = blobs[:, self._rng_word].long() & 0xFFFFFFFF
         ctrl_sim = ctrl.repeat_interleave(K)
-        base_draws = blobs[:, self._rng_word].long() & 0xFFFFFFFF
-        props_t = torch.from_numpy(props).to(root_env.device)
-        ar_sim = torch.arange(R * K, device=root_env.device)
+        idle = None
+        if pad:
+            ctrl_sim = torch.cat((ctrl_sim, ctrl_sim.new_zeros(pad)))               # 0: randomise_uncertainty leaves the row alone
+            idle = torch.arange(n_sim, device=dev) >= live_rows
+        props_t = torch.from_numpy(props).to(dev)
         import time as _time
         t_start = _time.perf_counter()
         think = None if max_thinking_time is None else max_thinking_time * (counts / float(self.max_init_actions))      # policy.py:91
@@ -564,25 +683,58 @@ class ForwardSearch(object):
                 thinking = (_time.perf_counter() - t_start) < think                 # `while elapsed_time < thinking_time`
                 if not thinking.any():
                     break
-            ids = np.zeros((R, K), dtype=np.int64)
+            sel_ids = np.zeros((R, K), dtype=np.int64)
             for k in range(K):                                                      # one simulation after the other (:118-125)
-                a = self.stats.select(explore=True)
-                self.stats.start(a, np.flatnonzero(thinking))
-                ids[:, k] = a
+                a = stats.select(explore=True)
+                stats.start(a, np.flatnonzero(thinking))
+                sel_ids[:, k] = a
             # every simulation its own philox substream: offset the game stream's draw counter by a large stride
-            sub = (base_draws + (1 + rnd * K + (ar_sim % K)) * (1 << 22)) & 0xFFFFFFFF
-            blobs[:, self._rng_word] = torch.where(sub >= 2 ** 31, sub - 2 ** 32, sub).to(torch.int32)
-            self.sim_env.import_state(blobs)                                        # worker.py:44-45
+            stride = ((1 + rnd * K + (ar_sim % K)) * (1 << 22)) & 0xFFFFFFFF
+            if use_fork:
+                self.sim_env.fork_from(root_env, src_rows, None, stride)            # worker.py:44-45, on the device
+            else:
+                sub = (base_draws + stride) & 0xFFFFFFFF
+                blobs[:, self._rng_word] = torch.where(sub >= 2 ** 31, sub - 2 ** 32, sub).to(torch.int32)
+                import_rows(self.sim_env, blobs)                                   # worker.py:44-45
             self.sim_env.randomise_uncertainty(ctrl_sim)                            # :46
-            init = props_t[torch.arange(R, device=props_t.device).repeat_interleave(K), torch.from_numpy(ids.reshape(-1)).to(props_t.device)]
+            init = props_t[torch.arange(R, device=dev).repeat_interleave(K), torch.from_numpy(sel_ids.reshape(-1)).to(dev)]
+            if pad:
+                init = torch.cat((init, init.new_zeros((pad, init.shape[1]))))
             vals = simulate(self.sim_env, self.policy, ctrl_sim, init, self.max_depth, self.gamma, deterministic, self.gen,
-                            self.autocast_dtype, None if deterministic else self.graphed, hidden=hid_sim, init_hidden=init_sim).reshape(R, K)
+                            self.autocast_dtype, None if deterministic else self.graphed, hidden=hid_sim, init_hidden=init_sim,
+                            idle=idle)[:live_rows].reshape(R, K)
             rows = np.flatnonzero(thinking)
             for k in range(K):
-                self.stats.update(vals[rows, k], ids[rows, k], rows)
+                stats.update(vals[rows, k], sel_ids[rows, k], rows)
             self.sims_run += int(rows.size) * K
-        best = self.stats.select(explore=False)
+        best = stats.select(explore=False)
         best = np.where(counts == 1, 0, best)
         chosen = props[np.arange(R), best]
-        return chosen, {"n_proposed": counts, "best": best, "finished_each": self.stats.finished_each.copy(),
-                        "mean_value": self.stats.exploit / np.maximum(self.stats.finished_each, 1), "next_hidden": next_hidden}
+        info = {"n_proposed": counts, "best": best, "finished_each": stats.finished_each.copy(),
+                "mean_value": stats.exploit / np.maximum(stats.finished_each, 1), "next_hidden": next_hidden}
+        if games is not None:
+            self.stats.put(ids, stats)
+            chosen = chosen[pos]
+            info = {k: (None if v is None else (v[:, torch.from_numpy(pos).to(v.device)] if torch.is_tensor(v) else v[pos])) for k, v in info.items()}
+        return chosen, info
+
+
+def export_games(env, games):
+    """the canonical blobs of the games `games` (device int64; None: all) of a device env or a CPU test env"""
+    if games is None:
+        return env.export_state()
+    if getattr(env, "takes_game_lists", False):                                     # export_state(env_idx) / import_state(blobs, env_idx)
+        return env.export_state(games)
+    return env.export_state()[games]
+
+
+def import_rows(env, blobs):
+    """blobs [m, 736] into the first m games of `env` (m <= env.n); the other games keep their states"""
+    if blobs.shape[0] == env.n:
+        env.import_state(blobs)
+    elif getattr(env, "takes_game_lists", False):
+        env.import_state(blobs, torch.arange(blobs.shape[0], device=blobs.device))
+    else:                                                                           # an env that only imports all of its games
+        full = env.export_state().clone()
+        full[:blobs.shape[0]] = blobs
+        env.import_state(full)

@@ -86,6 +86,8 @@ def install(**defaults):
         # the offline evaluator (evaluation/run_evaluations.py:8-9)
         "evaluation.evaluation_manager": (("make_evaluation_manager", "make_offline_evaluation_manager"),),
         "evaluation.vec_evaluation": (("SubProcEvaluationManager", "OfflineEvaluationManager"),),
+        # the planner of evaluation/run_forward_search_evaluation.py:10
+        "RL.forward_search_policy.policy": ("ForwardSearchPolicy",),
     }
     if "evaluation" not in sys.modules:
         try:
@@ -933,6 +935,68 @@ class OfflineEvaluationManager(object):
 
     def close(self):
         self.closed = True
+
+
+# ------------------------------------------------------------------------------------------------ the planner as a policy
+class ForwardSearchPolicy(object):
+    """RL/forward_search_policy/policy.py:17-21: the planner's constructor signature and `policy_type`, over
+    `forward_search.ForwardSearch`.  There are no worker processes: `num_subprocesses` and `subprocess_start_method` are accepted
+    and ignored, and `sample_actions_fn` is always `forward_search.propose_actions` (the restated default_sample_actions).
+    base_policy_state_dict: a reference state dict, or a CatanPolicy.  Extension keywords: sims_per_root (a fixed number of
+    simulations per decision; None keeps the reference's wall-clock rule with `max_thinking_time` seconds), sims_per_round,
+    state_broadcast, and the device / seed / make_policy / autocast_dtype extras of the managers above.
+    The object holds the settings and the base net; `make_searcher(n_games)` builds the batched planner that
+    `evaluation.run_evaluation_episodes(searchers={0: ...})` calls, with one simulation env of n_games * sims_per_round games."""
+    policy_type = "forward_search"
+
+    def __init__(self, base_policy_state_dict, sample_actions_fn=None, max_init_actions=10, max_depth=20, max_thinking_time=10, gamma=0.999,
+                 num_subprocesses=11, subprocess_start_method=None, player_id=None, zero_opponent_hidden_states=True,
+                 consider_all_moves_for_opening_placement=False, dont_propose_devcards=False, dont_propose_trades=False, lstm_size=256, *,
+                 sims_per_root=None, sims_per_round=16, state_broadcast=None, device=_UNSET, seed=_UNSET, make_policy=_UNSET,
+                 autocast_dtype=_UNSET):
+        device = _default("device", device)
+        self._device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+        self._seed, self._autocast = _default("seed", seed), _default("autocast_dtype", autocast_dtype)
+        if isinstance(base_policy_state_dict, dict):
+            net = (_default("make_policy", make_policy) or CatanPolicy)().to(self._device).eval()
+            net.load_reference_state_dict(base_policy_state_dict)
+        else:
+            net = base_policy_state_dict
+        self.base_policy = net
+        self.player_id, self.lstm_size = player_id, lstm_size
+        self.dummy_param = torch.empty(size=(1,), device="cpu")
+        self.consider_all_moves_for_opening_placement = bool(consider_all_moves_for_opening_placement)
+        self.dont_propose_devcards, self.dont_propose_trades = bool(dont_propose_devcards), bool(dont_propose_trades)
+        self.zero_opponent_hidden_states = bool(zero_opponent_hidden_states)
+        self.max_init_actions, self.max_depth, self.max_thinking_time, self.gamma = max_init_actions, max_depth, max_thinking_time, gamma
+        self.num_subprocesses = num_subprocesses
+        self.sims_per_root, self.sims_per_round, self.state_broadcast = sims_per_root, int(sims_per_round), state_broadcast
+
+    def initialise_policy(self):
+        pass
+
+    def eval(self):
+        return self
+
+    def make_searcher(self, n_games, make_sim_env=None):
+        """-> forward_search.ForwardSearch for n_games evaluation games; make_sim_env(n) -> dense-reward env without auto-reset
+        (default: VecCatanEnv on this object's device)"""
+        from . import forward_search as fs
+        if make_sim_env is None:
+            from .env import VecCatanEnv
+            make_sim_env = lambda n: VecCatanEnv(n, seed=self._seed + 104729, dense_reward=True, auto_reset=False, device=self._device)  # noqa: E731
+        ac = self._autocast
+        if ac == "auto":
+            ac = torch.bfloat16 if self._device.type == "cuda" else None
+        K = self.sims_per_round
+        kw = {} if self.state_broadcast is None else {"state_broadcast": self.state_broadcast}
+        sr = fs.ForwardSearch(self.base_policy, make_sim_env, n_games, self.max_init_actions, self.max_depth, self.gamma,
+                              sims_per_root=self.sims_per_root if self.sims_per_root is not None else K, sims_per_round=K,
+                              consider_all_moves_for_opening_placement=self.consider_all_moves_for_opening_placement, seed=self._seed,
+                              autocast_dtype=ac, dont_propose_devcards=self.dont_propose_devcards, dont_propose_trades=self.dont_propose_trades, **kw)
+        sr.zero_opponent_hidden_states = self.zero_opponent_hidden_states
+        sr.max_thinking_time = None if self.sims_per_root is not None else self.max_thinking_time
+        return sr
 
 
 def run_evaluation_protocol(evaluation_manager, central_policy, earlier_policies, random_policy, args, update_num, *_ignored):
