@@ -89,20 +89,20 @@ int32_t catan_step_fused_algorithmic_bytes(void);
 int catan_set_deferred_fused(catan_env_t* env, int32_t on);
 int32_t catan_deferred_fused(const catan_env_t* env);
 
-/* Environment switches read at catan_create (A/B diagnostics of the schedules; results never depend on them; defaults are the measured best,
- * DESIGN.md 4.0 / profiles/r05_s5_pass_experiments.txt):
+/* Environment switches, read once per handle at catan_create (csrc/catan_abi.hip: sched_from_env; setting one afterwards does not reach an existing
+ * handle).  A/B diagnostics of the schedules: results never depend on them; defaults are the measured best, DESIGN.md 4.0 /
+ * profiles/r05_s5_pass_experiments.txt:
+ *   CATAN_STEP_WAVE_GAMES=64|32|16, CATAN_DEFERRED_FUSED=0|1   as the setters above
  *   CATAN_STEP_BIN_ORDER=0        k_step's bins over the launch's waves in index order instead of longest-lasting first
- *   CATAN_LR_MID_BUDGET=b         budget of the middle tier of a deferred window (default 256; 0: every tier-2 request straight to k_lr_heavy)
- *   CATAN_LR_MID_HEAVY_GRID=g     workgroups of k_lr_heavy behind the middle tier (default 32)
- *   CATAN_T1_GROUP=1              one tier-1 launch per pass of the library's own deferred loop instead of one per two passes
- *   CATAN_T1_DEPTH=2              ... then with two rotating tier-1 slots instead of three
- *   CATAN_LR_SPLIT=0 | 2          tier 1 as search + lane-per-game completion never / in every schedule (default: where a launch has two passes)
- *   CATAN_LR_GRID=g               workgroups of k_lr_finish (default 4 096 inside a lock-step step, 3 072 in the deferred schedules)
- *   CATAN_STEP_WAVES_PER_BLOCK=4  four-wave k_step workgroups;  CATAN_STEP_WAVE_GAMES, CATAN_DEFERRED_FUSED: as the setters above
  *   CATAN_FUSED_SUBS=s            sub-lists per sort bin in the fused-sampling loop: 1, 2, 4, 8 (default) or 16
+ *   CATAN_T1_GROUP=1              the sampler form of the library's own deferred loop: one tier-1 launch per pass (on three rotating slots) instead of
+ *                                 one per two passes
  *   CATAN_T1_DELAY_US=k           the fused-sampling loop: tier 1 staggered k microseconds behind the group's last k_step (default 4; 0: not staggered)
- *   CATAN_DEBUG_FUSED_CLOSE_UNORDERED=1, CATAN_DEBUG_STEP_DELAY_US=k   the fused loop's window close as it was ordered until round 6 / the closing pass's
- *                                 k_step k microseconds late: reproduce the round-5 parity failures at will (tools/fused_close_race.py; these two DO change results) */
+ *   CATAN_LR_SPLIT=0 | 2          tier 1 as search + lane-per-game completion never / in every schedule (default: where a launch has two passes)
+ *   CATAN_LR_GRID=g               workgroups of k_lr_finish in every schedule, g >= 64 (default 4 096 inside a lock-step step and in the fused-sampling
+ *                                 loop, 3 072 in the other deferred schedules)
+ *   CATAN_LR_MID_BUDGET=b         budget of the middle tier of a deferred window (default 256; 0: every tier-2 request straight to k_lr_heavy)
+ *   CATAN_LR_MID_HEAVY_GRID=g     workgroups of k_lr_heavy behind the middle tier, 8..256 (default 32) */
 
 #ifdef __cplusplus
 }

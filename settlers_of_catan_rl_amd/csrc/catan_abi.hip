@@ -25,11 +25,30 @@
 
 using namespace catan;
 
+// Every scheduling knob of a handle (results never depend on any of them).  Filled once, by sched_from_env at catan_create: the defaults below, then
+// the environment switches listed in include/catan_hip_tuning.h; the catan_set_* entry points write the same fields afterwards.
+struct Sched {
+    int step_games;       // games per k_step wave: 64, 32 or 16 (catan_set_step_wave_games, CATAN_STEP_WAVE_GAMES)
+    int step_bin_order;   // k_step: longest-lasting bins first (StepCfg::bin_order; CATAN_STEP_BIN_ORDER)
+    int deferred_fused;   // the library's own deferred loop in its fused-sampling form (catan_set_deferred_fused, CATAN_DEFERRED_FUSED)
+    int fused_subs;       // ... its sub-lists per bin (CATAN_FUSED_SUBS: 1, 2, 4, 8 or 16; Pending::nsub while that loop runs)
+    int t1_group;         // the sampler form of that loop: passes per tier-1 launch, 2 or 1 (CATAN_T1_GROUP)
+    int t1_delay_us;      // the fused-sampling loop: tier 1 staggered this many microseconds behind the group's last k_step (CATAN_T1_DELAY_US; <= 0: not staggered)
+    int lr_split;         // tier 1 as search (k_lr_finish<LRF_SPLIT>) + lane-per-game completion (k_lr_complete): 0 never, 1 where a launch has two passes, 2 everywhere (CATAN_LR_SPLIT)
+    int lr_grid;          // workgroups of k_lr_finish in every schedule (CATAN_LR_GRID, >= 64), or 0: each schedule's own (LR_GRID, LR_GRID_DEFERRED, LR_GRID_FUSED)
+    int lr_mid_budget;    // deferred windows: the middle tier's budget (0: off), and k_lr_heavy's workgroups behind it (CATAN_LR_MID_BUDGET, CATAN_LR_MID_HEAVY_GRID)
+    int lr_mid_heavy_grid;
+    int lr_budget[3];     // tier-1 longest-road iteration budget: [0] lock-step, [1] deferred (tails are amortised there), [2] the fused-sampling loop (catan_set_lr_budgets)
+    int lr_round[2];      // tier-2 iterations per bulk-synchronous round: [0] lock-step, [1] deferred (catan_set_lr_rounds)
+};
+
 struct catan_env {
     int device;
     long n, N;
     Ctx ctx;
     catan_cfg_t cfg;
+    Sched sched;
+    std::vector<void*> owned;   // every device allocation of catan_create (dev_alloc), freed by catan_destroy
     void* state;          // W rows then B rows
     u32* mpk;             // packed masks [N][16]
     u32* spec_state;      // shadow records / masks for speculative re-deals inside a lock-step step (enqueue_slow)
@@ -46,24 +65,13 @@ struct catan_env {
     Pending pend;         // tier-2 longest-road hand-off (device arrays)
     unsigned long long* prof; // device [12] phase profile of k_step, enabled by catan_profile_enable
     int prof_on;
-    int lr_mid_budget;    // deferred windows: the middle tier's budget (0: off), and k_lr_heavy's workgroups behind it
-    int lr_mid_heavy_grid;
-    int t1_group;         // the library's own deferred loop: passes per tier-1 launch (1, or 2: deferred_iter_grouped)
-    int g_open, g_slot, g_passes; int64_t g_count;   // ... its running group
-    int lr_split;         // tier 1 as search (k_lr_finish<LRF_SPLIT>) + lane-per-game completion (k_lr_complete)
-    int step_bin_order;   // k_step: longest-lasting bins first (StepCfg::bin_order)
-    int step_wpb;         // waves per k_step workgroup (4: one workgroup per CU, a SIMD per wave; 1: one-wave workgroups)
+    int g_open, g_slot, g_passes; int64_t g_count;   // the sampler form of the library's own deferred loop: its running tier-1 group
     u32* prof_wave;       // [N/64][8] per-wave phase ticks of the last k_step (catan_profile_enable(env, 2))
     u32* pctr;            // [N] per-game decision counters of the random policy (deferred rollouts)
-    int lr_budget[3];     // tier-1 longest-road iteration budget: [0] lock-step, [1] deferred (tails are amortised there), [2] the fused-sampling loop
-    int lr_round[2];      // tier-2 iterations per bulk-synchronous round: [0] lock-step, [1] deferred
-    int deferred_fused;   // catan_set_deferred_fused (CATAN_DEFERRED_FUSED at creation)
-    int fused_subs;       // ... its sub-lists per bin (CATAN_FUSED_SUBS at creation: 1, 2, 4, 8 or 16; Pending::nsub while that loop runs)
-    int step_games;       // games per k_step wave: 64, 32 or 16 (catan_set_step_wave_games; CATAN_STEP_WAVE_GAMES at creation)
     hipStream_t side;     // re-deals run here, concurrently with the longest-road kernels on the caller's stream
     hipEvent_t ev_fork, ev_join;
-    hipStream_t fstream[2];  // deferred rollouts: tier-1 longest road + completion of iteration t run on fstream[t & 1] during t+1
-    hipEvent_t ev_fready[3], ev_fdone[3];   // per tier-1 slot (the library's own deferred loop rotates three: deferred_iter_legacy)
+    hipStream_t fstream;  // deferred rollouts: tier-1 longest road + completion run here during the passes that follow
+    hipEvent_t ev_fready[3], ev_fdone[3];   // per tier-1 slot (the sampler loop with a tier-1 launch per pass rotates three)
     float* f_reward;      // [n][4] / [n]: outputs of the completions that run on fstream (scratch)
     u8* f_done;
     hipStream_t sstream;  // deferred rollouts: tier 2 + re-deals of window w run here during window w+1
@@ -104,6 +112,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
         hipError_t e_ = (x);                                                                         \
         if (e_ != hipSuccess) return fail(CATAN_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
     } while (0)
+#define OK_OR_RETURN(x) do { int r_ = (x); if (r_ != CATAN_OK) return r_; } while (0)   // ... and for the helpers that return a CATAN_* code themselves
 
 template <class T>
 static int attn_dispatch(bool bwd, const void* qkv, const int* lens, const void* dout, void* out, long B, int L, int H, int HD, hipStream_t st) {
@@ -311,6 +320,70 @@ static int lnw_res_dispatch(const void* x, const float* w, const float* b, const
     return CATAN_OK;
 }
 
+// The handle's scheduling knobs at creation: the measured defaults, then the environment (the ONLY place the library reads it: a switch set after a
+// handle's creation does not reach that handle; A/B diagnostics of the schedules, listed in include/catan_hip_tuning.h).
+static Sched sched_from_env() {
+    Sched k;
+    auto env_int = [](const char* name, int& v) { const char* t = getenv(name); if (t) v = atoi(t); return t != nullptr; };
+    int v = 0;
+    k.step_games = DEFAULT_STEP_WAVE_GAMES;
+    if (env_int("CATAN_STEP_WAVE_GAMES", v) && (v == 64 || v == 32 || v == 16)) k.step_games = v;
+    k.step_bin_order = 1;   // on since round 5 (54.5 -> 52.3-53.4 us per pass: profiles/r05_s5_pass_experiments.txt); CATAN_STEP_BIN_ORDER=0: bins in index order
+    if (env_int("CATAN_STEP_BIN_ORDER", v)) k.step_bin_order = v != 0;
+    // the fused-sampling loop is the library's own deferred loop since round 6 (one kernel per pass on the main stream; with per-bin sub-lists,
+    // 32-game waves and the middle tier: 38.9 us per pass against 41.4 for sampler + k_step, profiles/r06_fused_loop_ab.txt); CATAN_DEFERRED_FUSED=0: the sampler form
+    k.deferred_fused = 1;
+    if (env_int("CATAN_DEFERRED_FUSED", v)) k.deferred_fused = v != 0;
+    k.fused_subs = DEFAULT_FUSED_SUBS;
+    static_assert(DEFAULT_FUSED_SUBS <= MAX_SUBS, "sub-lists per bin");
+    if (env_int("CATAN_FUSED_SUBS", v) && (v == 1 || v == 2 || v == 4 || v == 8 || v == 16)) k.fused_subs = v;
+    k.t1_group = 2;       // on since round 5 (47.8 -> 45.5 us per pass at 88.9 instead of 90.0 % active games: +3.6 % env-steps/s, profiles/r05_s5_pass_experiments.txt);
+    if (env_int("CATAN_T1_GROUP", v)) k.t1_group = v == 1 ? 1 : 2;   // CATAN_T1_GROUP=1: a tier-1 launch per pass, three rotating slots (deferred_iter_sampler)
+    k.t1_delay_us = T1_STAGGER_US;
+    env_int("CATAN_T1_DELAY_US", k.t1_delay_us);
+    // tier 1 as search + lane-per-game completion: in the library's own deferred loop since round 5 (a tier-1 launch there has two passes to finish and its
+    // waves share the SIMDs with the sampler and k_step: 44.7 -> 43.8 us per pass), not inside a lock-step step (one more kernel on its critical path:
+    // 184 -> 197 us) nor in catan_step_deferred (a launch per call: 64.0 -> 65.3 us per call).
+    // CATAN_LR_SPLIT=0: never, 2: everywhere
+    k.lr_split = 1;
+    if (env_int("CATAN_LR_SPLIT", v)) k.lr_split = v == 0 ? 0 : (v == 2 ? 2 : 1);
+    k.lr_grid = 0;
+    if (env_int("CATAN_LR_GRID", v) && v >= 64) k.lr_grid = v;
+    // the middle tier of a deferred window: on since round 5 (budget 256, 32 tier-2 workgroups behind it: 53.9 -> 51.2-51.6 us per pass,
+    // same file); CATAN_LR_MID_BUDGET=0: every tier-2 request straight to k_lr_heavy on 128 workgroups
+    k.lr_mid_budget = 256; k.lr_mid_heavy_grid = 32;
+    if (env_int("CATAN_LR_MID_BUDGET", v)) { k.lr_mid_budget = v > 0 ? v : 0; if (k.lr_mid_budget == 0) k.lr_mid_heavy_grid = 128; }
+    if (env_int("CATAN_LR_MID_HEAVY_GRID", v) && v >= 8 && v <= 256) k.lr_mid_heavy_grid = v;
+    k.lr_budget[0] = LR_BUDGET; k.lr_budget[1] = LR_BUDGET_DEFERRED; k.lr_budget[2] = LR_BUDGET_FUSED;
+    k.lr_round[0] = LR_ROUND_LOCKSTEP; k.lr_round[1] = LR_ROUND;
+    return k;
+}
+// one device allocation of catan_create, owned by the handle until catan_destroy; nothing is tried after the first failure (rc)
+template <class T>
+static void dev_alloc(catan_env* e, hipError_t& rc, T*& p, size_t bytes) {
+    if (rc != hipSuccess) return;
+    rc = hipMalloc((void**)&p, bytes);
+    if (rc == hipSuccess) e->owned.push_back(p);
+}
+// Pending as a lock-step step wants it, and as every deferred schedule leaves it behind
+static void pend_lockstep(catan_env* e) {
+    e->pend.fa = 0; e->pend.ftag = 1; e->pend.sa = 0; e->pend.stag = 1; e->pend.sample = 0; e->pend.brel = -1; e->pend.nsub = 1;
+}
+// ... and for one pass of a deferred schedule: tier-1 slot fa (request list, busy tag), window slot sa (tag 4 + sa), the sort's sets
+static void pend_pass(catan_env* e, int fa, int ftag, int sa, int bsel, int bclear) {
+    e->pend.fa = fa; e->pend.ftag = ftag; e->pend.sa = sa; e->pend.stag = 4 + sa; e->pend.bsel = bsel; e->pend.bclear = bclear;
+    e->pend.sample = 0; e->pend.brel = -1; e->pend.nsub = 1;
+}
+
+static inline unsigned blocks(long n, int b) { return (unsigned)((n + b - 1) / b); }
+// k_step with G games per wave in one-wave workgroups; pend.sample (fused-sampling rollouts): actions from / to the side rows
+template <int G>
+static void launch_step(catan_env_t* e, const int32_t* actions, float* reward, uint8_t* done, hipStream_t st, const StepCfg& sc, const u32* bins) {
+    const dim3 grid(blocks(e->N, G) + SORT_PAD_WAVES);
+    if (e->pend.sample) hipLaunchKernelGGL((k_step<G, true>), grid, dim3(64), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, bins);
+    else hipLaunchKernelGGL((k_step<G, false>), grid, dim3(64), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, bins);
+}
+
 extern "C" {
 
 const char* catan_last_error(void) { return g_err.c_str(); }
@@ -336,7 +409,6 @@ int32_t catan_state_bytes_per_game(void) { return STATE_BYTES_PER_GAME; }
 int64_t catan_num_envs(const catan_env_t* e) { return e ? e->n : 0; }
 
 static inline hipStream_t S(catan_stream_t s) { return (hipStream_t)s; }
-static inline unsigned blocks(long n, int b) { return (unsigned)((n + b - 1) / b); }
 
 static int launch_masks(catan_env_t* e, hipStream_t st) {
     hipLaunchKernelGGL(k_masks, dim3(blocks(e->N, BLOCK)), dim3(BLOCK), 0, st, e->ctx, e->mpk, limits_of(e));
@@ -352,116 +424,70 @@ int catan_create(catan_env_t** out, int device, int64_t n_envs, uint64_t seed, u
     HIPCHK(hipSetDevice(device));
     catan_env* e = new (std::nothrow) catan_env();
     if (!e) return fail(CATAN_ENOMEM, "catan_create: host allocation failed");
-    memset(e, 0, sizeof *e);
     e->device = device;
     e->n = n_envs;
     e->N = (n_envs + BLOCK - 1) / BLOCK * BLOCK;
     if (cfg) e->cfg = *cfg; else catan_cfg_default(&e->cfg);
-    size_t bytes = (size_t)e->N * STATE_BYTES_PER_GAME;
-    hipError_t rc = hipMalloc(&e->state, bytes);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->mpk, (size_t)e->N * MPK_STRIDE * sizeof(u32));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->spec_state, (size_t)e->N * REC * sizeof(u32));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->spec_mpk, (size_t)e->N * MPK_STRIDE * sizeof(u32));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->err, 64);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->scratch_actions, (size_t)e->n * ACTION_WORDS * sizeof(i32));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->scratch_reward, (size_t)e->n * 4 * sizeof(float));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->scratch_done, (size_t)e->n);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.ctr, CTR_WORDS * sizeof(u32));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.req[0], (size_t)e->N * sizeof(u64));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.req[1], (size_t)e->N * sizeof(u64));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.req[2], (size_t)e->N * sizeof(u64));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->f_reward, (size_t)e->n * 4 * sizeof(float));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->f_done, (size_t)e->n);
+    e->sched = sched_from_env();
+    const size_t bytes = (size_t)e->N * STATE_BYTES_PER_GAME, games = (size_t)e->N, envs = (size_t)e->n;
+    hipError_t rc = hipSuccess;
+    dev_alloc(e, rc, e->state, bytes);
+    dev_alloc(e, rc, e->mpk, games * MPK_STRIDE * sizeof(u32));
+    dev_alloc(e, rc, e->spec_state, games * REC * sizeof(u32));
+    dev_alloc(e, rc, e->spec_mpk, games * MPK_STRIDE * sizeof(u32));
+    dev_alloc(e, rc, e->err, 64);
+    dev_alloc(e, rc, e->scratch_actions, envs * ACTION_WORDS * sizeof(i32));
+    dev_alloc(e, rc, e->scratch_reward, envs * 4 * sizeof(float));
+    dev_alloc(e, rc, e->scratch_done, envs);
+    dev_alloc(e, rc, e->pend.ctr, CTR_WORDS * sizeof(u32));
+    for (int i = 0; i < 3; i++) dev_alloc(e, rc, e->pend.req[i], games * sizeof(u64));
+    dev_alloc(e, rc, e->f_reward, envs * 4 * sizeof(float));
+    dev_alloc(e, rc, e->f_done, envs);
     // HIP multiplexes streams onto 4 hardware queues; streams that share a queue serialise.  Caller's stream + side +
-    // fstream + sstream = 4, so the two tier-1 slots share one stream (tier 1 of an iteration must fit in one iteration).
+    // fstream + sstream = 4, so the tier-1 slots share one stream (tier 1 of an iteration must fit in one iteration).
     // (A second tier-1 stream was measured with GPU_MAX_HW_QUEUES=4 and 8: 883 M and 447 M env-steps/s against 1 015 M -
     // two tier-1 launches in flight take the SIMDs from k_step.)
-    // CATAN_LR_CUS=k (diagnostics, tools/pass_experiments.py): the tier-1 stream confined to k of the CUs (every (cus / k)-th bit of the
-    // CU mask), so that its one-wave workgroups do not hold LDS on the CUs k_step's 29 KB workgroups need
-    int lr_cus = getenv("CATAN_LR_CUS") ? atoi(getenv("CATAN_LR_CUS")) : 0;
-    if (rc == hipSuccess && lr_cus > 0) {
-        hipDeviceProp_t prop; int dev = 0;
-        int cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-        if (lr_cus > cus) lr_cus = cus;
-        std::vector<uint32_t> mask((cus + 31) / 32, 0u);
-        const char* pat = getenv("CATAN_LR_CUS_PATTERN");             // "block": the first k CUs; default: evenly spread
-        for (int k = 0; k < lr_cus; k++) { const int b = (pat && pat[0] == 'b') ? k : (int)((long)k * cus / lr_cus); mask[b >> 5] |= 1u << (b & 31); }
-        rc = hipExtStreamCreateWithCUMask(&e->fstream[0], (uint32_t)mask.size(), mask.data());
-    } else if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&e->fstream[0], hipStreamNonBlocking);
-    e->fstream[1] = e->fstream[0];
+    if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&e->fstream, hipStreamNonBlocking);
     for (int i = 0; i < 3 && rc == hipSuccess; i++) {
         rc = hipEventCreateWithFlags(&e->ev_fready[i], EV_SYNC);
         if (rc == hipSuccess) rc = hipEventCreateWithFlags(&e->ev_fdone[i], EV_SYNC);
     }
-    for (int i = 0; i < 2 && rc == hipSuccess; i++) {
-        rc = hipMalloc((void**)&e->pend.heavy[i], (size_t)e->N * sizeof(u64));
-        if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.resets[i][0], (size_t)e->N * sizeof(i32));
-        if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.resets[i][1], (size_t)e->N * sizeof(i32));
-        if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.resets[i][2], (size_t)e->N * sizeof(i32));
+    for (int i = 0; i < 2; i++) {
+        dev_alloc(e, rc, e->pend.heavy[i], games * sizeof(u64));
+        for (int k = 0; k < 3; k++) dev_alloc(e, rc, e->pend.resets[i][k], games * sizeof(i32));
         if (rc == hipSuccess) rc = hipEventCreateWithFlags(&e->ev_sdone[i], EV_SYNC);
     }
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.heavy2, (size_t)e->N * sizeof(u64));
+    dev_alloc(e, rc, e->pend.heavy2, games * sizeof(u64));
     if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&e->sstream, hipStreamNonBlocking);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->s_reward, (size_t)e->n * 4 * sizeof(float));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->s_done, (size_t)e->n);
+    dev_alloc(e, rc, e->s_reward, envs * 4 * sizeof(float));
+    dev_alloc(e, rc, e->s_done, envs);
     // the sort's lists: BIN_SETS sets x NBINS bins x (fused-sampling rollouts) fused_subs sub-lists of up to N game ids each - a game is in at most
     // one list, so no sub-list can overflow whatever the split; only what is used is ever touched (65 536 games, 8 sub-lists: 151 MB of address space)
-    e->fused_subs = DEFAULT_FUSED_SUBS;
-    if (const char* fs = getenv("CATAN_FUSED_SUBS")) { const int v = atoi(fs); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) e->fused_subs = v; }
-    static_assert(DEFAULT_FUSED_SUBS <= MAX_SUBS, "sub-lists per bin");
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.lists, (size_t)BIN_SETS * NBINS * e->fused_subs * e->N * sizeof(i32));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.bctr, (size_t)BIN_SETS * NBINS * MAX_SUBS * BCTR_PAD * sizeof(u32));
+    dev_alloc(e, rc, e->pend.lists, (size_t)BIN_SETS * NBINS * e->sched.fused_subs * games * sizeof(i32));
+    dev_alloc(e, rc, e->pend.bctr, (size_t)BIN_SETS * NBINS * MAX_SUBS * BCTR_PAD * sizeof(u32));
     if (rc == hipSuccess) rc = hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking);
     if (rc == hipSuccess) rc = hipEventCreateWithFlags(&e->ev_fork, EV_SYNC);
     if (rc == hipSuccess) rc = hipEventCreateWithFlags(&e->ev_join, EV_SYNC);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.type, (size_t)e->N);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.who, (size_t)e->N);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.len, (size_t)e->N * sizeof(u64));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.arrive, (size_t)e->N * sizeof(u32));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.spec, (size_t)e->N * sizeof(u64));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pend.busy, (size_t)e->N);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->pctr, (size_t)e->N * sizeof(u32));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->prof_wave, (size_t)prof_wave_rows(e->N) * 8 * sizeof(u32));
-    if (rc == hipSuccess) rc = hipMalloc((void**)&e->prof, PROF_WORDS * sizeof(unsigned long long));
+    dev_alloc(e, rc, e->pend.type, games);
+    dev_alloc(e, rc, e->pend.who, games);
+    dev_alloc(e, rc, e->pend.len, games * sizeof(u64));
+    dev_alloc(e, rc, e->pend.arrive, games * sizeof(u32));
+    dev_alloc(e, rc, e->pend.spec, games * sizeof(u64));
+    dev_alloc(e, rc, e->pend.busy, games);
+    dev_alloc(e, rc, e->pctr, games * sizeof(u32));
+    dev_alloc(e, rc, e->prof_wave, (size_t)prof_wave_rows(e->N) * 8 * sizeof(u32));
+    dev_alloc(e, rc, e->prof, PROF_WORDS * sizeof(unsigned long long));
     if (rc != hipSuccess) { catan_destroy(e); return fail(CATAN_ENOMEM, std::string("catan_create: hipMalloc: ") + hipGetErrorString(rc)); }
     HIPCHK(hipMemset(e->state, 0, bytes));
     HIPCHK(hipMemset(e->err, 0, 64));
-    HIPCHK(hipMemset(e->spec_mpk, 0, (size_t)e->N * MPK_STRIDE * sizeof(u32)));   // no shadow carries the tag of a step yet (epochs start at 1)
+    HIPCHK(hipMemset(e->spec_mpk, 0, games * MPK_STRIDE * sizeof(u32)));   // no shadow carries the tag of a step yet (epochs start at 1)
     HIPCHK(hipMemset(e->pend.ctr, 0, CTR_WORDS * sizeof(u32)));
-    HIPCHK(hipMemset(e->pend.type, 0, (size_t)e->N));
-    HIPCHK(hipMemset(e->pend.busy, 0, (size_t)e->N));
-    HIPCHK(hipMemset(e->pend.len, 0, (size_t)e->N * sizeof(u64)));      // (bit 63 of a game's word is k_lr_finish<LRF_SPLIT>'s mark for k_lr_complete)
-    HIPCHK(hipMemset(e->pctr, 0, (size_t)e->N * sizeof(u32)));
-    e->lr_budget[0] = LR_BUDGET; e->lr_budget[1] = LR_BUDGET_DEFERRED; e->lr_budget[2] = LR_BUDGET_FUSED;
-    e->lr_round[0] = LR_ROUND_LOCKSTEP; e->lr_round[1] = LR_ROUND;
-    e->step_games = DEFAULT_STEP_WAVE_GAMES;
-    // the fused-sampling loop is the library's own deferred loop since round 6 (one kernel per pass on the main stream; with per-bin sub-lists,
-    // 32-game waves and the middle tier: 38.9 us per pass against 41.4 for sampler + k_step, profiles/r06_fused_loop_ab.txt); CATAN_DEFERRED_FUSED=0: the sampler form
-    e->deferred_fused = 1;
-    if (const char* df = getenv("CATAN_DEFERRED_FUSED")) e->deferred_fused = atoi(df) != 0;
-    // one-wave workgroups by default.  Four waves per workgroup (CATAN_STEP_WAVES_PER_BLOCK=4: one 116 KB workgroup per CU, a SIMD per wave) was
-    // measured SLOWER (k_step 31.8 -> 39.6 us, pass 54.4 -> 61.8 us, profiles/r05_k_step_pass_experiments.txt): the tier-1 waves of the
-    // previous pass hold LDS on most CUs, so a 116 KB workgroup often has to wait for a CU where the 29 KB one-wave workgroup fits at once
-    e->step_wpb = 1;
-    if (const char* wp = getenv("CATAN_STEP_WAVES_PER_BLOCK")) e->step_wpb = atoi(wp) == 4 ? 4 : 1;
-    e->step_bin_order = 1;   // on since round 5 (54.5 -> 52.3-53.4 us per pass: profiles/r05_s5_pass_experiments.txt); CATAN_STEP_BIN_ORDER=0: bins in index order
-    if (const char* bo = getenv("CATAN_STEP_BIN_ORDER")) e->step_bin_order = atoi(bo) != 0;
-    // tier 1 as search + lane-per-game completion: in the library's own deferred loop since round 5 (a tier-1 launch there has two passes to finish and its
-    // waves share the SIMDs with the sampler and k_step: 44.7 -> 43.8 us per pass), not inside a lock-step step (one more kernel on its critical path:
-    // 184 -> 197 us) nor in catan_step_deferred (a launch per call: 64.0 -> 65.3 us per call).
-    // CATAN_LR_SPLIT=0: never, 2: everywhere
-    e->lr_split = 1;
-    e->t1_group = 2;       // on since round 5 (47.8 -> 45.5 us per pass at 88.9 instead of 90.0 % active games: +3.6 % env-steps/s, profiles/r05_s5_pass_experiments.txt);
-    if (const char* tg = getenv("CATAN_T1_GROUP")) e->t1_group = atoi(tg) == 1 ? 1 : 2;   // CATAN_T1_GROUP=1: a tier-1 launch per pass (deferred_iter_legacy, CATAN_T1_DEPTH slots)
-    // the middle tier of a deferred window: on since round 5 (budget 256, 32 tier-2 workgroups behind it: 53.9 -> 51.2-51.6 us per pass,
-    // same file); CATAN_LR_MID_BUDGET=0: every tier-2 request straight to k_lr_heavy on 128 workgroups
-    e->lr_mid_budget = 256; e->lr_mid_heavy_grid = 32;
-    if (const char* mb = getenv("CATAN_LR_MID_BUDGET")) { e->lr_mid_budget = atoi(mb) > 0 ? atoi(mb) : 0; if (e->lr_mid_budget == 0) e->lr_mid_heavy_grid = 128; }
-    if (const char* mg = getenv("CATAN_LR_MID_HEAVY_GRID")) { const int g = atoi(mg); if (g >= 8 && g <= 256) e->lr_mid_heavy_grid = g; }
-    if (const char* ls = getenv("CATAN_LR_SPLIT")) e->lr_split = atoi(ls) == 0 ? 0 : (atoi(ls) == 2 ? 2 : 1);
-    if (const char* sg = getenv("CATAN_STEP_WAVE_GAMES")) { const int g = atoi(sg); if (g == 64 || g == 32 || g == 16) e->step_games = g; }
-    e->pend.fa = 0; e->pend.ftag = 1; e->pend.sa = 0; e->pend.stag = 1; e->pend.sample = 0; e->pend.bnext = 0; e->pend.brel = -1; e->pend.bclear = 1; e->pend.lrq_clear = -1;
-    e->pend.nsub = 1;
+    HIPCHK(hipMemset(e->pend.type, 0, games));
+    HIPCHK(hipMemset(e->pend.busy, 0, games));
+    HIPCHK(hipMemset(e->pend.len, 0, games * sizeof(u64)));      // (bit 63 of a game's word is k_lr_finish<LRF_SPLIT>'s mark for k_lr_complete)
+    HIPCHK(hipMemset(e->pctr, 0, games * sizeof(u32)));
+    pend_lockstep(e);
+    e->pend.bnext = 0; e->pend.bclear = 1; e->pend.lrq_clear = -1;
     HIPCHK(hipMemset(e->pend.bctr, 0, (size_t)BIN_SETS * NBINS * MAX_SUBS * BCTR_PAD * sizeof(u32)));
     HIPCHK(hipMemset(e->mpk, 0, (size_t)e->N * MPK_STRIDE * sizeof(u32)));
     e->ctx.R = (u32*)e->state;
@@ -478,50 +504,14 @@ int catan_create(catan_env_t** out, int device, int64_t n_envs, uint64_t seed, u
 void catan_destroy(catan_env_t* e) {
     if (!e) return;
     hipSetDevice(e->device);
-    if (e->state) hipFree(e->state);
-    if (e->mpk) hipFree(e->mpk);
-    if (e->spec_state) hipFree(e->spec_state);
-    if (e->spec_mpk) hipFree(e->spec_mpk);
-    if (e->err) hipFree(e->err);
-    if (e->scratch_actions) hipFree(e->scratch_actions);
-    if (e->scratch_reward) hipFree(e->scratch_reward);
-    if (e->scratch_done) hipFree(e->scratch_done);
-    if (e->prof) hipFree(e->prof);
-    if (e->pend.ctr) hipFree(e->pend.ctr);
-    if (e->pend.req[0]) hipFree(e->pend.req[0]);
-    if (e->pend.req[1]) hipFree(e->pend.req[1]);
-    if (e->pend.req[2]) hipFree(e->pend.req[2]);
-    if (e->f_reward) hipFree(e->f_reward);
-    if (e->f_done) hipFree(e->f_done);
-    if (e->fstream[0]) hipStreamDestroy(e->fstream[0]);
-    for (int i = 0; i < 3; i++) { if (e->ev_fready[i]) hipEventDestroy(e->ev_fready[i]); if (e->ev_fdone[i]) hipEventDestroy(e->ev_fdone[i]); }
-    for (int i = 0; i < 2; i++) {
-        if (e->pend.heavy[i]) hipFree(e->pend.heavy[i]);
-        if (e->pend.resets[i][0]) hipFree(e->pend.resets[i][0]);
-        if (e->pend.resets[i][1]) hipFree(e->pend.resets[i][1]);
-        if (e->pend.resets[i][2]) hipFree(e->pend.resets[i][2]);
-        if (e->ev_sdone[i]) hipEventDestroy(e->ev_sdone[i]);
-    }
-    if (e->pend.heavy2) hipFree(e->pend.heavy2);
-    if (e->sstream) hipStreamDestroy(e->sstream);
-    if (e->s_reward) hipFree(e->s_reward);
-    if (e->s_done) hipFree(e->s_done);
-    if (e->pend.lists) hipFree(e->pend.lists);
-    if (e->pend.bctr) hipFree(e->pend.bctr);
+    for (void* p : e->owned) hipFree(p);
     if (e->mt_dev) hipFree(e->mt_dev);
     if (e->bcfg_dev) hipFree(e->bcfg_dev);
     if (e->bcfg_idx_dev) hipFree(e->bcfg_idx_dev);
-    if (e->side) hipStreamDestroy(e->side);
-    if (e->ev_fork) hipEventDestroy(e->ev_fork);
-    if (e->ev_join) hipEventDestroy(e->ev_join);
-    if (e->pend.type) hipFree(e->pend.type);
-    if (e->pend.who) hipFree(e->pend.who);
-    if (e->pend.len) hipFree(e->pend.len);
-    if (e->pend.arrive) hipFree(e->pend.arrive);
-    if (e->pend.spec) hipFree(e->pend.spec);
-    if (e->pend.busy) hipFree(e->pend.busy);
-    if (e->pctr) hipFree(e->pctr);
-    if (e->prof_wave) hipFree(e->prof_wave);
+    for (hipStream_t st : { e->fstream, e->sstream, e->side }) if (st) hipStreamDestroy(st);
+    for (hipEvent_t ev : { e->ev_fready[0], e->ev_fready[1], e->ev_fready[2], e->ev_fdone[0], e->ev_fdone[1], e->ev_fdone[2], e->ev_sdone[0], e->ev_sdone[1],
+                           e->ev_fork, e->ev_join })
+        if (ev) hipEventDestroy(ev);
     delete e;
 }
 
@@ -643,7 +633,7 @@ int catan_set_board_configs(catan_env_t* e, const catan_board_cfg_t* cfgs, int32
     // the old table may still be read by re-deals in flight on any of the handle's streams
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipStreamSynchronize(e->side));
-    HIPCHK(hipStreamSynchronize(e->fstream[0]));
+    HIPCHK(hipStreamSynchronize(e->fstream));
     HIPCHK(hipStreamSynchronize(e->sstream));
     BoardCfg* tab = nullptr;
     u8* idx = nullptr;
@@ -684,7 +674,7 @@ static StepCfg step_cfg(const catan_env_t* e) {
     sc.prof = e->prof_on ? e->prof : nullptr;
     sc.prof_wave = e->prof_on >= 2 ? e->prof_wave : nullptr;
     sc.prof_timeline = e->prof_on == 3;
-    sc.bin_order = e->step_bin_order;
+    sc.bin_order = e->sched.step_bin_order;
     return sc;
 }
 // One env step = the games listed by action type (k_sample_random / k_classify), then k_step (fused: apply + done/reward +
@@ -717,40 +707,26 @@ static int enqueue_fast(catan_env_t* e, const int32_t* actions, float* reward, u
                            e->pend.ctr + 4, 12, sc.validate ? e->err : (u32*)nullptr);
         if (ev) HIPCHK(hipEventRecord(ev[1], st));
     }
-    if (e->pend.sample) {                                 // fused-sampling rollouts: actions from / to the side rows
-        if (e->step_games == 64 && e->step_wpb == 4) hipLaunchKernelGGL((k_step<64, true, 4>), dim3(blocks(blocks(e->N, 64) + SORT_PAD_WAVES, 4)), dim3(256), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, (const u32*)bins);
-        else if (e->step_games == 64) hipLaunchKernelGGL((k_step<64, true>), dim3(blocks(e->N, 64) + SORT_PAD_WAVES), dim3(64), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, (const u32*)bins);
-        else if (e->step_games == 32) hipLaunchKernelGGL((k_step<32, true>), dim3(blocks(e->N, 32) + SORT_PAD_WAVES), dim3(64), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, (const u32*)bins);
-        else hipLaunchKernelGGL((k_step<16, true>), dim3(blocks(e->N, 16) + SORT_PAD_WAVES), dim3(64), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, (const u32*)bins);
-        if (ev) HIPCHK(hipEventRecord(ev[2], st));
-        HIPCHK(hipGetLastError());
-        return CATAN_OK;
-    }
-    switch (e->step_games) {
-    case 16: hipLaunchKernelGGL(k_step<16>, dim3(blocks(e->N, 16) + SORT_PAD_WAVES), dim3(64), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, (const u32*)bins); break;
-    case 32: hipLaunchKernelGGL(k_step<32>, dim3(blocks(e->N, 32) + SORT_PAD_WAVES), dim3(64), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, (const u32*)bins); break;
-    default:
-        if (e->step_wpb == 4) hipLaunchKernelGGL((k_step<64, false, 4>), dim3(blocks(blocks(e->N, 64) + SORT_PAD_WAVES, 4)), dim3(256), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, (const u32*)bins);
-        else hipLaunchKernelGGL(k_step<64>, dim3(blocks(e->N, 64) + SORT_PAD_WAVES), dim3(64), 0, st, e->ctx, actions, e->mpk, reward, done, e->err, sc, e->pend, (const u32*)bins);
-        break;
+    switch (e->sched.step_games) {
+    case 16: launch_step<16>(e, actions, reward, done, st, sc, bins); break;
+    case 32: launch_step<32>(e, actions, reward, done, st, sc, bins); break;
+    default: launch_step<64>(e, actions, reward, done, st, sc, bins); break;
     }
     if (ev) HIPCHK(hipEventRecord(ev[2], st));
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
 // tier 1 + completion of request list `fl` on stream `st`.  ev (optional): recorded on st: [8] before, [6] after
-// workgroups of k_lr_finish (CATAN_LR_GRID: diagnostics, tools/pass_experiments.py).  Deferred schedules (tags >= 2): 3 072 - three tier-1 waves
+// workgroups of k_lr_finish: `grid` (the fused-sampling loop's), else by the schedule (Sched::lr_grid overrides all three: diagnostics, tools/pass_experiments.py).
+// Deferred schedules (tags >= 2): 3 072 - three tier-1 waves
 // per SIMD leave registers for a sampler / k_step wave beside them (4 x 120 of a SIMD's 512 do not), and the launch - one per two passes - has the
 // time to take its ~4 000 requests in two rounds: 45.6 -> 44.9 us per pass (profiles/r05_s5_pass_experiments.txt, run 9)
-static int lr_grid(bool deferred) {
-    static const int g = (getenv("CATAN_LR_GRID") && atoi(getenv("CATAN_LR_GRID")) >= 64) ? atoi(getenv("CATAN_LR_GRID")) : 0;
-    return g ? g : (deferred ? LR_GRID_DEFERRED : LR_GRID);
-}
 static int enqueue_tier1(catan_env_t* e, float* reward, uint8_t* done, hipStream_t st, hipEvent_t* ev, int fl, int lr_budget, bool two_passes = false, int grid = 0) {
-    if (grid <= 0 || getenv("CATAN_LR_GRID")) grid = lr_grid(e->pend.ftag >= 2);
+    if (grid <= 0) grid = e->pend.ftag >= 2 ? LR_GRID_DEFERRED : LR_GRID;
+    if (e->sched.lr_grid) grid = e->sched.lr_grid;
     StepCfg sc = step_cfg(e);
     if (ev) HIPCHK(hipEventRecord(ev[8], st));
-    if (e->lr_split == 2 || (e->lr_split == 1 && two_passes)) {     // (1: only where a launch has two passes to finish - the library's own deferred loops)
+    if (e->sched.lr_split == 2 || (e->sched.lr_split == 1 && two_passes)) {     // (1: only where a launch has two passes to finish - the library's own deferred loops)
         hipLaunchKernelGGL(k_lr_finish<LRF_SPLIT>, dim3(grid), dim3(64), 0, st, e->ctx, e->mpk, reward, done, sc, e->pend, fl, lr_budget,
                            sc.prof && e->prof_on < 2 ? sc.prof + 2 * PROF_PHASES : nullptr, reinterpret_cast<unsigned long long*>(e->err + 4));
         hipLaunchKernelGGL(k_lr_complete, dim3(LR_COMPLETE_GRID), dim3(64), 0, st, e->ctx, e->mpk, reward, done, sc, e->pend, fl);
@@ -785,16 +761,16 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
         }
     }
     if (ev) HIPCHK(hipEventRecord(ev[9], st));
-    if (!lockstep && e->lr_mid_budget > 0) {     // (both forms of the deferred loop since round 6: the fused loop's failures with it were its own window-close race, deferred_iter)
+    if (!lockstep && e->sched.lr_mid_budget > 0) {     // (both forms of the deferred loop since round 6: the fused loop's failures with it were its own window-close race, deferred_iter)
         // the middle tier: one wave per tier-2 request with a large budget; k_lr_heavy - fewer workgroups: few requests are left - takes the rest
         HIPCHK(hipMemsetAsync(e->pend.ctr + CTR_HEAVY2, 0, sizeof(u32), st));
-        hipLaunchKernelGGL(k_lr_finish<LRF_MID>, dim3(LR_MID_GRID), dim3(64), 0, st, e->ctx, e->mpk, reward, done, sc, e->pend, 0, e->lr_mid_budget,
+        hipLaunchKernelGGL(k_lr_finish<LRF_MID>, dim3(LR_MID_GRID), dim3(64), 0, st, e->ctx, e->mpk, reward, done, sc, e->pend, 0, e->sched.lr_mid_budget,
                            (unsigned long long*)nullptr, (unsigned long long*)nullptr);
-        hipLaunchKernelGGL(k_lr_heavy, dim3(e->lr_mid_heavy_grid), dim3(LR_HEAVY_THREADS), 0, st, e->ctx, (const u32*)(e->pend.ctr + CTR_HEAVY2), (const u64*)e->pend.heavy2,
-                           e->pend.len, e->lr_round[1], e->mpk, reward, done, sc, e->pend);
+        hipLaunchKernelGGL(k_lr_heavy, dim3(e->sched.lr_mid_heavy_grid), dim3(LR_HEAVY_THREADS), 0, st, e->ctx, (const u32*)(e->pend.ctr + CTR_HEAVY2), (const u64*)e->pend.heavy2,
+                           e->pend.len, e->sched.lr_round[1], e->mpk, reward, done, sc, e->pend);
     } else
     hipLaunchKernelGGL(k_lr_heavy, dim3(heavy_grid), dim3(LR_HEAVY_THREADS), 0, st, e->ctx, (const u32*)sctr, (const u64*)e->pend.heavy[sa], e->pend.len,
-                       e->lr_round[lockstep ? 0 : 1], e->mpk, reward, done, sc, e->pend);   // search + completion
+                       e->sched.lr_round[lockstep ? 0 : 1], e->mpk, reward, done, sc, e->pend);   // search + completion
     if (ev) HIPCHK(hipEventRecord(ev[3], st));
     if (ev) HIPCHK(hipEventRecord(ev[7], st));
     if (e->cfg.auto_reset) {
@@ -818,7 +794,7 @@ constexpr int EV_PER_STEP = 10;
 // sample_step != nullptr: the random policy draws the actions first (into `actions`), fused with the sort's histogram
 static int step_impl(catan_env_t* e, int32_t* actions, float* reward, uint8_t* done, hipStream_t st, hipEvent_t* ev = nullptr,
                      const uint32_t* sample_step = nullptr) {
-    e->pend.fa = 0; e->pend.ftag = 1; e->pend.sa = 0; e->pend.stag = 1; e->pend.sample = 0; e->pend.brel = -1; e->pend.nsub = 1;
+    pend_lockstep(e);
     { int rr = mt_refill(e, st); if (rr != CATAN_OK) return rr; }
     if (ev) HIPCHK(hipEventRecord(ev[5], st));
     // the step's first kernel zeroes the slow-path list counters (ctr[4..15]) and k_step the count set of the NEXT sort, so a
@@ -840,7 +816,7 @@ static int step_impl(catan_env_t* e, int32_t* actions, float* reward, uint8_t* d
                            (const u32*)(e->pend.ctr + 6), (const u64*)e->pend.spec, e->spec_state, e->spec_mpk, e->spec_epoch, e->pend);
         HIPCHK(hipEventRecord(e->ev_join, e->side));
     }
-    if (r == CATAN_OK) r = enqueue_tier1(e, reward, done, st, ev, 0, e->lr_budget[0]);
+    if (r == CATAN_OK) r = enqueue_tier1(e, reward, done, st, ev, 0, e->sched.lr_budget[0]);
     if (r == CATAN_OK) r = enqueue_slow(e, reward, done, st, ev, LR_HEAVY_GRID);
     return r;
 }
@@ -983,133 +959,117 @@ int catan_random_rollout(catan_env_t* e, uint32_t step_idx0, int64_t steps, cata
     return CATAN_OK;
 }
 
-// The deferred iteration in its round 1-3 form (the default: catan_set_deferred_fused): a sampling + sorting kernel in front of
-// every k_step, busy tags cleared by it.  Window w = it / window uses slot w & 1 with tag 4 + (w & 1); the sort's bin sets alternate.
-// Tier 1 rotates D slots (request list, busy tag 2 / 3 / 6, event pair) by it % D: tier 1 of pass `it` runs on the side stream during
-// the passes that follow and its games play again in pass it + D.  D = 2 is the default.  With D = 2 the loop's period is tied to a
-// dependency cycle: k_step(it) -> [event hand-over to the side stream, ~11 us] -> k_lr_finish (~40 us: its slowest search) -> [hand-over
-// back, ~11 us] -> sampler(it + 2), i.e. 2 P >= 62 us + sampler + k_step (profiles/r05_k_step_pass_experiments.txt).  D = 3
-// (CATAN_T1_DEPTH=3) frees the cycle (P >= 36 us) - measured (same file, session 12): 54.3 -> 52.8 us per pass, but the longest-road
-// games sit out one more pass (92.6 -> 90.0 % of the games active): 1.118 G env-steps/s either way.  What keeps the pass above the main
-// stream's own 45 us is then the event record / wait packets around every pass (~7 us of gaps) and the side work's share of the CUs.
-static int t1_depth() {
-    static const int D = (getenv("CATAN_T1_DEPTH") && atoi(getenv("CATAN_T1_DEPTH")) == 2) ? 2 : 3;
-    return D;
+// ---- the deferred schedules' windows.  Pass (or call) `it` belongs to window w = it / window, which uses slot sa = w & 1 (busy tag 4 + sa, the four
+// counters ctr[8 + 4 sa ..], its tier-2 / re-deal lists).  The window's slow path runs on the window stream (sstream) during window w + 1 and its
+// games play again when window w + 2 opens - on the same slot, which is why that pass first waits for ev_sdone[sa].
+struct Win {
+    int64_t w; int sa;
+    bool opens;           // the window's first pass
+    bool back;            // ... which takes the slot over from window w - 2: that window's games come back
+    bool closes, last;    // the window's last pass (the call's last pass closes its window early); the call's last pass
+};
+// iters < 0: a sequence of unknown length (catan_step_deferred; catan_step_flush closes the window that is still open)
+static Win win_of(int64_t it, int64_t iters, int window) {
+    Win x;
+    x.w = it / window; x.sa = (int)(x.w & 1);
+    x.opens = it % window == 0; x.back = x.opens && x.w >= 2;
+    x.last = it + 1 == iters; x.closes = (it + 1) % window == 0 || x.last;
+    return x;
 }
-static int deferred_iter_legacy(catan_env_t* e, int64_t it, int64_t iters, int window, hipStream_t st, hipEvent_t* ev) {
-    const int D = t1_depth();
-    const int fa = (int)(it % D);                              // tier-1 slot of this pass
-    const int ftag = fa < 2 ? 2 + fa : 6;                      // (4, 5 are the window slots' tags)
-    const int ba = (int)(it & 1);                              // bin-count / list set of this pass
-    e->ctr_clean = 0;                                          // (the lock-step path re-initialises the counters after this)
-    const int64_t w = it / window;
-    const int sa = (int)(w & 1);
-    const bool opens = it % window == 0, last = it + 1 == iters, closes = (it + 1) % window == 0 || last;
-    if (it >= D) HIPCHK(hipStreamWaitEvent(st, e->ev_fdone[fa], 0));        // tier 1 of iteration it-D is complete
+// the slow path of window w-2 is complete (the fused-sampling loop then enqueues its games: k_release_window)
+static int window_wait(catan_env_t* e, const Win& win, hipStream_t st) {
+    if (win.back) HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[win.sa], 0));
+    return CATAN_OK;
+}
+// a sequence's first pass zeroes every counter, a pass that opens a later window the four of the window's slot
+static int window_clear(catan_env_t* e, const Win& win, int64_t it, hipStream_t st) {
     if (it == 0) HIPCHK(hipMemsetAsync(e->pend.ctr, 0, CTR_WORDS * sizeof(u32), st));
-    else if (opens) {
-        if (w >= 2) HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[sa], 0));     // the slow path of window w-2 is complete
-        HIPCHK(hipMemsetAsync(e->pend.ctr + 8 + 4 * sa, 0, 4 * sizeof(u32), st));
-    }
-    e->pend.fa = fa; e->pend.ftag = ftag; e->pend.sa = sa; e->pend.stag = 4 + sa; e->pend.bsel = ba; e->pend.bclear = ba ^ 1; e->pend.sample = 0; e->pend.brel = -1; e->pend.nsub = 1;
-    if (ev) HIPCHK(hipEventRecord(ev[5], st));
-    hipLaunchKernelGGL(k_sample_random<BLOCK>, dim3(blocks(e->n, BLOCK)), dim3(BLOCK), 0, st, e->ctx, (const u32*)e->mpk, 0u, e->scratch_actions,
-                       e->pctr, e->pend.busy, ftag, (opens && w >= 2) ? 4 + sa : 0, it == 0 ? (u32*)nullptr : e->pend.ctr + (fa < 2 ? 4 + fa : 7), 1,
-                       e->pend.ctr + 16 + NBINS * ba, e->pend.lists + (size_t)ba * NBINS * e->N);
-    int r = enqueue_fast(e, e->scratch_actions, e->scratch_reward, e->scratch_done, st, ev, true);
+    else if (win.opens) HIPCHK(hipMemsetAsync(e->pend.ctr + 8 + 4 * win.sa, 0, 4 * sizeof(u32), st));
+    return CATAN_OK;
+}
+// The window's slow path (enqueue_slow for pend.sa == win.sa) on the window stream.  Its tier-2 / re-deal lists are complete once the outstanding
+// tier-1 launches are (t1_cnt of them, slots t1_first ^ 0, ^ 1, ..: two slots from either, or all three from slot 0; one side stream: the latest
+// implies the others) AND the closing pass's k_step has
+// appended the games it ends.  A tier-1 launch behind that k_step orders the two; where there is none, the caller passes an event recorded behind
+// the k_step (step_done).  reward / done: the result rows of the completions.
+static int window_close(catan_env_t* e, const Win& win, hipEvent_t* ev, float* reward, uint8_t* done, int t1_first, int t1_cnt, hipEvent_t step_done = nullptr) {
+    if (t1_cnt > (t1_first == 0 ? 3 : 2)) return fail(CATAN_EINVAL, "window_close: three tier-1 slots are waited for from slot 0 only");
+    for (int k = 0; k < t1_cnt; k++) HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fdone[t1_first ^ k], 0));
+    if (step_done) HIPCHK(hipStreamWaitEvent(e->sstream, step_done, 0));
+    int r = enqueue_slow(e, reward, done, e->sstream, ev, LR_HEAVY_GRID_DEFERRED);
     if (r != CATAN_OK) return r;
-    // CATAN_DEBUG_EXTRA_EVENTS=k (diagnostics): k more event records per pass - what a queue packet on the main stream costs
-    // (profiles/r05_k_step_pass_experiments.txt: +2.9 .. 3.5 us per pass each; the loop has two, this record and the wait above)
-    static const int extra = getenv("CATAN_DEBUG_EXTRA_EVENTS") ? atoi(getenv("CATAN_DEBUG_EXTRA_EVENTS")) : 0;
-    for (int k = 0; k < extra; k++) HIPCHK(hipEventRecord(e->ev_fork, st));
-    HIPCHK(hipEventRecord(e->ev_fready[fa], st));
-    HIPCHK(hipStreamWaitEvent(e->fstream[0], e->ev_fready[fa], 0));
-    r = enqueue_tier1(e, e->f_reward, e->f_done, e->fstream[0], ev, fa, e->lr_budget[1]);
-    if (r != CATAN_OK) return r;
-    HIPCHK(hipEventRecord(e->ev_fdone[fa], e->fstream[0]));
-    if (closes) {
-        // the window's tier-2 / re-deal lists are complete once the outstanding tier-1 launches are (one side stream: the latest implies the others)
-        for (int k = 0; k < D && k <= it; k++) HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fdone[(fa + D - k) % D], 0));
-        r = enqueue_slow(e, e->s_reward, e->s_done, e->sstream, ev, LR_HEAVY_GRID_DEFERRED);
-        if (r != CATAN_OK) return r;
-        HIPCHK(hipEventRecord(e->ev_sdone[sa], e->sstream));
-        if (last) {                                   // the call returns with every step complete and no busy game
-            HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[sa], 0));
-            if (w >= 1) HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[sa ^ 1], 0));
-            hipLaunchKernelGGL(k_release_tags, dim3(blocks(e->N, BLOCK)), dim3(BLOCK), 0, st, e->ctx, e->pend.busy);
-            e->pend.fa = 0; e->pend.ftag = 1; e->pend.sa = 0; e->pend.stag = 1;
-        }
-    }
-    return r;
+    HIPCHK(hipEventRecord(e->ev_sdone[win.sa], e->sstream));
+    return CATAN_OK;
+}
+// the end of a sequence: the main stream joins the slow paths of its last window and of the one before (the caller then releases every game)
+static int window_join(catan_env_t* e, const Win& win, hipStream_t st) {
+    HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[win.sa], 0));
+    if (win.w >= 1) HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[win.sa ^ 1], 0));
+    return CATAN_OK;
 }
 
-// One iteration of the deferred rollout (schedule above), fused-sampling form (round 4): the main stream runs ONE kernel per
-// pass.  k_step takes each game's action from the game's side row, and for every game it completes it draws the next action
-// from the new masks and appends the game to the next pass's lists; a game on the slow path is simply in no list until the
-// kernel that completes its step (k_lr_finish: the pass after next; tier 2 / re-deal: the window after next, through the
-// window's release list) has drawn its next action and enqueued it.  Every draw is a pure function of (game, decision index,
-// state), so the games' trajectories are the lock-step ones whoever draws.  Three sets of bin counts / lists / tier-1 request
-// lists rotate (pass % 3): k_step(t) reads set t, appends to set t + 1 and zeroes set t + 2, which k_lr_finish(t) and
-// k_step(t + 1) then fill.
-// The same iteration with tier 1 forked once per GROUP of two passes (the default since round 5; catan_env::t1_group, CATAN_T1_GROUP=1 for the form above): both passes push their
-// longest-road requests to the group's list under the group's tag, tier 1 runs behind the second pass's k_step, and the group's games
-// play again when the slot is used next (two groups later: the games of the first pass sit out three passes, those of the second two).
-// The event record behind k_step and the event wait in front of the sampler - ~3.3 us of drained main stream each - are then paid
-// once per two passes.  A window's last pass (and a call's last) closes its group early, so the window's slow path still sees every
+// The deferred iteration in its sampler form (rounds 1-5; catan_set_deferred_fused(env, 0)): a sampling + sorting kernel in front of every
+// k_step, busy tags cleared by it; the sort's bin sets alternate.
+// Tier 1 is forked once per GROUP of P = Sched::t1_group passes (2 since round 5): both passes push their longest-road requests to the group's list
+// under the group's tag, tier 1 runs on the side stream behind the group's last k_step, and the group's games play again when the slot (request
+// list, busy tag 2 / 3 / 6, event pair; D of them rotate) is used next: two groups later - the games of the first pass sit out three passes, those
+// of the second two.  The event record behind k_step and the event wait in front of the sampler - ~3.3 us of drained main stream each - are
+// then paid once per two passes.  A window's last pass (and a call's last) closes its group early, so the window's slow path still sees every
 // tier-1 launch that can hand it work.
-static int deferred_iter_grouped(catan_env_t* e, int64_t it, int64_t iters, int window, hipStream_t st, hipEvent_t* ev) {
-    constexpr int D = 2;                                       // group slots
-    const int ba = (int)(it & 1);
-    e->ctr_clean = 0;
-    const int64_t w = it / window;
-    const int sa = (int)(w & 1);
-    const bool opens = it % window == 0, last = it + 1 == iters, closes = (it + 1) % window == 0 || last;
+// P = 1 (CATAN_T1_GROUP=1, diagnostics): a group per pass.  With D = 2 slots the loop's period would be tied to a dependency cycle:
+// k_step(it) -> [event hand-over to the side stream, ~11 us] -> k_lr_finish (~40 us: its slowest search) -> [hand-over back, ~11 us] ->
+// sampler(it + 2), i.e. 2 P >= 62 us + sampler + k_step (profiles/r05_k_step_pass_experiments.txt).  D = 3 frees the cycle (P >= 36 us) -
+// measured (same file, session 12): 54.3 -> 52.8 us per pass, but the longest-road games sit out one more pass (92.6 -> 90.0 % of the games
+// active): 1.118 G env-steps/s either way.  What keeps the pass above the main stream's own 45 us is then the event record / wait packets
+// around every pass (~7 us of gaps) and the side work's share of the CUs.
+static int deferred_iter_sampler(catan_env_t* e, int64_t it, int64_t iters, int window, hipStream_t st, hipEvent_t* ev) {
+    const int P = e->sched.t1_group, D = P == 1 ? 3 : 2;       // passes per group, group slots
+    const int ba = (int)(it & 1);                              // bin-count / list set of this pass
+    e->ctr_clean = 0;                                          // (the lock-step path re-initialises the counters after this)
+    const Win win = win_of(it, iters, window);
     if (it == 0) { e->g_open = 0; e->g_count = 0; }
     const bool g_opens = !e->g_open;
     if (g_opens) { e->g_slot = (int)(e->g_count % D); e->g_passes = 0; e->g_open = 1; }
-    const int fa = e->g_slot, ftag = 2 + fa;
+    const int fa = e->g_slot, ftag = fa < 2 ? 2 + fa : 6;      // (4, 5 are the window slots' tags)
+    u32* const req_ctr = e->pend.ctr + (fa < 2 ? 4 + fa : 7);  // the length of the slot's request list (lrq_ctr)
     if (g_opens && e->g_count >= D) HIPCHK(hipStreamWaitEvent(st, e->ev_fdone[fa], 0));   // tier 1 of the group that used this slot last is complete
-    if (it == 0) HIPCHK(hipMemsetAsync(e->pend.ctr, 0, CTR_WORDS * sizeof(u32), st));
-    else if (opens) {
-        if (w >= 2) HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[sa], 0));
-        HIPCHK(hipMemsetAsync(e->pend.ctr + 8 + 4 * sa, 0, 4 * sizeof(u32), st));
-    }
-    e->pend.fa = fa; e->pend.ftag = ftag; e->pend.sa = sa; e->pend.stag = 4 + sa; e->pend.bsel = ba; e->pend.bclear = ba ^ 1; e->pend.sample = 0; e->pend.brel = -1; e->pend.nsub = 1;
+    OK_OR_RETURN(window_wait(e, win, st));
+    OK_OR_RETURN(window_clear(e, win, it, st));
+    pend_pass(e, fa, ftag, win.sa, ba, ba ^ 1);
     if (ev) HIPCHK(hipEventRecord(ev[5], st));
     // the group's first pass releases the slot's previous games (tag) and empties its request list; the second touches neither
     hipLaunchKernelGGL(k_sample_random<512>, dim3(blocks(e->n, 512)), dim3(512), 0, st, e->ctx, (const u32*)e->mpk, 0u, e->scratch_actions,
-                       e->pctr, e->pend.busy, g_opens ? ftag : 0, (opens && w >= 2) ? 4 + sa : 0,
-                       (g_opens && it != 0) ? e->pend.ctr + 4 + fa : (u32*)nullptr, 1,
+                       e->pctr, e->pend.busy, g_opens ? ftag : 0, win.back ? 4 + win.sa : 0,
+                       (g_opens && it != 0) ? req_ctr : (u32*)nullptr, 1,
                        e->pend.ctr + 16 + NBINS * ba, e->pend.lists + (size_t)ba * NBINS * e->N);
-    int r = enqueue_fast(e, e->scratch_actions, e->scratch_reward, e->scratch_done, st, ev, true);
-    if (r != CATAN_OK) return r;
+    OK_OR_RETURN(enqueue_fast(e, e->scratch_actions, e->scratch_reward, e->scratch_done, st, ev, true));
     e->g_passes++;
-    if (e->g_passes == 2 || closes) {                          // close the group: its tier 1 on the side stream
+    if (e->g_passes == P || win.closes) {                      // close the group: its tier 1 on the side stream
         HIPCHK(hipEventRecord(e->ev_fready[fa], st));
-        HIPCHK(hipStreamWaitEvent(e->fstream[0], e->ev_fready[fa], 0));
-        r = enqueue_tier1(e, e->f_reward, e->f_done, e->fstream[0], ev, fa, e->lr_budget[1], true);
-        if (r != CATAN_OK) return r;
-        HIPCHK(hipEventRecord(e->ev_fdone[fa], e->fstream[0]));
+        HIPCHK(hipStreamWaitEvent(e->fstream, e->ev_fready[fa], 0));
+        OK_OR_RETURN(enqueue_tier1(e, e->f_reward, e->f_done, e->fstream, ev, fa, e->sched.lr_budget[1], P == 2));
+        HIPCHK(hipEventRecord(e->ev_fdone[fa], e->fstream));
         e->g_open = 0; e->g_count++;
     }
-    if (closes) {
-        for (int k = 0; k < D && k < e->g_count; k++) HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fdone[k], 0));
-        r = enqueue_slow(e, e->s_reward, e->s_done, e->sstream, ev, LR_HEAVY_GRID_DEFERRED);
-        if (r != CATAN_OK) return r;
-        HIPCHK(hipEventRecord(e->ev_sdone[sa], e->sstream));
-        if (last) {
-            HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[sa], 0));
-            if (w >= 1) HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[sa ^ 1], 0));
+    if (win.closes) {
+        OK_OR_RETURN(window_close(e, win, ev, e->s_reward, e->s_done, 0, (int)(e->g_count < D ? e->g_count : D)));
+        if (win.last) {                               // the call returns with every step complete and no busy game
+            OK_OR_RETURN(window_join(e, win, st));
             hipLaunchKernelGGL(k_release_tags, dim3(blocks(e->N, BLOCK)), dim3(BLOCK), 0, st, e->ctx, e->pend.busy);
-            e->pend.fa = 0; e->pend.ftag = 1; e->pend.sa = 0; e->pend.stag = 1;
+            pend_lockstep(e);
         }
     }
-    return r;
+    return CATAN_OK;
 }
 
+// One iteration of the deferred rollout (schedule above), fused-sampling form (round 4; the default since round 6): the main stream runs ONE
+// kernel per pass.  k_step takes each game's action from the game's side row, and for every game it completes it draws the next action
+// from the new masks and appends the game to the next pass's lists; a game on the slow path is simply in no list until the
+// kernel that completes its step (k_lr_finish: the group after next; tier 2 / re-deal: the window after next, through the
+// window's release list) has drawn its next action and enqueued it.  Every draw is a pure function of (game, decision index,
+// state), so the games' trajectories are the lock-step ones whoever draws.
 static int deferred_iter(catan_env_t* e, int64_t it, int64_t iters, int window, hipStream_t st, hipEvent_t* ev) {
-    if (!e->deferred_fused && e->t1_group == 2) return deferred_iter_grouped(e, it, iters, window, st, ev);
-    if (!e->deferred_fused) return deferred_iter_legacy(e, it, iters, window, st, ev);
+    if (!e->sched.deferred_fused) return deferred_iter_sampler(e, it, iters, window, st, ev);
     // Tier 1 is forked once per GROUP of P passes (P = 2): a k_lr_finish launch lasts as long as its slowest search (~45 us next
     // to k_step) whatever the number of requests, the launches of consecutive groups serialise on one side stream, and the games
     // of group g return in the first pass of group g + 2 - with P = 1 the chain k_step -> k_lr_finish -> k_step two passes later
@@ -1117,83 +1077,59 @@ static int deferred_iter(catan_env_t* e, int64_t it, int64_t iters, int window, 
     // S = P + 2 sets of bin counts / lists rotate: k_step(t) reads set t % S, appends to set (t + 1) % S and empties set
     // (t - 1) % S (its reader is done), which k_lr_finish(g) - launched behind the last pass of group g - and the k_steps before
     // pass (g + 2) P then fill.  Three tier-1 request lists rotate by group.
-    static const int P = (getenv("CATAN_T1_PERIOD") && atoi(getenv("CATAN_T1_PERIOD")) == 1) ? 1 : 2;
-    const int S = P + 2;
+    constexpr int P = 2, S = P + 2;
     const int64_t g = it / P;
     const int ga = (int)(g & 1), gl = (int)(g % 3), rs = (int)(it % S);
     const bool gfirst = it % P == 0, glast = (it + 1) % P == 0;
     e->ctr_clean = 0;                                          // (the lock-step path re-initialises the counters after this)
-    const int64_t w = it / window;
-    const int sa = (int)(w & 1);
-    const bool opens = it % window == 0, last = it + 1 == iters, closes = (it + 1) % window == 0 || last;
+    const Win win = win_of(it, iters, window);
     if (gfirst && g >= 2) HIPCHK(hipStreamWaitEvent(st, e->ev_fdone[ga], 0));   // tier 1 of group g-2 is complete (its games are in this pass's lists)
     if (ev) HIPCHK(hipEventRecord(ev[5], st));
-    e->pend.fa = gl; e->pend.ftag = 2 + ga; e->pend.sa = sa; e->pend.stag = 4 + sa;
-    e->pend.bsel = rs; e->pend.bnext = (rs + 1) % S; e->pend.bclear = (rs + S - 1) % S; e->pend.sample = 1; e->pend.nsub = e->fused_subs;
+    pend_pass(e, gl, 2 + ga, win.sa, rs, (rs + S - 1) % S);
+    e->pend.bnext = (rs + 1) % S; e->pend.sample = 1; e->pend.nsub = e->sched.fused_subs;
+    OK_OR_RETURN(window_wait(e, win, st));
+    if (win.back)                                              // ... its games play again
+        hipLaunchKernelGGL(k_release_window, dim3(64), dim3(BLOCK), 0, st, e->ctx, (const u32*)e->mpk, (const u32*)(e->pend.ctr + 11 + 4 * win.sa),
+                           (const i32*)e->pend.resets[win.sa][2], e->pend, rs);
+    OK_OR_RETURN(window_clear(e, win, it, st));
     if (it == 0) {
-        HIPCHK(hipMemsetAsync(e->pend.ctr, 0, CTR_WORDS * sizeof(u32), st));
         HIPCHK(hipMemsetAsync(e->pend.bctr, 0, (size_t)BIN_SETS * NBINS * MAX_SUBS * BCTR_PAD * sizeof(u32), st));
         hipLaunchKernelGGL(k_sample_first, dim3(blocks(e->N, BLOCK)), dim3(BLOCK), 0, st, e->ctx, e->mpk, (const u32*)e->pctr, e->pend, rs);
-    } else if (opens) {
-        if (w >= 2) {                                                       // the slow path of window w-2 is complete: its games play again
-            HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[sa], 0));
-            hipLaunchKernelGGL(k_release_window, dim3(64), dim3(BLOCK), 0, st, e->ctx, (const u32*)e->mpk, (const u32*)(e->pend.ctr + 11 + 4 * sa),
-                               (const i32*)e->pend.resets[sa][2], e->pend, rs);
-        }
-        HIPCHK(hipMemsetAsync(e->pend.ctr + 8 + 4 * sa, 0, 4 * sizeof(u32), st));
     }
     e->pend.lrq_clear = glast ? (gl + 1) % 3 : -1;             // the next group's request list (read last by tier 1 of group g-2: complete)
     e->pend.brel = (int)(((g + 2) * P) % S);                   // tier 1 of this group: its games return in the first pass of group g + 2
-    // CATAN_DEBUG_STEP_DELAY_US=k (diagnostics): the k_step of a pass that closes a window in the middle of its group starts k microseconds late
-    static const int dbg_delay_us = getenv("CATAN_DEBUG_STEP_DELAY_US") ? atoi(getenv("CATAN_DEBUG_STEP_DELAY_US")) : 0;
-    if (dbg_delay_us > 0 && closes && !(glast || last)) hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, st, (long long)dbg_delay_us * 100);
-    int r = enqueue_fast(e, e->scratch_actions, e->scratch_reward, e->scratch_done, st, ev, true);
-    if (r != CATAN_OK) return r;
-    if (glast || last) {
-        static const bool t1_serial = getenv("CATAN_T1_SERIAL") != nullptr;     // (diagnostics: tier 1 on the main stream, no overlap: k_step alone)
-        hipStream_t fs = t1_serial ? st : e->fstream[ga];
+    OK_OR_RETURN(enqueue_fast(e, e->scratch_actions, e->scratch_reward, e->scratch_done, st, ev, true));
+    const bool forks = glast || win.last;                      // the group's tier 1 on the side stream
+    if (forks) {
         HIPCHK(hipEventRecord(e->ev_fready[ga], st));
-        HIPCHK(hipStreamWaitEvent(fs, e->ev_fready[ga], 0));
+        HIPCHK(hipStreamWaitEvent(e->fstream, e->ev_fready[ga], 0));
         // (search + lane-per-game completion only with CATAN_LR_SPLIT=2: measured 41.0 us per pass with the split against 38.9 without - here the
         // completion kernel samples and enqueues lane per game with one atomic each, and tier 1's launches are not what bounds this loop)
-        // tier 1 staggered behind the next pass's dispatch (T1_STAGGER_US above; CATAN_T1_DELAY_US=k: k microseconds, 0: not staggered)
-        static const int t1_delay_us = getenv("CATAN_T1_DELAY_US") ? atoi(getenv("CATAN_T1_DELAY_US")) : T1_STAGGER_US;
+        // tier 1 staggered behind the next pass's dispatch (T1_STAGGER_US above; Sched::t1_delay_us)
         // (the instrumented loop - catan_random_rollout_timed - has an event record in front of every k_step, which holds that launch back by ~3 us: the
         // stagger is lengthened by 4 us there, so that the ORDER of dispatch - and with it k_step's duration by the events - is the uninstrumented
         // loop's: 30.2 us by the events against 30.1 us by rocprofv3 over the plain loop; without the compensation the events read 33 us)
-        const int t1_us = t1_delay_us > 0 && ev != nullptr ? t1_delay_us + 4 : t1_delay_us;
-        if (t1_us > 0 && !t1_serial) hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, fs, (long long)t1_us * 100);
-        r = enqueue_tier1(e, e->f_reward, e->f_done, fs, ev, gl, e->lr_budget[2], false, LR_GRID_FUSED);
-        if (r != CATAN_OK) return r;
-        HIPCHK(hipEventRecord(e->ev_fdone[ga], fs));
+        const int t1_us = e->sched.t1_delay_us > 0 && ev != nullptr ? e->sched.t1_delay_us + 4 : e->sched.t1_delay_us;
+        if (t1_us > 0) hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, e->fstream, (long long)t1_us * 100);
+        OK_OR_RETURN(enqueue_tier1(e, e->f_reward, e->f_done, e->fstream, ev, gl, e->sched.lr_budget[2], false, LR_GRID_FUSED));
+        HIPCHK(hipEventRecord(e->ev_fdone[ga], e->fstream));
     }
-    if (closes) {
-        // the window's tier-2 / re-deal lists are complete once the outstanding tier-1 launches are ...
-        HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fdone[ga], 0));
-        if (g >= 1) HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fdone[ga ^ 1], 0));
-        // ... AND this pass's k_step, which appends the games it ends to the window's re-deal list.  When the pass is its group's last, the
-        // tier-1 launch behind it (ev_fdone above) orders the two; a window of an ODD number of passes closes in the MIDDLE of a group, and
-        // until round 6 nothing did: the re-deal kernel could read the list's length while k_step was still appending, a game that ended in
-        // that pass was then never re-dealt and dropped out of every list (its counter is zeroed when the slot opens again) - the intermittent
-        // trajectory-parity failures of the windows of 1 and 5 passes (HISTORY.md round 5; reproduced at will with CATAN_DEBUG_STEP_DELAY_US
-        // + CATAN_DEBUG_FUSED_CLOSE_UNORDERED, profiles/r06_fused_close_race.txt).
-        static const bool dbg_unordered = getenv("CATAN_DEBUG_FUSED_CLOSE_UNORDERED") != nullptr;    // (diagnostics: the round-4/5 ordering)
-        if (!(glast || last) && !dbg_unordered) {
-            HIPCHK(hipEventRecord(e->ev_fready[2], st));
-            HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fready[2], 0));
-        }
+    if (win.closes) {
+        // When the pass is its group's last, the tier-1 launch behind it orders its k_step before the window's slow path.  A window of an ODD number
+        // of passes closes in the MIDDLE of a group, and until round 6 nothing did: the re-deal kernel could read the re-deal list's length while k_step
+        // was still appending, a game that ended in that pass was then never re-dealt and dropped out of every list (its counter is zeroed when the
+        // slot opens again) - the intermittent trajectory-parity failures of the windows of 1 and 5 passes (HISTORY.md round 5,
+        // DESIGN.md 4.0; guard: test_deferred_small_windows_repeated_with_the_middle_tier).
+        if (!forks) HIPCHK(hipEventRecord(e->ev_fready[2], st));
         e->pend.brel = -1;                                     // tier 2 / re-deals: into the window's release list
-        r = enqueue_slow(e, e->s_reward, e->s_done, e->sstream, ev, LR_HEAVY_GRID_DEFERRED);
-        if (r != CATAN_OK) return r;
-        HIPCHK(hipEventRecord(e->ev_sdone[sa], e->sstream));
-        if (last) {                                   // the call returns with every step complete and no game left waiting
-            HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[sa], 0));
-            if (w >= 1) HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[sa ^ 1], 0));
+        OK_OR_RETURN(window_close(e, win, ev, e->s_reward, e->s_done, ga, g >= 1 ? 2 : 1, forks ? nullptr : e->ev_fready[2]));
+        if (win.last) {                               // the call returns with every step complete and no game left waiting
+            OK_OR_RETURN(window_join(e, win, st));
             hipLaunchKernelGGL(k_finish_rollout, dim3(blocks(e->N, BLOCK)), dim3(BLOCK), 0, st, e->ctx, (const u32*)e->mpk, e->pctr, e->pend.busy);
-            e->pend.fa = 0; e->pend.ftag = 1; e->pend.sa = 0; e->pend.stag = 1; e->pend.sample = 0; e->pend.nsub = 1;
+            pend_lockstep(e);
         }
     }
-    return r;
+    return CATAN_OK;
 }
 
 int catan_random_rollout_deferred(catan_env_t* e, int64_t iters, int32_t window, catan_stream_t stream) {
@@ -1207,8 +1143,8 @@ int catan_random_rollout_deferred(catan_env_t* e, int64_t iters, int32_t window,
     return CATAN_OK;
 }
 
-// ---- the deferred schedule for caller-supplied actions.  Call `it` of a sequence is iteration `it` of deferred_iter_legacy with
-// k_classify_deferred in the sampler's place; what differs is WHEN the waiting games are released: at the end of the call before
+// ---- the deferred schedule for caller-supplied actions.  Call `it` of a sequence is iteration `it` of deferred_iter_sampler with a tier-1 launch per
+// call on two slots and k_classify_deferred in the sampler's place; what differs is WHEN the waiting games are released: at the end of the call before
 // the one they play in again (k_deliver), not at its start - the caller needs their completed state (observation, masks) to choose
 // the action it passes to that call.  Every kernel writes a step's reward / done into the handle's result rows (f_reward /
 // f_done: one row per game, written by whichever kernel completes the game's step); k_deliver hands them over.
@@ -1224,37 +1160,26 @@ int catan_step_deferred(catan_env_t* e, const int32_t* actions, int32_t window, 
         return fail(CATAN_EINVAL, "catan_step_deferred: window and stream must stay the same between two flushes");
     const int64_t it = e->d_it;
     const int fa = (int)(it & 1);
-    const int64_t w = it / window;
-    const int sa = (int)(w & 1);
-    const bool opens = it % window == 0, closes = (it + 1) % window == 0;
+    const Win win = win_of(it, -1, window);
     e->ctr_clean = 0;                                          // (the lock-step path re-initialises the counters after this)
     e->d_window = window; e->d_stream = st;
     // (tier 1 of call it-2 and, when this call opens window w, the slow path of window w-2 were joined at the end of call it-1)
-    if (it == 0) HIPCHK(hipMemsetAsync(e->pend.ctr, 0, CTR_WORDS * sizeof(u32), st));
-    else if (opens) HIPCHK(hipMemsetAsync(e->pend.ctr + 8 + 4 * sa, 0, 4 * sizeof(u32), st));
-    e->pend.fa = fa; e->pend.ftag = 2 + fa; e->pend.sa = sa; e->pend.stag = 4 + sa; e->pend.bsel = fa; e->pend.bclear = fa ^ 1; e->pend.sample = 0; e->pend.brel = -1; e->pend.nsub = 1;
+    OK_OR_RETURN(window_clear(e, win, it, st));
+    pend_pass(e, fa, 2 + fa, win.sa, fa, fa ^ 1);
     hipLaunchKernelGGL(k_classify_deferred, dim3(blocks(e->N, BLOCK)), dim3(BLOCK), 0, st, e->ctx, actions, (const u8*)e->pend.busy, e->pend.ctr + 16 + NBINS * fa,
                        e->pend.lists + (size_t)fa * NBINS * e->N, it == 0 ? (u32*)nullptr : e->pend.ctr + 4 + fa, 1, e->cfg.validate_actions ? e->err : (u32*)nullptr);
-    int r = enqueue_fast(e, actions, e->f_reward, e->f_done, st, nullptr, true);
-    if (r != CATAN_OK) return r;
+    OK_OR_RETURN(enqueue_fast(e, actions, e->f_reward, e->f_done, st, nullptr, true));
     HIPCHK(hipEventRecord(e->ev_fready[fa], st));
-    HIPCHK(hipStreamWaitEvent(e->fstream[fa], e->ev_fready[fa], 0));
-    r = enqueue_tier1(e, e->f_reward, e->f_done, e->fstream[fa], nullptr, fa, e->lr_budget[1]);
-    if (r != CATAN_OK) return r;
-    HIPCHK(hipEventRecord(e->ev_fdone[fa], e->fstream[fa]));
-    if (closes) {                                              // the window's tier-2 / re-deal lists are complete once the outstanding tier-1 launches are
-        HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fdone[fa], 0));
-        if (it >= 1) HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fdone[fa ^ 1], 0));
-        r = enqueue_slow(e, e->f_reward, e->f_done, e->sstream, nullptr, LR_HEAVY_GRID_DEFERRED);
-        if (r != CATAN_OK) return r;
-        HIPCHK(hipEventRecord(e->ev_sdone[sa], e->sstream));
-    }
+    HIPCHK(hipStreamWaitEvent(e->fstream, e->ev_fready[fa], 0));
+    OK_OR_RETURN(enqueue_tier1(e, e->f_reward, e->f_done, e->fstream, nullptr, fa, e->sched.lr_budget[1]));
+    HIPCHK(hipEventRecord(e->ev_fdone[fa], e->fstream));
+    if (win.closes) OK_OR_RETURN(window_close(e, win, nullptr, e->f_reward, e->f_done, fa, it >= 1 ? 2 : 1));
     // what call it+1 needs: tier 1 of call it-1 complete (its games play again), and - if it opens window w' >= 2 - the slow path of w'-2
-    const int64_t nit = it + 1, nw = nit / window;
-    const bool nopens = nit % window == 0;
+    const int64_t nit = it + 1;
+    const Win next = win_of(nit, -1, window);
     if (nit >= 2) HIPCHK(hipStreamWaitEvent(st, e->ev_fdone[nit & 1], 0));
-    if (nopens && nw >= 2) HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[nw & 1], 0));
-    hipLaunchKernelGGL(k_deliver, dim3(blocks(e->n, BLOCK)), dim3(BLOCK), 0, st, e->ctx, e->pend.busy, nit >= 2 ? 2 + (int)(nit & 1) : 0, (nopens && nw >= 2) ? 4 + (int)(nw & 1) : 0, 0,
+    OK_OR_RETURN(window_wait(e, next, st));
+    hipLaunchKernelGGL(k_deliver, dim3(blocks(e->n, BLOCK)), dim3(BLOCK), 0, st, e->ctx, e->pend.busy, nit >= 2 ? 2 + (int)(nit & 1) : 0, next.back ? 4 + next.sa : 0, 0,
                        (const float*)e->f_reward, (const u8*)e->f_done, reward, done, status);
     HIPCHK(hipGetLastError());
     e->d_it = nit;
@@ -1267,23 +1192,16 @@ int catan_step_flush(catan_env_t* e, float* reward, uint8_t* done, uint8_t* stat
     const int64_t it = e->d_it;
     if (it > 0) {
         if (st != e->d_stream) return fail(CATAN_EINVAL, "catan_step_flush: not the stream of the open sequence");
-        const int window = e->d_window;
-        const int64_t lw = (it - 1) / window;                  // the window of the last call
-        if (it % window != 0) {                                // ... is still open: close it (its pend.sa / stag are still set)
-            HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fdone[0], 0));
-            if (it >= 2) HIPCHK(hipStreamWaitEvent(e->sstream, e->ev_fdone[1], 0));
-            int r = enqueue_slow(e, e->f_reward, e->f_done, e->sstream, nullptr, LR_HEAVY_GRID_DEFERRED);
-            if (r != CATAN_OK) return r;
-            HIPCHK(hipEventRecord(e->ev_sdone[lw & 1], e->sstream));
-        }
+        const Win win = win_of(it - 1, -1, e->d_window);        // the window of the last call
+        // ... is still open: close it (its pend.sa / stag are still set)
+        if (!win.closes) OK_OR_RETURN(window_close(e, win, nullptr, e->f_reward, e->f_done, 0, it >= 2 ? 2 : 1));
         HIPCHK(hipStreamWaitEvent(st, e->ev_fdone[0], 0));
         if (it >= 2) HIPCHK(hipStreamWaitEvent(st, e->ev_fdone[1], 0));
-        HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[lw & 1], 0));
-        if (lw >= 1) HIPCHK(hipStreamWaitEvent(st, e->ev_sdone[(lw & 1) ^ 1], 0));
+        OK_OR_RETURN(window_join(e, win, st));
     }
     hipLaunchKernelGGL(k_deliver, dim3(blocks(e->n, BLOCK)), dim3(BLOCK), 0, st, e->ctx, e->pend.busy, 0, 0, 1, (const float*)e->f_reward, (const u8*)e->f_done, reward, done, status);
     HIPCHK(hipGetLastError());
-    e->pend.fa = 0; e->pend.ftag = 1; e->pend.sa = 0; e->pend.stag = 1; e->pend.sample = 0; e->pend.nsub = 1;
+    pend_lockstep(e);
     e->d_it = 0;
     return CATAN_OK;
 }
@@ -1303,22 +1221,22 @@ int catan_set_policy_counters(catan_env_t* e, const uint32_t* in, catan_stream_t
 
 int catan_set_step_wave_games(catan_env_t* e, int32_t games) {
     if (!e || (games != 64 && games != 32 && games != 16)) return fail(CATAN_EINVAL, "catan_set_step_wave_games: 64, 32 or 16");
-    e->step_games = games;
+    e->sched.step_games = games;
     return CATAN_OK;
 }
 
 int32_t catan_hip_runtime_version(void) { int v = 0; return hipRuntimeGetVersion(&v) == hipSuccess ? (int32_t)v : -1; }
 int32_t catan_step_algorithmic_bytes(void) { return STEP_ALGO_BYTES; }
 int32_t catan_step_fused_algorithmic_bytes(void) { return STEP_FUSED_ALGO_BYTES; }
-int32_t catan_deferred_fused(const catan_env_t* e) { return e ? e->deferred_fused : -1; }
+int32_t catan_deferred_fused(const catan_env_t* e) { return e ? e->sched.deferred_fused : -1; }
 int catan_set_deferred_fused(catan_env_t* e, int32_t on) {
     if (!e) return fail(CATAN_EINVAL, "catan_set_deferred_fused: null handle");
-    e->deferred_fused = on != 0;
+    e->sched.deferred_fused = on != 0;
     return CATAN_OK;
 }
 int catan_set_lr_budgets(catan_env_t* e, int32_t lockstep, int32_t deferred) {
     if (!e || lockstep < 1 || deferred < 1) return fail(CATAN_EINVAL, "catan_set_lr_budgets: bad arguments");
-    e->lr_budget[0] = lockstep; e->lr_budget[1] = deferred; e->lr_budget[2] = deferred;
+    e->sched.lr_budget[0] = lockstep; e->sched.lr_budget[1] = deferred; e->sched.lr_budget[2] = deferred;
     return CATAN_OK;
 }
 
@@ -1331,7 +1249,7 @@ int catan_slow_path_counts(catan_env_t* e, catan_stream_t stream, uint64_t* out3
 
 int catan_set_lr_rounds(catan_env_t* e, int32_t lockstep, int32_t deferred) {
     if (!e || lockstep < 1 || deferred < 1) return fail(CATAN_EINVAL, "catan_set_lr_rounds: bad arguments");
-    e->lr_round[0] = lockstep; e->lr_round[1] = deferred;
+    e->sched.lr_round[0] = lockstep; e->sched.lr_round[1] = deferred;
     return CATAN_OK;
 }
 
@@ -1362,7 +1280,7 @@ int catan_random_rollout_timed(catan_env_t* e, uint32_t step_idx0, int64_t steps
         if (r != CATAN_OK) return r;
     }
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipStreamSynchronize(e->fstream[0]));
+    HIPCHK(hipStreamSynchronize(e->fstream));
     HIPCHK(hipStreamSynchronize(e->sstream));
     for (int k = 0; k < 5; k++) kernel_ms[k] = 0.0f;
     for (int64_t s = 0; s < steps; s++) {
@@ -1382,10 +1300,8 @@ int catan_random_rollout_timed(catan_env_t* e, uint32_t step_idx0, int64_t steps
 
 int catan_obs(catan_env_t* e, float* out_f, int32_t* out_lists, int32_t* out_lens, catan_stream_t stream) {
     if (!e || !out_f || !out_lists || !out_lens) return fail(CATAN_EINVAL, "catan_obs: null argument");
-    static const bool v1 = getenv("CATAN_OBS_V1") != nullptr;          // (the round-1 kernel, kept for A/B timing)
-    if (v1) hipLaunchKernelGGL(k_obs, dim3(blocks(e->N, 64)), dim3(64), 0, S(stream), e->ctx, out_f, out_lists, out_lens);
-    else hipLaunchKernelGGL((k_obs_rows<ObsF32, OBS_OG>), dim3(blocks(e->n, OBS_OG)), dim3(64), 0, S(stream), e->ctx, out_f, out_lists, out_lens,
-                            (float*)nullptr, (signed char*)nullptr, (signed char*)nullptr, (const long long*)nullptr, (const u8*)nullptr, (const i32*)nullptr, (long)e->n);
+    hipLaunchKernelGGL((k_obs_rows<ObsF32, OBS_OG>), dim3(blocks(e->n, OBS_OG)), dim3(64), 0, S(stream), e->ctx, out_f, out_lists, out_lens,
+                       (float*)nullptr, (signed char*)nullptr, (signed char*)nullptr, (const long long*)nullptr, (const u8*)nullptr, (const i32*)nullptr, (long)e->n);
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
@@ -1415,13 +1331,11 @@ static int obs_rows_impl(catan_env_t* e, int32_t bf16, void* dense_f, int32_t* d
         return fail(CATAN_EINVAL, "catan_obs_rows: lists and lens come together");
     if (rows_f && (!t_idx || !sel)) return fail(CATAN_EINVAL, "catan_obs_rows: row stores need t_idx and sel");
     if ((rows_lists && !rows_f) || (dense_lists && !dense_f)) return fail(CATAN_EINVAL, "catan_obs_rows: lists without their observation rows");
-    static const int og = getenv("CATAN_OBS_OG") ? atoi(getenv("CATAN_OBS_OG")) : OBS_OG;      // (A/B: games per wave 16 / 8 / 4)
-    const dim3 grid(blocks(n_rows, og == 16 ? 16 : og == 4 ? 4 : 8));
-#define CATAN_OBS_LAUNCH(OT, CT, G) hipLaunchKernelGGL((k_obs_rows<OT, G>), grid, dim3(64), 0, S(stream), e->ctx, (CT*)dense_f, dense_lists, dense_lens, \
-                                                       (CT*)rows_f, (signed char*)rows_lists, (signed char*)rows_lens, (const long long*)t_idx, sel, games, (long)n_rows)
-    if (bf16) { if (og == 16) CATAN_OBS_LAUNCH(ObsBF16, unsigned short, 16); else if (og == 4) CATAN_OBS_LAUNCH(ObsBF16, unsigned short, 4); else CATAN_OBS_LAUNCH(ObsBF16, unsigned short, 8); }
-    else { if (og == 16) CATAN_OBS_LAUNCH(ObsF32, float, 16); else if (og == 4) CATAN_OBS_LAUNCH(ObsF32, float, 4); else CATAN_OBS_LAUNCH(ObsF32, float, 8); }
-#undef CATAN_OBS_LAUNCH
+    const dim3 grid(blocks(n_rows, OBS_OG));
+    if (bf16) hipLaunchKernelGGL((k_obs_rows<ObsBF16, OBS_OG>), grid, dim3(64), 0, S(stream), e->ctx, (unsigned short*)dense_f, dense_lists, dense_lens, (unsigned short*)rows_f,
+                                 (signed char*)rows_lists, (signed char*)rows_lens, (const long long*)t_idx, sel, games, (long)n_rows);
+    else hipLaunchKernelGGL((k_obs_rows<ObsF32, OBS_OG>), grid, dim3(64), 0, S(stream), e->ctx, (float*)dense_f, dense_lists, dense_lens, (float*)rows_f,
+                            (signed char*)rows_lists, (signed char*)rows_lens, (const long long*)t_idx, sel, games, (long)n_rows);
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }

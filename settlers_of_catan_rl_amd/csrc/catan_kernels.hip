@@ -94,7 +94,7 @@ struct StOps {
     DEVI int pile(int i) const { return self().cold(B_PILE + i); }
     DEVI void set_pile(int i, int v) const { self().scold(B_PILE + i, v); }
 };
-// view 1: the game's record in HBM (k_masks, k_reset, k_sample_random, export/import, k_obs, tier-2 longest road)
+// view 1: the game's record in HBM (k_masks, k_reset, k_sample_random, export/import, k_obs_rows, tier-2 longest road)
 struct St : StOps<St> {
     u32* P;           // the game's record
     long e;
@@ -2008,20 +2008,22 @@ DEVI void finish_step(const Ctx& c, const S& s, StepScratch* scratch, const Step
 // SAMPLE (fused-sampling deferred rollouts): the action comes from the game's side row, the step advances the game's decision
 // counter, and for every game it completes it draws the NEXT action from the new masks (still in registers) and appends the
 // game to the next pass's bin lists - the sampler / sort kernel and its re-read of the masks are gone from the pass.
-// WPB waves per workgroup, every wave with a tile of its own and no workgroup-level synchronisation.  WPB = 4 (the default for 64 games
-// per wave): the hardware spreads a workgroup's waves over the four SIMDs of its CU and the 116 KB of LDS admit one workgroup per CU,
-// so every working wave has a SIMD to itself.  As 1 041 one-wave workgroups the dispatcher used 800 of the 1 024 SIMDs and put two to
-// four waves on 208 of them (tools/step_timeline.py, profiles/r05_k_step_timeline.txt): the launch lasted as long as those.
-template <int G, bool SAMPLE = false, int WPB = 1>
-__global__ __launch_bounds__(64 * WPB) void k_step(Ctx c, const i32* __restrict__ actions, u32* __restrict__ mpk,
+// One-wave workgroups.  Four waves per workgroup (one 116 KB workgroup per CU, a SIMD per wave) were measured SLOWER (k_step 31.8 -> 39.6 us,
+// pass 54.4 -> 61.8 us, profiles/r05_k_step_pass_experiments.txt): the tier-1 waves of the previous pass hold LDS on most CUs, so a 116 KB
+// workgroup often has to wait for a CU where the 29 KB one-wave workgroup fits at once.
+template <int G, bool SAMPLE = false>
+__global__ __launch_bounds__(64) void k_step(Ctx c, const i32* __restrict__ actions, u32* __restrict__ mpk,
                                              float* __restrict__ reward, u8* __restrict__ done,
                                              u32* __restrict__ err, StepCfg cfg, Pending pend, const u32* __restrict__ bins) {
     constexpr int TSG = G + 1;
     typedef StLT<TSG> StG;
-    __shared__ u32 tile_all[WPB][ROWS_HOT * TSG];
-    __shared__ u64 tct_all[WPB][20];                        // corner mask per tile: a per-lane tile index costs one LDS read
+    // (The tile keeps a [waves per workgroup] dimension of 1 and the wave's index in its workgroup, which is always 0.  With plain arrays, lane =
+    // threadIdx.x and wv = blockIdx.x the compiler allocates and schedules all six instantiations differently (138-193 VGPRs instead of 140-181,
+    // other spills): a change of the hot kernel's code that has to come with measurements of its own, not with a change of the host code.)
+    __shared__ u32 tile_all[1][ROWS_HOT * TSG];
+    __shared__ u64 tct_all[1][20];                          // corner mask per tile: a per-lane tile index costs one LDS read
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    const int wv = (int)blockIdx.x * WPB + wib;             // this wave's position among the sorted waves
+    const int wv = (int)blockIdx.x + wib;                   // this wave's position among the sorted waves
     u32* const tile = tile_all[wib];
     u64* const tct = tct_all[wib];
     if constexpr (SAMPLE) {
@@ -3220,8 +3222,7 @@ __global__ __launch_bounds__(BLOCK) void k_calib_copy(const uint4* __restrict__ 
 }
 
 // One wave that idles for `ticks` of the 100 MHz wall clock.  In front of tier 1 on its side stream it STAGGERS that launch behind the next pass's
-// k_step (catan_abi.hip: T1_STAGGER_US); in front of a k_step (CATAN_DEBUG_STEP_DELAY_US, diagnostics) it makes that launch late, which turns a
-// missing stream dependency on it into a deterministic failure (the fused loop's window close).
+// k_step (catan_abi.hip: T1_STAGGER_US).
 __global__ __launch_bounds__(64) void k_spin(long long ticks) {
     const long long t0 = wall_clock64();
     while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);

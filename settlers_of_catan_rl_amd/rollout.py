@@ -2,7 +2,7 @@
 
 Replaces `GamesAndPoliciesManager.gather_rollouts` / `_after_rollouts` / `reset` (reference RL/ppo/game_manager.py:35-59,
 69-150) and the worker/pipe layer above it (RL/ppo/vec_gather_experience.py) by one lock-step device loop over all games:
-every iteration encodes the observation of each game's deciding player (k_obs), runs the policy of that seat, steps
+every iteration encodes the observation of each game's deciding player (k_obs_rows), runs the policy of that seat, steps
 all games (k_step) and updates the per-game bookkeeping with vectorised tensor ops.  Only the decisions of each game's
 ACTIVE seat (the seat mapped to the central policy) are stored; rewards are accumulated across the other seats' moves.
 
@@ -238,7 +238,7 @@ class RolloutCollector(object):
         n_complete = torch.zeros((), dtype=torch.int64, device=dev)
         packed_from_env = hasattr(env, "get_action_masks_packed")
         # one kernel writes the dense observations the policy pass reads (in the storage's dtype: every value is exact in bf16)
-        # AND appends the active seats' rows to the storage (k_obs_rows; round 2: k_obs, a cast pass and a masked row store)
+        # AND appends the active seats' rows to the storage (k_obs_rows; round 2: a lane-per-game encoder, a cast pass and a masked row store)
         fused_obs = hasattr(env, "get_obs_rows") and st.obs_f.is_cuda and st.obs_f.dtype in (torch.float32, torch.bfloat16)
         obs_out = mask_out = None
         # ... and two kernels do the per-game bookkeeping of an iteration (catan_collector_pre / _post) instead of ~40 tensor operations

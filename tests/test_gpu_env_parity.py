@@ -118,7 +118,7 @@ def test_deferred_small_windows_repeated_with_the_middle_tier(oracle, hip_lib, f
 
 
 @pytest.mark.parametrize("switches", [
-    {"CATAN_T1_GROUP": "1"},                                              # a tier-1 launch per pass (three rotating slots)
+    {"CATAN_T1_GROUP": "1", "CATAN_DEFERRED_FUSED": "0"},                 # the sampler form with a tier-1 launch per pass (three rotating slots)
     {"CATAN_LR_SPLIT": "0"},                                              # the search waves complete their games themselves
     {"CATAN_LR_SPLIT": "2"},                                              # ... search + lane-per-game completion in every schedule
     {"CATAN_LR_MID_BUDGET": "0"},                                         # no middle tier: every tier-2 request to k_lr_heavy
@@ -126,13 +126,14 @@ def test_deferred_small_windows_repeated_with_the_middle_tier(oracle, hip_lib, f
     {"CATAN_STEP_BIN_ORDER": "0"},                                        # bins over the waves in index order
     {"CATAN_STEP_WAVE_GAMES": "64"},                                      # games per k_step wave: 64 / 16 (the default is 32)
     {"CATAN_STEP_WAVE_GAMES": "16", "CATAN_LR_SPLIT": "0"},
-    {"CATAN_T1_GROUP": "1", "CATAN_LR_SPLIT": "2", "CATAN_LR_MID_BUDGET": "0", "CATAN_STEP_BIN_ORDER": "0"},
+    {"CATAN_T1_GROUP": "1", "CATAN_DEFERRED_FUSED": "0", "CATAN_LR_SPLIT": "2", "CATAN_LR_MID_BUDGET": "0", "CATAN_STEP_BIN_ORDER": "0"},
 ])
 def test_deferred_schedule_switches_keep_the_trajectories(oracle, hip_lib, monkeypatch, switches):
     """The schedule pieces of round 5 (include/catan_hip_tuning.h: groups of two passes per tier-1 launch, the search / completion
     split, the middle tier, the bin order) are read from the environment when a handle is created and move only WHEN a game's slow
     path runs: under every setting each game must follow its lock-step trajectory (state, masks, decision counters against the
-    oracle), in the library's own loop and - lock-step - through catan_random_rollout (CATAN_LR_SPLIT=2 reaches it)."""
+    oracle), in the library's own loop and - lock-step - through catan_random_rollout (CATAN_LR_SPLIT=2 reaches it).  CATAN_T1_GROUP is
+    read by the sampler form of that loop only, so its two cases select that form (CATAN_DEFERRED_FUSED=0); the others run the default."""
     for k, v in switches.items():
         monkeypatch.setenv(k, v)
     n, seed, window = 2048, 21, 8

@@ -1,5 +1,5 @@
 """Diagnostics (GPU box): microseconds per pass of the deferred random-policy loop at 65 536 games under the process's environment
-(CATAN_STEP_WAVES_PER_BLOCK, CATAN_DEFERRED_FUSED, CATAN_STEP_WAVE_GAMES ...; WINDOW = the deferred window), and the per-kernel HIP-event durations.  One line."""
+(CATAN_DEFERRED_FUSED, CATAN_STEP_WAVE_GAMES, CATAN_LR_GRID ...; WINDOW = the deferred window), and the per-kernel HIP-event durations.  One line."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -25,8 +25,6 @@ run k_step_type_split timeout 600 python $REPO/tools/step_type_split.py
 run lr_finish_profile timeout 300 python $REPO/tools/lr_finish_profile.py
 run soak_fused timeout 900 python $REPO/tools/soak_deferred.py 4 8000 1
 run soak_sampler_loop timeout 900 python $REPO/tools/soak_deferred.py 2 8000 0
-run fused_close_race_unordered env CATAN_DEBUG_FUSED_CLOSE_UNORDERED=1 CATAN_DEBUG_STEP_DELAY_US=60 timeout 300 python $REPO/tools/fused_close_race.py
-run fused_close_race_ordered env CATAN_DEBUG_STEP_DELAY_US=60 timeout 300 python $REPO/tools/fused_close_race.py
 run learner_rooflines timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/learner -o learner -- python $REPO/tools/learner_rooflines_workload.py
 find $OUT/learner -name "*kernel_stats.csv" -exec cp {} $OUT/learner_kernels_kernel_stats.csv \;
 run train_step timeout 900 env STEPS=3 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/train -o train -- python $REPO/tools/pmc_policy_workload.py
