@@ -16,39 +16,24 @@
 extern "C" {
 #endif
 
-/* Backward of the tile encoder's pointwise sub-layer x_out = x + linear2(relu(linear1(LayerNorm(x)))) (width 64, hidden 128) for
- * everything but the weight gradients, one pass over the token rows (csrc/catan_te_bwd.hip).  bf16 row-major: dx [rows][64] = the
- * gradient of x_out; h [rows][128] = relu(linear1(.)); x [rows][64] = the LayerNorm's input; w2t [128][64] = linear2.weight^T;
- * w1t [64][128] = linear1.weight^T; ln_w float [64].  Out: dh [rows][128] = the gradient of linear1's output (catan_linear_wgrad
- * takes it for both weight gradients), dx_out [rows][64] = the gradient of x (LayerNorm backward + the residual dx); dln_w / dln_b
- * float [64] are ACCUMULATED into (zero first). */
-int catan_ffn_bwd_dx(const void* dx, const void* h, const void* x, const void* w2t, const void* w1t, const float* ln_w, float eps, void* dh, void* dx_out,
-                     float* dln_w, float* dln_b, int64_t rows, catan_stream_t stream);
-
-/* catan_ffn_bwd_dx AND the sub-layer's two weight gradients in one pass (k_ffn_bwd_w): additionally n [rows][64] = LayerNorm(x) as the
- * forward stored it, OR n = NULL and ln_b float [64] = the LayerNorm's bias: the pass recomputes n from x (the forward need not store
- * it; ln_b may be NULL when n is given); dw2 float [64][128], db2 [64], dw1 [128][64], db1 [128] are ACCUMULATED into (zero first);
- * dh is not written. */
-int catan_ffn_bwd(const void* dx, const void* h, const void* x, const void* n, const void* w2t, const void* w1t, const float* ln_w, const float* ln_b, float eps,
-                  void* dx_out, float* dw2, float* db2, float* dw1, float* db1, float* dln_w, float* dln_b, int64_t rows, catan_stream_t stream);
-/* catan_ffn_bwd plus the backward of the out-projection that produced x (x = x_in + o Wo^T + bo): d_o [rows][64] = dx_out Wo,
- * dwo float [64][64] and dbo [64] accumulated, from the dx_out rows while they are on chip.  o [rows][64] = the attention output,
- * wot = Wo^T bf16 [64][64] (k_ffn_bwd_w<true>). */
-int catan_ffn_outproj_bwd(const void* dx, const void* h, const void* x, const void* n, const void* w2t, const void* w1t, const float* ln_w, const float* ln_b, float eps,
+/* Backward of the tile encoder's pointwise sub-layer x_out = x + linear2(relu(linear1(LayerNorm(x)))) (width 64, hidden 128) with its two
+ * weight gradients, plus the backward of the out-projection that produced x (x = x_in + o Wo^T + bo), in one pass over the token rows
+ * (k_ffn_bwd_w, csrc/catan_te_bwd.hip).  bf16 row-major: dx [rows][64] = the gradient of x_out; h [rows][128] = relu(linear1(.));
+ * x [rows][64] = the LayerNorm's input; w2t [128][64] = linear2.weight^T; w1t [64][128] = linear1.weight^T; o [rows][64] = the attention
+ * output; wot [64][64] = Wo^T.  ln_w / ln_b float [64] = the LayerNorm's weight and bias: the pass recomputes LayerNorm(x) from x, the
+ * forward need not store it.  Out: dx_out [rows][64] = the gradient of x (LayerNorm backward + the residual dx), d_o [rows][64] = dx_out Wo.
+ * dw2 float [64][128], db2 [64], dw1 [128][64], db1 [128], dln_w / dln_b [64], dwo [64][64] and dbo [64] are ACCUMULATED into (zero
+ * first). */
+int catan_ffn_outproj_bwd(const void* dx, const void* h, const void* x, const void* w2t, const void* w1t, const float* ln_w, const float* ln_b, float eps,
                           void* dx_out, float* dw2, float* db2, float* dw1, float* db1, float* dln_w, float* dln_b,
                           const void* o, const void* wot, void* d_o, float* dwo, float* dbo, int64_t rows, catan_stream_t stream);
-/* catan_ffn_outproj_bwd with the FFN's hidden activation RECOMPUTED instead of read: h = relu(LayerNorm(x) w1^T + b1) from the rows of x
- * the pass stages anyway (w1 bf16 [128][64] row-major and b1 float [128], as the forward kernel reads them: the W1 block / b1 slice of
- * catan_tile_encoder_fwd's packed parameters), so the training forward need not store h (catan_te_saves_t.h[l] = NULL).  The LayerNorm
- * output is always recomputed (ln_b required). */
-int catan_ffn_outproj_bwd_rh(const void* dx, const void* x, const void* w2t, const void* w1t, const void* w1, const float* b1, const float* ln_w, const float* ln_b, float eps,
-                             void* dx_out, float* dw2, float* db2, float* dw1, float* db1, float* dln_w, float* dln_b,
-                             const void* o, const void* wot, void* d_o, float* dwo, float* dbo, int64_t rows, catan_stream_t stream);
 /* The attention sub-layer's input side x_mid = x + out_proj(attention(qkv(LayerNorm(x)))) (width 64): the gradient of x from dqkv
  * [rows][192] (catan_attention_bwd's output) - (dqkv . Wqkv) through the LayerNorm backward, plus the residual gradient dres = d(x_mid)
- * [rows][64] - in one pass.  wt = Wqkv^T bf16 [64][192]; x [rows][64] = the LayerNorm's input; dln_w / dln_b float [64] ACCUMULATED into. */
-int catan_qkv_bwd_dx(const void* dqkv, const void* x, const void* dres, const void* wt, const float* ln_w, float eps, void* dx_out, float* dln_w, float* dln_b,
-                     int64_t rows, catan_stream_t stream);
+ * [rows][64] - and the QKV product's weight gradient in one pass (k_qkv_bwd_w).  wt = Wqkv^T bf16 [64][192]; x [rows][64] = the
+ * LayerNorm's input; ln_w / ln_b float [64] (LayerNorm(x) is recomputed from x, as in catan_ffn_outproj_bwd).  dw float [192][64],
+ * db [192] and dln_w / dln_b [64] are ACCUMULATED into (zero first). */
+int catan_qkv_bwd(const void* dqkv, const void* x, const void* dres, const void* wt, const float* ln_w, const float* ln_b, float eps, void* dx_out,
+                  float* dw, float* db, float* dln_w, float* dln_b, int64_t rows, catan_stream_t stream);
 
 /* Every image of the net's fp32 parameters that a training step reads (bf16 copies, transposed bf16 copies, the fused tile
  * encoder's packed blocks), refreshed by one launch after the optimiser step (the reference relies on autocast's per-use casts,
@@ -85,12 +70,6 @@ typedef struct catan_adam_chunk { int32_t tensor; int32_t count; int64_t offset;
 int32_t catan_adam_chunk_elements(void);
 int catan_adam_step(const void* tensors, const void* chunks, int32_t n_chunks, const void* grads, int32_t n_tensors, int32_t none_is_zero, void* partial,
                     float max_norm, float lr, float beta1, float beta2, float eps, float* norm_out, catan_stream_t stream);
-
-/* catan_qkv_bwd_dx AND the QKV product's weight gradient in one pass (k_qkv_bwd_w): additionally n [rows][64] = LayerNorm 1's output,
- * or n = NULL and ln_b = the LayerNorm's bias (n recomputed from x, as catan_ffn_bwd); dw float [192][64] and db [192] are
- * ACCUMULATED into (zero first). */
-int catan_qkv_bwd(const void* dqkv, const void* x, const void* dres, const void* n, const void* wt, const float* ln_w, const float* ln_b, float eps, void* dx_out,
-                  float* dw, float* db, float* dln_w, float* dln_b, int64_t rows, catan_stream_t stream);
 
 /* Row gathers of the learner (RL/ppo/ppo.py:44-50 builds a minibatch with `[obs[i] for i in indices]`; here the rollout is one
  * (T + 1, N, 1 787) bf16 tensor and a minibatch 204 800 of its 3 574-byte rows).
@@ -236,8 +215,8 @@ typedef struct catan_te_saves {
     void* qkv[2];       /* [192] Q | K | V */
     void* o[2];         /* [64]  attention output */
     void* xmid[2];      /* [64]  residual stream after the attention sub-layer */
-    void* n2[2];        /* [64]  LayerNorm 2 output; may be NULL: catan_ffn_bwd / catan_ffn_outproj_bwd recompute it from xmid */
-    void* h[2];         /* [128] relu(linear1); may be NULL: catan_ffn_outproj_bwd_rh recomputes it */
+    void* n2[2];        /* [64]  LayerNorm 2 output; may be NULL: catan_ffn_outproj_bwd recomputes it from xmid */
+    void* h[2];         /* [128] relu(linear1); may be NULL (no backward entry point recomputes it: for callers that do not run the backward) */
     void* xfin;         /* [64]  last layer's output */
     void* p;            /* [25]  out_proj output, before the final LayerNorm + ReLU */
 } catan_te_saves_t;

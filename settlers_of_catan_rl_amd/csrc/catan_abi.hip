@@ -222,6 +222,14 @@ static void wgrad_grid(long R, int I, int O, long& nb, long& per) {
     per = (stages + nb - 1) / nb * WG_KT;
     nb = (R + per - 1) / per;
 }
+// ... and the rows of the tile encoder's one-pass backward kernels (k_ffn_bwd_w, k_qkv_bwd_w): every block ends with up to 20 864
+// atomics, so several stages of FW_ROWS rows per block and at most 512 blocks
+static void te_bwd_grid(long R, long& nb, long& per) {
+    const long stages = (R + FW_ROWS - 1) / FW_ROWS;
+    nb = stages / 16 < 1 ? 1 : (stages / 16 < 512 ? stages / 16 : 512);
+    per = (stages + nb - 1) / nb * FW_ROWS;
+    nb = (R + per - 1) / per;
+}
 template <int OTW>
 static int wgrad_launch_slice(const void* x, const void* dy, float* dw, float* db, long R, int ld, int col0, int W, int O, hipStream_t st) {
     long nb, per;
@@ -1623,30 +1631,6 @@ int catan_scatter_rows_ranges(const void* dy, int64_t dy_pitch_bytes, const int6
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
-int catan_ffn_bwd_dx(const void* dx, const void* h, const void* x, const void* w2t, const void* w1t, const float* ln_w, float eps, void* dh, void* dx_out,
-                     float* dln_w, float* dln_b, int64_t rows, catan_stream_t stream) {
-    if (!dx || !h || !x || !w2t || !w1t || !ln_w || !dh || !dx_out || !dln_w || !dln_b || rows <= 0 ||
-        (((uintptr_t)dx | (uintptr_t)h | (uintptr_t)x | (uintptr_t)w2t | (uintptr_t)w1t | (uintptr_t)dh | (uintptr_t)dx_out) & 15))
-        return fail(CATAN_EINVAL, "catan_ffn_bwd_dx: null or misaligned argument");
-    long nb = ((rows + 15) / 16 + 3) / 4;
-    if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(k_ffn_bwd_dx, dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dx, (const unsigned short*)h, (const unsigned short*)x,
-                       (const unsigned short*)w2t, (const unsigned short*)w1t, ln_w, eps, (unsigned short*)dh, (unsigned short*)dx_out, dln_w, dln_b, (long)rows);
-    HIPCHK(hipGetLastError());
-    return CATAN_OK;
-}
-int catan_qkv_bwd_dx(const void* dqkv, const void* x, const void* dres, const void* wt, const float* ln_w, float eps, void* dx_out, float* dln_w, float* dln_b,
-                     int64_t rows, catan_stream_t stream) {
-    if (!dqkv || !x || !dres || !wt || !ln_w || !dx_out || !dln_w || !dln_b || rows <= 0 ||
-        (((uintptr_t)dqkv | (uintptr_t)x | (uintptr_t)dres | (uintptr_t)wt | (uintptr_t)dx_out) & 15))
-        return fail(CATAN_EINVAL, "catan_qkv_bwd_dx: null or misaligned argument");
-    long nb = ((rows + 15) / 16 + 3) / 4;
-    if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(k_qkv_bwd_dx, dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dqkv, (const unsigned short*)x, (const unsigned short*)dres,
-                       (const unsigned short*)wt, ln_w, eps, (unsigned short*)dx_out, dln_w, dln_b, (long)rows);
-    HIPCHK(hipGetLastError());
-    return CATAN_OK;
-}
 int64_t catan_wgrad_big_workspace_floats(int64_t rows, int in_features, int out_features) {
     if (rows <= 0 || in_features <= 0 || out_features <= 0) return 0;
     const int tiles_i = (in_features + 1 + WB_T - 1) / WB_T;
@@ -1692,77 +1676,30 @@ int catan_weight_images(const void* table, int32_t n, catan_stream_t stream) {
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
-int catan_ffn_bwd(const void* dx, const void* h, const void* x, const void* n, const void* w2t, const void* w1t, const float* ln_w, const float* ln_b, float eps,
-                  void* dx_out, float* dw2, float* db2, float* dw1, float* db1, float* dln_w, float* dln_b, int64_t rows, catan_stream_t stream) {
-    if (!dx || !h || !x || (!n && !ln_b) || !w2t || !w1t || !ln_w || !dx_out || !dw2 || !db2 || !dw1 || !db1 || !dln_w || !dln_b || rows <= 0 ||
-        (((uintptr_t)dx | (uintptr_t)h | (uintptr_t)x | (uintptr_t)n | (uintptr_t)w2t | (uintptr_t)w1t | (uintptr_t)dx_out) & 15))
-        return fail(CATAN_EINVAL, "catan_ffn_bwd: null or misaligned argument");
-    // every block ends with 16 640 atomics: several stages of 64 rows per block, at most 512 blocks (the grid rule of wgrad_grid)
-    const long stages = (rows + FW_ROWS - 1) / FW_ROWS;
-    long nb = stages / 16 < 1 ? 1 : (stages / 16 < 512 ? stages / 16 : 512);
-    const long per = (stages + nb - 1) / nb * FW_ROWS;
-    nb = (rows + per - 1) / per;
-    FfnOutProj op = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    if (n) hipLaunchKernelGGL((k_ffn_bwd_w<false, false>), dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dx, (const unsigned short*)h, (const unsigned short*)x,
-                       (const unsigned short*)n, (const unsigned short*)w2t, (const unsigned short*)w1t, ln_w, ln_b, eps, (unsigned short*)dx_out, dw2, db2, dw1, db1,
-                       dln_w, dln_b, (long)rows, per, op);
-    else hipLaunchKernelGGL((k_ffn_bwd_w<false, true>), dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dx, (const unsigned short*)h, (const unsigned short*)x,
-                       (const unsigned short*)n, (const unsigned short*)w2t, (const unsigned short*)w1t, ln_w, ln_b, eps, (unsigned short*)dx_out, dw2, db2, dw1, db1,
-                       dln_w, dln_b, (long)rows, per, op);
-    HIPCHK(hipGetLastError());
-    return CATAN_OK;
-}
-int catan_ffn_outproj_bwd(const void* dx, const void* h, const void* x, const void* n, const void* w2t, const void* w1t, const float* ln_w, const float* ln_b, float eps,
+int catan_ffn_outproj_bwd(const void* dx, const void* h, const void* x, const void* w2t, const void* w1t, const float* ln_w, const float* ln_b, float eps,
                           void* dx_out, float* dw2, float* db2, float* dw1, float* db1, float* dln_w, float* dln_b,
                           const void* o, const void* wot, void* d_o, float* dwo, float* dbo, int64_t rows, catan_stream_t stream) {
-    if (!dx || !h || !x || (!n && !ln_b) || !w2t || !w1t || !ln_w || !dx_out || !dw2 || !db2 || !dw1 || !db1 || !dln_w || !dln_b || !o || !wot || !d_o || !dwo || !dbo || rows <= 0 ||
-        (((uintptr_t)dx | (uintptr_t)h | (uintptr_t)x | (uintptr_t)n | (uintptr_t)w2t | (uintptr_t)w1t | (uintptr_t)dx_out | (uintptr_t)o | (uintptr_t)wot | (uintptr_t)d_o) & 15))
+    if (!dx || !h || !x || !w2t || !w1t || !ln_w || !ln_b || !dx_out || !dw2 || !db2 || !dw1 || !db1 || !dln_w || !dln_b || !o || !wot || !d_o || !dwo || !dbo || rows <= 0 ||
+        (((uintptr_t)dx | (uintptr_t)h | (uintptr_t)x | (uintptr_t)w2t | (uintptr_t)w1t | (uintptr_t)dx_out | (uintptr_t)o | (uintptr_t)wot | (uintptr_t)d_o) & 15))
         return fail(CATAN_EINVAL, "catan_ffn_outproj_bwd: null or misaligned argument");
-    const long stages = (rows + FW_ROWS - 1) / FW_ROWS;
-    long nb = stages / 16 < 1 ? 1 : (stages / 16 < 512 ? stages / 16 : 512);
-    const long per = (stages + nb - 1) / nb * FW_ROWS;
-    nb = (rows + per - 1) / per;
+    long nb, per;
+    te_bwd_grid(rows, nb, per);
     FfnOutProj op = { (const unsigned short*)o, (const unsigned short*)wot, (unsigned short*)d_o, dwo, dbo };
-    if (n) hipLaunchKernelGGL((k_ffn_bwd_w<true, false>), dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dx, (const unsigned short*)h, (const unsigned short*)x,
-                       (const unsigned short*)n, (const unsigned short*)w2t, (const unsigned short*)w1t, ln_w, ln_b, eps, (unsigned short*)dx_out, dw2, db2, dw1, db1,
-                       dln_w, dln_b, (long)rows, per, op);
-    else hipLaunchKernelGGL((k_ffn_bwd_w<true, true>), dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dx, (const unsigned short*)h, (const unsigned short*)x,
-                       (const unsigned short*)n, (const unsigned short*)w2t, (const unsigned short*)w1t, ln_w, ln_b, eps, (unsigned short*)dx_out, dw2, db2, dw1, db1,
+    hipLaunchKernelGGL(k_ffn_bwd_w, dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dx, (const unsigned short*)h, (const unsigned short*)x,
+                       (const unsigned short*)w2t, (const unsigned short*)w1t, ln_w, ln_b, eps, (unsigned short*)dx_out, dw2, db2, dw1, db1,
                        dln_w, dln_b, (long)rows, per, op);
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
-int catan_ffn_outproj_bwd_rh(const void* dx, const void* x, const void* w2t, const void* w1t, const void* w1, const float* b1, const float* ln_w, const float* ln_b, float eps,
-                             void* dx_out, float* dw2, float* db2, float* dw1, float* db1, float* dln_w, float* dln_b,
-                             const void* o, const void* wot, void* d_o, float* dwo, float* dbo, int64_t rows, catan_stream_t stream) {
-    if (!dx || !x || !w2t || !w1t || !w1 || !b1 || !ln_w || !ln_b || !dx_out || !dw2 || !db2 || !dw1 || !db1 || !dln_w || !dln_b || !o || !wot || !d_o || !dwo || !dbo || rows <= 0 ||
-        (((uintptr_t)dx | (uintptr_t)x | (uintptr_t)w2t | (uintptr_t)w1t | (uintptr_t)w1 | (uintptr_t)dx_out | (uintptr_t)o | (uintptr_t)wot | (uintptr_t)d_o) & 15))
-        return fail(CATAN_EINVAL, "catan_ffn_outproj_bwd_rh: null or misaligned argument");
-    const long stages = (rows + FW_ROWS - 1) / FW_ROWS;
-    long nb = stages / 16 < 1 ? 1 : (stages / 16 < 512 ? stages / 16 : 512);
-    const long per = (stages + nb - 1) / nb * FW_ROWS;
-    nb = (rows + per - 1) / per;
-    FfnOutProj op = { (const unsigned short*)o, (const unsigned short*)wot, (unsigned short*)d_o, dwo, dbo };
-    FfnRecomputeH rh = { (const unsigned short*)w1, b1 };
-    hipLaunchKernelGGL((k_ffn_bwd_w<true, true, true>), dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dx, (const unsigned short*)nullptr, (const unsigned short*)x,
-                       (const unsigned short*)nullptr, (const unsigned short*)w2t, (const unsigned short*)w1t, ln_w, ln_b, eps, (unsigned short*)dx_out, dw2, db2, dw1, db1,
-                       dln_w, dln_b, (long)rows, per, op, rh);
-    HIPCHK(hipGetLastError());
-    return CATAN_OK;
-}
-int catan_qkv_bwd(const void* dqkv, const void* x, const void* dres, const void* n, const void* wt, const float* ln_w, const float* ln_b, float eps, void* dx_out,
+int catan_qkv_bwd(const void* dqkv, const void* x, const void* dres, const void* wt, const float* ln_w, const float* ln_b, float eps, void* dx_out,
                   float* dw, float* db, float* dln_w, float* dln_b, int64_t rows, catan_stream_t stream) {
-    if (!dqkv || !x || !dres || (!n && !ln_b) || !wt || !ln_w || !dx_out || !dw || !db || !dln_w || !dln_b || rows <= 0 ||
-        (((uintptr_t)dqkv | (uintptr_t)x | (uintptr_t)dres | (uintptr_t)n | (uintptr_t)wt | (uintptr_t)dx_out) & 15))
+    if (!dqkv || !x || !dres || !wt || !ln_w || !ln_b || !dx_out || !dw || !db || !dln_w || !dln_b || rows <= 0 ||
+        (((uintptr_t)dqkv | (uintptr_t)x | (uintptr_t)dres | (uintptr_t)wt | (uintptr_t)dx_out) & 15))
         return fail(CATAN_EINVAL, "catan_qkv_bwd: null or misaligned argument");
-    const long stages = (rows + FW_ROWS - 1) / FW_ROWS;
-    long nb = stages / 16 < 1 ? 1 : (stages / 16 < 512 ? stages / 16 : 512);
-    const long per = (stages + nb - 1) / nb * FW_ROWS;
-    nb = (rows + per - 1) / per;
-    if (n) hipLaunchKernelGGL(k_qkv_bwd_w<false>, dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dqkv, (const unsigned short*)x, (const unsigned short*)dres,
-                       (const unsigned short*)n, (const unsigned short*)wt, ln_w, ln_b, eps, (unsigned short*)dx_out, dw, db, dln_w, dln_b, (long)rows, per);
-    else hipLaunchKernelGGL(k_qkv_bwd_w<true>, dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dqkv, (const unsigned short*)x, (const unsigned short*)dres,
-                       (const unsigned short*)n, (const unsigned short*)wt, ln_w, ln_b, eps, (unsigned short*)dx_out, dw, db, dln_w, dln_b, (long)rows, per);
+    long nb, per;
+    te_bwd_grid(rows, nb, per);
+    hipLaunchKernelGGL(k_qkv_bwd_w, dim3((unsigned)nb), dim3(256), 0, S(stream), (const unsigned short*)dqkv, (const unsigned short*)x, (const unsigned short*)dres,
+                       (const unsigned short*)nullptr, (const unsigned short*)wt, ln_w, ln_b, eps, (unsigned short*)dx_out, dw, db, dln_w, dln_b, (long)rows, per);
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }

@@ -330,7 +330,7 @@ __global__ __launch_bounds__(TE_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             if (SAVE && sv.n2[l] != nullptr) te_dump<64>(Nb, TE_PX, sv.n2[l], t0, nt, tid);
             te_gemm<64, 128, 1>(Nb, TE_PX, w1, vl + 512, Q, TE_PH, lane, wave);
             __syncthreads();
-            if (SAVE && sv.h[l] != nullptr) te_dump<128>(Q, TE_PH, sv.h[l], t0, nt, tid);   // (optional: catan_ffn_outproj_bwd_rh recomputes it)
+            if (SAVE && sv.h[l] != nullptr) te_dump<128>(Q, TE_PH, sv.h[l], t0, nt, tid);   // (optional, as catan_te_saves_t says)
             te_gemm<128, 64, 2>(Q, TE_PH, w2, vl + 640, X, TE_PX, lane, wave);
             __syncthreads();
         }

@@ -903,40 +903,59 @@ _TE_SAVES = (("tiles64", 64), ("a0", 64), ("xin0", 64), ("xin1", 64), ("n1_0", 6
              ("xmid0", 64), ("xmid1", 64), ("n2_0", 64), ("n2_1", 64), ("h0", 128), ("h1", 128), ("xfin", 64), ("p", 25))     # catan_te_saves_t's order
 
 
+# The parameters' positions in _te_params' list, which is also the order of _TileEncoderTrain.backward's gradients: the head, sixteen
+# per encoder layer, the tail.  _te_params and the backward both go through these names.
+_TE_HEAD = ("first_w", "first_b", "norm2_w", "norm2_b")
+_TE_LAYER = ("ln1_w", "ln1_b", "wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2")
+_TE_TAIL = ("out_w", "out_b", "norm_w", "norm_b")
+_TE_LAYERS = 2
+
+
+def _te_pos(name, l=None):
+    """the position of a parameter in _te_params' list; the per-layer names take their layer l"""
+    if l is not None:
+        return len(_TE_HEAD) + len(_TE_LAYER) * l + _TE_LAYER.index(name)
+    return _TE_HEAD.index(name) if name in _TE_HEAD else len(_TE_HEAD) + len(_TE_LAYER) * _TE_LAYERS + _TE_TAIL.index(name)
+
+
 def _te_params(te):
-    ps = [te.first_layer.weight, te.first_layer.bias, te.norm_2.weight, te.norm_2.bias]
+    named = dict(first_w=te.first_layer.weight, first_b=te.first_layer.bias, norm2_w=te.norm_2.weight, norm2_b=te.norm_2.bias,
+                 out_w=te.out_proj.weight, out_b=te.out_proj.bias, norm_w=te.norm.weight, norm_b=te.norm.bias)
+    ps = [named[n] for n in _TE_HEAD]
     for layer in te.encoder_layers:
         mha, ffn = layer.multi_headed_attention, layer.pointwise_net
-        ps += [layer.sublayers[0].norm.weight, layer.sublayers[0].norm.bias]
-        for n in mha.qkv_nets:
-            ps += [n.weight, n.bias]
-        ps += [mha.out_proj_net.weight, mha.out_proj_net.bias, layer.sublayers[1].norm.weight, layer.sublayers[1].norm.bias,
-               ffn.linear1.weight, ffn.linear1.bias, ffn.linear2.weight, ffn.linear2.bias]
-    return ps + [te.out_proj.weight, te.out_proj.bias, te.norm.weight, te.norm.bias]
+        q, k, v = mha.qkv_nets
+        per = dict(ln1_w=layer.sublayers[0].norm.weight, ln1_b=layer.sublayers[0].norm.bias, wq=q.weight, bq=q.bias, wk=k.weight, bk=k.bias,
+                   wv=v.weight, bv=v.bias, wo=mha.out_proj_net.weight, bo=mha.out_proj_net.bias, ln2_w=layer.sublayers[1].norm.weight,
+                   ln2_b=layer.sublayers[1].norm.bias, w1=ffn.linear1.weight, b1=ffn.linear1.bias, w2=ffn.linear2.weight, b2=ffn.linear2.bias)
+        ps += [per[n] for n in _TE_LAYER]
+    return ps + [named[n] for n in _TE_TAIL]
 
 
-def _rows_product(x2, wt, aux=None, mode=MODE_NONE):
-    """x2 [rows, K] @ wt[N, K].T (bf16), optional ReLU-backward mask: the row kernel, or the library for shapes outside its range"""
-    y = _linear_rows(x2, wt, None, aux, mode)
-    if y is None:
-        y = torch.nn.functional.linear(x2, wt)
-        if mode == MODE_RELU_MASK:
-            y = y * (aux > 0).to(y.dtype)
-    return y
+def _te_accumulators(device, **shapes):
+    """ONE zeroed fp32 accumulator (one fill) cut into a tensor of each given shape, in the order given -> {name: tensor}"""
+    sizes = [int(torch.Size(sh).numel()) for sh in shapes.values()]
+    acc = grad_zeros((sum(sizes),), device)
+    out, o = {}, 0
+    for (name, sh), n in zip(shapes.items(), sizes):
+        out[name] = acc[o:o + n].view(sh)
+        o += n
+    return out
 
 
-def _ln_backward(x, w, b, dy, eps, relu, dres=None):
-    """-> (dx, dw, db) of LayerNorm (+ ReLU) over the last dim of bf16 x [rows, D]; dres: a second gradient of x added in"""
+def _rows_product(x2, wt):
+    """x2 [rows, K] @ wt[N, K].T (bf16): the row kernel, or the library for shapes outside its range"""
+    y = _linear_rows(x2, wt, None)
+    return y if y is not None else torch.nn.functional.linear(x2, wt)
+
+
+def _ln_backward(x, w, b, dy, eps, relu):
+    """-> (dx, dw, db) of LayerNorm (+ ReLU) over the last dim of bf16 x [rows, D]"""
     rows, D = x.shape
     dx = torch.empty_like(x)
     dwb = grad_zeros((2, D), x.device)
     wf, bf = w.detach().float().contiguous(), b.detach().float().contiguous()
-    L = _lib.lib()
-    if dres is None:
-        _lib.check(L.catan_layer_norm_bwd(_ptr(x), _ptr(wf), _ptr(bf), _ptr(dy), _ptr(dx), _ptr(dwb[0]), _ptr(dwb[1]), rows, D, float(eps), int(relu), 1, _stream()))
-    else:
-        _lib.check(L.catan_layer_norm_bwd_res(_ptr(x), _ptr(wf), _ptr(bf), _ptr(dy), _ptr(dres), _ptr(dx), _ptr(dwb[0]), _ptr(dwb[1]), rows, D, float(eps),
-                                              int(relu), 1, _stream()))
+    _lib.check(_lib.lib().catan_layer_norm_bwd(_ptr(x), _ptr(wf), _ptr(bf), _ptr(dy), _ptr(dx), _ptr(dwb[0]), _ptr(dwb[1]), rows, D, float(eps), int(relu), 1, _stream()))
     return dx, dwb[0], dwb[1]
 
 
@@ -1041,7 +1060,7 @@ class _TeWorkspace(object):
 
     @classmethod
     def lease(cls, n, device):
-        if cls.busy or os.environ.get("CATAN_TE_WORKSPACE", "1") == "0":
+        if cls.busy or not TE_WORKSPACE:
             return None
         if cls.buf is None or cls.buf.device != torch.device(device) or cls.buf.numel() < n:
             cls.buf = None                      # (free the old one first)
@@ -1050,15 +1069,18 @@ class _TeWorkspace(object):
         return cls.Lease(cls.buf)
 
 
-def _te_backward_fused_w():
-    """The tile encoder's backward runs k_ffn_bwd_w / k_qkv_bwd_w (the default; the toggles select the older chains for tests)."""
-    return os.environ.get("CATAN_TE_BWD_UNFUSED") != "1" and os.environ.get("CATAN_TE_BWD_W", "1") == "1"
+# CATAN_TE_WORKSPACE=0: every training forward of the tile encoder takes its activations from the allocator (the way out for retain_graph).
+# CATAN_TE_TRAIN_UNFUSED=1: the encoder trains through its sub-layers' kernels with autograd between them - the path of unsupported
+# shapes and dtypes, and the oracle of the fused path's test, which sets the attribute.  Both are read here, once.
+TE_WORKSPACE = os.environ.get("CATAN_TE_WORKSPACE", "1") != "0"
+TE_TRAIN_UNFUSED = os.environ.get("CATAN_TE_TRAIN_UNFUSED") == "1"
+# what the training forward stores for the backward: catan_te_saves_t's fields without the LayerNorm outputs (see _TileEncoderTrain.forward)
+_TE_STORED = tuple((n, w) for n, w in _TE_SAVES if not n.startswith(("n1_", "n2_")))
 
 
 class _TileEncoderTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tiles, te, out_cols, *params):
-        import ctypes as C
         if weight_images.enabled:
             im = _te_images(te)
             wts, vecs = im.wts, im.vecs
@@ -1072,36 +1094,22 @@ class _TileEncoderTrain(torch.autograd.Function):
         # caching allocator every step, the slightly different sizes fragment it (reserved memory grew from 100 to 190 GB in three
         # updates).  ONE workspace is kept instead and leased to the forward whose backward has not run yet; a second forward
         # in flight (gradient accumulation) gets a fresh buffer as before.
-        # The LayerNorm outputs n1 / n2 are NOT stored when the backward runs the one-pass kernels with the weight gradients: k_qkv_bwd_w
-        # and k_ffn_bwd_w recompute them from the LayerNorm inputs they read anyway (at no cost: 754 vs 769 us and 1.35 vs 1.37 ms at
-        # 3.9 M rows), and the forward writes 512 B per token less (3.04 -> 2.76 ms at 204 800 boards).  CATAN_TE_RECOMPUTE_N=1: only n1
-        # recomputed, 0: both stored and read (tools/bench_te_n_recompute.py, the tests).
-        level = int(os.environ.get("CATAN_TE_RECOMPUTE_N", "2")) if _te_backward_fused_w() else 0
-        drop = ("n1_", "n2_")[:level]
-        # CATAN_TE_RECOMPUTE_H=1: the FFN's hidden activation h (the widest one: 256 of the 1 024 bytes per token and layer) is not stored either:
-        # k_ffn_bwd_w<., true, true> recomputes it from the recomputed n2 - one more 16 x 64 x 128 product per wave and stage.  OFF by default:
-        # measured at config 3's minibatch (tools/ab_step_switches.py, profiles/r05_ab_recompute_h.txt) the step is 22.12 ms with h stored
-        # and 22.25 ms with h recomputed - the pass is not bound by the bytes it reads, the product costs what the 9.7 KB per board save
-        ctx.recompute_h = level == 2 and os.environ.get("CATAN_TE_RECOMPUTE_H", "0") == "1" and os.environ.get("CATAN_TE_BWD_OP", "1") == "1"
-        if ctx.recompute_h:
-            drop = drop + ("h",)
-            ctx.packed = (wts, vecs)
-        names = [(n, w) for n, w in _TE_SAVES if not (drop and n.startswith(drop))]
-        need = T * sum(w for _, w in names)
+        # The LayerNorm outputs n1 / n2 are NOT stored: k_qkv_bwd_w and k_ffn_bwd_w recompute them from the LayerNorm inputs they read
+        # anyway (at no cost: 754 vs 769 us and 1.35 vs 1.37 ms at 3.9 M rows), and the forward writes 512 B per token less (3.04 ->
+        # 2.76 ms at 204 800 boards).
+        need = T * sum(w for _, w in _TE_STORED)
         lease = _TeWorkspace.lease(need, x.device)
         ctx.lease = lease
         buf = lease.buf if lease is not None else torch.empty((need,), dtype=torch.bfloat16, device=x.device)
-        saves, off = [], 0
-        for _, w in names:
-            saves.append(buf[off:off + T * w].view(T, w))
+        saves, off = {}, 0
+        for n, w in _TE_STORED:
+            saves[n] = buf[off:off + T * w].view(T, w)
             off += T * w
-        by_name = dict(zip([n for n, _ in names], saves))
-        ptrs = (C.c_void_p * len(_TE_SAVES))(*[by_name[n].data_ptr() if n in by_name else None for n, _ in _TE_SAVES])
-        ctx.save_names = [n for n, _ in names]
+        ptrs = (C.c_void_p * len(_TE_SAVES))(*[saves[n].data_ptr() if n in saves else None for n, _ in _TE_SAVES])
         # out_cols > 475: board rows padded with zero columns to whole 16-byte pieces (nn_kernels.expand_rows, aligned GEMM operands)
         out = (torch.empty if out_cols == 475 else torch.zeros)((B, out_cols), dtype=torch.bfloat16, device=x.device)
         _lib.check(_lib.lib().catan_tile_encoder_fwd_train(_ptr(x), _ptr(wts), _ptr(vecs), _ptr(out), out_cols, C.cast(ptrs, C.c_void_p), B, _stream()))
-        ctx.save_for_backward(*saves, *params)
+        ctx.save_for_backward(*saves.values(), *params)
         ctx.eps = float(te.norm.eps)
         ctx.B = B
         return out
@@ -1115,113 +1123,70 @@ class _TileEncoderTrain(torch.autograd.Function):
             raise RuntimeError("_TileEncoderTrain: second backward over a forward whose activation workspace has been released "
                                "(retain_graph is not supported with the shared workspace; set CATAN_TE_WORKSPACE=0)")
         ctx.consumed = True
-        ns = len(ctx.save_names)
-        sv = dict(zip(ctx.save_names, ctx.saved_tensors[:ns]))
+        ns = len(_TE_STORED)
+        sv = dict(zip([n for n, _ in _TE_STORED], ctx.saved_tensors[:ns]))
         P = ctx.saved_tensors[ns:]
         B, eps, bf = ctx.B, ctx.eps, torch.bfloat16
         T = B * 19
         g = [None] * len(P)
+        pos = _te_pos
         im = _te_images(ctx.te) if weight_images.enabled else None
         L = _lib.lib()
+
+        def wt(*names, l=None):                 # the transposed bf16 weight(s) [in][sum of outs] as a per-use cast (weight_images off)
+            return torch.cat([P[pos(n, l)] for n in names], 0).to(bf).t().contiguous()
+
+        def f32(name, l):                       # a LayerNorm vector as the kernels read it
+            return P[pos(name, l)].detach().float().contiguous()
+
         with torch.autocast("cuda", enabled=False):
+            # ---- the final LayerNorm (+ ReLU) and the output projection
             d = _aligned(dout[:, :475].reshape(T, 25).to(bf))
-            dp, g[38], g[39] = _ln_backward(sv["p"], P[38], P[39], d, eps, True)
-            dx = _rows_product(dp, im.wpt if im is not None else P[36].to(bf).t().contiguous())   # [T, 64]
-            g[36], g[37] = _wgrad(sv["xfin"], dp, True)
-            for l in (1, 0):
-                b = 4 + 16 * l
-                xin, n1, qkv, o, xmid, n2, h = (sv.get(k + str(l)) for k in ("xin", "n1_", "qkv", "o", "xmid", "n2_", "h"))
+            dp, g[pos("norm_w")], g[pos("norm_b")] = _ln_backward(sv["p"], P[pos("norm_w")], P[pos("norm_b")], d, eps, True)
+            dx = _rows_product(dp, im.wpt if im is not None else wt("out_w"))                     # [T, 64]
+            g[pos("out_w")], g[pos("out_b")] = _wgrad(sv["xfin"], dp, True)
+            for l in reversed(range(_TE_LAYERS)):
+                xin, qkv, o, xmid, h = (sv[k + str(l)] for k in ("xin", "qkv", "o", "xmid", "h"))
                 if im is not None:
                     w2t, w1t, wot, wqt = im.w2t[l], im.w1t[l], im.wot[l], im.wqt[l]
                 else:
-                    w2t, w1t, wot = P[b + 14].to(bf).t().contiguous(), P[b + 12].to(bf).t().contiguous(), P[b + 8].to(bf).t().contiguous()
-                    wqt = torch.cat([P[b + 2], P[b + 4], P[b + 6]], 0).to(bf).t().contiguous()
-                if _te_backward_fused_w():
-                    # k_ffn_bwd_w: the chain below AND both weight gradients in one pass over the rows (dH never leaves the chip)
-                    dxmid = torch.empty_like(xmid)
-                    acc = grad_zeros((64 * 128 + 64 + 128 * 64 + 128 + 128 + 64 * 64 + 64,), xmid.device)
-                    dw2, db2, dw1, db1, dl = acc[:8192], acc[8192:8256], acc[8256:16448], acc[16448:16576], acc[16576:16704]
-                    dwo, dbo = acc[16704:20800], acc[20800:]
-                    lw, lb = P[b + 10].detach().float().contiguous(), P[b + 11].detach().float().contiguous()
-                    if h is None:                                           # (recompute_h) ... h recomputed from the rows of xmid, with the out-projection's backward
-                        do = torch.empty_like(o)
-                        wts, vecs = ctx.packed                              # the forward's packed parameters: W1 [128][64] and b1 [128] of layer l
-                        w1 = wts[4096 + 32768 * l + 16384:4096 + 32768 * l + 16384 + 8192]
-                        b1 = vecs[192 + 704 * l + 512:192 + 704 * l + 640]
-                        _lib.check(_lib.lib().catan_ffn_outproj_bwd_rh(_ptr(dx), _ptr(xmid), _ptr(w2t), _ptr(w1t), _ptr(w1), _ptr(b1), _ptr(lw), _ptr(lb), eps, _ptr(dxmid),
-                                                                       _ptr(dw2), _ptr(db2), _ptr(dw1), _ptr(db1), _ptr(dl[:64]), _ptr(dl[64:]),
-                                                                       _ptr(o), _ptr(wot), _ptr(do), _ptr(dwo), _ptr(dbo), T, _stream()))
-                        g[b + 8], g[b + 9] = dwo.view(64, 64), dbo
-                    elif os.environ.get("CATAN_TE_BWD_OP", "1") == "1":     # ... and the out-projection's dO and weight gradient from the same rows
-                        do = torch.empty_like(o)
-                        _lib.check(_lib.lib().catan_ffn_outproj_bwd(_ptr(dx), _ptr(h), _ptr(xmid), _ptr(n2) if n2 is not None else None, _ptr(w2t), _ptr(w1t), _ptr(lw), _ptr(lb), eps, _ptr(dxmid),
-                                                                    _ptr(dw2), _ptr(db2), _ptr(dw1), _ptr(db1), _ptr(dl[:64]), _ptr(dl[64:]),
-                                                                    _ptr(o), _ptr(wot), _ptr(do), _ptr(dwo), _ptr(dbo), T, _stream()))
-                        g[b + 8], g[b + 9] = dwo.view(64, 64), dbo
-                    else:
-                        do = None
-                        _lib.check(_lib.lib().catan_ffn_bwd(_ptr(dx), _ptr(h), _ptr(xmid), _ptr(n2) if n2 is not None else None, _ptr(w2t), _ptr(w1t), _ptr(lw), _ptr(lb), eps, _ptr(dxmid),
-                                                            _ptr(dw2), _ptr(db2), _ptr(dw1), _ptr(db1), _ptr(dl[:64]), _ptr(dl[64:]), T, _stream()))
-                    g[b + 14], g[b + 15], g[b + 12], g[b + 13], g[b + 10], g[b + 11] = dw2.view(64, 128), db2, dw1.view(128, 64), db1, dl[:64], dl[64:]
-                    dh = None
-                elif os.environ.get("CATAN_TE_BWD_UNFUSED") == "1":
-                    dh = _rows_product(dx, w2t, h, MODE_RELU_MASK)                        # (dx @ w2) where h > 0
-                    dn2 = _rows_product(dh, w1t)
-                    dxmid, g[b + 10], g[b + 11] = _ln_backward(xmid, P[b + 10], P[b + 11], dn2, eps, False, dres=dx)
-                else:                           # the same three steps in one pass over the rows (k_ffn_bwd_dx)
-                    dh, dxmid = torch.empty_like(h), torch.empty_like(xmid)
-                    dl = grad_zeros((2, 64), h.device)
-                    lw = P[b + 10].detach().float().contiguous()                          # (named: alive until the launch is queued)
-                    _lib.check(_lib.lib().catan_ffn_bwd_dx(_ptr(dx), _ptr(h), _ptr(xmid), _ptr(w2t), _ptr(w1t), _ptr(lw), eps, _ptr(dh), _ptr(dxmid),
-                                                           _ptr(dl[0]), _ptr(dl[1]), T, _stream()))
-                    g[b + 10], g[b + 11] = dl[0], dl[1]
-                if dh is not None:
-                    g[b + 14], g[b + 15] = _wgrad(h, dx, True)
-                    g[b + 12], g[b + 13] = _wgrad(n2, dh, True)
-                if dh is not None or do is None:
-                    do = _rows_product(dxmid, wot)
-                    g[b + 8], g[b + 9] = _wgrad(o, dxmid, True)
+                    w2t, w1t, wot, wqt = wt("w2", l=l), wt("w1", l=l), wt("wo", l=l), wt("wq", "wk", "wv", l=l)
+                # ---- k_ffn_bwd_w: the pointwise sub-layer's dX chain, both weight gradients, and the out-projection's dO and weight
+                #      gradient in one pass over the rows (dH never leaves the chip)
+                dxmid, do = torch.empty_like(xmid), torch.empty_like(o)
+                a = _te_accumulators(xmid.device, w2=(64, 128), b2=(64,), w1=(128, 64), b1=(128,), ln2_w=(64,), ln2_b=(64,), wo=(64, 64), bo=(64,))
+                lw, lb = f32("ln2_w", l), f32("ln2_b", l)                                         # (named: alive until the launch is queued)
+                _lib.check(L.catan_ffn_outproj_bwd(_ptr(dx), _ptr(h), _ptr(xmid), _ptr(w2t), _ptr(w1t), _ptr(lw), _ptr(lb), eps, _ptr(dxmid),
+                                                   _ptr(a["w2"]), _ptr(a["b2"]), _ptr(a["w1"]), _ptr(a["b1"]), _ptr(a["ln2_w"]), _ptr(a["ln2_b"]),
+                                                   _ptr(o), _ptr(wot), _ptr(do), _ptr(a["wo"]), _ptr(a["bo"]), T, _stream()))
+                for n, t in a.items():                                                            # (these accumulators carry _TE_LAYER's names)
+                    g[pos(n, l)] = t
+                # ---- the attention
                 dqkv = torch.empty_like(qkv)
-                _lib.check(_lib.lib().catan_attention_bwd(_ptr(qkv), None, _ptr(do), _ptr(dqkv), B, 19, 4, 16, 1, _stream()))
-                fused_w = _te_backward_fused_w()
-                if fused_w:                     # k_qkv_bwd_w: the QKV product's weight gradient and the dX chain in one pass over the rows
-                    dx = torch.empty_like(xin)
-                    acc = grad_zeros((192 * 64 + 192 + 128,), xin.device)
-                    dwq, dbq, dl = acc[:12288].view(192, 64), acc[12288:12480], acc[12480:]
-                    lw, lb = P[b].detach().float().contiguous(), P[b + 1].detach().float().contiguous()
-                    _lib.check(_lib.lib().catan_qkv_bwd(_ptr(dqkv), _ptr(xin), _ptr(dxmid), _ptr(n1) if n1 is not None else None, _ptr(wqt), _ptr(lw), _ptr(lb), eps,
-                                                        _ptr(dx), _ptr(dwq), _ptr(dbq),
-                                                        _ptr(dl[:64]), _ptr(dl[64:]), T, _stream()))
-                    g[b], g[b + 1] = dl[:64], dl[64:]
-                else:
-                    dwq, dbq = _wgrad(n1, dqkv, True)
-                for k in range(3):
-                    g[b + 2 + 2 * k], g[b + 3 + 2 * k] = dwq[64 * k:64 * k + 64], dbq[64 * k:64 * k + 64]
-                if fused_w:
-                    pass
-                elif os.environ.get("CATAN_TE_BWD_UNFUSED") == "1":
-                    dn1 = _rows_product(dqkv, wqt)
-                    dx, g[b], g[b + 1] = _ln_backward(xin, P[b], P[b + 1], dn1, eps, False, dres=dxmid)
-                else:                           # the same two steps in one pass over the rows (k_qkv_bwd_dx)
-                    dx = torch.empty_like(xin)
-                    dl = grad_zeros((2, 64), xin.device)
-                    lw = P[b].detach().float().contiguous()
-                    _lib.check(_lib.lib().catan_qkv_bwd_dx(_ptr(dqkv), _ptr(xin), _ptr(dxmid), _ptr(wqt), _ptr(lw), eps, _ptr(dx), _ptr(dl[0]), _ptr(dl[1]), T, _stream()))
-                    g[b], g[b + 1] = dl[0], dl[1]
-            da0, g[2], g[3] = _ln_backward(sv["a0"], P[2], P[3], dx, eps, True)
-            dw0, g[1] = _wgrad(sv["tiles64"], da0, True)
-            g[0] = dw0[:, :60]
+                _lib.check(L.catan_attention_bwd(_ptr(qkv), None, _ptr(do), _ptr(dqkv), B, 19, 4, 16, 1, _stream()))
+                # ---- k_qkv_bwd_w: the QKV product's weight gradient and the dX chain in one pass over the rows
+                dx = torch.empty_like(xin)
+                a = _te_accumulators(xin.device, wqkv=(192, 64), bqkv=(192,), ln1_w=(64,), ln1_b=(64,))
+                lw, lb = f32("ln1_w", l), f32("ln1_b", l)
+                _lib.check(L.catan_qkv_bwd(_ptr(dqkv), _ptr(xin), _ptr(dxmid), _ptr(wqt), _ptr(lw), _ptr(lb), eps, _ptr(dx), _ptr(a["wqkv"]), _ptr(a["bqkv"]),
+                                           _ptr(a["ln1_w"]), _ptr(a["ln1_b"]), T, _stream()))
+                g[pos("ln1_w", l)], g[pos("ln1_b", l)] = a["ln1_w"], a["ln1_b"]
+                for k, n in enumerate("qkv"):
+                    g[pos("w" + n, l)], g[pos("b" + n, l)] = a["wqkv"][64 * k:64 * k + 64], a["bqkv"][64 * k:64 * k + 64]
+            # ---- the first LayerNorm (+ ReLU) and the first layer
+            da0, g[pos("norm2_w")], g[pos("norm2_b")] = _ln_backward(sv["a0"], P[pos("norm2_w")], P[pos("norm2_b")], dx, eps, True)
+            dw0, g[pos("first_b")] = _wgrad(sv["tiles64"], da0, True)
+            g[pos("first_w")] = dw0[:, :60]
         if ctx.lease is not None:
             ctx.lease.release()
         return (None, None, None) + tuple(g)
 
 
 def tile_encoder_train_supported(te, tiles):
-    """training on the GPU under bf16 autocast, the reference's sizes; CATAN_TE_TRAIN_UNFUSED=1 keeps the sub-layer kernels"""
-    import os
+    """training on the GPU under bf16 autocast, the reference's sizes; TE_TRAIN_UNFUSED keeps the sub-layer kernels"""
     if not torch.is_grad_enabled() or not tiles.is_cuda or tiles.dim() != 3 or tuple(tiles.shape[1:]) != (19, 60) or tiles.requires_grad:
         return False
-    if os.environ.get("CATAN_TE_TRAIN_UNFUSED") == "1":
+    if TE_TRAIN_UNFUSED:
         return False
     if not (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16):
         return False

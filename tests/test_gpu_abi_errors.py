@@ -48,10 +48,13 @@ def test_bad_arguments_are_reported_not_crashed(hip_lib):
     assert "outside the permutation" in err(L.catan_scatter_rows_ranges(P(b16), 1024, P(idx), 8, C.cast(rng3, C.c_void_p), 1, None, None, P(b16), 1024, st))
     rng6 = (C.c_int64 * 6)(0, 4, 0, 2, 6, 9)          # the second range's rows of dy do not follow the first's
     assert "consecutive" in err(L.catan_scatter_rows_ranges(P(b16), 1024, P(idx), 8, C.cast(rng6, C.c_void_p), 2, None, None, P(b16), 1024, st))
-    assert "null or misaligned" in err(L.catan_ffn_bwd_dx(P(b16), None, P(b16), P(b16), P(b16), P(dw), 1e-5, P(b16), P(b16), P(dw), P(dw), 16, st))
-    assert "null or misaligned" in err(L.catan_qkv_bwd_dx(P(b16), P(b16), C.c_void_p(b16.data_ptr() + 8), P(b16), P(dw), 1e-5, P(b16), P(dw), P(dw), 16, st))
-    assert "null or misaligned" in err(L.catan_ffn_bwd(P(b16), P(b16), P(b16), None, P(b16), P(b16), P(dw), None, 1e-5, P(b16), P(dw), P(dw), P(dw), P(dw), P(dw), P(dw), 16, st))
-    assert "null or misaligned" in err(L.catan_qkv_bwd(P(b16), P(b16), P(b16), P(b16), C.c_void_p(b16.data_ptr() + 4), P(dw), P(dw), 1e-5, P(b16), P(dw), P(dw), P(dw), P(dw), 16, st))
+    ffn = lambda h, x: L.catan_ffn_outproj_bwd(P(b16), h, x, P(b16), P(b16), P(dw), P(dw), 1e-5, P(b16), P(dw), P(dw), P(dw), P(dw), P(dw), P(dw),
+                                               P(b16), P(b16), P(b16), P(dw), P(dw), 16, st)
+    qkv = lambda wt, ln_b: L.catan_qkv_bwd(P(b16), P(b16), P(b16), wt, P(dw), ln_b, 1e-5, P(b16), P(dw), P(dw), P(dw), P(dw), 16, st)
+    assert "null or misaligned" in err(ffn(None, P(b16)))
+    assert "null or misaligned" in err(ffn(P(b16), C.c_void_p(b16.data_ptr() + 8)))
+    assert "null or misaligned" in err(qkv(P(b16), None))
+    assert "null or misaligned" in err(qkv(C.c_void_p(b16.data_ptr() + 4), P(dw)))
     assert "bad arguments" in err(L.catan_weight_images(None, 3, st)) and "bad arguments" in err(L.catan_weight_images(P(b16), 0, st))
     saves = (C.c_void_p * 18)(*([b16.data_ptr()] * 16 + [0, b16.data_ptr()]))    # xfin missing (p, the last, is optional)
     assert "save buffer" in err(L.catan_tile_encoder_fwd_train(P(b16), P(b16), P(dw), P(b16), 475, C.cast(saves, C.c_void_p), 4, st))

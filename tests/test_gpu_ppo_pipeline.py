@@ -1104,11 +1104,15 @@ def test_fused_tile_encoder_training_forward_vs_unfused(hip_lib, monkeypatch):
     (catan_tile_encoder_fwd_train + nn_kernels._TileEncoderTrain) against the unfused training path (one kernel per sub-layer,
     autograd between them): same output within bf16 rounding, and every parameter's gradient as close to the fp32 gradient of
     the same module as the unfused bf16 path's is.  1 037 boards take the library fall-backs of the row products, 14 518 boards
-    (275 842 token rows) the row kernels; ragged counts exercise partial groups of boards."""
+    (275 842 token rows) the row kernels; ragged counts exercise partial groups of boards.  The fused chain's gradients are also held
+    directly against the unfused chain's, which shares no backward code with it: per parameter within FUSED_VS_UNFUSED of the scale,
+    twice the largest distance measured over the three sizes before the fused chain's older variants were removed (0.106607; the
+    factor 2 for the run-to-run spread of the fp32-atomic accumulation order; profiles/te_backward_refactor_gradients.txt)."""
     import torch
     from settlers_of_catan_rl_amd import nn_kernels
     from settlers_of_catan_rl_amd.env import VecCatanEnv
     from settlers_of_catan_rl_amd.policy import CatanPolicy
+    FUSED_VS_UNFUSED = 2 * 0.106607
     torch.manual_seed(0)
     net = CatanPolicy().cuda()
     with torch.no_grad():
@@ -1127,12 +1131,7 @@ def test_fused_tile_encoder_training_forward_vs_unfused(hip_lib, monkeypatch):
         if mode == "fp32":
             out = te(tiles.float())
         else:
-            monkeypatch.setenv("CATAN_TE_TRAIN_UNFUSED", "1" if mode == "unfused" else "0")
-            monkeypatch.setenv("CATAN_TE_BWD_UNFUSED", "1" if mode == "fused, backward in separate steps" else "0")
-            monkeypatch.setenv("CATAN_TE_BWD_W", "0" if mode == "fused, weight gradients in their own kernels" else "1")
-            monkeypatch.setenv("CATAN_TE_BWD_OP", "0" if mode == "fused, out-projection backward in its own kernels" else "1")
-            monkeypatch.setenv("CATAN_TE_RECOMPUTE_N", {"fused, LayerNorm outputs stored": "0", "fused, LayerNorm-2 outputs stored": "1"}.get(mode, "2"))
-            monkeypatch.setenv("CATAN_TE_RECOMPUTE_H", "1" if mode == "fused, hidden FFN activation recomputed" else "0")
+            monkeypatch.setattr(nn_kernels, "TE_TRAIN_UNFUSED", mode == "unfused")
             with torch.autocast("cuda", dtype=torch.bfloat16):
                 assert nn_kernels.tile_encoder_train_supported(te, tiles) == (mode != "unfused")
                 out = te(tiles)
@@ -1145,31 +1144,11 @@ def test_fused_tile_encoder_training_forward_vs_unfused(hip_lib, monkeypatch):
         o32, g32 = run(tiles, "fp32")
         ou, gu = run(tiles, "unfused")
         of, gf = run(tiles, "fused")
-        oc, gc = run(tiles, "fused, backward in separate steps")      # the pointwise sub-layer's backward as three kernels instead of k_ffn_bwd_dx
-        ow, gw_ = run(tiles, "fused, weight gradients in their own kernels")   # k_ffn_bwd_dx + two catan_linear_wgrad instead of k_ffn_bwd_w
-        oo, go_ = run(tiles, "fused, out-projection backward in its own kernels")   # k_ffn_bwd_w<false> + row product + catan_linear_wgrad
-        # the default backward recomputes the LayerNorm outputs n1 / n2 from their inputs (k_qkv_bwd_w<true>, k_ffn_bwd_w<., true>);
-        # here the forward stores both and the passes read them / stores n2 only
-        on, gn = run(tiles, "fused, LayerNorm outputs stored")
-        on2, gn2 = run(tiles, "fused, LayerNorm-2 outputs stored")
-        # ... and with the FFN's hidden activation h = relu(n2 W1^T + b1) recomputed instead of stored (k_ffn_bwd_w<true, true, true>; off by
-        # default: measured at parity).  The recomputed h is the forward kernel's own arithmetic on the same bf16 inputs, so the two
-        # backward passes see the same h up to MFMA summation order
-        oh, gh = run(tiles, "fused, hidden FFN activation recomputed")
-        assert torch.equal(oh, of)
+        assert of.shape == (B, 475)
+        # the fused chain against the independently written unfused one, directly
         for n in names:
             scale = float(g32[n].norm()) + 1e-3 * max(float(x.norm()) for x in g32.values())
-            assert float((gf[n] - gh[n]).norm()) / scale <= 0.01, (B, n, float((gf[n] - gh[n]).norm()) / scale)
-        assert of.shape == (B, 475) and torch.equal(oc, of) and torch.equal(ow, of) and torch.equal(oo, of) and torch.equal(on, of) and torch.equal(on2, of)
-        for n in names:
-            scale = float(g32[n].norm()) + 1e-3 * max(float(x.norm()) for x in g32.values())
-            assert float((gf[n] - go_[n]).norm()) / scale <= 0.02, (B, n, float((gf[n] - go_[n]).norm()) / scale)
-            assert float((gf[n] - gn[n]).norm()) / scale <= 0.01, (B, n, float((gf[n] - gn[n]).norm()) / scale)
-            assert float((gf[n] - gn2[n]).norm()) / scale <= 0.01, (B, n, float((gf[n] - gn2[n]).norm()) / scale)
-        for n in names:
-            scale = float(g32[n].norm()) + 1e-3 * max(float(x.norm()) for x in g32.values())
-            assert float((gf[n] - gc[n]).norm()) / scale <= 0.02, (B, n, float((gf[n] - gc[n]).norm()) / scale)
-            assert float((gf[n] - gw_[n]).norm()) / scale <= 0.02, (B, n, float((gf[n] - gw_[n]).norm()) / scale)
+            assert float((gf[n] - gu[n]).norm()) / scale <= FUSED_VS_UNFUSED, (B, n, float((gf[n] - gu[n]).norm()) / scale)
         e_f, e_u = float((of - o32).abs().max()), float((ou - o32).abs().max())
         assert e_f <= max(2.0 * e_u, 0.06), (B, e_f, e_u)
         assert set(gf) == set(names)

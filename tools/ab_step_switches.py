@@ -37,11 +37,10 @@ def set_gather_ranges(on): nn_kernels.GATHER_RANGES = on
 def set_fanout(on): nn_kernels.FANOUT_GATHER = on
 def set_concat(on): nn_kernels.CONCAT_ROWS = on
 def set_wgrad_big(on): nn_kernels.WGRAD_BIG = on
-def set_recompute_h(on): os.environ["CATAN_TE_RECOMPUTE_H"] = "1" if on else "0"      # (read by every tile-encoder forward)
 
 
 def set_cat_bits(on): nn_kernels.CATEGORICAL_BITS = on
-SW = {"cat_bits": set_cat_bits, "wgrad_big": set_wgrad_big, "recompute_h": set_recompute_h, "grad_arena": set_arena, "tuned_gemms": set_tuned, "grouped_wgrad": set_grouped, "deferred_wgrad": set_deferred, "recurrent_batched": set_recurrent, "gather_ranges": set_gather_ranges, "fanout_gather": set_fanout, "concat_rows": set_concat}
+SW = {"cat_bits": set_cat_bits, "wgrad_big": set_wgrad_big, "grad_arena": set_arena, "tuned_gemms": set_tuned, "grouped_wgrad": set_grouped, "deferred_wgrad": set_deferred, "recurrent_batched": set_recurrent, "gather_ranges": set_gather_ranges, "fanout_gather": set_fanout, "concat_rows": set_concat}
 if hasattr(pol_mod, "TRUNK_WINDOWS"):
     SW["trunk_windows"] = set_trunk
 
@@ -64,7 +63,6 @@ def run():
     return (t["b"] - t["a"]) / STEPS * 1e3
 
 
-DEFAULT_OFF = {"recompute_h"}
 names = [n for n in os.environ.get("SWITCHES", ",".join(SW)).split(",") if n in SW]
 run()                                                   # warm-up (GEMM kernels, arena size)
 for rnd in range(3):
@@ -72,4 +70,4 @@ for rnd in range(3):
         for on in (False, True):
             SW[n](on)
             print(f"round {rnd}: {n}={'on ' if on else 'off'}: {run():.2f} ms per minibatch step", flush=True)
-        SW[n](n not in DEFAULT_OFF)                      # back to the library's default before the next pair
+        SW[n](True)                                      # back to the library's default before the next pair

@@ -5,7 +5,7 @@ on the matrix cores - its MFMA FLOP/s against the dense bf16 peak.
 
 Kernels: the two fused learner kernels north_star names (k_gae, k_ppo_loss), the observation encoder of a rollout pass
 (k_obs_rows), the fused tile encoder of every inference pass and of the training forward (k_tile_encoder_fwd), the one-pass
-backward kernels of its sub-layers (k_ffn_bwd_dx, k_qkv_bwd_dx), the row gathers of a minibatch, one fused action-head evaluation
+backward kernels of its sub-layers (k_ffn_bwd_w, k_qkv_bwd_w), the row gathers of a minibatch, one fused action-head evaluation
 (k_head_fwd), and the longest other hand-written kernels of a minibatch step by the kernel trace (profiles/r03_train_step_kernel_stats.csv):
 the tile encoder's attention backward, a row product, a LayerNorm backward and a weight gradient.  The library GEMMs of the
 step are not listed: they are rocBLAS / hipBLASLt code."""
@@ -84,37 +84,31 @@ def learner_rooflines(env, net, T=200, rows_mb=204800):
     out.append(_entry("k_tile_encoder_fwd<SAVE> (training forward: + the activations the backward reads)", f"{boards} boards", us,
                       (2280 + 950 + 19 * 1273 * 2) * boards, flops=2 * macs * boards, note="includes the per-step re-pack of the encoder's weights (~60 small launches)"))
     del tiles
-    # ---- the backward of the encoder's sub-layers up to the weight gradients, one pass each (csrc/catan_te_bwd.hip)
+    # ---- the backward of the encoder's sub-layers WITH their weight gradients, one pass each (csrc/catan_te_bwd.hip: what the update's backward runs)
     tokf = boards * 19
     dxg = torch.randn(tokf, 64, device=dev, generator=g).to(torch.bfloat16); hh = torch.relu(torch.randn(tokf, 128, device=dev, generator=g)).to(torch.bfloat16)
     xm = torch.randn(tokf, 64, device=dev, generator=g).to(torch.bfloat16)
     w2t = torch.randn(128, 64, device=dev, generator=g).to(torch.bfloat16); w1t = torch.randn(64, 128, device=dev, generator=g).to(torch.bfloat16)
-    lw = torch.ones(64, device=dev); dh = torch.empty_like(hh); dxo = torch.empty_like(xm); dl = torch.zeros(2, 64, device=dev)
+    lw = torch.ones(64, device=dev); dxo = torch.empty_like(xm); dl = torch.zeros(2, 64, device=dev)
     from settlers_of_catan_rl_amd import _lib
     P, S = nn_kernels._ptr, nn_kernels._stream
-    us = _time_us(lambda: _lib.check(_lib.lib().catan_ffn_bwd_dx(P(dxg), P(hh), P(xm), P(w2t), P(w1t), P(lw), 1e-5, P(dh), P(dxo), P(dl[0]), P(dl[1]), tokf, S())), reps=5)
-    out.append(_entry("k_ffn_bwd_dx (masked dX W2, dH W1, LayerNorm backward + residual)", f"{tokf} rows", us, (64 + 128 + 64 + 128 + 64) * 2 * tokf,
-                      flops=2 * 2 * 64 * 128 * tokf, note="dX, H, X in; dH, dX' out"))
     dq = torch.randn(tokf, 192, device=dev, generator=g).to(torch.bfloat16); wqt = torch.randn(64, 192, device=dev, generator=g).to(torch.bfloat16)
-    us = _time_us(lambda: _lib.check(_lib.lib().catan_qkv_bwd_dx(P(dq), P(xm), P(dxg), P(wqt), P(lw), 1e-5, P(dxo), P(dl[0]), P(dl[1]), tokf, S())), reps=5)
-    out.append(_entry("k_qkv_bwd_dx (dQKV Wqkv, LayerNorm backward + residual)", f"{tokf} rows", us, (192 + 64 + 64 + 64) * 2 * tokf, flops=2 * 192 * 64 * tokf))
-    # ---- the same chains WITH the sub-layers' weight gradients in the pass (k_ffn_bwd_w, k_qkv_bwd_w: what the update's backward runs)
-    oo = torch.randn(tokf, 64, device=dev, generator=g).to(torch.bfloat16); n2 = torch.randn(tokf, 64, device=dev, generator=g).to(torch.bfloat16)
+    oo = torch.randn(tokf, 64, device=dev, generator=g).to(torch.bfloat16)
     wot = torch.randn(64, 64, device=dev, generator=g).to(torch.bfloat16)
     do, lb = torch.empty_like(oo), torch.randn(64, device=dev, generator=g)
     accw = torch.zeros(64 * 128 + 64 + 128 * 64 + 128 + 192 * 64 + 192 + 64 * 64 + 64, device=dev)
-    # (the update's configuration: n = NULL - the LayerNorm outputs are recomputed from X in the passes, the forward does not store them)
-    us = _time_us(lambda: _lib.check(_lib.lib().catan_ffn_outproj_bwd(P(dxg), P(hh), P(xm), None, P(w2t), P(w1t), P(lw), P(lb), 1e-5, P(dxo), P(accw[:8192]),
+    # (the LayerNorm outputs are recomputed from X in the passes, the forward does not store them)
+    us = _time_us(lambda: _lib.check(_lib.lib().catan_ffn_outproj_bwd(P(dxg), P(hh), P(xm), P(w2t), P(w1t), P(lw), P(lb), 1e-5, P(dxo), P(accw[:8192]),
                                                                       P(accw[8192:8256]), P(accw[8256:16448]), P(accw[16448:16576]), P(dl[0]), P(dl[1]),
                                                                       P(oo), P(wot), P(do), P(accw[29056:33152]), P(accw[33152:33216]), tokf, S())), reps=5)
-    out.append(_entry("k_ffn_bwd_w<out-projection> (k_ffn_bwd_dx + dW2, dW1 + the out-projection's dO, dWo in the same pass)", f"{tokf} rows", us,
+    out.append(_entry("k_ffn_bwd_w (masked dX W2, dH W1, LayerNorm backward + residual, dW2, dW1 + the out-projection's dO, dWo in one pass)", f"{tokf} rows", us,
                       (64 + 128 + 64 + 64 + 64 + 64) * 2 * tokf, flops=(2 * 4 * 64 * 128 + 2 * 2 * 64 * 64) * tokf,
                       note="dX, H, X, O in; dX', dO out; dH and N stay in LDS"))
-    us = _time_us(lambda: _lib.check(_lib.lib().catan_qkv_bwd(P(dq), P(xm), P(dxg), None, P(wqt), P(lw), P(lb), 1e-5, P(dxo), P(accw[16576:28864]), P(accw[28864:29056]),
+    us = _time_us(lambda: _lib.check(_lib.lib().catan_qkv_bwd(P(dq), P(xm), P(dxg), P(wqt), P(lw), P(lb), 1e-5, P(dxo), P(accw[16576:28864]), P(accw[28864:29056]),
                                                               P(dl[0]), P(dl[1]), tokf, S())), reps=5)
-    out.append(_entry("k_qkv_bwd_w<N recomputed> (k_qkv_bwd_dx + dWqkv = dQKV^T N in the same pass)", f"{tokf} rows", us, (192 + 64 + 64 + 64) * 2 * tokf,
+    out.append(_entry("k_qkv_bwd_w (dQKV Wqkv, LayerNorm backward + residual, dWqkv = dQKV^T N in one pass)", f"{tokf} rows", us, (192 + 64 + 64 + 64) * 2 * tokf,
                       flops=2 * 2 * 192 * 64 * tokf, note="dQKV, X, the residual gradient in; dX out; N from X"))
-    del dxg, hh, xm, dh, dxo, dq, oo, do, n2
+    del dxg, hh, xm, dxo, dq, oo, do
     # ---- row movement of a minibatch: the distinct boards' tile features out of the rollout rows (2-byte aligned 3 574-byte rows),
     #      a per-board result spread to the rows, the rows' gradients summed per board
     rows_all = 16 * rows_mb

@@ -41,26 +41,24 @@ tok = rows_mb * 19
 dx = torch.randn(tok, 64, device=dev, generator=g).to(torch.bfloat16); h = torch.relu(torch.randn(tok, 128, device=dev, generator=g)).to(torch.bfloat16)
 xm = torch.randn(tok, 64, device=dev, generator=g).to(torch.bfloat16)
 w2t = torch.randn(128, 64, device=dev, generator=g).to(torch.bfloat16); w1t = torch.randn(64, 128, device=dev, generator=g).to(torch.bfloat16)
-lw = torch.ones(64, device=dev); dh = torch.empty_like(h); dxo = torch.empty_like(xm); dl = torch.zeros(2, 64, device=dev)
-for _ in range(REPS): _lib.check(L.catan_ffn_bwd_dx(P(dx), P(h), P(xm), P(w2t), P(w1t), P(lw), 1e-5, P(dh), P(dxo), P(dl[0]), P(dl[1]), tok, S()))
+lw = torch.ones(64, device=dev); dxo = torch.empty_like(xm); dl = torch.zeros(2, 64, device=dev)
 dq = torch.randn(tok, 192, device=dev, generator=g).to(torch.bfloat16); wqt = torch.randn(64, 192, device=dev, generator=g).to(torch.bfloat16)
-for _ in range(REPS): _lib.check(L.catan_qkv_bwd_dx(P(dq), P(xm), P(dx), P(wqt), P(lw), 1e-5, P(dxo), P(dl[0]), P(dl[1]), tok, S()))
-# the same chains with the sub-layers' weight gradients (and the out-projection's backward) in the pass: what the update's backward runs
-lb = torch.randn(64, device=dev, generator=g); n2 = torch.randn(tok, 64, device=dev, generator=g).to(torch.bfloat16); oo = torch.randn(tok, 64, device=dev, generator=g).to(torch.bfloat16)
+# the sub-layers' dX chains with their weight gradients (and the out-projection's backward) in the pass: what the update's backward runs
+lb = torch.randn(64, device=dev, generator=g); oo = torch.randn(tok, 64, device=dev, generator=g).to(torch.bfloat16)
 wot = torch.randn(64, 64, device=dev, generator=g).to(torch.bfloat16); do = torch.empty_like(oo)
 acc = torch.zeros(64 * 128 + 64 + 128 * 64 + 128 + 64 * 64 + 64 + 192 * 64 + 192, device=dev)
 for _ in range(REPS):
-    _lib.check(L.catan_ffn_outproj_bwd(P(dx), P(h), P(xm), None, P(w2t), P(w1t), P(lw), P(lb), 1e-5, P(dxo), P(acc[:8192]), P(acc[8192:8256]), P(acc[8256:16448]),
+    _lib.check(L.catan_ffn_outproj_bwd(P(dx), P(h), P(xm), P(w2t), P(w1t), P(lw), P(lb), 1e-5, P(dxo), P(acc[:8192]), P(acc[8192:8256]), P(acc[8256:16448]),
                                        P(acc[16448:16576]), P(dl[0]), P(dl[1]), P(oo), P(wot), P(do), P(acc[16576:20672]), P(acc[20672:20736]), tok, S()))
 for _ in range(REPS):
-    _lib.check(L.catan_qkv_bwd(P(dq), P(xm), P(dx), None, P(wqt), P(lw), P(lb), 1e-5, P(dxo), P(acc[20736:33024]), P(acc[33024:33216]), P(dl[0]), P(dl[1]), tok, S()))
-del n2, oo, do
+    _lib.check(L.catan_qkv_bwd(P(dq), P(xm), P(dx), P(wqt), P(lw), P(lb), 1e-5, P(dxo), P(acc[20736:33024]), P(acc[33024:33216]), P(dl[0]), P(dl[1]), tok, S()))
+del oo, do
 # a weight gradient and a row product at the encoder's shapes
 for _ in range(REPS): nn_kernels.wgrad(h, dx)
 w = torch.randn(128, 64, device=dev, generator=g).to(torch.bfloat16); bb = torch.zeros(128, device=dev, dtype=torch.bfloat16)
 with torch.no_grad():
     for _ in range(REPS): nn_kernels.linear_inference(xm, w, bb)
-del dx, h, xm, dh, dxo, dq
+del dx, h, xm, dxo, dq
 # row movement
 rows_all = 16 * rows_mb
 store = torch.randn(rows_all // 16, 16 * 1787, device=dev, generator=g).to(torch.bfloat16).view(rows_all, 1787)
