@@ -280,7 +280,8 @@ int64_t catan_inconsistent_deal_count(catan_env_t* env, catan_stream_t stream);
  *                       tile encoder, the action heads, the dev-card modules, the LSTM cell, the masked categorical)
  *   catan_hip_tuning.h  scheduling knobs, counters and profilers of the env kernels (benchmarks and diagnostics only), and
  *                       catan_longest_path, the diagnostic entry to the longest-road search, and catan_state_fork (search support:
- *                       games copied from one handle into another on the device, what export -> import does through the blob) */
+ *                       games copied from one handle into another on the device, what export -> import does through the blob), and
+ *                       catan_episode_stats_*: statistics of the finished games, which auto_reset re-deals before the caller sees them */
 
 
 #ifdef __cplusplus

@@ -1,7 +1,9 @@
 /*
  * catan_hip_tuning.h - scheduling knobs, counters and profilers of the env kernels in libcatan_hip.so.  Benchmarks, sweeps and
  * diagnostics only (bench.py, tools): results never depend on any of them, and nothing a reference-side binding needs is
- * declared here (that is catan_hip.h).  One section is no knob: "search support" (catan_state_fork), which the forward search uses.
+ * declared here (that is catan_hip.h).  Two sections are no knobs: "search support" (catan_state_fork), which the forward search uses,
+ * and "finished-game statistics" (catan_episode_stats_*), which the rollout collector uses: the reference has no such interface to replace,
+ * and catan_hip.h stays the reference's boundary.
  */
 #ifndef CATAN_HIP_TUNING_H
 #define CATAN_HIP_TUNING_H
@@ -43,6 +45,43 @@ int catan_longest_path(catan_env_t* env, const int32_t* players, int32_t* out, c
  * devices, an open deferred sequence on either handle, a handle under the MT19937 contract on either side. */
 int catan_state_fork(catan_env_t* dst, const catan_env_t* src, const int64_t* src_idx, const int64_t* dst_idx,
                      const uint32_t* draw_offset, int64_t cnt, catan_stream_t stream);
+
+/* ---- finished-game statistics ----
+ * Gathered on the device.  With auto_reset = 1 a finished game is re-dealt inside the call that ended it -
+ * RL/ppo/game_manager.py:112-113 (`if done: ... env.reset()`) throws the finished game away the same way - and all the caller sees
+ * of it is done = 1 and the winner's win_reward.  While statistics are enabled, every finished game is counted ONCE, from its final
+ * state and just before its re-deal, on every schedule (catan_step, catan_random_rollout, catan_step_deferred / catan_step_flush,
+ * catan_random_rollout_deferred in both forms); a game is counted when its re-deal is consumed, i.e. at the latest when the call that
+ * reports its done flag (or the flush) returns.  Off, the default, not one kernel more is launched.
+ * The block is catan_episode_stats_words() = 48 uint64 counters, all sums over the finished games unless stated otherwise:
+ *    [0]      episodes
+ *    [1..4]   wins_by_player          index = PlayerId-1
+ *    [5..8]   wins_by_turn_order      index = the winner's position in player_order (0 = first mover)
+ *    [9]      turns_sum               Game.turn of the final state
+ *    [10]     turns_sumsq
+ *    [11]     turns_max               a MAXIMUM
+ *    [12..27] turns_hist              16 bins of 32 turns: bin = min(turn / 32, 15) (the last bin is open-ended)
+ *    [28..31] vp_sum_by_player        index = PlayerId-1
+ *    [32]     winner_vp_sum           [33] loser_vp_sum (the three losers together)
+ *    [34]     winner_has_longest_road [35] winner_has_largest_army
+ *    [36]     games_with_longest_road [37] games_with_largest_army  (somebody holds it at the end)
+ *    [38]     winner_settlements_sum  settlements the winner has on the board (5 - settlements left)
+ *    [39]     winner_cities_sum       cities (4 - cities left)
+ *    [40]     dev_cards_played_sum    all four players
+ *    [41]     focus_episodes          finished games with a focus player      [42] focus_wins      [43] focus_vp_sum
+ *    [44..47] focus_turn_order_wins   index = the focus player's position in player_order, in the games he won
+ * focus_pid: DEVICE int32 [n], PlayerId 1..4 per game, 0 = none, or NULL (the focus counters stay 0): the seat whose results are wanted -
+ * a collector's central policy sits on another PlayerId in every game.  The array is the caller's, is read when a game finishes and must
+ * stay valid until statistics are disabled or the handle destroyed.
+ * A game's length in DECISIONS is not counted: the state holds actions_this_turn only, a per-game decision count would be a new field
+ * for the step kernel to maintain.
+ * catan_episode_stats_enable(on != 0) zeroes the block (again on every call); on == 0 stops counting.  catan_episode_stats_read copies the
+ * block to HOST memory, zeroes it behind the copy when reset != 0, and synchronises the stream.  Use the stream of the handle's step calls.
+ * CATAN_EINVAL: a handle with auto_reset = 0 (nothing is re-dealt: read the final states), a handle under the MT19937 contract, an open
+ * deferred sequence (both calls), and catan_episode_stats_read while statistics are off. */
+int32_t catan_episode_stats_words(void);
+int catan_episode_stats_enable(catan_env_t* env, int on, const int32_t* focus_pid, catan_stream_t stream);
+int catan_episode_stats_read(catan_env_t* env, uint64_t* out_host, int reset, catan_stream_t stream);
 
 /* the rollout loops with a hipEvent around every kernel launch (recorded on the stream the kernel runs on); window <= 0: the
  * lock-step loop (step_idx0 as in catan_random_rollout), window > 0: the deferred loop (step_idx0 ignored).  kernel_ms is a HOST

@@ -303,15 +303,31 @@ _SIGS = {
     "catan_linear_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, _vp]),
     "catan_linear_wgrad_grouped": (C.c_int, [C.POINTER(CatanWgradProblem), C.c_int32, _vp]),
     "catan_set_board_configs": (C.c_int, [_vp, C.POINTER(CatanBoardCfg), C.c_int32, _vp, _vp]),
+    "catan_episode_stats_words": (C.c_int32, []),
+    "catan_episode_stats_enable": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "catan_episode_stats_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int, _vp]),
 }
 # bound only where the library exports them: the same callers also load oracle/libcatan_cpu.so, which implements the env ABI
 # without these
-_OPTIONAL = {"catan_set_board_configs"}
+_OPTIONAL = {"catan_set_board_configs", "catan_episode_stats_words", "catan_episode_stats_enable", "catan_episode_stats_read"}
 
 
 def declared_symbols():
     """Every entry point include/*.h declares (the CPU test-suite checks the built .so exports them)."""
     return sorted(_SIGS)
+
+
+def bind(L, names=None):
+    """Gives the entry points `names` (None: every declared one) of the loaded library L their ctypes signatures; an _OPTIONAL one that L
+    does not export is skipped (oracle/libcatan_cpu.so), any other missing one raises AttributeError.  -> the names bound"""
+    bound = []
+    for name in (_SIGS if names is None else names):
+        if name in _OPTIONAL and not hasattr(L, name):
+            continue
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = _SIGS[name]
+        bound.append(name)
+    return bound
 
 
 def lib():
@@ -324,11 +340,7 @@ def lib():
         # process ends up with two HIP runtimes and device pointers / streams cannot be shared.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            if name in _OPTIONAL and not hasattr(L, name):
-                continue
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
+        bind(L)
         have, want = L.catan_build_hash().decode(), source_hash()
         if have != want and not os.environ.get("CATAN_ALLOW_STALE_LIB"):
             raise CatanHipError(f"{LIB_PATH} was built from other sources (binary {have}, sources {want}): rebuild with "

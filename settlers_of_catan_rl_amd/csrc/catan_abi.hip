@@ -22,6 +22,7 @@
 #include "catan_te_bwd.hip"
 #include "catan_optim.hip"
 #include "catan_wgrad_big.hip"
+#include "catan_stats.hip"
 
 using namespace catan;
 
@@ -85,6 +86,9 @@ struct catan_env {
     MtPair* mt_dev;       // RNG contract (A): the handle's two MT19937 generators on the device (catan_seed_mt19937), else NULL
     BoardCfg* bcfg_dev;   // catan_set_board_configs: the layout table and the games' indices into it (ctx.bcfg / ctx.bcfg_idx), else NULL
     u8* bcfg_idx_dev;
+    unsigned long long* stats;   // catan_episode_stats_enable: the block of ES_WORDS counters (catan_stats.hip), allocated at the first enable
+    const i32* stats_focus;      // ... the caller's focus array (device int32 [n]) or NULL
+    int stats_on;
 };
 static_assert(sizeof(BoardCfg) == sizeof(catan_board_cfg_t) && sizeof(catan_board_cfg_t) == 56 &&
               offsetof(BoardCfg, terrain) == offsetof(catan_board_cfg_t, terrain) &&
@@ -384,6 +388,12 @@ static void pend_pass(catan_env* e, int fa, int ftag, int sa, int bsel, int bcle
 }
 
 static inline unsigned blocks(long n, int b) { return (unsigned)((n + b - 1) / b); }
+// Finished-game statistics (catan_episode_stats_enable): the games of a re-deal list are counted on the stream of the kernel that consumes the
+// list, immediately in front of it - their records are still the final states.  Off (the default): nothing is launched.
+static void enqueue_episode_stats(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!e->stats_on) return;
+    hipLaunchKernelGGL(k_episode_stats, dim3(EPISODE_STATS_GRID), dim3(64), 0, st, e->ctx, count_p, list, e->stats_focus, e->stats);
+}
 // k_step with G games per wave in one-wave workgroups; pend.sample (fused-sampling rollouts): actions from / to the side rows
 template <int G>
 static void launch_step(catan_env_t* e, const int32_t* actions, float* reward, uint8_t* done, hipStream_t st, const StepCfg& sc, const u32* bins) {
@@ -763,6 +773,7 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
         if (!lockstep) {
             HIPCHK(hipEventRecord(e->ev_fork, st));
             HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
+            enqueue_episode_stats(e, sctr + 1, e->pend.resets[sa][0], e->side);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 1),
                                (const i32*)e->pend.resets[sa][0], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
             HIPCHK(hipEventRecord(e->ev_join, e->side));
@@ -784,12 +795,15 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
     if (e->cfg.auto_reset) {
         if (lockstep) {
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));      // the side stream's launch of step_impl: it had the whole slow path to finish
+            enqueue_episode_stats(e, sctr + 3, e->pend.resets[sa][2], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 3), (const i32*)e->pend.resets[sa][2], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
+            enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2), (const i32*)e->pend.resets[sa][1], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
         } else {
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));
+            enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2),
                                (const i32*)e->pend.resets[sa][1], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
         }
@@ -819,6 +833,7 @@ static int step_impl(catan_env_t* e, int32_t* actions, float* reward, uint8_t* d
         HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
         // ... and every game on the longest-road path that this step may end (k_step's list pend.spec) gets a speculative successor
         e->spec_epoch++;
+        enqueue_episode_stats(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);       // (the real list only: the speculative successors are no episodes)
         hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, limits_of(e),
                            (const u32*)(e->pend.ctr + 8 + 1), (const i32*)e->pend.resets[0][0], e->pend.busy, step_cfg(e).prof,
                            (const u32*)(e->pend.ctr + 6), (const u64*)e->pend.spec, e->spec_state, e->spec_mpk, e->spec_epoch, e->pend);
@@ -954,6 +969,33 @@ int64_t catan_invalid_action_count(catan_env_t* e, catan_stream_t stream) {
     if (hipMemcpyAsync(&v, e->err, sizeof v, hipMemcpyDeviceToHost, S(stream)) != hipSuccess) return -1;
     if (hipStreamSynchronize(S(stream)) != hipSuccess) return -1;
     return (int64_t)v;
+}
+
+// ---- finished-game statistics (catan_stats.hip)
+int32_t catan_episode_stats_words(void) { return ES_WORDS; }
+int catan_episode_stats_enable(catan_env_t* e, int on, const int32_t* focus_pid, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_episode_stats_enable: null handle");
+    if (!e->cfg.auto_reset) return fail(CATAN_EINVAL, "catan_episode_stats_enable: the handle has auto_reset = 0 (no game is re-dealt: read the final states themselves)");
+    NOT_DEFERRED(e, "catan_episode_stats_enable");
+    NOT_MT(e, "catan_episode_stats_enable");
+    if (!on) { e->stats_on = 0; e->stats_focus = nullptr; return CATAN_OK; }
+    if (!e->stats) {
+        hipError_t rc = hipSuccess;
+        dev_alloc(e, rc, e->stats, ES_WORDS * sizeof(unsigned long long));
+        if (rc != hipSuccess) return fail(CATAN_ENOMEM, std::string("catan_episode_stats_enable: hipMalloc: ") + hipGetErrorString(rc));
+    }
+    HIPCHK(hipMemsetAsync(e->stats, 0, ES_WORDS * sizeof(unsigned long long), S(stream)));
+    e->stats_focus = focus_pid; e->stats_on = 1;
+    return CATAN_OK;
+}
+int catan_episode_stats_read(catan_env_t* e, uint64_t* out_host, int reset, catan_stream_t stream) {
+    if (!e || !out_host) return fail(CATAN_EINVAL, "catan_episode_stats_read: null argument");
+    if (!e->stats_on) return fail(CATAN_EINVAL, "catan_episode_stats_read: statistics are not enabled on this handle (catan_episode_stats_enable)");
+    NOT_DEFERRED(e, "catan_episode_stats_read");      // (the side streams of an open sequence are joined by catan_step_flush)
+    HIPCHK(hipMemcpyAsync(out_host, e->stats, ES_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, S(stream)));
+    if (reset) HIPCHK(hipMemsetAsync(e->stats, 0, ES_WORDS * sizeof(unsigned long long), S(stream)));
+    HIPCHK(hipStreamSynchronize(S(stream)));
+    return CATAN_OK;
 }
 
 int catan_random_rollout(catan_env_t* e, uint32_t step_idx0, int64_t steps, catan_stream_t stream) {

@@ -117,6 +117,34 @@ class VecCatanEnv(object):
             _lib.check(self.L.catan_set_reward_f64_buffer(self.h, _ptr(self.reward64)))
         return self.reward64
 
+    def enable_episode_stats(self, focus_pid=None, on=True):
+        """Finished games are counted on the device from now on, from their final states and just before their re-deal
+        (include/catan_hip_tuning.h catan_episode_stats_enable); the counters start at zero.  focus_pid: PlayerId 1..4 per game (0: none) of the
+        seat whose own results are wanted - the env keeps an int32 copy on the device, later edits of the argument are not seen.
+        on=False stops counting."""
+        if not hasattr(self.L, "catan_episode_stats_enable"):
+            raise _lib.CatanHipError("the loaded library has no catan_episode_stats_enable")
+        focus = None
+        if on and focus_pid is not None:
+            focus = torch.as_tensor(focus_pid, device=self.device).to(torch.int32).contiguous().clone()
+            if focus.shape != (self.n,):
+                raise ValueError(f"focus_pid: one PlayerId per game ({self.n}), got shape {tuple(focus.shape)}")
+        _lib.check(self.L.catan_episode_stats_enable(self.h, int(bool(on)), _ptr(focus), _stream()))
+        self._episode_focus = focus              # (the library reads it whenever a game finishes)
+
+    def episode_stats_words(self, reset=False):
+        """-> the raw counter block (list of spec.EPISODE_STATS_WORDS ints); waits for the current stream"""
+        out = (C.c_uint64 * spec.EPISODE_STATS_WORDS)()
+        assert int(self.L.catan_episode_stats_words()) == spec.EPISODE_STATS_WORDS
+        _lib.check(self.L.catan_episode_stats_read(self.h, out, int(bool(reset)), _stream()))
+        return [int(x) for x in out]
+
+    def episode_stats(self, reset=False):
+        """-> dict (spec.episode_stats_dict): the counters of the games finished since statistics were enabled (or last read with reset=True)
+        by name, plus the derived means (mean_turns, win_rate_by_turn_order, focus_win_rate, ...).  A game's length in decisions is not
+        among them: the state does not hold it."""
+        return spec.episode_stats_dict(self.episode_stats_words(reset))
+
     def close(self):
         if getattr(self, "h", None):
             self.L.catan_destroy(self.h)

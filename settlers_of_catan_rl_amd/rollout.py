@@ -43,6 +43,7 @@ class RolloutStorage(object):
         self.action_log_probs = torch.zeros((T, N), dtype=torch.float32, device=device)
         self.action_masks = torch.zeros((T, N, 11), dtype=torch.int32, device=device)   # packed 325-bit masks
         self.games_complete = 0
+        self.episode_stats = None     # RolloutCollector(episode_stats=True): the finished games of the last gather_rollouts (env.episode_stats)
         self.generation = 0           # bumped by every gather_rollouts (consumers cache per-rollout derived data on it)
 
     def unpack_action_masks(self, packed):
@@ -74,7 +75,8 @@ def pack_action_masks(m):
 class RolloutCollector(object):
     GRAPH_ACT_MIN_GAMES = 8192
 
-    def __init__(self, env, policy, num_steps, opponents=None, seed=0, autocast_dtype=None, graph_act=None, deferred_window=None, act_buckets=None):
+    def __init__(self, env, policy, num_steps, opponents=None, seed=0, autocast_dtype=None, graph_act=None, deferred_window=None, act_buckets=None,
+                 episode_stats=False):
         """policy: central net (policy 0); opponents: list of up to 3 nets for policy slots 1..3 of every game (None =
         every seat plays the central policy).  A league (league.League.assign) installs per-game opponents instead.
         deferred_window: step the env with catan_step_deferred (window of that many iterations) instead of catan_step - the
@@ -82,7 +84,10 @@ class RolloutCollector(object):
         needs the slow path waits for it while the others go on (device collector only; 0 = catan_step; None = 4 where the env
         has the call: measured at 65 536 games x T = 200, tools/rollout_schedules.py: 2.50 s with catan_step, 2.44 s with W = 4).
         act_buckets: row counts of the captured policy passes (graph_act): once the games that still miss observations fit a
-        smaller bucket, only they are evaluated (None = N, N/2, ... N/16 with graph_act, else N only)."""
+        smaller bucket, only they are evaluated (None = N, N/2, ... N/16 with graph_act, else N only).
+        episode_stats: the env counts its finished games on the device (VecCatanEnv.enable_episode_stats, the active seat as the focus
+        player); every gather_rollouts leaves the dict of the games that finished during it in storage.episode_stats - one read after
+        the loop, none inside it."""
         self.env, self.policy, self.T = env, policy, num_steps
         self.deferred_window = self.DEFAULT_DEFERRED_WINDOW if deferred_window is None else int(deferred_window)
         self.act_buckets = None if act_buckets is None else tuple(sorted(set(int(b) for b in act_buckets) | {env.n}))
@@ -122,6 +127,9 @@ class RolloutCollector(object):
         # game_manager.py:94-95 sums the env's rewards (Python floats) over the other seats' moves and process_batch.py:63
         # rounds the sum to fp32: the env leaves its unrounded rewards in a float64 buffer for that
         self.reward64 = env.enable_reward64() if hasattr(env, "enable_reward64") else None
+        self.episode_stats = bool(episode_stats)
+        if self.episode_stats:
+            env.enable_episode_stats(self.active_pid)
         self.reset()
 
     def set_opponents(self, nets, opp_index):
@@ -422,6 +430,8 @@ class RolloutCollector(object):
             self.done_since = fl[0].bool()
             self.pending_obs = torch.zeros(N, dtype=torch.bool, device=dev)
         st.games_complete += int(n_complete)
+        if self.episode_stats:
+            st.episode_stats = env.episode_stats(reset=True)
         st.generation += 1
         self.iters = int(n_live_iters) if max_iters is None else iters
         return st

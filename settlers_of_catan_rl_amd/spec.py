@@ -182,3 +182,46 @@ def board_config_from_state(blob):
     return {"randomise_number_placement": True, "fixed_terrain_placements": res,
             "fixed_number_order": [val[t] for t in NUMBER_PLACEMENT_INDS if res[t] != 0]}
 
+
+
+# ---------------------------------------------------------------- finished-game statistics (include/catan_hip_tuning.h catan_episode_stats_*)
+# the block of uint64 counters, in order: (name, words); csrc/catan_stats.hip holds the same layout as ES_* offsets
+EPISODE_STATS_FIELDS = [
+    ("episodes", 1), ("wins_by_player", 4), ("wins_by_turn_order", 4), ("turns_sum", 1), ("turns_sumsq", 1), ("turns_max", 1),
+    ("turns_hist", 16), ("vp_sum_by_player", 4), ("winner_vp_sum", 1), ("loser_vp_sum", 1),
+    ("winner_has_longest_road", 1), ("winner_has_largest_army", 1), ("games_with_longest_road", 1), ("games_with_largest_army", 1),
+    ("winner_settlements_sum", 1), ("winner_cities_sum", 1), ("dev_cards_played_sum", 1),
+    ("focus_episodes", 1), ("focus_wins", 1), ("focus_vp_sum", 1), ("focus_turn_order_wins", 4),
+]
+EPISODE_STATS_WORDS = sum(n for _, n in EPISODE_STATS_FIELDS)      # 48
+EPISODE_STATS_HIST_BIN_TURNS = 32                                 # turns_hist: bin = min(turn // 32, 15)
+
+
+def episode_stats_dict(words):
+    """The counter block catan_episode_stats_read fills (EPISODE_STATS_WORDS integers) -> a dict: every counter by name (an int, or a
+    list of ints for the indexed ones) plus the derived means, None where nothing was counted:
+    mean_turns, std_turns, mean_winner_vp, mean_loser_vp (per losing player), win_rate_by_player / win_rate_by_turn_order (lists),
+    longest_road_decides / largest_army_decides (share of the games whose winner holds it), mean_dev_cards_played (per game),
+    focus_win_rate, focus_mean_vp."""
+    w = [int(x) for x in words]
+    if len(w) != EPISODE_STATS_WORDS:
+        raise ValueError(f"an episode-statistics block has {EPISODE_STATS_WORDS} words, got {len(w)}")
+    out, o = OrderedDict(), 0
+    for name, n in EPISODE_STATS_FIELDS:
+        out[name] = w[o] if n == 1 else w[o:o + n]
+        o += n
+    ep, fe = out["episodes"], out["focus_episodes"]
+    per = lambda x, d: (x / d) if d else None
+    out["mean_turns"] = per(out["turns_sum"], ep)
+    var = per(out["turns_sumsq"], ep)
+    out["std_turns"] = max(var - out["mean_turns"] ** 2, 0.0) ** 0.5 if ep else None
+    out["mean_winner_vp"] = per(out["winner_vp_sum"], ep)
+    out["mean_loser_vp"] = per(out["loser_vp_sum"], 3 * ep)
+    out["win_rate_by_player"] = [per(x, ep) for x in out["wins_by_player"]]
+    out["win_rate_by_turn_order"] = [per(x, ep) for x in out["wins_by_turn_order"]]
+    out["longest_road_decides"] = per(out["winner_has_longest_road"], ep)
+    out["largest_army_decides"] = per(out["winner_has_largest_army"], ep)
+    out["mean_dev_cards_played"] = per(out["dev_cards_played_sum"], ep)
+    out["focus_win_rate"] = per(out["focus_wins"], fe)
+    out["focus_mean_vp"] = per(out["focus_vp_sum"], fe)
+    return out

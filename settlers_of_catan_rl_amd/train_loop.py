@@ -118,9 +118,12 @@ class TrainingLoop(object):
         self.update_num += 1
         if self.checkpoint_path and (not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0):
             self.save(self.checkpoint_path)                                                 # :155-156
-        return {"update": u, "losses": losses, "games_complete": st.games_complete, "entropy_coef": self.entropy_coef,
-                "reward_weight": self.reward_weight, "policy_steps": self.steps_per_update * (u + 1),
-                "hours": (time.time() - self.start_time) / 3600.0, "eval": summary}
+        out = {"update": u, "losses": losses, "games_complete": st.games_complete, "entropy_coef": self.entropy_coef,
+               "reward_weight": self.reward_weight, "policy_steps": self.steps_per_update * (u + 1),
+               "hours": (time.time() - self.start_time) / 3600.0, "eval": summary}
+        if getattr(st, "episode_stats", None) is not None:       # RolloutCollector(episode_stats=True): the games this rollout finished
+            out["episodes"] = st.episode_stats
+        return out
 
     def save(self, path):
         torch.save({"central_policy": {k: v.detach().cpu() for k, v in self.policy.state_dict().items()},
