@@ -130,7 +130,8 @@ class _MHA(nn.Module):
         if lens is not None:
             key_mask = torch.arange(L, device=x.device)[None, :] < lens[:, None]
             scores = scores.masked_fill(~key_mask[:, None, None, :], float("-inf"))
-        o = torch.matmul(torch.softmax(scores.float(), -1).to(v.dtype), v)
+        # (softmax in at least fp32; a double module - the CPU check of tests/te_reference.py - stays double)
+        o = torch.matmul(torch.softmax(scores, -1, dtype=torch.promote_types(scores.dtype, torch.float32)).to(v.dtype), v)
         return self.out_proj_net(o.transpose(1, 2).reshape(B, L, D)), False
 
 

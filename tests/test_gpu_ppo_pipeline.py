@@ -1107,7 +1107,10 @@ def test_fused_tile_encoder_training_forward_vs_unfused(hip_lib, monkeypatch):
     (275 842 token rows) the row kernels; ragged counts exercise partial groups of boards.  The fused chain's gradients are also held
     directly against the unfused chain's, which shares no backward code with it: per parameter within FUSED_VS_UNFUSED of the scale,
     twice the largest distance measured over the three sizes before the fused chain's older variants were removed (0.106607; the
-    factor 2 for the run-to-run spread of the fp32-atomic accumulation order; profiles/te_backward_refactor_gradients.txt)."""
+    factor 2 for the run-to-run spread of the fp32-atomic accumulation order; profiles/te_backward_refactor_gradients.txt).
+    This is the chain end to end with a loose bound (a fifth of a gradient's norm): the TIGHT bound on each kernel of the chain - every
+    output of catan_ffn_outproj_bwd and catan_qkv_bwd and every stored activation of catan_tile_encoder_fwd_train against fp64, within
+    twice what bf16 storage alone costs - is tests/test_gpu_te_backward.py."""
     import torch
     from settlers_of_catan_rl_amd import nn_kernels
     from settlers_of_catan_rl_amd.env import VecCatanEnv
