@@ -12,7 +12,7 @@ import random as _py_random
 import numpy as np
 import torch
 
-from . import spec
+from . import acting, spec
 from .forward_search import export_games
 
 PLAYER_IDS = [2, 4, 3, 1]            # [Blue, Red, Orange, White] - the list the reference shuffles (evaluation_manager.py:27)
@@ -158,11 +158,7 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
             if rec:
                 L, seat = int(net.lstm_size), deciding[idx] - 1
                 kw.update(hidden=(hid[0, idx, seat, :L], hid[1, idx, seat, :L]), nonterminal=torch.ones(idx.numel(), device=dev))
-            if autocast_dtype is not None:
-                with torch.autocast(device_type="cuda", dtype=autocast_dtype):
-                    res = net.act(*args, **kw)
-            else:
-                res = net.act(*args, **kw)
+            res = acting.act(net, args, autocast_dtype, **kw)
             actions[idx] = res[1]
             if rec:
                 hid[0, idx, seat, :L], hid[1, idx, seat, :L] = res[3][0].float(), res[3][1].float()

@@ -28,7 +28,8 @@ import random as _py_random
 import numpy as np
 import torch
 
-from . import spec
+from . import acting, spec
+from .acting import GraphedAct     # (the name tools and tests import from here)
 
 MAX_PROP_TRADE_ACTIONS = 3                                   # sample_actions_fn.py:6
 PRIORITIES = [["settlement", "city", "move_robber", "steal", "discard"], ["road"], ["play_dev"], ["exchange_res", "prop_trade"]]
@@ -148,91 +149,6 @@ class UCBStats(object):
         self.last_std[rows] = np.where(np.isnan(std), 0.1, std)       # `except: std = 0.1` / isnan
 
 
-# ---------------------------------------------------------------------------------------------------- small-batch inference
-class GraphedAct(object):
-    """policy.act for SMALL batches as hipGraph replays.  Towards the end of a round only a few simulations are still
-    running, and a policy pass is then ~1 300 tiny kernels - launch-bound at ~10 ms whatever the batch.  For a few bucket
-    sizes the pass is captured once (torch.cuda.CUDAGraph: the library GEMMs and the hand-written attention / LayerNorm
-    launches alike, all on the capture stream) with static input buffers and replayed; rows beyond the live ones are
-    padding and ignored.  Sampling uses torch's default CUDA generator, which graphs advance correctly.  Falls back to the
-    eager call if capture is unavailable."""
-
-    def __init__(self, policy, buckets=(512, 4096, 16384), autocast_dtype=None, deterministic=False, generator=None):
-        """generator: the CUDA torch.Generator the sampling draws from (registered with every captured graph, so replays
-        advance it as eager calls would); None = torch's default CUDA generator."""
-        self.policy, self.buckets, self.autocast_dtype, self.deterministic = policy, tuple(sorted(buckets)), autocast_dtype, deterministic
-        self.generator = generator
-        self.graphs = {}
-        self.failed = False
-
-    def _run(self, f, lists, lens, masks):
-        kw = {} if self.generator is None else {"generator": self.generator}
-        if self.autocast_dtype is not None:
-            with torch.autocast(device_type="cuda", dtype=self.autocast_dtype):
-                return self.policy.act(f, lists, lens, masks, deterministic=self.deterministic, **kw)
-        return self.policy.act(f, lists, lens, masks, deterministic=self.deterministic, **kw)
-
-    def _capture(self, B, f, lists, lens, masks):
-        st = {"f": f[:1].expand(B, -1).clone(), "lists": lists[:1].expand(B, -1, -1).clone(),
-              "lens": lens[:1].expand(B, -1).clone(), "masks": masks[:1].expand(B, -1).clone()}
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._run(st["f"], st["lists"], st["lens"], st["masks"])
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        if self.generator is not None:
-            g.register_generator_state(self.generator)
-        with torch.cuda.graph(g):
-            v, a, lp = self._run(st["f"], st["lists"], st["lens"], st["masks"])[:3]
-        st["g"], st["v"], st["a"], st["lp"] = g, v, a, lp
-        st["sig"] = self._signature()
-        return st
-
-    def _signature(self):
-        """where the policy's parameters live: a captured graph reads exactly these addresses"""
-        ps = list(self.policy.parameters())
-        return (len(ps), hash(tuple(p.data_ptr() for p in ps)), ps[0].dtype) if ps else ()   # EVERY parameter: one replaced in the middle is stale too
-
-    def static_inputs(self, B):
-        """The captured graph's own input buffers (f, lists, lens, masks) for bucket B, or None before the capture: a producer that
-        writes straight into them (the collector's k_obs_rows / mask expansion) saves the copy of every replay."""
-        st = self.graphs.get(B)
-        return None if st is None else (st["f"], st["lists"], st["lens"], st["masks"])
-
-    def __call__(self, f, lists, lens, masks, with_logp=False, clone=True):
-        """-> (value [n,1], actions [n,18]) (+ log-prob [n,1] with `with_logp`) for n rows; eager when n exceeds the largest
-        bucket.  Inputs that ARE the graph's static buffers (static_inputs) are not copied; clone=False hands out the graph's
-        output buffers themselves (valid until the next replay)."""
-        n = f.shape[0]
-        B = next((b for b in self.buckets if n <= b), None)
-        if B is None or self.failed or not f.is_cuda:
-            v, a, lp = self._run(f, lists, lens, masks)[:3]
-            return (v, a, lp) if with_logp else (v, a)
-        if B not in self.graphs:
-            try:
-                self.graphs[B] = self._capture(B, f, lists, lens, masks)
-            except Exception:                                   # capture not available: stay eager
-                self.failed = True
-                torch.cuda.synchronize()
-                v, a, lp = self._run(f, lists, lens, masks)[:3]
-                return (v, a, lp) if with_logp else (v, a)
-        st = self.graphs[B]
-        if st["sig"] != self._signature():                  # the parameters moved (a .to() / a rebuilt module): the graph is stale
-            self.graphs.clear()
-            return self.__call__(f, lists, lens, masks, with_logp)
-        refresh = getattr(self.policy, "refresh_kernel_packs", None)
-        if refresh is not None:
-            refresh()                                           # host-side parameter packs a replay would not rebuild
-        for k, x in (("f", f), ("lists", lists), ("lens", lens), ("masks", masks)):
-            if x.data_ptr() != st[k].data_ptr():
-                st[k][:n] = x
-        st["g"].replay()
-        out = (st["v"][:n], st["a"][:n], st["lp"][:n]) if with_logp else (st["v"][:n], st["a"][:n])
-        return tuple(o.clone() for o in out) if clone else out
-
-
 # ---------------------------------------------------------------------------------------------------- simulations
 @torch.no_grad()
 def simulate(env, policy, ctrl, init_actions, max_depth=20, gamma=0.999, deterministic=False, generator=None, autocast_dtype=None,
@@ -292,15 +208,10 @@ def simulate(env, policy, ctrl, init_actions, max_depth=20, gamma=0.999, determi
             # the live rows + the net's cast + the copy into the graph's buffers were 15 % of a batch of root decisions
             games = idx.to(torch.int32)
             nl = int(idx.numel())
-            B = next(b for b in graphed.buckets if nl <= b)
-            bufs = graphed.static_inputs(B)
             odt = autocast_dtype if autocast_dtype in (torch.bfloat16,) else torch.float32
-            if bufs is not None and bufs[0].dtype == odt and bufs[1].dtype == torch.int32 and bufs[2].dtype == torch.int32 and bufs[3].dtype == torch.float32:
-                f, lists, lens = env.get_obs_rows(odt, out=tuple(x[:nl] for x in bufs[:3]), games=games)
-                masks = env.get_action_masks(bufs[3][:nl], games=games)
-            else:
-                f, lists, lens = env.get_obs_rows(odt, games=games)
-                masks = env.get_action_masks(games=games)
+            bufs = graphed.input_rows(next(b for b in graphed.buckets if nl <= b), nl, odt)
+            f, lists, lens = env.get_obs_rows(odt, out=None if bufs is None else bufs[:3], games=games)
+            masks = env.get_action_masks(None if bufs is None else bufs[3], games=games)
             args = (f, lists, lens, masks)
         else:
             f, lists, lens = env.get_obs()
@@ -312,12 +223,8 @@ def simulate(env, policy, ctrl, init_actions, max_depth=20, gamma=0.999, determi
             kw = {"hidden": (hid[0, idx, seat], hid[1, idx, seat]), "nonterminal": torch.ones(idx.numel(), device=dev)}
         if graphed is not None and idx.numel() <= graphed.buckets[-1]:
             value_s, action_s = graphed(*args)                                             # hipGraph replay of the pass at the next bucket size (a pass is launch-bound at every width up to 65 536 rows)
-        elif autocast_dtype is not None:
-            with torch.autocast(device_type="cuda", dtype=autocast_dtype):
-                res = policy.act(*args, deterministic=deterministic, generator=generator, **kw)
-            value_s, action_s = res[0], res[1]
         else:
-            res = policy.act(*args, deterministic=deterministic, generator=generator, **kw)
+            res = acting.act(policy, args, autocast_dtype, deterministic=deterministic, generator=generator, **kw)
             value_s, action_s = res[0], res[1]
         if rec:
             hid[0, idx, seat], hid[1, idx, seat] = res[3][0].float(), res[3][1].float()     # :95
@@ -399,11 +306,7 @@ def propose_actions(policy, f, lists, lens, masks, max_actions=10, initial_settl
         mk = torch.from_numpy(m[rows]).to(dev)
         args = (f[idx], lists[idx], lens[idx].long(), mk)
         kw = {"hidden": (h_in[0][idx], h_in[1][idx]), "nonterminal": torch.ones(idx.numel(), device=dev)} if rec else {}
-        if autocast_dtype is not None:
-            with torch.autocast(device_type="cuda", dtype=autocast_dtype):
-                res = policy.act(*args, deterministic=deterministic, generator=generator, condition_on_action_type=forced, **kw)
-        else:
-            res = policy.act(*args, deterministic=deterministic, generator=generator, condition_on_action_type=forced, **kw)
+        res = acting.act(policy, args, autocast_dtype, deterministic=deterministic, generator=generator, condition_on_action_type=forced, **kw)
         if rec:
             h_next[0][idx], h_next[1][idx] = res[3][0].float(), res[3][1].float()
         return res[1].cpu().numpy()

@@ -17,7 +17,8 @@ no-op for type < 0): `env.VecCatanEnv` on the GPU; the CPU tests use an oracle-b
 """
 import torch
 
-from . import spec
+from . import _lib, acting, spec
+from .env import _ptr, _stream
 
 
 class RolloutStorage(object):
@@ -49,15 +50,12 @@ class RolloutStorage(object):
     def unpack_action_masks(self, packed):
         """int32 [..., 11] -> float32 [..., 325]"""
         if packed.is_cuda and packed.dtype == torch.int32:            # one kernel (catan_expand_masks) instead of shift / and / slice / cast passes
-            import ctypes as C
-            from . import _lib
             p = packed.contiguous()
             rows = p.numel() // p.shape[-1]
             out = torch.empty(packed.shape[:-1] + (spec.MASK_WORDS,), dtype=torch.float32, device=p.device)
             if rows == 0:                                             # an empty selection (empty minibatch / group): nothing to expand
                 return out
-            _lib.check(_lib.lib().catan_expand_masks(C.c_void_p(p.data_ptr()), rows, int(p.shape[-1]), C.c_void_p(out.data_ptr()),
-                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _lib.check(_lib.lib().catan_expand_masks(_ptr(p), rows, int(p.shape[-1]), _ptr(out), _stream()))
             return out
         bits = (packed[..., None] >> torch.arange(32, device=packed.device, dtype=torch.int32)) & 1
         return bits.reshape(packed.shape[:-1] + (352,))[..., :spec.MASK_WORDS].float()
@@ -70,6 +68,67 @@ def pack_action_masks(m):
     b[:, :spec.MASK_WORDS] = (m > 0).long()
     w = (b.reshape(N, 11, 32) << torch.arange(32, device=m.device)).sum(-1)
     return torch.where(w >= 2 ** 31, w - 2 ** 32, w).int()
+
+
+def route_rows(pol, opp_index, n_opponents):
+    """The net of each row of a league pass (0 = the central policy, 1 + k = opponent k) from the policy slot of its deciding seat (pol
+    int64 [n]) and opp_index int64 [n, 3].  -> (order, counts): the rows sorted by net, ascending within a net (one stable sort), and
+    the rows of each of the 1 + n_opponents nets (ONE host read per pass)."""
+    ar = torch.arange(pol.shape[0], device=pol.device)
+    net_id = torch.where(pol == 0, torch.zeros_like(pol), 1 + opp_index[ar, (pol - 1).clamp(min=0)])
+    return torch.argsort(net_id, stable=True), torch.bincount(net_id, minlength=n_opponents + 1).tolist()
+
+
+class _LaggedLiveCount(object):
+    """(device loop) How many games still missed observations `lag` iterations ago: an upper bound of today's count (frozen games stay
+    frozen) that costs no host wait per iteration - each one copies its count into a pinned ring and records an event."""
+
+    def __init__(self, n, lag):
+        self.lag, self.ring, self.bound = lag, lag + 2, n
+        self.pin = torch.empty(self.ring, dtype=torch.int64).pin_memory()
+        self.events = [torch.cuda.Event() for _ in range(self.ring)]
+
+    def read(self, iters):
+        j = iters - self.lag
+        if j >= 1:
+            self.events[j % self.ring].synchronize()
+            self.bound = int(self.pin[j % self.ring])
+        return self.bound
+
+    def post(self, iters, count):
+        self.pin[iters % self.ring].copy_(count, non_blocking=True)
+        self.events[iters % self.ring].record()
+
+
+class _PassRows(object):
+    """(device loop) The rows of the policy pass: all N games, then - once the games that still miss observations fit a smaller captured
+    bucket - the list of them as of that bucket change (a game that has frozen since just gets the no-op); row j is game games[j]."""
+
+    def __init__(self, N):
+        self.N, self.B, self.cnt = N, N, N           # games; rows of the captured pass; rows of it in use
+        self.games = self.games_l = None             # the listed games as int32 (the env's kernels) and int64 (index_copy_); None: all
+        self.inputs = None                           # GraphedAct.input_rows of this bucket, once the env writes into them
+        self.full = None                             # (actions, logp) with one row per game
+
+    def shrink(self, newB, live_now, sel):
+        """-> whether the live games fit newB rows (ONE nonzero: the host read of a bucket change); then they are the list.  A game that
+        froze since the count was taken would lose its last observation's append if this iteration's catan_obs_rows left it out: sel stays."""
+        games_l = (live_now | sel.bool()).nonzero(as_tuple=True)[0]
+        if games_l.numel() > newB:
+            return False
+        self.games_l, self.games, self.cnt, self.B = games_l, games_l.to(torch.int32).contiguous(), int(games_l.numel()), newB
+        self.inputs = None                           # (the previous bucket's)
+        if self.full is None:
+            self.full = (sel.new_zeros((self.N, spec.ACTION_WORDS), dtype=torch.int64), sel.new_zeros((self.N,), dtype=torch.float32))
+        return True
+
+    def one_per_game(self, actions, logp):
+        """a pass's rows scattered back to one row per game (the games outside the list are frozen: no-ops)"""
+        if self.games is None:
+            return actions, logp
+        self.full[0].index_copy_(0, self.games_l, actions)
+        self.full[1].index_copy_(0, self.games_l, logp)
+        return self.full
 
 
 class RolloutCollector(object):
@@ -113,7 +172,7 @@ class RolloutCollector(object):
         self.recurrent = bool(getattr(policy, "include_lstm", False))
         # Self-play with one feed-forward net: the policy pass of an env iteration is ~500 small launches and host-bound
         # (7.0 ms of host time for 5.3 ms of kernels at 65 536 rows) - replayed as one captured hipGraph instead
-        # (forward_search.GraphedAct; sampling draws from the same registered generator).  graph_act: None = automatic.
+        # (acting.GraphedAct; sampling draws from the same registered generator).  graph_act: None = automatic.
         if graph_act is None:
             graph_act = (torch.device(self.device).type == "cuda" and not self.recurrent and hasattr(policy, "refresh_kernel_packs")
                          and self.N >= self.GRAPH_ACT_MIN_GAMES)
@@ -136,7 +195,7 @@ class RolloutCollector(object):
         """nets: the distinct opponent nets in play; opp_index int64 [N,3]: which of them plays policy slots 1..3 of
         each game (game_manager.py:15,28-31: the slot -> seat map of a game stays fixed)."""
         self._graphed_nets = {}                  # (captured per-net passes belong to the nets they were captured with)
-        self.opponent_nets = [n.inference_copy(self.autocast_dtype) if (getattr(self, "autocast_dtype", None) is not None and hasattr(n, "inference_copy")
+        self.opponent_nets = [n.inference_copy(self.autocast_dtype) if (self.autocast_dtype is not None and hasattr(n, "inference_copy")
                                                                         and getattr(n, "_inference_dtype", None) is None) else n for n in nets]
         self.opp_index = opp_index.to(self.device).long().contiguous() if len(self.opponent_nets) else None
 
@@ -162,13 +221,9 @@ class RolloutCollector(object):
     def _row_store(self, dst, src, t, sel):
         """dst[t[n], n] = src[n] where sel[n]; dst [steps, N, ...], src [N, ...] (same trailing shape and dtype)"""
         if dst.is_cuda and hasattr(self.env, "L"):
-            import ctypes as C
-            from . import _lib
             src = src.contiguous()
             row_bytes = src[0].numel() * src.element_size()
-            _lib.check(_lib.lib().catan_masked_row_store(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), C.c_void_p(t.data_ptr()),
-                                                         C.c_void_p(sel.data_ptr()), self.N, row_bytes, dst.stride(0) * dst.element_size(),
-                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _lib.check(_lib.lib().catan_masked_row_store(_ptr(dst), _ptr(src), _ptr(t), _ptr(sel), self.N, row_bytes, dst.stride(0) * dst.element_size(), _stream()))
             return
         idx = sel.nonzero(as_tuple=True)[0]
         if idx.numel():
@@ -220,140 +275,123 @@ class RolloutCollector(object):
     @torch.no_grad()
     def gather_rollouts(self, max_iters=None):
         """game_manager.py:69-140.  Returns the storage (first T(+1) entries per game are the rollout)."""
+        env, st, N, dev = self.env, self.storage, self.N, self.device
         try:
-            return self._gather_rollouts(max_iters)
+            self._ar = torch.arange(N, device=dev)
+            if self._shadow is not None:
+                self._shadow.load_from(self.policy)  # the central policy as of this rollout (game_manager.py:161-162 `_update_policy`)
+            self.racc.zero_()                        # `rewards = {...: 0}` at the start of every gather call (:76)
+            self.done_since.zero_()                  # `done_since_prev_turn = [False ...]` (:77)
+            term = st.masks[0].clone()               # `terminal_mask = terminal_masks[env_num][0]` (:74-75)
+            n_live_iters = torch.zeros((), dtype=torch.int64, device=dev)       # iterations in which some game still stepped
+            n_complete = torch.zeros((), dtype=torch.int64, device=dev)
+            # one kernel writes the dense observations the policy pass reads (in the storage's dtype: every value is exact in bf16)
+            # AND appends the active seats' rows to the storage (k_obs_rows)
+            fused_obs = hasattr(env, "get_obs_rows") and st.obs_f.is_cuda and st.obs_f.dtype in (torch.float32, torch.bfloat16)
+            # ... and two kernels do the per-game bookkeeping of an iteration (catan_collector_pre / _post) instead of ~40 tensor operations
+            if fused_obs and hasattr(env, "get_action_masks_packed") and not self.recurrent and hasattr(env, "L") and self.fused_bookkeeping:
+                iters = self._gather_device(max_iters, term, n_live_iters, n_complete)
+            else:
+                iters = self._gather_tensor(max_iters, term, n_live_iters, n_complete, fused_obs)
+            st.games_complete += int(n_complete)
+            if self.episode_stats:
+                st.episode_stats = env.episode_stats(reset=True)
+            st.generation += 1
+            self.iters = int(n_live_iters) if max_iters is None else iters
+            return st
         except BaseException:
             # an error inside the loop (a policy that raises, out of memory) must not leave a catan_step_deferred sequence open:
             # every later step / reset / export of the env would be refused until someone flushed it
-            flush = getattr(self.env, "step_flush", None)
-            if flush is not None and self.deferred_window:
+            if self.deferred_window and hasattr(env, "step_flush"):
                 try:
-                    flush()
+                    env.step_flush()
                 except Exception:
                     pass
             raise
 
-    def _gather_rollouts(self, max_iters=None):
+    def _gather_device(self, max_iters, term, n_live_iters, n_complete):
+        """catan_obs_rows, the policy pass, catan_collector_pre, the env step, catan_collector_post; no host wait but the lagged count"""
         env, st, T, N, dev = self.env, self.storage, self.T, self.N, self.device
-        ar = self._ar = torch.arange(N, device=dev)
-        if self._shadow is not None:
-            self._shadow.load_from(self.policy)  # the central policy as of this rollout (game_manager.py:161-162 `_update_policy`)
-        self.racc.zero_()                        # `rewards = {...: 0}` at the start of every gather call (:76)
-        self.done_since.zero_()                  # `done_since_prev_turn = [False ...]` (:77)
-        term = st.masks[0].clone()               # `terminal_mask = terminal_masks[env_num][0]` (:74-75)
+        fl = self._flags
+        fl[0].copy_(self.done_since)
+        fl[1].copy_(self.pending_obs)
+        live8, sel_next = fl[2], fl[3]
+        t_next = torch.empty(N, dtype=torch.int64, device=dev)
+        a_env = torch.empty((N, spec.ACTION_WORDS), dtype=torch.int32, device=dev)
+        deferred = bool(self.deferred_window) and hasattr(env, "step_deferred")
+        stat, sk = (torch.zeros((2, N), dtype=torch.uint8, device=dev) if deferred else None), 0     # status of the previous / of this catan_step_deferred call (alternating)
+        buckets = self._bucket_list() if ((self.graph_act or self.act_buckets is not None) and not self.opponent_nets and not self.recurrent) else (N,)
+        rows, live = _PassRows(N), _LaggedLiveCount(N, self.LIVE_LAG)
+        self.bucket_log = []         # (iteration, rows of the policy pass, listed games) at every bucket change of this rollout
+        storage_rows = (st.obs_f, st.lists, st.lens)
+        # which games append an observation where: afterwards written by catan_collector_post, which also counts the appends in n_obs
+        sel, t_obs = self.pending_obs & (self.n_obs < T + 1), self.n_obs.clamp(max=T)
         iters = 0
-        n_live_iters = torch.zeros((), dtype=torch.int64, device=dev)       # iterations in which some game still stepped
-        n_complete = torch.zeros((), dtype=torch.int64, device=dev)
-        packed_from_env = hasattr(env, "get_action_masks_packed")
-        # one kernel writes the dense observations the policy pass reads (in the storage's dtype: every value is exact in bf16)
-        # AND appends the active seats' rows to the storage (k_obs_rows; round 2: a lane-per-game encoder, a cast pass and a masked row store)
-        fused_obs = hasattr(env, "get_obs_rows") and st.obs_f.is_cuda and st.obs_f.dtype in (torch.float32, torch.bfloat16)
-        obs_out = mask_out = None
-        # ... and two kernels do the per-game bookkeeping of an iteration (catan_collector_pre / _post) instead of ~40 tensor operations
-        fused_book = fused_obs and packed_from_env and not self.recurrent and hasattr(env, "L") and self.fused_bookkeeping
-        if fused_book:
-            import ctypes as C
-            from . import _lib
-            L, P = _lib.lib(), (lambda x: C.c_void_p(x.data_ptr()))
-            fl = self._flags
-            fl[0].copy_(self.done_since)
-            fl[1].copy_(self.pending_obs)
-            t_next = torch.empty(N, dtype=torch.int64, device=dev)
-            a_env = torch.empty((N, spec.ACTION_WORDS), dtype=torch.int32, device=dev)
-            live8, sel_next = fl[2], fl[3]
-            first = True
-            deferred = bool(self.deferred_window) and hasattr(env, "step_deferred")
-            if deferred:             # status of the previous / of this catan_step_deferred call (alternating)
-                stat, sk = torch.zeros((2, N), dtype=torch.uint8, device=dev), 0
-            # Only the games that still miss observations are evaluated once they fit a smaller captured policy pass: `games` is
-            # the list of those games as of the last bucket change (a superset of them afterwards: a game that has frozen since
-            # just gets the no-op), row j of the policy pass is game games[j].
-            buckets = self._bucket_list() if ((self.graph_act or self.act_buckets is not None) and not self.opponent_nets and not self.recurrent) else (N,)
-            B, games, games_l, cnt = N, None, None, N
-            act_full = logp_full = None
-            RING = self.LIVE_LAG + 2
-            live_pin = torch.empty(RING, dtype=torch.int64).pin_memory() if dev != "cpu" and torch.device(dev).type == "cuda" else torch.empty(RING, dtype=torch.int64)
-            live_ev = [torch.cuda.Event() for _ in range(RING)]
-            live_bound = N
-            self.bucket_log = []         # (iteration, rows of the policy pass, listed games) at every bucket change of this rollout
         while True:
-            if fused_book:
-                if first:
-                    sel = self.pending_obs & (self.n_obs < T + 1)
-                    t_obs = self.n_obs.clamp(max=T)
-                else:
-                    sel, t_obs = sel_next, t_next       # written by catan_collector_post, which also counted the appends in n_obs
-                # the live-game count of LIVE_LAG iterations ago (an upper bound of today's: frozen games stay frozen)
-                j = iters - self.LIVE_LAG
-                if j >= 1:
-                    live_ev[j % RING].synchronize()
-                    live_bound = int(live_pin[j % RING])
-                done_all = live_bound == 0
-                newB = next(b for b in buckets if b >= max(live_bound, 1))
-                if newB < B and not done_all:
-                    live_now = self.n_obs < T + 1       # (host read: at most len(buckets) - 1 times per rollout)
-                    games_l = live_now.nonzero(as_tuple=True)[0]
-                    # a game that froze since the count was taken would lose the append of its last observation if it were dropped
-                    # from the list before this iteration's catan_obs_rows: keep the selected ones
-                    games_l = (live_now | sel.bool()).nonzero(as_tuple=True)[0]
-                    if games_l.numel() <= newB:
-                        games, cnt, B = games_l.to(torch.int32).contiguous(), int(games_l.numel()), newB
-                        self.bucket_log.append((iters, B, cnt))
-                        obs_out = mask_out = None
-                        if act_full is None:
-                            act_full = torch.zeros((N, spec.ACTION_WORDS), dtype=torch.int64, device=dev)
-                            logp_full = torch.zeros((N,), dtype=torch.float32, device=dev)
-                oo = None if obs_out is None else tuple(x[:cnt] for x in obs_out)
-                f, lists, lens = env.get_obs_rows(st.obs_f.dtype, out=oo, rows=(st.obs_f, st.lists, st.lens), t=t_obs, sel=sel, games=games) \
-                    if games is not None else env.get_obs_rows(st.obs_f.dtype, out=obs_out, rows=(st.obs_f, st.lists, st.lens), t=t_obs, sel=sel)
-                if first:
-                    self.n_obs += sel.long()
-                    first = False
-                if max_iters is not None and iters >= max_iters:
-                    break
-                if done_all:
-                    break
-                iters += 1
-                stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                deciding = env.deciding_player()                                                # :79
-                if games is not None:
-                    masks = env.get_action_masks(None if mask_out is None else mask_out[:cnt], games=games)
-                else:
-                    masks = env.get_action_masks(mask_out) if mask_out is not None else env.get_action_masks()   # :83
-                pol = self.policy_of_pid[ar, deciding.long() - 1] if self.opponent_nets else None
-                actions, logp = self._act(f, lists, lens, masks, pol, games=games)              # :85-89
-                if obs_out is None and self._graphed is not None and not self.opponent_nets:
-                    bufs = self._graphed.static_inputs(B)
-                    if bufs is not None and bufs[0].dtype == st.obs_f.dtype and bufs[1].dtype == torch.int32 and bufs[2].dtype == torch.int32:
-                        obs_out, mask_out = bufs[:3], bufs[3]
-                if games is not None:                   # back to one row per game (the games outside the list are frozen: no-ops)
-                    act_full.index_copy_(0, games_l, actions)
-                    logp_full.index_copy_(0, games_l, logp)
-                    actions, logp = act_full, logp_full
-                actions, logp = actions.contiguous(), logp.contiguous()
-                _lib.check(L.catan_collector_pre(N, T, P(self.n_obs), P(actions), P(a_env), P(live8), stream))
-                n_live_iters += live8.any()
-                pmasks = env.get_action_masks_packed()                                          # (before the step replaces them)
-                if deferred:
-                    wb, so = stat[sk], stat[sk ^ 1]
-                    reward, done, _ = env.step_deferred(a_env, self.deferred_window, status_out=so)
-                    sk ^= 1
-                else:
-                    wb = so = None
-                    reward, done = env.step(a_env)                                              # :91 (auto-reset == :113)
-                n_deciding = env.deciding_player()
-                _lib.check(L.catan_collector_post(N, T, P(self._cnt), P(self.racc), P(fl), P(term), P(t_next), P(self.active_pid), P(deciding), P(n_deciding),
-                                                  P(actions), P(logp), P(pmasks), P(reward), P(self.reward64) if self.reward64 is not None else None, P(done),
-                                                  P(st.actions), P(st.action_log_probs), P(st.action_masks), P(st.rewards), P(st.masks), P(n_complete),
-                                                  P(wb) if deferred else None, P(so) if deferred else None, stream))
-                slot = iters % RING
-                live_pin[slot].copy_((self.n_obs < T + 1).sum(), non_blocking=True)
-                live_ev[slot].record()
-                continue
+            bound = live.read(iters)
+            newB = next(b for b in buckets if b >= max(bound, 1))
+            if newB < rows.B and bound and rows.shrink(newB, self.n_obs < T + 1, sel):
+                self.bucket_log.append((iters, rows.B, rows.cnt))
+            f, lists, lens = env.get_obs_rows(st.obs_f.dtype, out=None if rows.inputs is None else rows.inputs[:3], rows=storage_rows, t=t_obs, sel=sel, games=rows.games)
+            if iters == 0:
+                self.n_obs += sel.long()
+            if bound == 0 or (max_iters is not None and iters >= max_iters):
+                break
+            iters += 1
+            deciding = env.deciding_player()                                                # :79
+            masks = env.get_action_masks(None if rows.inputs is None else rows.inputs[3], games=rows.games)  # :83
+            pol = self.policy_of_pid[self._ar, deciding.long() - 1] if self.opponent_nets else None
+            actions, logp = self._act(f, lists, lens, masks, pol, games=rows.games)         # :85-89
+            if rows.inputs is None and self._graphed is not None and not self.opponent_nets:
+                # once the pass of this bucket is captured the env writes straight into its input buffers (no copy per replay)
+                rows.inputs = self._graphed.input_rows(rows.B, rows.cnt, st.obs_f.dtype)
+            actions, logp = rows.one_per_game(actions, logp)
+            actions, logp = actions.contiguous(), logp.contiguous()
+            _lib.check(_lib.lib().catan_collector_pre(N, T, _ptr(self.n_obs), _ptr(actions), _ptr(a_env), _ptr(live8), _stream()))
+            n_live_iters += live8.any()
+            pmasks = env.get_action_masks_packed()                                          # (before the step replaces them)
+            if deferred:
+                wb, so = stat[sk], stat[sk ^ 1]
+                reward, done, _ = env.step_deferred(a_env, self.deferred_window, status_out=so)
+                sk ^= 1
+            else:
+                wb = so = None
+                reward, done = env.step(a_env)                                              # :91 (auto-reset == :113)
+            self._collector_post(term, t_next, n_complete, deciding, env.deciding_player(), actions, logp, pmasks, reward, done, wb, so)
+            live.post(iters, (self.n_obs < T + 1).sum())
+            sel, t_obs = sel_next, t_next
+        if deferred:
+            # the steps that are still outstanding (none when every game has frozen; some after `max_iters`): completed by the flush,
+            # their results booked as in the loop, the observations they make the active seat's appended.  Every game counts as having
+            # waited (`ones`): no decision is appended, none of deciding / actions / logp / pmasks read - the storage's tensors stand in
+            reward, done, so = env.step_flush()
+            ones = torch.ones(N, dtype=torch.uint8, device=dev)
+            deciding = env.deciding_player()
+            self._collector_post(term, t_next, n_complete, deciding, deciding, st.actions, st.action_log_probs, env.get_action_masks_packed(), reward, done, ones, so)
+            env.get_obs_rows(st.obs_f.dtype, rows=storage_rows, t=t_next, sel=sel_next, dense=False)
+        # (the loop left after an observation append: sel / pending_obs of the flags are consumed)
+        self.done_since = fl[0].bool()
+        self.pending_obs = torch.zeros(N, dtype=torch.bool, device=dev)
+        return iters
+
+    def _collector_post(self, term, t_next, n_complete, deciding, n_deciding, actions, logp, pmasks, reward, done, waiting_before, status):
+        """catan_collector_post (include/catan_hip.h): books an env step's results and leaves in flags[3] / t_next which games append their
+        next observation where.  waiting_before / status: of the previous / of this catan_step_deferred call, None with catan_step."""
+        st = self.storage
+        _lib.check(_lib.lib().catan_collector_post(
+            self.N, self.T, _ptr(self._cnt), _ptr(self.racc), _ptr(self._flags), _ptr(term), _ptr(t_next), _ptr(self.active_pid), _ptr(deciding),
+            _ptr(n_deciding), _ptr(actions), _ptr(logp), _ptr(pmasks), _ptr(reward), _ptr(self.reward64), _ptr(done), _ptr(st.actions),
+            _ptr(st.action_log_probs), _ptr(st.action_masks), _ptr(st.rewards), _ptr(st.masks), _ptr(n_complete), _ptr(waiting_before), _ptr(status), _stream()))
+
+    def _gather_tensor(self, max_iters, term, n_live_iters, n_complete, fused_obs):
+        """what the device loop's kernels are tested against; the only form for the CPU oracle env, LSTM policies, fused_bookkeeping = False"""
+        env, st, T, N, dev = self.env, self.storage, self.T, self.N, self.device
+        inp = None               # the captured policy pass's input buffers, once the env writes into them
+        iters = 0
+        while True:
             if fused_obs:
-                sel = self.pending_obs & (self.n_obs < T + 1)
-                t_obs = self.n_obs.clamp(max=T)
-                f, lists, lens = env.get_obs_rows(st.obs_f.dtype, out=obs_out, rows=(st.obs_f, st.lists, st.lens), t=t_obs, sel=sel)
+                sel, t_obs = self.pending_obs & (self.n_obs < T + 1), self.n_obs.clamp(max=T)
+                f, lists, lens = env.get_obs_rows(st.obs_f.dtype, out=None if inp is None else inp[:3], rows=(st.obs_f, st.lists, st.lens), t=t_obs, sel=sel)
                 self._store_obs(sel, None, None, None, t=t_obs)
             else:
                 f, lists, lens = env.get_obs()
@@ -361,100 +399,72 @@ class RolloutCollector(object):
                 self._store_obs(self.pending_obs & (self.n_obs < T + 1), f, lists, lens)
             self.pending_obs = torch.zeros(N, dtype=torch.bool, device=dev)
             frozen = self.n_obs >= T + 1                                                    # while len(observations) < T+1 (:78)
-            if max_iters is not None and iters >= max_iters:
-                break
-            if iters % self.CHECK_EVERY == 0 and bool(frozen.all()):
+            if (max_iters is not None and iters >= max_iters) or (iters % self.CHECK_EVERY == 0 and bool(frozen.all())):
                 break
             iters += 1
             live = ~frozen
             n_live_iters += live.any()
             deciding = env.deciding_player().long()                                         # :79
-            masks = env.get_action_masks(mask_out) if mask_out is not None else env.get_action_masks()   # :83
-            pol = self.policy_of_pid[ar, deciding - 1]
+            masks = env.get_action_masks(inp[3]) if inp is not None else env.get_action_masks()   # :83
+            pol = self.policy_of_pid[self._ar, deciding - 1]
             actions, logp = self._act(f, lists, lens, masks, pol, deciding, term, live)     # :85-89
-            if fused_obs and obs_out is None and self._graphed is not None and not self.opponent_nets:
-                # from now on the env writes straight into the captured graph's input buffers (no copy per replay)
-                bufs = self._graphed.static_inputs(N)
-                if bufs is not None and bufs[0].dtype == st.obs_f.dtype and bufs[1].dtype == torch.int32 and bufs[2].dtype == torch.int32:
-                    obs_out, mask_out = bufs[:3], bufs[3]
+            if fused_obs and inp is None and self._graphed is not None and not self.opponent_nets:
+                inp = self._graphed.input_rows(N, N, st.obs_f.dtype)                        # (as in the device loop)
             a_env = actions.to(torch.int32)
             a_env[:, 0] = torch.where(frozen, torch.full_like(a_env[:, 0], -1), a_env[:, 0])   # frozen games: no-op
-            pmasks = env.get_action_masks_packed() if packed_from_env else pack_action_masks(masks)   # (before the step replaces them)
+            pmasks = env.get_action_masks_packed() if hasattr(env, "get_action_masks_packed") else pack_action_masks(masks)   # (before the step replaces them)
             reward, done = env.step(a_env)                                                  # :91 (auto-reset == :113)
-            done = done.bool() & live
-            term = torch.where(live, 1.0 - done.float(), term)                              # :97
-            self.racc += (reward.double() if self.reward64 is None else self.reward64) * live[:, None]   # :94-95
-            was_active = (deciding == self.active_pid) & live                               # :102-105
-            t = self.n_act.clamp(max=T - 1)
-            self._col_store(st.actions, actions, t, was_active)
-            self._col_store(st.action_log_probs, logp, t, was_active)
-            self._col_store(st.action_masks, pmasks, t, was_active)
-            self.n_act += was_active.long()
-            n_deciding = env.deciding_player().long()                                       # after the step (and the reset)
-            next_active = (n_deciding == self.active_pid) & live
-            r_active = self.racc[ar, self.active_pid - 1]
-            # :106-110 (not done: uses the post-step deciding player) and :112-118 (done: exactly one reward is appended)
-            app = torch.where(done, torch.ones_like(done), next_active & (self.n_act > 0) & ~self.done_since) & live
-            self._col_store(st.rewards, r_active.float(), self.n_rew.clamp(max=T + 1), app)        # process_batch.py:63
-            self.n_rew += app.long()
-            self.racc[ar, self.active_pid - 1] = torch.where(app, torch.zeros_like(r_active), r_active)
-            # :112-124
-            self._col_store(st.masks, 0.0, self.n_msk.clamp(max=T + 1), done)
-            self.n_msk += done.long()
-            self.done_since = self.done_since & ~done
-            self.racc = torch.where(done[:, None], torch.zeros_like(self.racc), self.racc)
-            if self.recurrent:
-                self.hid = torch.where(done[None, :, None, None], torch.zeros_like(self.hid), self.hid)   # :121-124
-            n_complete += done.sum()
-            # :128-136
-            add_mask = next_active & ~done & ~self.done_since
-            self._col_store(st.masks, 1.0, self.n_msk.clamp(max=T + 1), add_mask)
-            self.n_msk += add_mask.long()
-            self.done_since = torch.where(next_active, torch.zeros_like(self.done_since),
-                                          torch.where(done & live, torch.ones_like(self.done_since), self.done_since))
-            self.pending_obs = next_active
-        if fused_book:
-            if deferred:
-                # the steps that are still outstanding (none when every game has frozen; some after `max_iters`): completed by the
-                # flush, their results booked as in the loop, the observations they make the active seat's appended
-                reward, done, so = env.step_flush()
-                ones = torch.ones(N, dtype=torch.uint8, device=dev)
-                deciding = n_deciding = env.deciding_player()
-                _lib.check(L.catan_collector_post(N, T, P(self._cnt), P(self.racc), P(fl), P(term), P(t_next), P(self.active_pid), P(deciding), P(n_deciding),
-                                                  P(actions) if iters else P(a_env), P(logp) if iters else P(term), P(env.get_action_masks_packed()), P(reward),
-                                                  P(self.reward64) if self.reward64 is not None else None, P(done),
-                                                  P(st.actions), P(st.action_log_probs), P(st.action_masks), P(st.rewards), P(st.masks), P(n_complete),
-                                                  P(ones), P(so), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-                env.get_obs_rows(st.obs_f.dtype, rows=(st.obs_f, st.lists, st.lens), t=t_next, sel=sel_next, dense=False)
-            # (the loop left after an observation append: sel / pending_obs of the flags are consumed)
-            self.done_since = fl[0].bool()
-            self.pending_obs = torch.zeros(N, dtype=torch.bool, device=dev)
-        st.games_complete += int(n_complete)
-        if self.episode_stats:
-            st.episode_stats = env.episode_stats(reset=True)
-        st.generation += 1
-        self.iters = int(n_live_iters) if max_iters is None else iters
-        return st
+            term = self._book_step(term, n_complete, live, deciding, actions, logp, pmasks, reward, done)
+        return iters
+
+    def _book_step(self, term, n_complete, live, deciding, actions, logp, pmasks, reward, done):
+        """game_manager.py:91-136 for the games that stepped (`live`), as tensor operations.  -> the new terminal masks."""
+        env, st, T, ar = self.env, self.storage, self.T, self._ar
+        done = done.bool() & live
+        term = torch.where(live, 1.0 - done.float(), term)                              # :97
+        self.racc += (reward.double() if self.reward64 is None else self.reward64) * live[:, None]   # :94-95
+        was_active = (deciding == self.active_pid) & live                               # :102-105
+        t = self.n_act.clamp(max=T - 1)
+        self._col_store(st.actions, actions, t, was_active)
+        self._col_store(st.action_log_probs, logp, t, was_active)
+        self._col_store(st.action_masks, pmasks, t, was_active)
+        self.n_act += was_active.long()
+        n_deciding = env.deciding_player().long()                                       # after the step (and the reset)
+        next_active = (n_deciding == self.active_pid) & live
+        r_active = self.racc[ar, self.active_pid - 1]
+        # :106-110 (not done: uses the post-step deciding player) and :112-118 (done: exactly one reward is appended)
+        app = torch.where(done, torch.ones_like(done), next_active & (self.n_act > 0) & ~self.done_since) & live
+        self._col_store(st.rewards, r_active.float(), self.n_rew.clamp(max=T + 1), app)        # process_batch.py:63
+        self.n_rew += app.long()
+        self.racc[ar, self.active_pid - 1] = torch.where(app, torch.zeros_like(r_active), r_active)
+        # :112-124
+        self._col_store(st.masks, 0.0, self.n_msk.clamp(max=T + 1), done)
+        self.n_msk += done.long()
+        self.done_since = self.done_since & ~done
+        self.racc = torch.where(done[:, None], torch.zeros_like(self.racc), self.racc)
+        if self.recurrent:
+            self.hid = torch.where(done[None, :, None, None], torch.zeros_like(self.hid), self.hid)   # :121-124
+        n_complete += done.sum()
+        # :128-136
+        add_mask = next_active & ~done & ~self.done_since
+        self._col_store(st.masks, 1.0, self.n_msk.clamp(max=T + 1), add_mask)
+        self.n_msk += add_mask.long()
+        self.done_since = torch.where(next_active, torch.zeros_like(self.done_since),
+                                      torch.where(done & live, torch.ones_like(self.done_since), self.done_since))
+        self.pending_obs = next_active
+        return term
 
     def _act(self, f, lists, lens, masks, pol, deciding=None, term=None, live=None, games=None):
         """One batched forward per distinct net in play: net 0 = central policy, net 1 + k = opponent_nets[k].
         With an LSTM policy the deciding seat's state goes in (multiplied by the previous step's terminal mask, :81,85-89)
         and its new state is kept for the games that really step."""
         N = f.shape[0]
+        central = self.policy if self._shadow is None else self._shadow
         if not self.opponent_nets:
-            groups = [(None, self.policy if self._shadow is None else self._shadow)]
+            groups = [(None, central)]
         else:
-            ar = torch.arange(N, device=f.device)
-            net_id = torch.where(pol == 0, torch.zeros_like(pol), 1 + self.opp_index[ar, (pol - 1).clamp(min=0)])
-            # the rows of every net in play, ascending within a net: one stable sort and ONE host read (the group sizes) per pass
-            # (round 5: torch.unique(...).tolist() and a nonzero() per net - five host waits per pass)
-            order = torch.argsort(net_id, stable=True)
-            counts = torch.bincount(net_id, minlength=len(self.opponent_nets) + 1).tolist()
-            groups, o = [], 0
-            for k, c in enumerate(counts):
-                if c:
-                    groups.append((order[o:o + c], (self.policy if self._shadow is None else self._shadow) if k == 0 else self.opponent_nets[k - 1]))
-                o += c
+            order, counts = route_rows(pol, self.opp_index, len(self.opponent_nets))
+            groups = [(idx, net) for idx, net in zip(order.split(counts), [central] + self.opponent_nets) if idx.numel()]
         actions = torch.zeros((N, spec.ACTION_WORDS), dtype=torch.int64, device=f.device)
         logp = torch.zeros((N,), dtype=torch.float32, device=f.device)
         if self.recurrent:
@@ -470,48 +480,41 @@ class RolloutCollector(object):
             if self.recurrent:
                 sel = slice(None) if idx is None else idx
                 kw.update(hidden=(h_in[sel], c_in[sel]), nonterminal=term[sel])
-            if idx is None and getattr(self, "graph_act", False) and not self.recurrent:
-                if self._graphed is None or self._graphed.policy is not net:
-                    from .forward_search import GraphedAct
-                    self._graphed = GraphedAct(net, buckets=self._bucket_list(), autocast_dtype=self.autocast_dtype, generator=self.sample_gen)
-                res = self._graphed(f, lists, lens, masks, with_logp=True, clone=False)
-            elif (idx is not None and getattr(self, "graph_act", False) and not self.recurrent and not getattr(net, "wants_games", False)
-                  and hasattr(net, "refresh_kernel_packs")):
-                # league opponents (round 6): one captured pass per net in play and row-count bucket instead of an eager pass per net
-                # (~150 launches each, host-bound: 9.4 s per rollout of T = 200 at 65 536 games against 2.4 s for self-play);
-                # the rows beyond the group are padding.  Same generator, registered with every graph.
-                from .forward_search import GraphedAct
-                g = self._graphed_nets.get(id(net))
-                if g is None or g.policy is not net:
-                    g = self._graphed_nets[id(net)] = GraphedAct(net, buckets=self._group_buckets(), autocast_dtype=self.autocast_dtype, generator=self.sample_gen)
-                res = g(*args, with_logp=True, clone=False)
-            elif self.autocast_dtype is not None:
-                with torch.autocast(device_type="cuda", dtype=self.autocast_dtype):
-                    res = net.act(*args, **kw)
-            else:
-                res = net.act(*args, **kw)
-            a, lp = res[1], res[2]
+            res = self._call_net(net, args, kw, idx is None)
             if self.recurrent:
                 new_h[sel], new_c[sel] = res[3][0].float(), res[3][1].float()
             if idx is None:
-                actions, logp = a, lp[:, 0]
+                actions, logp = res[1], res[2][:, 0]
             else:
-                actions[idx] = a
-                logp[idx] = lp[:, 0]
+                actions[idx] = res[1]
+                logp[idx] = res[2][:, 0]
         if self.recurrent:
             keep = live[:, None]
             self.hid[0, ar_all, seat] = torch.where(keep, new_h, h_in)                     # :89
             self.hid[1, ar_all, seat] = torch.where(keep, new_c, c_in)
         return actions, logp
 
+    def _call_net(self, net, args, kw, all_rows):
+        """net.act for one group of rows: with graph_act a captured pass (same generator, registered with every graph) - the self-play
+        pass over all rows, or a league net's share of them (one captured pass per net in play and bucket instead of ~150 host-bound
+        launches; the rows beyond the group are padding) -, else the eager call."""
+        if not (self.graph_act and not self.recurrent and (all_rows or (not getattr(net, "wants_games", False) and hasattr(net, "refresh_kernel_packs")))):
+            return acting.act(net, args, self.autocast_dtype, **kw)
+        g = self._graphed if all_rows else self._graphed_nets.get(id(net))
+        if g is None or g.policy is not net:
+            g = acting.GraphedAct(net, buckets=self._bucket_list() if all_rows else self._group_buckets(), autocast_dtype=self.autocast_dtype, generator=self.sample_gen)
+            if all_rows:
+                self._graphed = g
+            else:
+                self._graphed_nets[id(net)] = g
+        return g(*args, with_logp=True, clone=False)
+
     def close(self):
         """Drops what the collector holds on the device - the captured policy passes (hipGraphs and their pools), the acting copy of
         the net and the rollout storage - without waiting for the garbage collector; the collector cannot be used afterwards."""
-        if self._graphed is not None:
-            self._graphed.graphs.clear()
-        self._graphed = self._shadow = self.storage = None
-        for g in getattr(self, "_graphed_nets", {}).values():
+        for g in ([] if self._graphed is None else [self._graphed]) + list(self._graphed_nets.values()):
             g.graphs.clear()
+        self._graphed = self._shadow = self.storage = None
         self._graphed_nets = {}
         self.opponent_nets = []
 

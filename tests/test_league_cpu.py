@@ -62,16 +62,44 @@ class _TagNet(object):
         return torch.zeros(n, 1), a, torch.full((n, 1), float(self.tag))
 
 
+class _StubEnv(object):
+    """what RolloutCollector's constructor asks of an env"""
+    n, device = 37, torch.device("cpu")
+
+    def deciding_player(self):
+        return torch.ones(self.n, dtype=torch.int32)
+
+
+def _routing_inputs():
+    """37 games, 5 opponent nets: opp_index [N, 3] and the policy slot of the deciding seat of each game"""
+    g = torch.Generator().manual_seed(3)
+    opp_index = torch.randint(0, 5, (_StubEnv.n, 3), generator=g)
+    return opp_index, torch.randint(0, 4, (_StubEnv.n,), generator=g)
+
+
+def test_route_rows_sorts_every_game_to_its_net():
+    from settlers_of_catan_rl_amd.rollout import route_rows
+    N = _StubEnv.n
+    opp_index, pol = _routing_inputs()
+    order, counts = route_rows(pol, opp_index, 5)
+    assert isinstance(counts, list) and len(counts) == 6 and sum(counts) == N
+    assert sorted(order.tolist()) == list(range(N))
+    o = 0
+    for k, c in enumerate(counts):
+        rows = order[o:o + c]
+        o += c
+        assert rows.tolist() == sorted(rows.tolist())                 # ascending within a net
+        for gidx in rows.tolist():
+            slot = int(pol[gidx])
+            assert k == (0 if slot == 0 else 1 + int(opp_index[gidx, slot - 1]))
+
+
 def test_grouped_inference_routes_each_seat_to_its_net():
     from settlers_of_catan_rl_amd.rollout import RolloutCollector
-    N = 37
-    col = RolloutCollector.__new__(RolloutCollector)     # only the routing is under test
-    col.policy, col.autocast_dtype, col.sample_gen, col.recurrent, col._shadow = _TagNet(0), None, None, False, None
-    col.N, col.device = N, torch.device("cpu")
-    g = torch.Generator().manual_seed(3)
-    opp_index = torch.randint(0, 5, (N, 3), generator=g)
+    N = _StubEnv.n
+    col = RolloutCollector(_StubEnv(), _TagNet(0), 1)
+    opp_index, pol = _routing_inputs()
     col.set_opponents([_TagNet(10 + k) for k in range(5)], opp_index)
-    pol = torch.randint(0, 4, (N,), generator=g)          # policy slot of the deciding seat of each game
     f = torch.zeros((N, 4)); lists = torch.zeros((N, 5, 25)); lens = torch.ones((N, 5)); masks = torch.ones((N, 325))
     actions, logp = col._act(f, lists, lens, masks, pol)
     want = torch.where(pol == 0, torch.zeros_like(pol), 10 + opp_index[torch.arange(N), (pol - 1).clamp(min=0)])
