@@ -71,6 +71,28 @@ int32_t catan_adam_chunk_elements(void);
 int catan_adam_step(const void* tensors, const void* chunks, int32_t n_chunks, const void* grads, int32_t n_tensors, int32_t none_is_zero, void* partial,
                     float max_norm, float lr, float beta1, float beta2, float eps, float* norm_out, catan_stream_t stream);
 
+/* Diagnostics of one optimiser step of PPO.update, opt-in: what the clipped objective of catan_ppo_loss (catan_hip.h) did to the step's
+ * rows.  The six arrays are catan_ppo_loss's (float32 [B] on the device; logp / values as evaluated for the step), clip / use_norm /
+ * norm_mean / norm_std as given to it; entropy, grad_norm: device float scalars of the step (the mean entropy, the gradient norm before
+ * clipping) or NULL.  ACCUMULATED into `block`: device double [catan_ppo_diag_words()] = 20, owned and zeroed by the caller, one block
+ * per epoch.  With d = (double)logp - (double)old_logp, sums over the rows unless stated:
+ *    0 rows    1 steps (+1 per call)    2 sum(-d)    3 sum(expm1(d) - d)    4 max(d, 0)    5 max(-d, 0)
+ *    6 rows with ratio outside [1 - clip, 1 + clip]      7 rows whose policy gradient the clip zeroed
+ *    8 rows with |v - vp| > clip                         9 rows whose value gradient the clip zeroed
+ *   10, 11 sum ret, ret^2    12, 13 sum e, e^2 (e = ret - v)    14, 15 sum e0, e0^2 (e0 = ret - vp)   (vp, ret normalised when use_norm)
+ *   16 sum entropy    17 sum grad_norm    18 steps with grad_norm > max_grad_norm (never when max_grad_norm <= 0)    19 max grad_norm
+ * Words 16 (entropy NULL) and 17..19 (grad_norm NULL) are left untouched.  Words 6..9 are classified with the loss kernel's own fp32
+ * expressions; the sums are fp64.  workspace: device double [catan_ppo_diag_workspace_doubles()], ZERO before the first call and left
+ * all zero by every call.  The workgroup that finishes last is the only writer of the block and adds the per-workgroup partial sums
+ * in index order: there is no atomic on the block, and a given sequence of calls gives the same bits every time.
+ * ALL CALLS INTO ONE BLOCK (and on one workspace) MUST USE ONE STREAM: the block is read, added to and written back by each launch, and
+ * only the order of launches on a stream keeps two of them apart.  B < 1, a NULL array, block or workspace: CATAN_EINVAL. */
+int64_t catan_ppo_diag_words(void);
+int64_t catan_ppo_diag_workspace_doubles(void);
+int catan_ppo_diag(const float* logp, const float* old_logp, const float* adv, const float* values, const float* old_values,
+                   const float* returns, int64_t B, float clip, int use_norm, float norm_mean, float norm_std, const float* entropy,
+                   const float* grad_norm, float max_grad_norm, double* block, double* workspace, catan_stream_t stream);
+
 /* Row gathers of the learner (RL/ppo/ppo.py:44-50 builds a minibatch with `[obs[i] for i in indices]`; here the rollout is one
  * (T + 1, N, 1 787) bf16 tensor and a minibatch 204 800 of its 3 574-byte rows).
  * catan_gather_rows: dst row j = src row idx[j]; rows of `row_bytes` (even) at any even address and pitch.

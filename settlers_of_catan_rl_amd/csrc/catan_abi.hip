@@ -1437,6 +1437,24 @@ int catan_ppo_loss(const float* logp, const float* old_logp, const float* adv, c
     return CATAN_OK;
 }
 
+int64_t catan_ppo_diag_words(void) { return PPO_DIAG_WORDS; }
+int64_t catan_ppo_diag_workspace_doubles(void) { return PPO_DIAG_PART * PPO_BLOCKS + 1; }
+
+int catan_ppo_diag(const float* logp, const float* old_logp, const float* adv, const float* values, const float* old_values,
+                   const float* returns, int64_t B, float clip, int use_norm, float norm_mean, float norm_std, const float* entropy,
+                   const float* grad_norm, float max_grad_norm, double* block, double* workspace, catan_stream_t stream) {
+    if (B < 1) return fail(CATAN_EINVAL, "catan_ppo_diag: B must be at least 1");
+    if (!logp || !old_logp || !adv || !values || !old_values || !returns) return fail(CATAN_EINVAL, "catan_ppo_diag: a NULL input array");
+    if (!block || !workspace) return fail(CATAN_EINVAL, "catan_ppo_diag: a NULL block or workspace");
+    PpoDiagArgs a{ clip, norm_mean, norm_std, max_grad_norm, use_norm };
+    long nb = (B + PPO_THREADS - 1) / PPO_THREADS;
+    if (nb > PPO_BLOCKS) nb = PPO_BLOCKS;
+    hipLaunchKernelGGL(k_ppo_diag, dim3((unsigned)nb), dim3(PPO_THREADS), 0, S(stream), logp, old_logp, adv, values, old_values, returns, (long)B, a,
+                       entropy, grad_norm, block, workspace);
+    HIPCHK(hipGetLastError());
+    return CATAN_OK;
+}
+
 int catan_attention_fwd(const void* qkv, const int32_t* lens, void* out, int64_t B, int L, int H, int HD, int is_bf16, catan_stream_t stream) {
     if (!qkv || !out || B <= 0) return fail(CATAN_EINVAL, "catan_attention_fwd: bad arguments");
     return is_bf16 ? attn_dispatch<__hip_bfloat16>(false, qkv, lens, nullptr, out, B, L, H, HD, S(stream))

@@ -108,3 +108,167 @@ def ppo_loss(action_log_probs, values, old_action_log_probs, adv_targets, value_
     applies RL/models/utils.py:17-18 to value_preds and returns first, as RL/ppo/ppo.py:46-48 does."""
     return _loss_backend(action_log_probs, values, old_action_log_probs, adv_targets, value_preds, returns,
                          clip_param, value_loss_coef, value_normaliser)
+
+
+# ------------------------------------------------------------------------------------------------ update diagnostics
+# What the clipped objective did during an update (k_ppo_diag, csrc/catan_ppo.hip; the words are listed in include/catan_hip_nn.h
+# and DESIGN.md 8.7): accumulated on the device into one block of DIAG_WORDS doubles per epoch, read by the host once per update.
+DIAG_WORDS = 20
+DIAG_MAX_WORDS = (4, 5, 19)                                                        # maxima over calls (and over ranks)
+DIAG_PER_STEP_WORDS = (1, 16, 17, 18)        # the same on every rank (steps, and the step's global scalars): a sum over ranks / world size
+
+_DIAG_WS = {}
+
+
+def _diag_workspace(device):
+    """zeroed once; every k_ppo_diag call leaves it all zero (include/catan_hip_nn.h).  One per (device, STREAM), as _loss_workspace."""
+    key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0)
+    if key not in _DIAG_WS:
+        _DIAG_WS[key] = torch.zeros((_lib.lib().catan_ppo_diag_workspace_doubles(),), dtype=torch.float64, device=device)
+    return _DIAG_WS[key]
+
+
+def _check_diag_block(block):
+    if block.dtype != torch.float64 or block.numel() != DIAG_WORDS or not block.is_contiguous():
+        raise ValueError("ppo_diag: the block is a contiguous float64 tensor of %d words" % DIAG_WORDS)
+
+
+def _scalar(x, device):
+    if x is None:
+        return None
+    x = x.detach().float().reshape(-1)
+    if x.numel() != 1 or x.device != device:
+        raise ValueError("ppo_diag: entropy / grad_norm are one-element tensors on the rows' device")
+    return x
+
+
+def _hip_ppo_diag(block, logp, values, old_logp, adv, old_values, returns, clip, norm, entropy, grad_norm, max_grad_norm):
+    """k_ppo_diag on the current stream (all calls into one block must come from one stream)"""
+    _check_diag_block(block)
+    if not block.is_cuda or block.device != logp.device:
+        raise ValueError("ppo_diag: the block lives on the rows' device")
+    args = [x.detach().contiguous().float().view(-1) for x in (logp, old_logp, adv, values, old_values, returns)]
+    ent, gn = _scalar(entropy, logp.device), _scalar(grad_norm, logp.device)
+    use_norm, mean, std = (0, 0.0, 1.0) if norm is None else (1, float(norm[0]), float(norm[1]))
+    _lib.check(_lib.lib().catan_ppo_diag(*[_ptr(x) for x in args], args[0].numel(), float(clip), use_norm, mean, std,
+                                         None if ent is None else _ptr(ent), None if gn is None else _ptr(gn), float(max_grad_norm),
+                                         _ptr(block), _ptr(_diag_workspace(logp.device)), _stream()))
+
+
+def _torch_ppo_diag(block, logp, values, old_logp, adv, old_values, returns, clip, norm, entropy, grad_norm, max_grad_norm):
+    """The same twenty words as torch operations (tensors that are not on the device: the CPU tests, a CPU learner): the decisions of
+    words 6..9 in fp32 as the loss takes them, the sums in fp64."""
+    _check_diag_block(block)
+    f32 = torch.float32
+    lp, ol, ad, v, vp0, ret0 = (x.detach().reshape(-1).to(f32) for x in (logp, old_logp, adv, values, old_values, returns))
+    clip32 = torch.tensor(float(clip), dtype=f32)
+    vp, ret = vp0, ret0
+    if norm is not None:
+        mean32, den32 = torch.tensor(float(norm[0]), dtype=f32), torch.tensor(float(norm[1]), dtype=f32) + torch.tensor(1e-4, dtype=f32)
+        vp, ret = (vp0 - mean32) / den32, (ret0 - mean32) / den32
+    lo, hi = 1.0 - clip32, 1.0 + clip32
+    ratio = torch.exp(lp - ol)
+    s1, s2 = ratio * ad, torch.minimum(torch.maximum(ratio, lo), hi) * ad
+    inside = (ratio >= lo) & (ratio <= hi)
+    dv = v - vp
+    vc = vp + torch.minimum(torch.maximum(dv, -clip32), clip32)
+    l1, l2 = (v - ret) ** 2, (vc - ret) ** 2
+    vin = (dv >= -clip32) & (dv <= clip32)
+    d = lp.double() - ol.double()
+    vpd, rd = vp0.double(), ret0.double()
+    if norm is not None:
+        mean, den = float(mean32), float(torch.tensor(float(norm[1]), dtype=f32)) + 1e-4
+        vpd, rd = (vpd - mean) / den, (rd - mean) / den
+    e, e0 = rd - v.double(), rd - vpd
+    zero = torch.zeros((), dtype=torch.float64)
+    w = [zero] * DIAG_WORDS
+    w[0], w[1] = zero + float(lp.numel()), zero + 1.0
+    w[2], w[3] = (-d).sum(), (torch.expm1(d) - d).sum()
+    w[4], w[5] = torch.clamp(d, min=0.0).max(), torch.clamp(-d, min=0.0).max()
+    w[6], w[7] = (~inside).sum().double(), (~inside & (s1 > s2)).sum().double()
+    w[8], w[9] = (~vin).sum().double(), (~(l1 >= l2) & ~vin).sum().double()
+    w[10], w[11], w[12], w[13], w[14], w[15] = rd.sum(), (rd * rd).sum(), e.sum(), (e * e).sum(), e0.sum(), (e0 * e0).sum()
+    ent, gn = _scalar(entropy, lp.device), _scalar(grad_norm, lp.device)
+    touched = set(range(16))
+    if ent is not None:
+        w[16] = ent[0].double()
+        touched.add(16)
+    if gn is not None:
+        w[17], w[19] = gn[0].double(), gn[0].double()
+        w[18] = ((gn[0] > torch.tensor(float(max_grad_norm), dtype=f32)) & (float(max_grad_norm) > 0.0)).double()
+        touched.update((17, 18, 19))
+    new = torch.stack([x.to(block.device) for x in w]).reshape(block.shape)
+    is_max = torch.zeros(DIAG_WORDS, dtype=torch.bool, device=block.device)
+    is_max[list(DIAG_MAX_WORDS)] = True
+    keep = torch.ones(DIAG_WORDS, dtype=torch.bool, device=block.device)
+    keep[sorted(touched)] = False
+    block.copy_(torch.where(keep.reshape(block.shape), block, torch.where(is_max.reshape(block.shape), torch.maximum(block, new), block + new)))
+
+
+def _default_ppo_diag(block, logp, values, old_logp, adv, old_values, returns, clip, norm, entropy, grad_norm, max_grad_norm):
+    backend = _hip_ppo_diag if logp.is_cuda else _torch_ppo_diag       # (rows on the device and no library: an error, not the torch form)
+    return backend(block, logp, values, old_logp, adv, old_values, returns, clip, norm, entropy, grad_norm, max_grad_norm)
+
+
+_diag_backend = _default_ppo_diag    # (replaceable like _loss_backend)
+
+
+def ppo_diag(block, logp, values, old_logp, adv, old_values, returns, clip=0.2, value_normaliser=None, entropy=None, grad_norm=None,
+             max_grad_norm=0.0):
+    """One optimiser step's diagnostics, ADDED into `block` (float64 [20] on the rows' device, zeroed by the caller, one per epoch; all
+    calls into one block on one stream).  The first six row arguments and `clip`, `value_normaliser` are ppo_loss's; `entropy`,
+    `grad_norm`: one-element tensors of the step (or None: their words stay as they are).  No host read; `diag_summary` turns the
+    blocks of an update into numbers once they are on the host."""
+    _diag_backend(block, logp, values, old_logp, adv, old_values, returns, clip, value_normaliser, entropy, grad_norm, max_grad_norm)
+
+
+def _diag_numbers(w):
+    nan = float("nan")
+    rows, steps = float(w[0]), float(w[1])
+    per_row = (lambda x: float(x) / rows) if rows > 0 else (lambda x: nan)
+    per_step = (lambda x: float(x) / steps) if steps > 0 else (lambda x: nan)
+
+    def explained(s, ss):
+        if not rows > 0:
+            return nan
+        var_ret = float(w[11]) / rows - (float(w[10]) / rows) ** 2
+        if not var_ret > 0.0:
+            return nan
+        return 1.0 - (float(ss) / rows - (float(s) / rows) ** 2) / var_ret
+    return {"approx_kl": per_row(w[3]), "approx_kl_k1": per_row(w[2]), "max_log_ratio_up": float(w[4]), "max_log_ratio_down": float(w[5]),
+            "clip_fraction": per_row(w[6]), "policy_grad_zero_fraction": per_row(w[7]),
+            "value_clip_fraction": per_row(w[8]), "value_grad_zero_fraction": per_row(w[9]),
+            "explained_variance": explained(w[12], w[13]), "explained_variance_old": explained(w[14], w[15]),
+            "entropy": per_step(w[16]), "grad_norm_mean": per_step(w[17]), "grad_norm_max": float(w[19]),
+            "grad_clipped_fraction": per_step(w[18]), "rows": int(round(rows)), "steps": int(round(steps))}
+
+
+def diag_summary(blocks):
+    """blocks: HOST array [epochs][20] (the device blocks of an update, copied once) -> {key: [value per epoch], ...,
+    "update": {key: value over all epochs}}.  approx_kl = word 3 / rows (the k3 estimator E[(r - 1) - log r]), approx_kl_k1 = word 2 /
+    rows; the fractions are per row; explained_variance(_old) = 1 - Var(ret - v) / Var(ret) (v: the values being trained / the
+    epoch's re-evaluated predictions), NaN when Var(ret) is 0; entropy, grad_norm_mean and grad_clipped_fraction are per step."""
+    import numpy as np
+    b = np.asarray(blocks, dtype=np.float64).reshape(-1, DIAG_WORDS)
+    per = [_diag_numbers(row) for row in b]
+    out = {k: [p[k] for p in per] for k in _diag_numbers(np.zeros(DIAG_WORDS))}
+    total = b.sum(axis=0)
+    for k in DIAG_MAX_WORDS:
+        total[k] = b[:, k].max() if len(b) else 0.0
+    out["update"] = _diag_numbers(total)
+    return out
+
+
+def reduce_diag_over_ranks(block):
+    """In place, a device (or CPU, under gloo) tensor [..., 20] of blocks: two all-reduces over the default group - SUM, and MAX for
+    the maximum words - then the words that are the same on every rank (steps, entropy and gradient-norm sums, clipped steps: every
+    rank takes the same steps and the gradient norm is already global) divided by the world size.  Nothing without >1 rank."""
+    dist = torch.distributed
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return block
+    mx = block[..., list(DIAG_MAX_WORDS)].contiguous()
+    dist.all_reduce(block, op=dist.ReduceOp.SUM)
+    dist.all_reduce(mx, op=dist.ReduceOp.MAX)
+    block[..., list(DIAG_MAX_WORDS)] = mx
+    block[..., list(DIAG_PER_STEP_WORDS)] /= dist.get_world_size()
+    return block

@@ -734,6 +734,7 @@ def storage_from_reference_lists(rollouts, num_steps, device, lstm_dim=0):
 # ------------------------------------------------------------------------------------------------ PPO (L4)
 _GAE = ppo_kernels.compute_gae          # the fused HIP kernels; module attributes so that CPU tests can put stand-ins here
 _LOSS = ppo_kernels.ppo_loss
+_DIAG = ppo_kernels.ppo_diag
 
 
 class PPO(object):
@@ -750,10 +751,14 @@ class PPO(object):
         self.optimiser = FusedAdam(actor_critic.parameters(), lr=args.lr, eps=args.eps, none_grad_is_zero=True)
         self.bucket = cdist.GradBucket(actor_critic.parameters(), assign_when_single_rank=True)     # persistent flat gradient buffer (one all-reduce per step)
         self.timings = {}
+        self.diagnostics = None       # ppo.diag_summary of the last update when args.ppo_diagnostics is set
 
     def update(self, rollout_storage):
         ac = self.actor_critic
         sums = None
+        diag = None
+        if getattr(self.args, "ppo_diagnostics", False):      # one block per epoch on the device, read once at the end
+            diag = torch.zeros((self.ppo_epoch, ppo_kernels.DIAG_WORDS), dtype=torch.float64, device=next(ac.parameters()).device)
         t_adv = t_opt = 0.0
         n_steps = 0
         for e in range(self.ppo_epoch):
@@ -784,8 +789,15 @@ class PPO(object):
                 s = torch.stack((parts[1].detach() * self.value_loss_coef, parts[0].detach(), entropy.detach().float() * self.entropy_coef))
                 sums = s if sums is None else sums + s
                 n_steps += 1
+                if diag is not None:
+                    _DIAG(diag[e], action_log_probs.detach(), values.detach(), old_action_log_probs_batch, adv_target, value_preds_batch,
+                          returns_batch, self.clip_param, value_normaliser=norm, entropy=entropy, grad_norm=self.optimiser.last_norm,
+                          max_grad_norm=self.max_grad_norm if self.max_grad_norm is not None else 0.0)
             t_adv += t1 - t0; t_opt += time.perf_counter() - t1
         self.timings = {"advantages_s": t_adv, "minibatches_s": t_opt}
+        self.diagnostics = None
+        if diag is not None:
+            self.diagnostics = ppo_kernels.diag_summary(ppo_kernels.reduce_diag_over_ranks(diag).cpu().numpy())
         vl, al, el = (sums / n_steps).tolist()                                               # ppo.py:70-79
         return vl, al, el
 

@@ -36,6 +36,8 @@ class PPOConfig(object):
     entropy_coef = 0.04
     max_grad_norm = 0.5
     truncated_seq_len = 10            # arguments.py:57-59 (LSTM policies only)
+    diagnostics = False               # per-epoch KL / clip fractions / explained variance / gradient norm of an update (ppo.ppo_diag): off launches nothing
+    target_kl = None                  # with diagnostics: skip an update's remaining epochs once an epoch's approx_kl exceeds this (one host read per epoch)
     value_chunk = 1048576      # rows per forward of the value pass (swept on MI355X at 13.2 M rows: 131 072: 184 ms, 262 144: 177, 524 288: 171, 1 048 576: 164; ~4 GB of activations)
 
     def __init__(self, **kw):
@@ -82,6 +84,9 @@ class PPOTrainer(object):
         self.gen = torch.Generator(device=dev).manual_seed(seed + 17 * (1 + (torch.distributed.get_rank()
                                                                          if torch.distributed.is_initialized() else 0)))
         self.timings = {}
+        if self.cfg.target_kl is not None and not self.cfg.diagnostics:
+            raise ValueError("PPOConfig.target_kl needs PPOConfig.diagnostics (the KL of an epoch is read from its diagnostics block)")
+        self.diagnostics = None       # ppo.diag_summary of the last update when cfg.diagnostics, else None
 
     def _autocast(self):
         if self.autocast_dtype is None:
@@ -210,8 +215,11 @@ class PPOTrainer(object):
         return self.policy.denormalise(out).reshape(T1, N)
 
     def update(self, st):
-        """-> (value_loss, action_loss, entropy_loss) averaged over the optimiser steps, as ppo.py:70-79."""
+        """-> (value_loss, action_loss, entropy_loss) averaged over the optimiser steps, as ppo.py:70-79.  With cfg.diagnostics the
+        update's read-out is left in `self.diagnostics` (ppo.diag_summary)."""
         cfg, pol = self.cfg, self.policy
+        if cfg.target_kl is not None and not cfg.diagnostics:
+            raise ValueError("PPOConfig.target_kl needs PPOConfig.diagnostics")
         T, N = st.T, st.N
         dev = st.obs_f.device
         total = T * N
@@ -239,7 +247,10 @@ class PPOTrainer(object):
         timed_allreduce = dev.type == "cuda" and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
         ar_events = []
         t_val = t_gae = t_opt = 0.0
-        for _ in range(cfg.ppo_epoch):
+        # one block of doubles per epoch, added to by one launch per step on this stream, copied to the host once at the end
+        diag = torch.zeros((cfg.ppo_epoch, ppo_kernels.DIAG_WORDS), dtype=torch.float64, device=dev) if cfg.diagnostics else None
+        epochs = steps = 0
+        for ep in range(cfg.ppo_epoch):
             t0 = time.perf_counter()
             values = self.compute_values(st)                                               # ppo.py:31-32
             self._sync(); t1 = time.perf_counter()
@@ -282,7 +293,8 @@ class PPOTrainer(object):
                         v, lp, ent = pol.evaluate_actions(cast(f_all[idx]), lists_all[idx], lens_all[idx].long(),
                                                           amasks(idx), acts_all[idx],
                                                           **({} if groupings is None else {"grouping": groupings[bi]}))
-                loss, parts = ppo_kernels.ppo_loss(lp.float(), v.float(), old_lp_all[idx], advf[idx], vpred[idx], ret[idx],
+                rows4 = (old_lp_all[idx], advf[idx], vpred[idx], ret[idx])                   # (gathered once: the diagnostics read them again)
+                loss, parts = ppo_kernels.ppo_loss(lp.float(), v.float(), *rows4,
                                                    cfg.clip_param, cfg.value_loss_coef,
                                                    value_normaliser=(pol.VALUE_MEAN, pol.VALUE_STD))     # ppo.py:46-63
                 self.bucket.zero()
@@ -307,9 +319,22 @@ class PPOTrainer(object):
                 nn_kernels.grad_arena.end_step()
                 nn_kernels.weight_images.refresh_all()                                     # every bf16 / transposed / packed image of the new weights: one launch
                 sums += torch.stack((parts[0], parts[1], ent.detach().float()))
+                steps += 1
+                if diag is not None:
+                    ppo_kernels.ppo_diag(diag[ep], lp.detach(), v.detach(), *rows4, cfg.clip_param,
+                                         value_normaliser=(pol.VALUE_MEAN, pol.VALUE_STD), entropy=ent, grad_norm=self.optimiser.last_norm,
+                                         max_grad_norm=cfg.max_grad_norm)
             self._sync(); t3 = time.perf_counter()
             t_val += t1 - t0; t_gae += t2 - t1; t_opt += t3 - t2
-        n = cfg.ppo_epoch * len(batches)
+            epochs += 1
+            if cfg.target_kl is not None:                 # the one host read per epoch: this epoch's rows and k3 sum, over all ranks
+                rows, k3 = ppo_kernels.reduce_diag_over_ranks(diag[ep].clone())[[0, 3]].tolist()
+                if k3 / rows > cfg.target_kl:
+                    break
+        n = steps
+        self.diagnostics = None
+        if diag is not None:
+            self.diagnostics = ppo_kernels.diag_summary(ppo_kernels.reduce_diag_over_ranks(diag[:epochs].clone()).cpu().numpy())
         self.timings = {"values_s": t_val, "gae_s": t_gae, "minibatches_s": t_opt}
         if timed_allreduce:                               # device time inside the gradient all-reduces (part of minibatches_s)
             self._sync()

@@ -123,6 +123,8 @@ class TrainingLoop(object):
                "hours": (time.time() - self.start_time) / 3600.0, "eval": summary}
         if getattr(st, "episode_stats", None) is not None:       # RolloutCollector(episode_stats=True): the games this rollout finished
             out["episodes"] = st.episode_stats
+        if getattr(self.trainer, "diagnostics", None) is not None:   # PPOConfig(diagnostics=True): what the clipped objective did in this update
+            out["ppo"] = self.trainer.diagnostics
         return out
 
     def save(self, path):

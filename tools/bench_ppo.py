@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--league", type=int, default=0,
                     help="K > 0: opponents from the snapshot league, at most K distinct nets in play (league.League, bounded "
                          "variant); 0: every seat plays the central policy")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="PPOConfig.diagnostics: per-epoch approx_kl / clip_fraction / explained_variance of every update (one more launch per step)")
     args = ap.parse_args()
     import torch
     from settlers_of_catan_rl_amd import dist as cdist
@@ -50,7 +52,8 @@ def main():
     cdist.broadcast_parameters(net)                         # every rank starts from rank 0's weights
     ac = None if args.fp32 else torch.bfloat16
     col = RolloutCollector(env, net, args.num_steps, seed=rank, autocast_dtype=ac)
-    tr = PPOTrainer(net, PPOConfig(ppo_epoch=args.ppo_epoch, num_mini_batch=args.num_mini_batch), autocast_dtype=ac, seed=rank)
+    tr = PPOTrainer(net, PPOConfig(ppo_epoch=args.ppo_epoch, num_mini_batch=args.num_mini_batch, diagnostics=args.diagnostics),
+                    autocast_dtype=ac, seed=rank)
     lg = None
     if args.league > 0:
         from settlers_of_catan_rl_amd.league import League
@@ -72,6 +75,12 @@ def main():
             lg.assign(col, make_net)
         res.append(dict(rollout_s=cdist.max_over_ranks(t1 - t0), update_s=cdist.max_over_ranks(t2 - t1), env_iters=col.iters,
                         value_loss=vl, action_loss=al, entropy_loss=el, **tr.timings))
+        if tr.diagnostics is not None:
+            res[-1]["ppo"] = tr.diagnostics
+            if rank == 0:
+                fmt = lambda xs: " ".join("%.3e" % x for x in xs)
+                for k in ("approx_kl", "clip_fraction", "explained_variance"):
+                    print(f"update {u} {k:18s} per epoch: {fmt(tr.diagnostics[k])}   update: {tr.diagnostics['update'][k]:.3e}", flush=True)
     if rank == 0:
         last = res[-1]
         dec = world * n * args.num_steps

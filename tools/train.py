@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--checkpoint", type=str, default="")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lstm", action="store_true", help="include_lstm (build_agent_model.py:26): LSTM policy + truncated BPTT")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="PPOConfig.diagnostics: every update's line carries \"ppo\" (per-epoch KL, clip fractions, explained variance, gradient norm)")
     args = ap.parse_args()
     import torch
     from settlers_of_catan_rl_amd import dist as cdist
@@ -44,7 +46,7 @@ def main():
     net = CatanPolicy(include_lstm=args.lstm).cuda()
     cdist.broadcast_parameters(net)
     col = RolloutCollector(env, net, args.num_steps, seed=rank, autocast_dtype=torch.bfloat16)
-    tr = PPOTrainer(net, PPOConfig(ppo_epoch=args.ppo_epoch, num_mini_batch=args.num_mini_batch), seed=rank)
+    tr = PPOTrainer(net, PPOConfig(ppo_epoch=args.ppo_epoch, num_mini_batch=args.num_mini_batch, diagnostics=args.diagnostics), seed=rank)
     random_net = CatanPolicy(include_lstm=args.lstm).cuda().eval()                                   # robust_train.py:76-78: the evaluation opponent
 
     def evaluate(policy, update_num):
@@ -61,6 +63,10 @@ def main():
         if rank == 0:
             if out["eval"]:
                 print(out["eval"])
+            if "ppo" in out:
+                fmt = lambda xs: " ".join("%.3e" % x for x in xs)
+                for k in ("approx_kl", "clip_fraction", "explained_variance"):
+                    print(f"update {out['update']} {k:18s} per epoch: {fmt(out['ppo'][k])}", flush=True)
             print(json.dumps({k: v for k, v in out.items() if k != "eval"}), flush=True)
     cdist.finalize()
 
