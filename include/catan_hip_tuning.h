@@ -1,9 +1,10 @@
 /*
  * catan_hip_tuning.h - scheduling knobs, counters and profilers of the env kernels in libcatan_hip.so.  Benchmarks, sweeps and
  * diagnostics only (bench.py, tools): results never depend on any of them, and nothing a reference-side binding needs is
- * declared here (that is catan_hip.h).  Two sections are no knobs: "search support" (catan_state_fork), which the forward search uses,
- * and "finished-game statistics" (catan_episode_stats_*), which the rollout collector uses: the reference has no such interface to replace,
- * and catan_hip.h stays the reference's boundary.
+ * declared here (that is catan_hip.h).  Three sections are no knobs: "search support" (catan_state_fork), which the forward search uses,
+ * "finished-game statistics" (catan_episode_stats_*), which the rollout collector uses, and "rule-based player"
+ * (catan_sample_scripted_actions), a fixed-strength opponent: the reference has no such interface to replace, and catan_hip.h stays the
+ * reference's boundary.
  */
 #ifndef CATAN_HIP_TUNING_H
 #define CATAN_HIP_TUNING_H
@@ -82,6 +83,22 @@ int catan_state_fork(catan_env_t* dst, const catan_env_t* src, const int64_t* sr
 int32_t catan_episode_stats_words(void);
 int catan_episode_stats_enable(catan_env_t* env, int on, const int32_t* focus_pid, catan_stream_t stream);
 int catan_episode_stats_read(catan_env_t* env, uint64_t* out_host, int reset, catan_stream_t stream);
+
+/* ---- rule-based player ----
+ * The "builder" bot (csrc/catan_scripted.hip): a deterministic scripted policy - the same state always gives the same
+ * action, every action is legal under the game's masks, it never proposes a trade - decided by one lane-per-game kernel.  It decides for
+ * the deciding player of catan_deciding_seat (discarder, then trade target, then players_go).
+ * actions: DEVICE int32 [n_rows][18].  games == NULL: row j is game j and n_rows <= n; otherwise games is a DEVICE int32 [n_rows] and row j
+ * is game games[j], as in catan_masks_of (any number of rows; a game may be listed more than once).
+ * The handle's packed masks are REQUIRED to be current, exactly as for catan_sample_random_actions: the kernel reads them and does not
+ * recompute them (they are current after catan_create, catan_reset, catan_step, catan_state_import, catan_state_fork and for every game
+ * that is not waiting inside a catan_step_deferred sequence).  A negative or out-of-range id, and a game that waits for its deferred
+ * step, gets EndTurn - the answer to the placeholder mask row catan_masks_of gives such a game; catan_step_deferred ignores it.
+ * catan_scripted_fallback_count: decisions since creation that no row of the rule but its last ("any legal type") could take - expected
+ * 0; synchronises the stream; -1 on a null handle or a HIP error.
+ * CATAN_EINVAL, nothing launched: a null handle, null actions, n_rows <= 0, n_rows > n with games == NULL. */
+int catan_sample_scripted_actions(catan_env_t* env, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream);
+int64_t catan_scripted_fallback_count(catan_env_t* env, catan_stream_t stream);
 
 /* the rollout loops with a hipEvent around every kernel launch (recorded on the stream the kernel runs on); window <= 0: the
  * lock-step loop (step_idx0 as in catan_random_rollout), window > 0: the deferred loop (step_idx0 ignored).  kernel_ms is a HOST

@@ -23,6 +23,7 @@
 #include "catan_optim.hip"
 #include "catan_wgrad_big.hip"
 #include "catan_stats.hip"
+#include "catan_scripted.hip"
 
 using namespace catan;
 
@@ -89,6 +90,7 @@ struct catan_env {
     unsigned long long* stats;   // catan_episode_stats_enable: the block of ES_WORDS counters (catan_stats.hip), allocated at the first enable
     const i32* stats_focus;      // ... the caller's focus array (device int32 [n]) or NULL
     int stats_on;
+    unsigned long long* script_fallback;   // catan_sample_scripted_actions: decisions taken by the fall-back row (catan_scripted.hip), allocated at the first call
 };
 static_assert(sizeof(BoardCfg) == sizeof(catan_board_cfg_t) && sizeof(catan_board_cfg_t) == 56 &&
               offsetof(BoardCfg, terrain) == offsetof(catan_board_cfg_t, terrain) &&
@@ -996,6 +998,34 @@ int catan_episode_stats_read(catan_env_t* e, uint64_t* out_host, int reset, cata
     if (reset) HIPCHK(hipMemsetAsync(e->stats, 0, ES_WORDS * sizeof(unsigned long long), S(stream)));
     HIPCHK(hipStreamSynchronize(S(stream)));
     return CATAN_OK;
+}
+
+// ---- the rule-based player (catan_scripted.hip)
+int catan_sample_scripted_actions(catan_env_t* e, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_sample_scripted_actions: null handle");
+    if (!actions) return fail(CATAN_EINVAL, "catan_sample_scripted_actions: null actions");
+    if (n_rows <= 0) return fail(CATAN_EINVAL, "catan_sample_scripted_actions: n_rows <= 0");
+    if (!games && n_rows > e->n) return fail(CATAN_EINVAL, "catan_sample_scripted_actions: n_rows exceeds the handle's games (games == NULL)");
+    if (!e->script_fallback) {
+        hipError_t rc = hipSuccess;
+        dev_alloc(e, rc, e->script_fallback, sizeof(unsigned long long));
+        if (rc != hipSuccess) return fail(CATAN_ENOMEM, std::string("catan_sample_scripted_actions: hipMalloc: ") + hipGetErrorString(rc));
+        // zeroed synchronously at its allocation (once per handle): in place before a call on ANY stream can count into it
+        HIPCHK(hipMemset(e->script_fallback, 0, sizeof(unsigned long long)));
+        HIPCHK(hipStreamSynchronize(nullptr));
+    }
+    hipLaunchKernelGGL(k_sample_scripted, dim3(blocks(n_rows, SCRIPT_BLOCK)), dim3(SCRIPT_BLOCK), 0, S(stream), e->ctx, (const u32*)e->mpk, games, (long)n_rows,
+                       e->d_it > 0 ? (const u8*)e->pend.busy : (const u8*)nullptr, actions, e->script_fallback);
+    HIPCHK(hipGetLastError());
+    return CATAN_OK;
+}
+int64_t catan_scripted_fallback_count(catan_env_t* e, catan_stream_t stream) {
+    if (!e) return -1;
+    if (!e->script_fallback) return 0;
+    unsigned long long v = 0;
+    if (hipMemcpyAsync(&v, e->script_fallback, sizeof v, hipMemcpyDeviceToHost, S(stream)) != hipSuccess) return -1;
+    if (hipStreamSynchronize(S(stream)) != hipSuccess) return -1;
+    return (int64_t)v;
 }
 
 int catan_random_rollout(catan_env_t* e, uint32_t step_idx0, int64_t steps, catan_stream_t stream) {

@@ -257,6 +257,25 @@ class VecCatanEnv(object):
         _lib.check(self.L.catan_sample_random_actions(self.h, int(step_idx), _ptr(out), _stream()))
         return out
 
+    def sample_scripted_actions(self, games=None, out=None):
+        """catan_sample_scripted_actions (include/catan_hip_tuning.h): the rule-based "builder" player's action for the deciding player of
+        every game -> int32 [rows][18].  games (int32 [k]): row j is game games[j], as in get_action_masks(games=...); None: all n games.
+        The masks must be current (they are after reset / step / import_state)."""
+        if games is not None:
+            games = games if (games.dtype == torch.int32 and games.is_contiguous() and games.device == self.device) else \
+                games.to(device=self.device, dtype=torch.int32).contiguous()
+        rows = self.n if games is None else games.numel()
+        if out is None:
+            out = torch.empty((rows, spec.ACTION_WORDS), dtype=torch.int32, device=self.device)
+        assert out.shape == (rows, spec.ACTION_WORDS) and out.dtype == torch.int32 and out.is_contiguous(), (out.shape, out.dtype)
+        if rows:
+            _lib.check(self.L.catan_sample_scripted_actions(self.h, _ptr(games), rows, _ptr(out), _stream()))
+        return out
+
+    def scripted_fallback_count(self):
+        """decisions of sample_scripted_actions that only the rule's fall-back row could take (expected 0)"""
+        return int(self.L.catan_scripted_fallback_count(self.h, _stream()))
+
     def random_rollout(self, step_idx0, steps):
         _lib.check(self.L.catan_random_rollout(self.h, int(step_idx0), int(steps), _stream()))
 

@@ -152,6 +152,9 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
                     ent_p[idx], val_p[idx], lp_p[idx], rec_p[idx] = ex["entropy"], ex["value"], ex["logp"], ex["head_log"]
                 continue
             kw = {"deterministic": deterministic, "generator": generator}
+            if getattr(net, "wants_games", False):       # a policy that reads the games themselves (scripted.ScriptedPolicy): row j is game idx[j];
+                kw["games"] = idx                        # no entropy, no head log - as policy 0 its statistics are zeros, as a searched decision's
+                want = False
             if want:
                 kw.update(return_entropy=True, return_head_log=detailed)
             rec = getattr(net, "include_lstm", False)
@@ -220,21 +223,40 @@ def _stats_result(decisions, ent_sum, val_sum, type_counts, trace_typ, trace_lp,
     return out
 
 
-def run_evaluation_protocol(make_env, central_policy, opponent_policy, num_eval_episodes, update_num=0, rng=None, **kw):
+def _protocol_entry(res):
+    return {"policy_win_frac": float(np.mean(res["winner"] == 0)), "avg_game_length": float(np.mean(res["game_steps"])),
+            "avg_policy_decisions": float(np.mean(res["policy_decisions"])), "avg_victory_points": float(np.mean(res["victory_points"]))}
+
+
+def _protocol_paragraph(name, num_eval_episodes, res, r):
+    return ("{} games against {}. Policy won {}/{}. Avg. game length: {}. Avg num policy decisions: {}. "
+            "Avg victory points for policy: {}. \n\n").format(num_eval_episodes, name, int(np.sum(res["winner"] == 0)), num_eval_episodes,
+                                                             r["avg_game_length"], r["avg_policy_decisions"], r["avg_victory_points"])
+
+
+def run_evaluation_protocol(make_env, central_policy, opponent_policy, num_eval_episodes, update_num=0, rng=None, baselines=None, **kw):
     """run_evaluation_protocol.py: the central policy against three copies of `opponent_policy` (the protocol's "random"
-    opponent).  make_env(n) -> n freshly reset games without auto-reset.  -> (log dict, summary string)."""
+    opponent).  make_env(n) -> n freshly reset games without auto-reset.  -> (log dict, summary string).
+    baselines {name: policy}: fixed opponents beside the protocol's (e.g. {"scripted": scripted.ScriptedPolicy} - the class or an
+    instance); for each, the same number of episodes is played against three copies of it, on a fresh env it is bound to
+    (`rebind`), after the protocol's own games; log[name] holds the four keys of log["random"], the summary one more paragraph.
+    None: the reference's protocol and nothing else."""
     env = make_env(num_eval_episodes)
     res = run_evaluation_episodes(env, [central_policy, opponent_policy, opponent_policy, opponent_policy],
                                   sample_orders(num_eval_episodes, rng), **kw)
-    log = {"update": update_num, "random": {
-        "policy_win_frac": float(np.mean(res["winner"] == 0)), "avg_game_length": float(np.mean(res["game_steps"])),
-        "avg_policy_decisions": float(np.mean(res["policy_decisions"])), "avg_victory_points": float(np.mean(res["victory_points"]))}}
-    r = log["random"]
-    summary = ("\n\n---------------------- EVALUATION (after {} updates) ----------------------\n"
-               "{} games against random. Policy won {}/{}. Avg. game length: {}. Avg num policy decisions: {}. "
-               "Avg victory points for policy: {}. \n\n").format(update_num, num_eval_episodes, int(np.sum(res["winner"] == 0)),
-                                                               num_eval_episodes, r["avg_game_length"], r["avg_policy_decisions"],
-                                                               r["avg_victory_points"])
+    log = {"update": update_num, "random": _protocol_entry(res)}
+    summary = ("\n\n---------------------- EVALUATION (after {} updates) ----------------------\n".format(update_num)
+               + _protocol_paragraph("random", num_eval_episodes, res, log["random"]))
+    for name, base in (baselines or {}).items():
+        if name in log:
+            raise ValueError(f"run_evaluation_protocol: the baseline name {name!r} is taken by the protocol's own log")
+        env = make_env(num_eval_episodes)
+        base = base() if isinstance(base, type) else base
+        if hasattr(base, "rebind"):
+            base.rebind(env)
+        res = run_evaluation_episodes(env, [central_policy, base, base, base], sample_orders(num_eval_episodes, rng), **kw)
+        log[name] = _protocol_entry(res)
+        summary += _protocol_paragraph(name, num_eval_episodes, res, log[name])
     return log, summary
 
 

@@ -840,7 +840,9 @@ class SubProcEvaluationManager(object):
         self._nets = nets
         return [True] * len(self.processes)
 
-    def run_evaluation_episodes(self, total_episodes):
+    def run_evaluation_episodes(self, total_episodes, scripted_baseline=False):
+        """scripted_baseline: the three opponents are the rule-based player (scripted.ScriptedPolicy on this call's env) instead of
+        the nets of update_policies - run_evaluation_protocol's opt-in `args.eval_scripted_baseline`"""
         from . import evaluation
         eps = total_episodes // len(self.processes)
         n = eps * len(self.processes)
@@ -854,7 +856,11 @@ class SubProcEvaluationManager(object):
         ac = self._autocast
         if ac == "auto":
             ac = torch.bfloat16 if torch.device(env.device).type == "cuda" else None
-        res = evaluation.run_evaluation_episodes(env, self._nets, evaluation.sample_orders(n), autocast_dtype=ac)
+        nets = self._nets
+        if scripted_baseline:
+            from .scripted import ScriptedPolicy
+            nets = [self._nets[0]] + [ScriptedPolicy(env)] * 3
+        res = evaluation.run_evaluation_episodes(env, nets, evaluation.sample_orders(n), autocast_dtype=ac)
         out = []
         for p in range(len(self.processes)):
             sl = slice(p * eps, (p + 1) * eps)
@@ -1026,4 +1032,13 @@ def run_evaluation_protocol(evaluation_manager, central_policy, earlier_policies
     summary += ("{} games against random. Policy won {}/{}. Avg. game length: {}. Avg num policy decisions: {}. "
                 "Avg victory points for policy: {}. \n\n").format(args.num_eval_episodes, int(np.sum(winners == 0)), args.num_eval_episodes,
                                                                 np.mean(game_lengths), np.mean(policy_steps), np.mean(victory_points))
+    if getattr(args, "eval_scripted_baseline", False):      # opt-in, not in the reference: the same games against the rule-based player
+        results = list(zip(*evaluation_manager.run_evaluation_episodes(args.num_eval_episodes, scripted_baseline=True)))
+        winners, game_lengths = np.concatenate(results[0]), np.concatenate(results[1])
+        victory_points, policy_steps = np.concatenate(results[2]), np.concatenate(results[3])
+        log["scripted"] = {"policy_win_frac": np.mean(winners == 0), "avg_game_length": np.mean(game_lengths),
+                           "avg_policy_decisions": np.mean(policy_steps), "avg_victory_points": np.mean(victory_points)}
+        summary += ("{} games against scripted. Policy won {}/{}. Avg. game length: {}. Avg num policy decisions: {}. "
+                    "Avg victory points for policy: {}. \n\n").format(args.num_eval_episodes, int(np.sum(winners == 0)), args.num_eval_episodes,
+                                                                    np.mean(game_lengths), np.mean(policy_steps), np.mean(victory_points))
     return log, summary

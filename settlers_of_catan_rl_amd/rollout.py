@@ -137,7 +137,9 @@ class RolloutCollector(object):
     def __init__(self, env, policy, num_steps, opponents=None, seed=0, autocast_dtype=None, graph_act=None, deferred_window=None, act_buckets=None,
                  episode_stats=False):
         """policy: central net (policy 0); opponents: list of up to 3 nets for policy slots 1..3 of every game (None =
-        every seat plays the central policy).  A league (league.League.assign) installs per-game opponents instead.
+        every seat plays the central policy).  A league (league.League.assign) installs per-game opponents instead.  An opponent
+        may be a `scripted.ScriptedPolicy(env)` bound to this env: a fixed anchor beside the nets (its rows' log-probs are 0 and,
+        like every opponent's, never stored).
         deferred_window: step the env with catan_step_deferred (window of that many iterations) instead of catan_step - the
         reference's workers advance every env independently (game_manager.py:78-113), and so do the games here: one whose step
         needs the slow path waits for it while the others go on (device collector only; 0 = catan_step; None = 4 where the env
@@ -195,7 +197,9 @@ class RolloutCollector(object):
         """nets: the distinct opponent nets in play; opp_index int64 [N,3]: which of them plays policy slots 1..3 of
         each game (game_manager.py:15,28-31: the slot -> seat map of a game stays fixed)."""
         self._graphed_nets = {}                  # (captured per-net passes belong to the nets they were captured with)
+        # (a policy that reads the games themselves - scripted.ScriptedPolicy, bound to this collector's env - has no weights to copy)
         self.opponent_nets = [n.inference_copy(self.autocast_dtype) if (self.autocast_dtype is not None and hasattr(n, "inference_copy")
+                                                                        and not getattr(n, "wants_games", False)
                                                                         and getattr(n, "_inference_dtype", None) is None) else n for n in nets]
         self.opp_index = opp_index.to(self.device).long().contiguous() if len(self.opponent_nets) else None
 
@@ -475,8 +479,10 @@ class RolloutCollector(object):
         for idx, net in groups:
             args = (f, lists, lens, masks) if idx is None else (f[idx], lists[idx], lens[idx], masks[idx])
             kw = {"generator": self.sample_gen}
-            if games is not None and getattr(net, "wants_games", False):
-                kw["games"] = games                      # (test policies keyed by game: row j of this pass is game games[j])
+            if getattr(net, "wants_games", False) and (games is not None or idx is not None):
+                # policies keyed by game (scripted.ScriptedPolicy, test policies): row j of this call is game games[j] - of the pass's
+                # list, or of the net's share of the rows
+                kw["games"] = games if idx is None else (idx if games is None else games[idx])
             if self.recurrent:
                 sel = slice(None) if idx is None else idx
                 kw.update(hidden=(h_in[sel], c_in[sel]), nonterminal=term[sel])

@@ -31,12 +31,22 @@ class TrainArgs(object):
     update_opponent_policies_every = 1
     eval_every = 25
     num_eval_episodes = 128
+    eval_scripted_baseline = False       # opt-in: the evaluation also plays the rule-based player (scripted.ScriptedPolicy) -> log["scripted"]
 
     def __init__(self, **kw):
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise AttributeError(k)
             setattr(self, k, v)
+
+
+def eval_baselines(args):
+    """The fixed opponents `args` adds to the evaluation protocol, as evaluation.run_evaluation_protocol(baselines=...) takes them;
+    None (the default): the reference's protocol alone."""
+    if not getattr(args, "eval_scripted_baseline", False):
+        return None
+    from .scripted import ScriptedPolicy
+    return {"scripted": ScriptedPolicy}
 
 
 def linear_lr(update_num, num_updates, initial_lr):

@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--eval-every", type=int, default=25)
     ap.add_argument("--num-eval-episodes", type=int, default=128)
     ap.add_argument("--eval-max-steps", type=int, default=2500)
+    ap.add_argument("--eval-scripted-baseline", action="store_true",
+                    help="every evaluation also plays the rule-based player (scripted.ScriptedPolicy): log[\"scripted\"], comparable across runs")
     ap.add_argument("--checkpoint", type=str, default="")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lstm", action="store_true", help="include_lstm (build_agent_model.py:26): LSTM policy + truncated BPTT")
@@ -52,10 +54,12 @@ def main():
     def evaluate(policy, update_num):
         return evaluation.run_evaluation_protocol(lambda m: VecCatanEnv(m, seed=args.seed + 1000 + update_num, env_id0=1 << 40, auto_reset=False),
                                                   policy, random_net, args.num_eval_episodes, update_num,
-                                                  max_steps=args.eval_max_steps, autocast_dtype=torch.bfloat16)
+                                                  max_steps=args.eval_max_steps, autocast_dtype=torch.bfloat16,
+                                                  baselines=train_loop.eval_baselines(targs))
 
     lg = League(max_distinct=args.league, seed=rank) if args.league > 0 else None
-    targs = train_loop.TrainArgs(num_steps=args.num_steps, eval_every=args.eval_every, num_eval_episodes=args.num_eval_episodes)
+    targs = train_loop.TrainArgs(num_steps=args.num_steps, eval_every=args.eval_every, num_eval_episodes=args.num_eval_episodes,
+                                 eval_scripted_baseline=args.eval_scripted_baseline)
     loop = train_loop.TrainingLoop(env, net, col, tr, targs, league=lg, make_net=lambda: CatanPolicy(include_lstm=args.lstm).cuda(),
                                    evaluate=evaluate if rank == 0 else None, checkpoint_path=args.checkpoint or None)
     for _ in range(args.updates):
