@@ -4,7 +4,7 @@
  * declared here (that is catan_hip.h).  Three sections are no knobs: "search support" (catan_state_fork), which the forward search uses,
  * "finished-game statistics" (catan_episode_stats_*), which the rollout collector uses, and "rule-based player"
  * (catan_sample_scripted_actions), a fixed-strength opponent: the reference has no such interface to replace, and catan_hip.h stays the
- * reference's boundary.
+ * reference's boundary.  "league results" (catan_league_stats_*) is a fourth: the collector's per-opponent scoreboard.
  */
 #ifndef CATAN_HIP_TUNING_H
 #define CATAN_HIP_TUNING_H
@@ -83,6 +83,47 @@ int catan_state_fork(catan_env_t* dst, const catan_env_t* src, const int64_t* sr
 int32_t catan_episode_stats_words(void);
 int catan_episode_stats_enable(catan_env_t* env, int on, const int32_t* focus_pid, catan_stream_t stream);
 int catan_episode_stats_read(catan_env_t* env, uint64_t* out_host, int reset, catan_stream_t stream);
+
+/* ---- league results ----
+ * Who beat whom, counted on the device (csrc/catan_league_stats.hip).  A league rollout seats the central policy (policy slot 0) and up to
+ * three opponent nets (slots 1..3) in every game.  While enabled with CATAN_LEAGUE_STATS_REDEALS, every finished game is tallied ONCE, from
+ * its final state and just before its re-deal, at the very hook of the finished-game statistics above and on every schedule; both may be on
+ * together and neither knows of the other.  Off, the default, not one kernel more is launched.
+ * The maps are the caller's DEVICE arrays, are read whenever a game finishes and must stay valid until disable or catan_destroy:
+ *    slot_of_pid  int32 [n][4]   the policy slot 0..3 that PlayerId p+1 of game g plays (a permutation of 0..3 per game)
+ *    net_of_slot  int32 [n][3]   the net, in [0, num_nets), that plays slots 1..3 of game g; -1: the seat is not tallied
+ * The table is (num_nets + 1) rows of catan_league_stats_words() = 6 uint64 sums.  Row k < num_nets, over the opponent SEATS net k held in
+ * tallied games (a game is tallied if it has a winner 1..4 and a valid slot row):
+ *    [0] games          finished games with net k in them (once per game, however many seats it held)
+ *    [1] seats          seats it held in them
+ *    [2] net_wins       ... that won
+ *    [3] central_wins   ... whose game the central seat won
+ *    [4] net_vp_sum     victory points of those seats
+ *    [5] central_vp_sum the central seat's victory points, once per seat
+ * Counting per seat keeps the pair score balanced when a net holds several seats of a game: against an equally strong net every seat wins
+ * a quarter of the games, so central_wins == net_wins in expectation whether the net holds one seat or three.
+ * Row num_nets, the totals:
+ *    [0] finished games seen            [1] of them tallied          [2] central wins          [3] central victory points
+ *    [4] games skipped (no winner, no or an invalid slot row)        [5] seats skipped (net index neither -1 nor in [0, num_nets))
+ * Every index read from the maps is checked before it addresses anything.
+ * catan_league_stats_enable: `on` is 0 (stop counting) or mode bits.  CATAN_LEAGUE_STATS_REDEALS tallies the re-dealt games as described
+ * and needs auto_reset = 1; CATAN_LEAGUE_STATS_COUNT_ONLY alone launches nothing at the re-deals and is accepted on any handle: the table
+ * is then filled by catan_league_stats_count only (evaluation handles with auto_reset = 0, whose final states stay where they are).  Every
+ * call with on != 0 zeroes the table, re-allocating it when num_nets grew.
+ * catan_league_stats_count tallies, with the same kernel, the CURRENT records of games[0..m-1] (DEVICE int32; NULL: games 0..m-1, m <= n)
+ * into the same table, in either mode; a game listed twice is counted twice.
+ * catan_league_stats_read copies the table, (num_nets + 1) * 6 words, to HOST memory, zeroes it behind the copy when reset != 0, and
+ * synchronises the stream.  Use the stream of the handle's step calls.
+ * CATAN_EINVAL: a null handle; CATAN_LEAGUE_STATS_REDEALS on a handle with auto_reset = 0; an open deferred sequence; a handle under the
+ * MT19937 contract; num_nets < 1 or > 65536; a null map with on != 0; unknown mode bits; read and count while off; count with m < 1, or
+ * m > n with games == NULL. */
+#define CATAN_LEAGUE_STATS_REDEALS 1
+#define CATAN_LEAGUE_STATS_COUNT_ONLY 2
+int32_t catan_league_stats_words(void);
+int catan_league_stats_enable(catan_env_t* env, int on, const int32_t* slot_of_pid, const int32_t* net_of_slot, int32_t num_nets,
+                              catan_stream_t stream);
+int catan_league_stats_read(catan_env_t* env, uint64_t* out_host, int reset, catan_stream_t stream);
+int catan_league_stats_count(catan_env_t* env, const int32_t* games, int64_t m, catan_stream_t stream);
 
 /* ---- rule-based player ----
  * The "builder" bot (csrc/catan_scripted.hip): a deterministic scripted policy - the same state always gives the same

@@ -24,6 +24,7 @@
 #include "catan_wgrad_big.hip"
 #include "catan_stats.hip"
 #include "catan_scripted.hip"
+#include "catan_league_stats.hip"
 
 using namespace catan;
 
@@ -90,6 +91,11 @@ struct catan_env {
     unsigned long long* stats;   // catan_episode_stats_enable: the block of ES_WORDS counters (catan_stats.hip), allocated at the first enable
     const i32* stats_focus;      // ... the caller's focus array (device int32 [n]) or NULL
     int stats_on;
+    unsigned long long* lstats;  // catan_league_stats_enable: the table of (lstats_nets + 1) x LS_WORDS counters (catan_league_stats.hip); not in `owned`: it grows
+    const i32* lstats_slot;      // ... the caller's maps (device int32 [n][4] and [n][3])
+    const i32* lstats_net;
+    int lstats_nets, lstats_cap; // rows in use (without the totals row), and allocated
+    int lstats_on;               // 0 off, else the mode bits of catan_league_stats_enable
     unsigned long long* script_fallback;   // catan_sample_scripted_actions: decisions taken by the fall-back row (catan_scripted.hip), allocated at the first call
 };
 static_assert(sizeof(BoardCfg) == sizeof(catan_board_cfg_t) && sizeof(catan_board_cfg_t) == 56 &&
@@ -396,6 +402,18 @@ static void enqueue_episode_stats(catan_env_t* e, const u32* count_p, const i32*
     if (!e->stats_on) return;
     hipLaunchKernelGGL(k_episode_stats, dim3(EPISODE_STATS_GRID), dim3(64), 0, st, e->ctx, count_p, list, e->stats_focus, e->stats);
 }
+// Per-opponent results (catan_league_stats_enable): count_p / list as above, or count_p == nullptr and `count` games (list == nullptr: games 0..count-1)
+static void launch_league_stats(catan_env_t* e, const u32* count_p, u32 count, const i32* list, unsigned grid, hipStream_t st) {
+    if (e->lstats_nets <= LEAGUE_STATS_LDS_MAX_NETS)
+        hipLaunchKernelGGL(k_league_stats<true>, dim3(grid), dim3(64), 0, st, e->ctx, count_p, count, list, e->lstats_slot, e->lstats_net, e->lstats_nets, e->lstats);
+    else
+        hipLaunchKernelGGL(k_league_stats<false>, dim3(grid), dim3(64), 0, st, e->ctx, count_p, count, list, e->lstats_slot, e->lstats_net, e->lstats_nets, e->lstats);
+}
+// ... at the same hook as the finished-game statistics, and as independent of them.  Off (the default): nothing is launched.
+static void enqueue_league_stats(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!(e->lstats_on & CATAN_LEAGUE_STATS_REDEALS)) return;
+    launch_league_stats(e, count_p, 0u, list, LEAGUE_STATS_GRID, st);
+}
 // k_step with G games per wave in one-wave workgroups; pend.sample (fused-sampling rollouts): actions from / to the side rows
 template <int G>
 static void launch_step(catan_env_t* e, const int32_t* actions, float* reward, uint8_t* done, hipStream_t st, const StepCfg& sc, const u32* bins) {
@@ -528,6 +546,7 @@ void catan_destroy(catan_env_t* e) {
     if (e->mt_dev) hipFree(e->mt_dev);
     if (e->bcfg_dev) hipFree(e->bcfg_dev);
     if (e->bcfg_idx_dev) hipFree(e->bcfg_idx_dev);
+    if (e->lstats) hipFree(e->lstats);
     for (hipStream_t st : { e->fstream, e->sstream, e->side }) if (st) hipStreamDestroy(st);
     for (hipEvent_t ev : { e->ev_fready[0], e->ev_fready[1], e->ev_fready[2], e->ev_fdone[0], e->ev_fdone[1], e->ev_fdone[2], e->ev_sdone[0], e->ev_sdone[1],
                            e->ev_fork, e->ev_join })
@@ -776,6 +795,7 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             HIPCHK(hipEventRecord(e->ev_fork, st));
             HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
             enqueue_episode_stats(e, sctr + 1, e->pend.resets[sa][0], e->side);
+            enqueue_league_stats(e, sctr + 1, e->pend.resets[sa][0], e->side);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 1),
                                (const i32*)e->pend.resets[sa][0], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
             HIPCHK(hipEventRecord(e->ev_join, e->side));
@@ -798,14 +818,17 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
         if (lockstep) {
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));      // the side stream's launch of step_impl: it had the whole slow path to finish
             enqueue_episode_stats(e, sctr + 3, e->pend.resets[sa][2], st);
+            enqueue_league_stats(e, sctr + 3, e->pend.resets[sa][2], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 3), (const i32*)e->pend.resets[sa][2], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
             enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
+            enqueue_league_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2), (const i32*)e->pend.resets[sa][1], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
         } else {
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));
             enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
+            enqueue_league_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2),
                                (const i32*)e->pend.resets[sa][1], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
         }
@@ -836,6 +859,7 @@ static int step_impl(catan_env_t* e, int32_t* actions, float* reward, uint8_t* d
         // ... and every game on the longest-road path that this step may end (k_step's list pend.spec) gets a speculative successor
         e->spec_epoch++;
         enqueue_episode_stats(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);       // (the real list only: the speculative successors are no episodes)
+        enqueue_league_stats(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
         hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, limits_of(e),
                            (const u32*)(e->pend.ctr + 8 + 1), (const i32*)e->pend.resets[0][0], e->pend.busy, step_cfg(e).prof,
                            (const u32*)(e->pend.ctr + 6), (const u64*)e->pend.spec, e->spec_state, e->spec_mpk, e->spec_epoch, e->pend);
@@ -997,6 +1021,54 @@ int catan_episode_stats_read(catan_env_t* e, uint64_t* out_host, int reset, cata
     HIPCHK(hipMemcpyAsync(out_host, e->stats, ES_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, S(stream)));
     if (reset) HIPCHK(hipMemsetAsync(e->stats, 0, ES_WORDS * sizeof(unsigned long long), S(stream)));
     HIPCHK(hipStreamSynchronize(S(stream)));
+    return CATAN_OK;
+}
+
+// ---- per-opponent results of a league rollout (catan_league_stats.hip)
+int32_t catan_league_stats_words(void) { return LS_WORDS; }
+int catan_league_stats_enable(catan_env_t* e, int on, const int32_t* slot_of_pid, const int32_t* net_of_slot, int32_t num_nets, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_league_stats_enable: null handle");
+    if ((on & CATAN_LEAGUE_STATS_REDEALS) && !e->cfg.auto_reset)
+        return fail(CATAN_EINVAL, "catan_league_stats_enable: the handle has auto_reset = 0 (no game is re-dealt: enable with CATAN_LEAGUE_STATS_COUNT_ONLY and use catan_league_stats_count)");
+    NOT_DEFERRED(e, "catan_league_stats_enable");
+    NOT_MT(e, "catan_league_stats_enable");
+    if (!on) { e->lstats_on = 0; e->lstats_slot = e->lstats_net = nullptr; return CATAN_OK; }
+    if (on & ~(CATAN_LEAGUE_STATS_REDEALS | CATAN_LEAGUE_STATS_COUNT_ONLY)) return fail(CATAN_EINVAL, "catan_league_stats_enable: unknown mode bits in `on`");
+    if (num_nets < 1 || num_nets > LEAGUE_STATS_MAX_NETS) return fail(CATAN_EINVAL, "catan_league_stats_enable: num_nets must be in 1..65536");
+    if (!slot_of_pid || !net_of_slot) return fail(CATAN_EINVAL, "catan_league_stats_enable: null map (slot_of_pid and net_of_slot are device int32 [n][4] and [n][3])");
+    const size_t bytes = (size_t)(num_nets + 1) * LS_WORDS * sizeof(unsigned long long);
+    if (num_nets > e->lstats_cap) {
+        // (hipFree waits for the device: no tally of the old table is in flight behind it)
+        e->lstats_on = 0;
+        if (e->lstats) { HIPCHK(hipFree(e->lstats)); e->lstats = nullptr; e->lstats_cap = 0; }
+        hipError_t rc = hipMalloc((void**)&e->lstats, bytes);
+        if (rc != hipSuccess) { e->lstats = nullptr; return fail(CATAN_ENOMEM, std::string("catan_league_stats_enable: hipMalloc: ") + hipGetErrorString(rc)); }
+        e->lstats_cap = num_nets;
+    }
+    HIPCHK(hipMemsetAsync(e->lstats, 0, bytes, S(stream)));
+    e->lstats_slot = slot_of_pid; e->lstats_net = net_of_slot; e->lstats_nets = num_nets; e->lstats_on = on;
+    return CATAN_OK;
+}
+int catan_league_stats_read(catan_env_t* e, uint64_t* out_host, int reset, catan_stream_t stream) {
+    if (!e || !out_host) return fail(CATAN_EINVAL, "catan_league_stats_read: null argument");
+    if (!e->lstats_on) return fail(CATAN_EINVAL, "catan_league_stats_read: league results are not enabled on this handle (catan_league_stats_enable)");
+    NOT_DEFERRED(e, "catan_league_stats_read");       // (the side streams of an open sequence are joined by catan_step_flush)
+    const size_t bytes = (size_t)(e->lstats_nets + 1) * LS_WORDS * sizeof(unsigned long long);
+    HIPCHK(hipMemcpyAsync(out_host, e->lstats, bytes, hipMemcpyDeviceToHost, S(stream)));
+    if (reset) HIPCHK(hipMemsetAsync(e->lstats, 0, bytes, S(stream)));
+    HIPCHK(hipStreamSynchronize(S(stream)));
+    return CATAN_OK;
+}
+int catan_league_stats_count(catan_env_t* e, const int32_t* games, int64_t m, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_league_stats_count: null handle");
+    if (!e->lstats_on) return fail(CATAN_EINVAL, "catan_league_stats_count: league results are not enabled on this handle (catan_league_stats_enable)");
+    NOT_DEFERRED(e, "catan_league_stats_count");
+    NOT_MT(e, "catan_league_stats_count");
+    if (m <= 0 || m > 0x7fffffffll) return fail(CATAN_EINVAL, "catan_league_stats_count: m must be in 1..2^31-1");
+    if (!games && m > e->n) return fail(CATAN_EINVAL, "catan_league_stats_count: m exceeds the handle's games (games == NULL)");
+    const unsigned grid = blocks(m, 64) < 256u ? blocks(m, 64) : 256u;
+    launch_league_stats(e, nullptr, (u32)m, games, grid, S(stream));
+    HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
 

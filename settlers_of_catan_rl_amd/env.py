@@ -145,6 +145,46 @@ class VecCatanEnv(object):
         among them: the state does not hold it."""
         return spec.episode_stats_dict(self.episode_stats_words(reset))
 
+    def enable_league_stats(self, slot_of_pid, net_of_slot, num_nets, on=True, count_only=False):
+        """Per-opponent results of the finished games are counted on the device from now on (include/catan_hip_tuning.h "league results");
+        the table starts at zero.  slot_of_pid [n,4]: the policy slot 0..3 (0: the central policy) PlayerId p+1 of each game plays;
+        net_of_slot [n,3]: the net in [0, num_nets) on slots 1..3, -1 for a seat that is not tallied.  The env keeps int32 copies on the
+        device (the library reads them whenever a game finishes); later edits of the arguments are not seen.
+        count_only: nothing is tallied at the re-deals, only by league_stats_count (the one mode a handle without auto_reset takes).
+        on=False stops counting."""
+        if not hasattr(self.L, "catan_league_stats_enable"):
+            raise _lib.CatanHipError("the loaded library has no catan_league_stats_enable")
+        if not on:
+            _lib.check(self.L.catan_league_stats_enable(self.h, 0, None, None, 0, _stream()))
+            self._league_maps, self._league_nets = None, 0
+            return
+        maps = []
+        for name, t, cols in (("slot_of_pid", slot_of_pid, 4), ("net_of_slot", net_of_slot, 3)):
+            t = torch.as_tensor(t, device=self.device).to(torch.int32).contiguous().clone()
+            if t.shape != (self.n, cols):
+                raise ValueError(f"{name}: shape ({self.n}, {cols}) expected, got {tuple(t.shape)}")
+            maps.append(t)
+        mode = spec.LEAGUE_STATS_COUNT_ONLY if count_only else spec.LEAGUE_STATS_REDEALS
+        _lib.check(self.L.catan_league_stats_enable(self.h, mode, _ptr(maps[0]), _ptr(maps[1]), int(num_nets), _stream()))
+        self._league_maps, self._league_nets = maps, int(num_nets)
+
+    def league_stats(self, reset=False):
+        """-> int64 [num_nets + 1, spec.LEAGUE_STATS_WORDS] (host): a row per net (spec.LEAGUE_STATS_FIELDS) and the totals row
+        (spec.LEAGUE_STATS_TOTALS) of the games finished since the table was enabled (or last read with reset=True); waits for the
+        current stream.  spec.league_stats_table names the columns."""
+        rows = getattr(self, "_league_nets", 0) + 1
+        assert int(self.L.catan_league_stats_words()) == spec.LEAGUE_STATS_WORDS
+        out = torch.zeros((rows, spec.LEAGUE_STATS_WORDS), dtype=torch.int64)
+        _lib.check(self.L.catan_league_stats_read(self.h, C.cast(out.data_ptr(), C.POINTER(C.c_uint64)), int(bool(reset)), _stream()))
+        return out
+
+    def league_stats_count(self, games=None, count=None):
+        """Adds the CURRENT records of `games` (game ids; None: games 0..count-1, count None: every game) to the league table - for
+        handles whose finished games stay where they are (auto_reset=False: evaluation).  A game listed twice is counted twice."""
+        g = None if games is None else torch.as_tensor(games, device=self.device).to(torch.int32).contiguous()
+        m = int(g.numel()) if g is not None else (self.n if count is None else int(count))
+        _lib.check(self.L.catan_league_stats_count(self.h, _ptr(g), m, _stream()))
+
     def close(self):
         if getattr(self, "h", None):
             self.L.catan_destroy(self.h)

@@ -45,6 +45,7 @@ class RolloutStorage(object):
         self.action_masks = torch.zeros((T, N, 11), dtype=torch.int32, device=device)   # packed 325-bit masks
         self.games_complete = 0
         self.episode_stats = None     # RolloutCollector(episode_stats=True): the finished games of the last gather_rollouts (env.episode_stats)
+        self.league_stats = None      # RolloutCollector(league_stats=True): their results per opponent net, int64 [nets + 1, 6] (env.league_stats)
         self.generation = 0           # bumped by every gather_rollouts (consumers cache per-rollout derived data on it)
 
     def unpack_action_masks(self, packed):
@@ -135,7 +136,7 @@ class RolloutCollector(object):
     GRAPH_ACT_MIN_GAMES = 8192
 
     def __init__(self, env, policy, num_steps, opponents=None, seed=0, autocast_dtype=None, graph_act=None, deferred_window=None, act_buckets=None,
-                 episode_stats=False):
+                 episode_stats=False, league_stats=False):
         """policy: central net (policy 0); opponents: list of up to 3 nets for policy slots 1..3 of every game (None =
         every seat plays the central policy).  A league (league.League.assign) installs per-game opponents instead.  An opponent
         may be a `scripted.ScriptedPolicy(env)` bound to this env: a fixed anchor beside the nets (its rows' log-probs are 0 and,
@@ -148,8 +149,13 @@ class RolloutCollector(object):
         smaller bucket, only they are evaluated (None = N, N/2, ... N/16 with graph_act, else N only).
         episode_stats: the env counts its finished games on the device (VecCatanEnv.enable_episode_stats, the active seat as the focus
         player); every gather_rollouts leaves the dict of the games that finished during it in storage.episode_stats - one read after
-        the loop, none inside it."""
+        the loop, none inside it.
+        league_stats: the env also counts, per opponent net, who won the finished games (VecCatanEnv.enable_league_stats with this
+        collector's seat map and the opponent indices of set_opponents, which re-enables it - between rollouts, behind the read); every
+        gather_rollouts leaves the table, a row per net in the order of set_opponents' `nets` and a totals row, in storage.league_stats
+        (None while no opponent is installed).  The same single read after the loop."""
         self.env, self.policy, self.T = env, policy, num_steps
+        self.league_stats, self.policy_of_pid = bool(league_stats), None
         self.deferred_window = self.DEFAULT_DEFERRED_WINDOW if deferred_window is None else int(deferred_window)
         self.act_buckets = None if act_buckets is None else tuple(sorted(set(int(b) for b in act_buckets) | {env.n}))
         self.N, self.device = env.n, env.device
@@ -191,6 +197,7 @@ class RolloutCollector(object):
         self.episode_stats = bool(episode_stats)
         if self.episode_stats:
             env.enable_episode_stats(self.active_pid)
+        self._enable_league_stats()
         self.reset()
 
     def set_opponents(self, nets, opp_index):
@@ -202,6 +209,18 @@ class RolloutCollector(object):
                                                                         and not getattr(n, "wants_games", False)
                                                                         and getattr(n, "_inference_dtype", None) is None) else n for n in nets]
         self.opp_index = opp_index.to(self.device).long().contiguous() if len(self.opponent_nets) else None
+        self._enable_league_stats()
+
+    def _enable_league_stats(self):
+        """league_stats: the table for the opponents now installed, zeroed (called by set_opponents; the constructor calls it once its
+        seat map exists)"""
+        if not self.league_stats or self.policy_of_pid is None:
+            return
+        self._league_on = self.opp_index is not None
+        if self._league_on:
+            self.env.enable_league_stats(self.policy_of_pid, self.opp_index, len(self.opponent_nets))
+        elif hasattr(self.env, "enable_league_stats"):
+            self.env.enable_league_stats(None, None, 0, on=False)
 
     # game_manager.py:35-59 (the env itself is already reset: EnvWrapper.reset() happened in catan_create / env.reset())
     def reset(self):
@@ -300,6 +319,8 @@ class RolloutCollector(object):
             st.games_complete += int(n_complete)
             if self.episode_stats:
                 st.episode_stats = env.episode_stats(reset=True)
+            if self.league_stats:
+                st.league_stats = env.league_stats(reset=True) if self._league_on else None
             st.generation += 1
             self.iters = int(n_live_iters) if max_iters is None else iters
             return st

@@ -225,3 +225,28 @@ def episode_stats_dict(words):
     out["focus_win_rate"] = per(out["focus_wins"], fe)
     out["focus_mean_vp"] = per(out["focus_vp_sum"], fe)
     return out
+
+
+# ---------------------------------------------------------------- league results (include/catan_hip_tuning.h catan_league_stats_*)
+# one row of uint64 sums per opponent net, in order; csrc/catan_league_stats.hip holds the same layout as LS_* offsets
+LEAGUE_STATS_FIELDS = ["games", "seats", "net_wins", "central_wins", "net_vp_sum", "central_vp_sum"]
+LEAGUE_STATS_WORDS = len(LEAGUE_STATS_FIELDS)                      # 6
+# ... and the last row, the totals over every finished game
+LEAGUE_STATS_TOTALS = ["games_seen", "games_tallied", "central_wins", "central_vp_sum", "games_skipped", "seats_skipped"]
+LEAGUE_STATS_MAX_NETS = 65536
+LEAGUE_STATS_LDS_MAX_NETS = 127                                   # up to here the kernel accumulates in LDS (LEAGUE_STATS_LDS_MAX_NETS there)
+LEAGUE_STATS_REDEALS, LEAGUE_STATS_COUNT_ONLY = 1, 2              # mode bits of catan_league_stats_enable
+
+
+def league_stats_table(words, num_nets):
+    """The table catan_league_stats_read fills ((num_nets + 1) * LEAGUE_STATS_WORDS integers, or anything that reshapes to
+    [num_nets + 1, LEAGUE_STATS_WORDS]) -> OrderedDict: every LEAGUE_STATS_FIELDS name -> int64 array [num_nets], and "totals" -> a
+    dict of the LEAGUE_STATS_TOTALS names."""
+    import numpy as np
+    t = np.asarray(words, dtype=np.int64).reshape(-1)
+    if t.size != (int(num_nets) + 1) * LEAGUE_STATS_WORDS:
+        raise ValueError(f"a league table of {num_nets} nets has {(int(num_nets) + 1) * LEAGUE_STATS_WORDS} words, got {t.size}")
+    t = t.reshape(int(num_nets) + 1, LEAGUE_STATS_WORDS)
+    out = OrderedDict((name, t[:-1, i].copy()) for i, name in enumerate(LEAGUE_STATS_FIELDS))
+    out["totals"] = OrderedDict((name, int(t[-1, i])) for i, name in enumerate(LEAGUE_STATS_TOTALS))
+    return out

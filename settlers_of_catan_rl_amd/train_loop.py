@@ -13,6 +13,7 @@ import time
 import torch
 
 from . import dist as cdist
+from . import spec
 
 
 class TrainArgs(object):
@@ -108,6 +109,7 @@ class TrainingLoop(object):
             for g in self.trainer.optimiser.param_groups:
                 g["lr"] = lr
         st = self.collector.gather_rollouts()                                               # :101-102
+        league_totals, league_out = self._record_league(st), None
         losses = self.trainer.update(st)                                                    # :104
         self.collector.after_rollouts()
         self.entropy_coef = entropy_coef_at(u, a, self.entropy_coef)
@@ -119,6 +121,11 @@ class TrainingLoop(object):
         if self.league is not None:
             if u % a.add_policy_every == 0 and u > 0:                                       # :135-138
                 self.league.add(self.policy)
+            if league_totals is not None:     # the scoreboard as the draw below finds it: this rollout on record, this update's snapshot in
+                lg = self.league
+                league_out = {"serials": lg.serials(), "pairs": [float(lg.records[s][1]) if s in lg.records else 0.0 for s in lg.serials()],
+                              "central_share": [float(x) for x in lg.central_share()],
+                              "probabilities": [float(x) for x in lg.probabilities()], "totals": league_totals}
             if u % a.update_opponent_policies_every == 0:                                   # :140-141
                 self.league.assign(self.collector, self.make_net)
         summary = None
@@ -133,15 +140,38 @@ class TrainingLoop(object):
                "hours": (time.time() - self.start_time) / 3600.0, "eval": summary}
         if getattr(st, "episode_stats", None) is not None:       # RolloutCollector(episode_stats=True): the games this rollout finished
             out["episodes"] = st.episode_stats
+        if league_out is not None:                               # RolloutCollector(league_stats=True): the scoreboard per snapshot
+            out["league"] = league_out
         if getattr(self.trainer, "diagnostics", None) is not None:   # PPOConfig(diagnostics=True): what the clipped objective did in this update
             out["ppo"] = self.trainer.diagnostics
         return out
 
+    def _record_league(self, st):
+        """The rollout's league table (RolloutCollector(league_stats=True)) goes on the league's record, summed over the ranks.  -> its
+        totals row as a dict, or None: no table, no league, or opponents the league did not draw (the first rollout's random-initialised
+        nets are no snapshots)."""
+        table = getattr(st, "league_stats", None)
+        if table is None or self.league is None or getattr(self.league, "in_play", None) is None:
+            return None
+        reduce = None
+        if torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            def reduce(dense):
+                t = dense.to("cuda" if torch.distributed.get_backend() == "nccl" else "cpu")
+                torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.SUM)
+                return t.cpu()
+        self.league.record(table, reduce=reduce)
+        return {k: int(v) for k, v in zip(spec.LEAGUE_STATS_TOTALS, torch.as_tensor(table)[-1].tolist())}
+
     def save(self, path):
-        torch.save({"central_policy": {k: v.detach().cpu() for k, v in self.policy.state_dict().items()},
-                    "earlier_policies": list(self.league.earlier) if self.league is not None else [],
-                    "eval_logs": self.eval_logs, "update_num": self.update_num, "args": copy.copy(self.args.__dict__),
-                    "entropy_coef": self.entropy_coef, "reward_weight": self.reward_weight}, path)
+        ck = {"central_policy": {k: v.detach().cpu() for k, v in self.policy.state_dict().items()},
+              "earlier_policies": list(self.league.earlier) if self.league is not None else [],
+              "eval_logs": self.eval_logs, "update_num": self.update_num, "args": copy.copy(self.args.__dict__),
+              "entropy_coef": self.entropy_coef, "reward_weight": self.reward_weight}
+        # (only where the scoreboard is in use: without it a checkpoint holds what it always held)
+        if self.league is not None and (getattr(self.league, "records", None) or getattr(self.collector, "league_stats", False)):
+            ck["league_serials"] = self.league.serials()
+            ck["league_records"] = {int(s): [float(x) for x in r] for s, r in self.league.records.items()}
+        torch.save(ck, path)
 
     def save_reference_tuple(self, path):
         """The reference's own checkpoint layout (robust_train.py:155-156): the 5-tuple (central state-dict, deque of
@@ -177,6 +207,8 @@ class TrainingLoop(object):
         self.policy.load_state_dict(ck["central_policy"])
         if self.league is not None:
             self.league.earlier.clear(); self.league.earlier.extend(ck["earlier_policies"])
+            if "league_serials" in ck and hasattr(self.league, "restore"):                  # (absent in older checkpoints: numbered afresh, no records)
+                self.league.restore(ck["league_serials"], ck.get("league_records", {}))
             self.league.assign(self.collector, self.make_net)                               # :55-56
         self.eval_logs, self.update_num = ck["eval_logs"], ck["update_num"]
         self.entropy_coef, self.reward_weight = ck["entropy_coef"], ck["reward_weight"]

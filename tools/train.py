@@ -31,7 +31,12 @@ def main():
     ap.add_argument("--lstm", action="store_true", help="include_lstm (build_agent_model.py:26): LSTM policy + truncated BPTT")
     ap.add_argument("--diagnostics", action="store_true",
                     help="PPOConfig.diagnostics: every update's line carries \"ppo\" (per-epoch KL, clip fractions, explained variance, gradient norm)")
+    ap.add_argument("--league-stats", action="store_true",
+                    help="count on the device who won the finished games per opponent snapshot: every update's line carries \"league\"")
+    ap.add_argument("--league-sampling", choices=["reference", "pfsp"], default="reference",
+                    help="pfsp: draw the snapshots the central policy does badly against more often (implies --league-stats)")
     args = ap.parse_args()
+    league_stats = args.league > 0 and (args.league_stats or args.league_sampling == "pfsp")
     import torch
     from settlers_of_catan_rl_amd import dist as cdist
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -47,7 +52,7 @@ def main():
     env = VecCatanEnv(n, seed=args.seed, env_id0=env_id0)          # game_manager.py:16: EnvWrapper() defaults (sparse win reward)
     net = CatanPolicy(include_lstm=args.lstm).cuda()
     cdist.broadcast_parameters(net)
-    col = RolloutCollector(env, net, args.num_steps, seed=rank, autocast_dtype=torch.bfloat16)
+    col = RolloutCollector(env, net, args.num_steps, seed=rank, autocast_dtype=torch.bfloat16, **(dict(league_stats=True) if league_stats else {}))
     tr = PPOTrainer(net, PPOConfig(ppo_epoch=args.ppo_epoch, num_mini_batch=args.num_mini_batch, diagnostics=args.diagnostics), seed=rank)
     random_net = CatanPolicy(include_lstm=args.lstm).cuda().eval()                                   # robust_train.py:76-78: the evaluation opponent
 
@@ -57,7 +62,7 @@ def main():
                                                   max_steps=args.eval_max_steps, autocast_dtype=torch.bfloat16,
                                                   baselines=train_loop.eval_baselines(targs))
 
-    lg = League(max_distinct=args.league, seed=rank) if args.league > 0 else None
+    lg = League(max_distinct=args.league, seed=rank, sampling=args.league_sampling) if args.league > 0 else None
     targs = train_loop.TrainArgs(num_steps=args.num_steps, eval_every=args.eval_every, num_eval_episodes=args.num_eval_episodes,
                                  eval_scripted_baseline=args.eval_scripted_baseline)
     loop = train_loop.TrainingLoop(env, net, col, tr, targs, league=lg, make_net=lambda: CatanPolicy(include_lstm=args.lstm).cuda(),
@@ -71,6 +76,11 @@ def main():
                 fmt = lambda xs: " ".join("%.3e" % x for x in xs)
                 for k in ("approx_kl", "clip_fraction", "explained_variance"):
                     print(f"update {out['update']} {k:18s} per epoch: {fmt(out['ppo'][k])}", flush=True)
+            if "league" in out:
+                lo, hi = (f(range(len(out["league"]["serials"])), key=lambda i: out["league"]["central_share"][i]) for f in (min, max))
+                print("update %d central share: lowest %.3f against snapshot %d, highest %.3f against snapshot %d (%d snapshots, %d games tallied)"
+                      % (out["update"], out["league"]["central_share"][lo], out["league"]["serials"][lo], out["league"]["central_share"][hi],
+                         out["league"]["serials"][hi], len(out["league"]["serials"]), out["league"]["totals"]["games_tallied"]), flush=True)
             print(json.dumps({k: v for k, v in out.items() if k != "eval"}), flush=True)
     cdist.finalize()
 
