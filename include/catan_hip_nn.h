@@ -130,7 +130,10 @@ int catan_scatter_rows_ranges(const void* dy, int64_t dy_pitch_bytes, const int6
 /* Fused small-sequence multi-head attention of the policy net (RL/models/multi_headed_attention.py:25-54 as used by
  * tile_encoder.py:41-60 with L=19, 4 heads x 16 and by player_modules.py:55-69 with L<=25, 4 heads x 4).
  * qkv [B][L][3][H][HD] (fused Q/K/V projection), out [B][L][H*HD]; float32 or bfloat16 storage (is_bf16), fp32 math;
- * lens (int32 [B], may be NULL): keys >= lens[b] are masked.  bwd recomputes the probabilities. */
+ * lens (int32 [B], may be NULL): keys >= lens[b] are masked, 1 <= lens[b] (a sequence without keys has no softmax: the results are
+ * unspecified; no caller in this library passes one - the card lists, the only sequences that can be empty, go through
+ * catan_card_summary_fwd).  The mask is a key mask only: query rows >= lens[b] still get an output and gradients.  bwd recomputes the
+ * probabilities.  qkv, out, dout, dqkv: element-aligned; bf16 buffers that are all 16-byte aligned take the MFMA kernels. */
 int catan_attention_fwd(const void* qkv, const int32_t* lens, void* out, int64_t B, int L, int H, int HD, int is_bf16, catan_stream_t stream);
 int catan_attention_bwd(const void* qkv, const int32_t* lens, const void* dout, void* dqkv, int64_t B, int L, int H, int HD, int is_bf16, catan_stream_t stream);
 

@@ -111,29 +111,35 @@ def test_bf16_autocast_forward_close_to_fp32(hip_lib):
 @pytest.mark.parametrize("L,H,HD", [(19, 4, 16), (25, 4, 4)])
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
 def test_fused_attention_kernel_vs_torch(hip_lib, L, H, HD, dtype):
-    """csrc/catan_nn.hip against the reference formulation (multi_headed_attention.py:25-36) in fp32 torch ops."""
-    import math
+    """nn_kernels.small_attention - the autograd wrapper, not the ABI (tests/test_gpu_attention_fp64.py holds the kernels path by path):
+    a non-contiguous qkv, lens as int64, a non-contiguous gradient - against tests/attention_reference.py in fp64 with its rule (the
+    whole tensor and every sequence within twice the yardstick's error plus the floor), with and without lens at both shapes."""
+    import attention_reference as A
     from settlers_of_catan_rl_amd import nn_kernels
     dt = getattr(torch, dtype)
-    torch.manual_seed(0)
+    path = "fp32" if dtype == "float32" else "mfma"                 # torch's allocations are 16-byte aligned
     for B in (1, 5, 1001):
-        qkv = torch.randn(B, L, 3, H, HD, device="cuda").to(dt).requires_grad_(True)
-        lens = torch.randint(1, L + 1, (B,), device="cuda", dtype=torch.int32) if L == 25 else None
-        out = nn_kernels.small_attention(qkv, lens)
-        go = torch.randn_like(out.float()).to(dt)
-        out.backward(go)
-        g1 = qkv.grad.float().clone()
-        x = qkv.detach().float().requires_grad_(True)
-        q, k, v = x.permute(2, 0, 3, 1, 4)
-        s = q @ k.transpose(-2, -1) / math.sqrt(HD)
-        if lens is not None:
-            km = torch.arange(L, device="cuda")[None, :] < lens[:, None]
-            s = s.masked_fill(~km[:, None, None, :], float("-inf"))
-        ref = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(B, L, H * HD)
-        ref.backward(go.float())
-        tol = 1e-5 if dtype == "float32" else 3e-2
-        assert torch.allclose(out.float(), ref, atol=tol, rtol=tol), float((out.float() - ref).abs().max())
-        assert torch.allclose(g1, x.grad, atol=tol * 4, rtol=tol * 4), float((g1 - x.grad).abs().max())
+        for masked in (False, True):
+            lens = A.case_lens(L, B, start=B) if masked else None
+            c = A.make_case(L, H, HD, B, "unit", lens, dt)
+            wide = torch.zeros((B, L, 3, H, HD + 3), dtype=dt, device="cuda")
+            wide[..., :HD] = c["qkv"].cuda()
+            qkv = wide[..., :HD].requires_grad_(True)
+            assert not qkv.is_contiguous()
+            out = nn_kernels.small_attention(qkv, None if lens is None else lens.long().cuda())
+            go = c["dout"].cuda().transpose(1, 2).contiguous().transpose(1, 2)
+            assert not go.is_contiguous() or B * L == 1
+            g, = torch.autograd.grad(out, qkv, go)
+            assert out.dtype == dt and g.dtype == dt and g.shape == qkv.shape
+            got = {"out": out.detach().cpu(), "dq": g[:, :, 0].reshape(B, L, H * HD).cpu(), "dk": g[:, :, 1].reshape(B, L, H * HD).cpu(),
+                   "dv": g[:, :, 2].reshape(B, L, H * HD).cpu()}
+            ref = A.attention_ref(c["qkv"], lens, c["dout"])
+            yard = A.attention_yardstick(c["qkv"], lens, c["dout"], path)
+            for o in A.OUTPUTS:
+                ok, ek, ey, bound = A.accept(path, o, got[o], ref[o], yard[o])
+                assert ok, (B, masked, o, ek, ey, bound)
+                oks, eks, bounds = A.per_sequence(path, o, got[o], ref[o], yard[o])
+                assert bool(oks.all()), (B, masked, o, int((~oks).sum()))
 
 
 @pytest.mark.parametrize("D", [16, 25, 64, 128, 256, 512])
