@@ -137,9 +137,10 @@ int catan_scatter_rows_ranges(const void* dy, int64_t dy_pitch_bytes, const int6
 int catan_attention_fwd(const void* qkv, const int32_t* lens, void* out, int64_t B, int L, int H, int HD, int is_bf16, catan_stream_t stream);
 int catan_attention_bwd(const void* qkv, const int32_t* lens, const void* dout, void* dqkv, int64_t B, int L, int H, int HD, int is_bf16, catan_stream_t stream);
 
-/* LayerNorm over the last dimension D in {16, 25, 32, 64, 128, 256, 512} (x, y, dy, dx 16-byte aligned for D >= 128) with optional fused ReLU (the nn.LayerNorm + ReLU pairs of
+/* LayerNorm over the last dimension D in {16, 25, 32, 64, 128, 256, 512} with optional fused ReLU (the nn.LayerNorm + ReLU pairs of
  * RL/models/tile_encoder.py:83-91, player_modules.py:26-30,114-117).  x, y, dy, dx: [rows][D] float32 or bfloat16;
- * w, b, dw, db float32 [D]; dw/db are ACCUMULATED into (zero them first). */
+ * w, b, dw, db float32 [D]; dw/db are ACCUMULATED into (zero them first).  D >= 128: x, y, dy, dx 16-byte aligned, anything else is
+ * refused with CATAN_EINVAL.  D < 128: x, y, dy, dx element-aligned (buffers that are all 16-byte aligned take wider accesses). */
 int catan_layer_norm_fwd(const void* x, const float* w, const float* b, void* y, int64_t rows, int D, float eps, int relu, int is_bf16, catan_stream_t stream);
 int catan_layer_norm_bwd(const void* x, const float* w, const float* b, const void* dy, void* dx, float* dw, float* db, int64_t rows, int D,
                          float eps, int relu, int is_bf16, catan_stream_t stream);

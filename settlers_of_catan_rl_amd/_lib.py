@@ -53,7 +53,7 @@ _HASH_MARK = b"CATAN_BUILD_HASH="
 # with this flag is bit-stable, and tests/test_gpu_ppo_pipeline.py::test_fused_tile_encoder_forward_vs_unfused is the check)
 # -target-feature -packed-fp32-ops (round 5): the SLP flag only stops ONE source of those instructions; the load / store vectoriser and the
 # DAG combiner produced them too (llvm-objdump of the round-4 library: 12 v_pk_mul_f32 in each k_obs_rows<fp32>, one v_pk_add_f32 beside three
-# v_cvt_pk_bf16_f32 in k_lnw_bwd<bf16, 2, 64> - the very combination that misbehaved).  With the target feature off the back end cannot
+# v_cvt_pk_bf16_f32 in a bf16 LayerNorm backward - the very combination that misbehaved).  With the target feature off the back end cannot
 # select them at all, whoever asks; `check_no_packed_f32` disassembles every freshly built library and refuses one that has any.
 # The flag is NOT a no-op, although the build prints "'-packed-fp32-ops' is not a recognized feature for this target (ignoring feature)":
 # -Xclang reaches both halves of the compilation, the x86 HOST half does not know an AMDGPU feature and says so (LLVM's subtarget parser,

@@ -301,9 +301,9 @@ __global__ __launch_bounds__(256) void k_ln_bwd(const T* __restrict__ x, const f
 
 
 // ------------------------------------------------------------------------------------------------ LayerNorm, wide rows
-// D = GL * EPL: GL lanes per row, lane j owns the EPL contiguous elements j*EPL .. j*EPL+EPL-1 (one 4 / 8 / 16 B access per
-// lane, fully coalesced), moments by a GL-lane butterfly.  GL = 64 for D = 128, 256, 512 (the player / head / value modules,
-// RL/models/player_modules.py:26-30,114-117, action_heads_module.py, policy.py); GL = 8, EPL = 8 for D = 64 (the tile
+// D = GL * EPL: GL lanes per row, lane j owns the EPL = 8 contiguous elements j*EPL .. j*EPL+EPL-1 (16-byte accesses, fully
+// coalesced: every tensor is 16-byte aligned), moments by a GL-lane butterfly.  GL = 16, 32, 64 for D = 128, 256, 512 (the player /
+// head / value modules, RL/models/player_modules.py:26-30,114-117, action_heads_module.py, policy.py); GL = 8 for D = 64 (the tile
 // encoder's 1.2 M rows per pass: eight rows per wave, three shuffle steps instead of six).  In the backward every lane always
 // works on the same columns, so dw / db accumulate in registers and leave through one LDS reduction + atomics per block.
 template <class T, int EPL> struct RowVec;
@@ -318,11 +318,6 @@ template <int EPL> struct RowVec<float, EPL> {
         for (int e = 0; e < EPL; e += 4) *reinterpret_cast<float4*>(p + e) = make_float4(v[e], v[e + 1], v[e + 2], v[e + 3]);
     }
 };
-template <> struct RowVec<float, 2> {
-    static __device__ __forceinline__ float rounded(float a) { return a; }
-    static __device__ __forceinline__ void load(const float* p, float (&v)[2]) { const float2 u = *reinterpret_cast<const float2*>(p); v[0] = u.x; v[1] = u.y; }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[2]) { *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]); }
-};
 template <int EPL> struct RowVec<__hip_bfloat16, EPL> {
     static __device__ __forceinline__ float rounded(float a) { return __bfloat162float(__float2bfloat16(a)); }
     static __device__ __forceinline__ unsigned pack(float a, float b) {
@@ -330,15 +325,13 @@ template <int EPL> struct RowVec<__hip_bfloat16, EPL> {
     }
     static __device__ __forceinline__ void load(const __hip_bfloat16* p, float (&v)[EPL]) {
         unsigned w[EPL / 2];
-        if constexpr (EPL == 2) w[0] = *reinterpret_cast<const unsigned*>(p);
-        else if constexpr (EPL == 4) { const uint2 u = *reinterpret_cast<const uint2*>(p); w[0] = u.x; w[1] = u.y; }
+        if constexpr (EPL == 4) { const uint2 u = *reinterpret_cast<const uint2*>(p); w[0] = u.x; w[1] = u.y; }
         else { const uint4 u = *reinterpret_cast<const uint4*>(p); w[0] = u.x; w[1] = u.y; w[2] = u.z; w[3] = u.w; }
 #pragma unroll
         for (int k = 0; k < EPL / 2; k++) { v[2 * k] = __uint_as_float(w[k] << 16); v[2 * k + 1] = __uint_as_float(w[k] & 0xFFFF0000u); }
     }
     static __device__ __forceinline__ void store(__hip_bfloat16* p, const float (&v)[EPL]) {
-        if constexpr (EPL == 2) *reinterpret_cast<unsigned*>(p) = pack(v[0], v[1]);
-        else if constexpr (EPL == 4) *reinterpret_cast<uint2*>(p) = make_uint2(pack(v[0], v[1]), pack(v[2], v[3]));
+        if constexpr (EPL == 4) *reinterpret_cast<uint2*>(p) = make_uint2(pack(v[0], v[1]), pack(v[2], v[3]));
         else *reinterpret_cast<uint4*>(p) = make_uint4(pack(v[0], v[1]), pack(v[2], v[3]), pack(v[4], v[5]), pack(v[6], v[7]));
     }
 };

@@ -33,6 +33,19 @@ def test_bad_arguments_are_reported_not_crashed(hip_lib):
     assert "unsupported" in err(L.catan_attention_fwd(C.c_void_p(q.data_ptr()), None, C.c_void_p(q.data_ptr()), 4, 7, 2, 8, 0, st))
     assert "unsupported" in err(L.catan_layer_norm_fwd(C.c_void_p(q.data_ptr()), C.c_void_p(q.data_ptr()), C.c_void_p(q.data_ptr()),
                                                        C.c_void_p(q.data_ptr()), 4, 48, 1e-5, 0, 0, st))
+    # wide LayerNorm rows take 16-byte accesses: a misaligned x, y / dx or dy is refused at D >= 128 (no kernel is launched), taken below
+    f32 = torch.zeros((8 * 512 + 4,), device="cuda")
+    b16w = torch.zeros((8 * 512 + 8,), device="cuda", dtype=torch.bfloat16)
+    for buf, isb in ((f32, 0), (b16w, 1)):
+        ok, off = C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + buf.element_size())
+        for D in (128, 256, 512):
+            assert "16-byte" in err(L.catan_layer_norm_fwd(off, ok, ok, ok, 4, D, 1e-5, 0, isb, st))
+            assert "16-byte" in err(L.catan_layer_norm_fwd(ok, ok, ok, off, 4, D, 1e-5, 0, isb, st))
+            assert "16-byte" in err(L.catan_layer_norm_bwd(off, ok, ok, ok, ok, ok, ok, 4, D, 1e-5, 0, isb, st))
+            assert "16-byte" in err(L.catan_layer_norm_bwd(ok, ok, ok, off, ok, ok, ok, 4, D, 1e-5, 0, isb, st))
+            assert "16-byte" in err(L.catan_layer_norm_bwd(ok, ok, ok, ok, off, ok, ok, 4, D, 1e-5, 0, isb, st))
+    torch.cuda.synchronize()
+    assert bool((f32 == 0).all()) and bool((b16w == 0).all())
     # round 3's learner / collector entry points: misaligned, odd-sized or missing buffers are refused, nothing is launched
     P = lambda t: C.c_void_p(t.data_ptr())
     b16 = torch.zeros((64, 512), device="cuda", dtype=torch.bfloat16)
