@@ -1950,7 +1950,7 @@ int catan_linear_rows_supported(int64_t rows, int in_features, int out_features)
 int catan_linear_rows_fused(const void* x, const void* w, const void* bias, void* y, int64_t rows, int in_features, int out_features,
                             const void* aux, int mode, catan_stream_t stream) {
     if (!x || !w || !y || !catan_linear_rows_supported(rows, in_features, out_features))
-        return fail(CATAN_EINVAL, "catan_linear_rows: bad arguments / unsupported widths (in multiple of 8 and <= 192, out <= 192, ceil(in/32)*ceil(out/16) <= 24)");
+        return fail(CATAN_EINVAL, "catan_linear_rows: bad arguments / unsupported widths (in multiple of 8 and <= 192, out <= 192, instantiated k-steps (1, 2, 3, 4, 6) x n-tiles (1, 2, 4, 8, 12) <= 32)");
     if (mode < 0 || mode > 3 || (mode >= 2 && !aux) || (mode != 0 && (out_features & 7)))
         return fail(CATAN_EINVAL, "catan_linear_rows_fused: mode 0..3; modes 2, 3 need aux; a fused epilogue needs out_features % 8 == 0");
     if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)aux) & 15) return fail(CATAN_EINVAL, "catan_linear_rows: x, w, y, aux must be 16-byte aligned");
