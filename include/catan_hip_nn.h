@@ -302,7 +302,12 @@ int catan_head_chain_ex(const void* pre, int64_t pre_ld, const void* wts, const 
  * c3 = k / 180 % 3, c4 = k / 540 % 3, c5 = k / 1620) - or -1 for counts outside the deck.  The gradient is linear in dout, so a
  * caller may sum dout per pattern and differentiate catan_card_summary_patterns() synthetic lists instead of all rows;
  * only_unkeyed (int32 [rows], may be NULL) makes the backward skip the rows whose entry is >= 0 (those went through the patterns);
- * n_unkeyed (int32 [1] on the device, may be NULL; needs only_unkeyed): the launch returns at once when it holds 0. */
+ * n_unkeyed (int32 [1] on the device, may be NULL; needs only_unkeyed, else CATAN_EINVAL): the launch returns at once when it holds 0.
+ * lens[r] <= 0: a zero row, pattern 0 and no gradient.  Ids must lie in 0..5; any other value is counted in no class.  Nothing at or
+ * behind position min(lens[r], 25) of a row is read, so `pitch` may be smaller than 25 if every lens[r] <= pitch.  Rows whose dout is
+ * all zero are skipped by the backward.  The backward's sums (dparams, dpat) are formed by atomics in an order that differs from launch
+ * to launch: they are not reproducible to the bit.  The pattern table's last row (all six counts at the deck's limit: 26 cards) holds
+ * a list cut to its first 25 ids and can be reached by no list of at most 25 ids.  (tests/test_gpu_card_summary_fp64.py pins all of it.) */
 int32_t catan_card_summary_params(void);
 int32_t catan_card_summary_patterns(void);
 int catan_card_summary_fwd(const void* ids, int id_bytes, int64_t pitch, const int32_t* lens, const float* params, float eps, float* out,

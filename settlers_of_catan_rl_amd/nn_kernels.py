@@ -1342,7 +1342,7 @@ _PATTERN_LISTS = {}
 
 
 def _pattern_lists(device):
-    """the synthetic list of every count pattern (include/catan_hip.h): ids int8 [P, 25] and lens int32 [P]"""
+    """the synthetic list of every count pattern (include/catan_hip_nn.h): ids int8 [P, 25] and lens int32 [P]"""
     if device not in _PATTERN_LISTS:
         P = _lib.lib().catan_card_summary_patterns()
         k = torch.arange(P)
@@ -1399,7 +1399,7 @@ def card_summary_supported(ids, vocab, heads, hd, width):
 
 def card_summary(ids, lens, params, eps):
     """ids [rows, L<=25] integer (any row pitch), lens [rows], params float32 [544] (S, V, W, bias, LayerNorm weight / bias:
-    include/catan_hip.h) -> float32 [rows, 16]; gradient w.r.t. params."""
+    include/catan_hip_nn.h) -> float32 [rows, 16]; gradient w.r.t. params."""
     if ids.stride(1) != 1:
         ids = ids.contiguous()
     return _CardSummary.apply(ids, lens.to(torch.int32).contiguous(), params, eps)
@@ -1410,7 +1410,7 @@ _CARD_TABLES = weakref.WeakKeyDictionary()
 
 
 def card_summary_params(embedding, mha, norm):
-    """the 544 floats catan_card_summary_* read (include/catan_hip.h), from the module's weights"""
+    """the 544 floats catan_card_summary_* read (include/catan_hip_nn.h), from the module's weights"""
     import math
     V, H, hd = embedding.num_embeddings, mha.heads, mha.hd
     w = torch.cat([n.weight for n in mha.qkv_nets], 0).float()

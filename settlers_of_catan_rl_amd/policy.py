@@ -210,20 +210,22 @@ def _card_summary(ids, lens, embedding, mha, norm):
     if not torch.is_grad_enabled() and nn_kernels.card_summary_supported(ids, V, H, hd, H * hd):
         return nn_kernels.card_summary_lookup(ids, lens, embedding, mha, norm)       # inference: a table of the 4 860 count patterns
     with torch.autocast(device_type=ids.device.type, enabled=False):          # a few hundred flops per row: keep them fp32
-        w = torch.cat([n.weight for n in mha.qkv_nets], 0).float()
-        b = torch.cat([n.bias for n in mha.qkv_nets], 0).float()
-        qkv = F.linear(embedding.weight.float(), w, b).view(V, 3, H, hd)      # Q / K / V of each of the six ids
+        # (at least fp32; a double module - the CPU check of tests/card_summary_reference.py - stays double)
+        up = lambda t: t.to(torch.promote_types(t.dtype, torch.float32))
+        w = up(torch.cat([n.weight for n in mha.qkv_nets], 0))
+        b = up(torch.cat([n.bias for n in mha.qkv_nets], 0))
+        qkv = F.linear(up(embedding.weight), w, b).view(V, 3, H, hd)          # Q / K / V of each of the six ids
         s_ab = torch.einsum("ahd,bhd->hab", qkv[:, 0], qkv[:, 1]) * (1.0 / math.sqrt(hd))
         if nn_kernels.card_summary_supported(ids, V, H, hd, H * hd):           # GPU: one fused kernel, 26 B in / 64 B out per list
-            params = torch.cat((s_ab.reshape(-1), qkv[:, 2].reshape(-1), mha.out_proj_net.weight.float().reshape(-1),
-                                mha.out_proj_net.bias.float(), norm.weight.float(), norm.bias.float()))
+            params = torch.cat((s_ab.reshape(-1), qkv[:, 2].reshape(-1), mha.out_proj_net.weight.reshape(-1),
+                                mha.out_proj_net.bias, norm.weight, norm.bias)).float()
             return nn_kernels.card_summary(ids, lens, params, norm.eps)
-        valid = (torch.arange(L, device=ids.device)[None, :] < lens[:, None]).float()
-        cnt = torch.zeros((B, V), dtype=torch.float32, device=ids.device).scatter_add_(1, ids.long(), valid)     # valid tokens per id
+        valid = (torch.arange(L, device=ids.device)[None, :] < lens[:, None]).to(qkv.dtype)
+        cnt = torch.zeros((B, V), dtype=qkv.dtype, device=ids.device).scatter_add_(1, ids.long(), valid)     # valid tokens per id
         p = torch.softmax(s_ab[None] + torch.log(cnt)[:, None, None, :], -1)  # [B, H, 6, 6]; absent classes: log 0 = -inf
         attn = torch.einsum("rhab,bhd->rahd", p, qkv[:, 2]).reshape(B, V, H * hd)
-        rep = F.layer_norm(F.linear(attn, mha.out_proj_net.weight.float(), mha.out_proj_net.bias.float()), norm.normalized_shape,
-                           norm.weight.float(), norm.bias.float(), norm.eps)
+        rep = F.layer_norm(F.linear(attn, up(mha.out_proj_net.weight), up(mha.out_proj_net.bias)), norm.normalized_shape,
+                           up(norm.weight), up(norm.bias), norm.eps)
         return (rep * cnt[..., None]).sum(1)
 
 

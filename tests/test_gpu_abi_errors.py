@@ -83,6 +83,10 @@ def test_bad_arguments_are_reported_not_crashed(hip_lib):
     assert "bad game list" in err(L.catan_obs_rows_of(env.h, 0, P(dw), None, None, None, None, None, None, None, None, 4, st))
     assert "bad arguments" in err(L.catan_linear_wgrad_grouped(None, 3, st))
     assert "bad arguments" in err(L.catan_head_chain(P(b16), 1536, P(b16), P(dw), 1e-5, 12, 0, P(dw), P(dw), P(dw), None, None, None, None, P(idx), P(dw), 64, st))
+    # the card-list backward: n_unkeyed (the early return) needs only_unkeyed (the skip list it counts)
+    i8 = torch.zeros((64, 25), device="cuda", dtype=torch.int8)
+    i32 = torch.zeros((64,), device="cuda", dtype=torch.int32)
+    assert "bad arguments" in err(L.catan_card_summary_bwd(P(i8), 1, 25, P(i32), P(dw), 1e-5, P(dw), P(dw), None, P(i32), 64, st))
     with pytest.raises(_lib.CatanHipError):
         _lib.check(L.catan_random_rollout_deferred(env.h, 10, -3, st))
     # the handle is still usable after the failed calls
