@@ -315,11 +315,16 @@ _SIGS = {
     "catan_league_stats_enable": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int32, _vp]),
     "catan_league_stats_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int, _vp]),
     "catan_league_stats_count": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    "catan_record_enable": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
+    "catan_record_arm": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
+    "catan_record_status": (C.c_int, [_vp, _vp, _vp]),
+    "catan_record_read": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
 }
 # bound only where the library exports them: the same callers also load oracle/libcatan_cpu.so, which implements the env ABI
 # without these
 _OPTIONAL = {"catan_set_board_configs", "catan_episode_stats_words", "catan_episode_stats_enable", "catan_episode_stats_read",
-             "catan_league_stats_words", "catan_league_stats_enable", "catan_league_stats_read", "catan_league_stats_count"}
+             "catan_league_stats_words", "catan_league_stats_enable", "catan_league_stats_read", "catan_league_stats_count",
+             "catan_record_enable", "catan_record_arm", "catan_record_status", "catan_record_read"}
 
 
 def declared_symbols():

@@ -25,6 +25,7 @@
 #include "catan_stats.hip"
 #include "catan_scripted.hip"
 #include "catan_league_stats.hip"
+#include "catan_record.hip"
 
 using namespace catan;
 
@@ -97,6 +98,8 @@ struct catan_env {
     int lstats_nets, lstats_cap; // rows in use (without the totals row), and allocated
     int lstats_on;               // 0 off, else the mode bits of catan_league_stats_enable
     unsigned long long* script_fallback;   // catan_sample_scripted_actions: decisions taken by the fall-back row (catan_scripted.hip), allocated at the first call
+    RecordBuf rec;               // catan_record_enable: the recorder's slots (catan_record.hip); not in `owned`: freed and re-made by every enable
+    int rec_on;
 };
 static_assert(sizeof(BoardCfg) == sizeof(catan_board_cfg_t) && sizeof(catan_board_cfg_t) == 56 &&
               offsetof(BoardCfg, terrain) == offsetof(catan_board_cfg_t, terrain) &&
@@ -411,6 +414,12 @@ static void enqueue_league_stats(catan_env_t* e, const u32* count_p, const i32* 
     if (!(e->lstats_on & CATAN_LEAGUE_STATS_REDEALS)) return;
     launch_league_stats(e, count_p, 0u, list, LEAGUE_STATS_GRID, st);
 }
+// Game records (catan_record_enable; defined at the end of this file, see there): seal in front of a re-deal list's consumer, open behind
+// it, the append in front of the step, the seal over the done flags of a handle without auto_reset.  Off (the default): nothing is launched.
+static void enqueue_record_seal(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
+static void enqueue_record_open(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
+static void enqueue_record_append(catan_env_t* e, const i32* actions, const u8* busy, hipStream_t st);
+static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* status, const i32* actions, hipStream_t st);
 // k_step with G games per wave in one-wave workgroups; pend.sample (fused-sampling rollouts): actions from / to the side rows
 template <int G>
 static void launch_step(catan_env_t* e, const int32_t* actions, float* reward, uint8_t* done, hipStream_t st, const StepCfg& sc, const u32* bins) {
@@ -536,6 +545,7 @@ int catan_create(catan_env_t** out, int device, int64_t n_envs, uint64_t seed, u
     return CATAN_OK;
 }
 
+static void record_free(catan_env_t* e);
 void catan_destroy(catan_env_t* e) {
     if (!e) return;
     hipSetDevice(e->device);
@@ -544,6 +554,7 @@ void catan_destroy(catan_env_t* e) {
     if (e->bcfg_dev) hipFree(e->bcfg_dev);
     if (e->bcfg_idx_dev) hipFree(e->bcfg_idx_dev);
     if (e->lstats) hipFree(e->lstats);
+    record_free(e);
     for (hipStream_t st : { e->fstream, e->sstream, e->side }) if (st) hipStreamDestroy(st);
     for (hipEvent_t ev : { e->ev_fready[0], e->ev_fready[1], e->ev_fready[2], e->ev_fdone[0], e->ev_fdone[1], e->ev_fdone[2], e->ev_sdone[0], e->ev_sdone[1],
                            e->ev_fork, e->ev_join })
@@ -793,8 +804,10 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
             enqueue_episode_stats(e, sctr + 1, e->pend.resets[sa][0], e->side);
             enqueue_league_stats(e, sctr + 1, e->pend.resets[sa][0], e->side);
+            enqueue_record_seal(e, sctr + 1, e->pend.resets[sa][0], e->side);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 1),
                                (const i32*)e->pend.resets[sa][0], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
+            enqueue_record_open(e, sctr + 1, e->pend.resets[sa][0], e->side);
             HIPCHK(hipEventRecord(e->ev_join, e->side));
         }
     }
@@ -816,18 +829,24 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));      // the side stream's launch of step_impl: it had the whole slow path to finish
             enqueue_episode_stats(e, sctr + 3, e->pend.resets[sa][2], st);
             enqueue_league_stats(e, sctr + 3, e->pend.resets[sa][2], st);
+            enqueue_record_seal(e, sctr + 3, e->pend.resets[sa][2], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 3), (const i32*)e->pend.resets[sa][2], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
+            enqueue_record_open(e, sctr + 3, e->pend.resets[sa][2], st);
             enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_league_stats(e, sctr + 2, e->pend.resets[sa][1], st);
+            enqueue_record_seal(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2), (const i32*)e->pend.resets[sa][1], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
+            enqueue_record_open(e, sctr + 2, e->pend.resets[sa][1], st);
         } else {
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));
             enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_league_stats(e, sctr + 2, e->pend.resets[sa][1], st);
+            enqueue_record_seal(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2),
                                (const i32*)e->pend.resets[sa][1], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
+            enqueue_record_open(e, sctr + 2, e->pend.resets[sa][1], st);
         }
     }
     if (ev) HIPCHK(hipEventRecord(ev[4], st));
@@ -849,6 +868,7 @@ static int step_impl(catan_env_t* e, int32_t* actions, float* reward, uint8_t* d
         hipLaunchKernelGGL(k_sample_random<BLOCK>, dim3(blocks(e->n, BLOCK)), dim3(BLOCK), 0, st, e->ctx, (const u32*)e->mpk, *sample_step, actions,
                            (u32*)nullptr, (u8*)nullptr, 0, 0, e->pend.ctr + 4, 12, e->pend.ctr + 16 + NBINS * e->pend.bsel,
                            e->pend.lists + (size_t)e->pend.bsel * NBINS * e->N);
+    enqueue_record_append(e, actions, nullptr, st);              // (behind the sampler where it is the one that writes `actions`)
     int r = enqueue_fast(e, actions, reward, done, st, ev, sample_step != nullptr);
     if (r == CATAN_OK && e->cfg.auto_reset) {                    // the games that ended in k_step: re-dealt on the side stream from here on
         HIPCHK(hipEventRecord(e->ev_fork, st));
@@ -857,13 +877,16 @@ static int step_impl(catan_env_t* e, int32_t* actions, float* reward, uint8_t* d
         e->spec_epoch++;
         enqueue_episode_stats(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);       // (the real list only: the speculative successors are no episodes)
         enqueue_league_stats(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
+        enqueue_record_seal(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
         hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, limits_of(e),
                            (const u32*)(e->pend.ctr + 8 + 1), (const i32*)e->pend.resets[0][0], e->pend.busy, step_cfg(e).prof,
                            (const u32*)(e->pend.ctr + 6), (const u64*)e->pend.spec, e->spec_state, e->spec_mpk, e->spec_epoch, e->pend);
+        enqueue_record_open(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
         HIPCHK(hipEventRecord(e->ev_join, e->side));
     }
     if (r == CATAN_OK) r = enqueue_tier1(e, reward, done, st, ev, 0, e->sched.lr_budget[0]);
     if (r == CATAN_OK) r = enqueue_slow(e, reward, done, st, ev, LR_HEAVY_GRID);
+    if (r == CATAN_OK) enqueue_record_seal_done(e, done, nullptr, actions, st);
     return r;
 }
 
@@ -1068,6 +1091,8 @@ int catan_league_stats_count(catan_env_t* e, const int32_t* games, int64_t m, ca
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
+
+static int record_not_armed(catan_env_t* e, const char* what, hipStream_t st);      // (game records: at the end of this file)
 
 // ---- the rule-based player (catan_scripted.hip)
 int catan_sample_scripted_actions(catan_env_t* e, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
@@ -1285,6 +1310,7 @@ int catan_random_rollout_deferred(catan_env_t* e, int64_t iters, int32_t window,
     if (!e || iters < 0 || window <= 0) return fail(CATAN_EINVAL, "catan_random_rollout_deferred: bad arguments");
     NOT_DEFERRED(e, "catan_random_rollout_deferred");
     NOT_MT(e, "catan_random_rollout_deferred");
+    OK_OR_RETURN(record_not_armed(e, "catan_random_rollout_deferred", S(stream)));
     for (int64_t it = 0; it < iters; it++) {
         int r = deferred_iter(e, it, iters, window, S(stream), nullptr);
         if (r != CATAN_OK) return r;
@@ -1315,6 +1341,7 @@ int catan_step_deferred(catan_env_t* e, const int32_t* actions, int32_t window, 
     // (tier 1 of call it-2 and, when this call opens window w, the slow path of window w-2 were joined at the end of call it-1)
     OK_OR_RETURN(window_clear(e, win, it, st));
     pend_pass(e, fa, 2 + fa, win.sa, fa, fa ^ 1);
+    enqueue_record_append(e, actions, e->pend.busy, st);
     hipLaunchKernelGGL(k_classify_deferred, dim3(blocks(e->N, BLOCK)), dim3(BLOCK), 0, st, e->ctx, actions, (const u8*)e->pend.busy, e->pend.ctr + 16 + NBINS * fa,
                        e->pend.lists + (size_t)fa * NBINS * e->N, it == 0 ? (u32*)nullptr : e->pend.ctr + 4 + fa, 1, e->cfg.validate_actions ? e->err : (u32*)nullptr);
     OK_OR_RETURN(enqueue_fast(e, actions, e->f_reward, e->f_done, st, nullptr, true));
@@ -1330,6 +1357,7 @@ int catan_step_deferred(catan_env_t* e, const int32_t* actions, int32_t window, 
     OK_OR_RETURN(window_wait(e, next, st));
     hipLaunchKernelGGL(k_deliver, dim3(blocks(e->n, BLOCK)), dim3(BLOCK), 0, st, e->ctx, e->pend.busy, nit >= 2 ? 2 + (int)(nit & 1) : 0, next.back ? 4 + next.sa : 0, 0,
                        (const float*)e->f_reward, (const u8*)e->f_done, reward, done, status);
+    enqueue_record_seal_done(e, done, status, nullptr, st);
     HIPCHK(hipGetLastError());
     e->d_it = nit;
     return CATAN_OK;
@@ -1349,6 +1377,7 @@ int catan_step_flush(catan_env_t* e, float* reward, uint8_t* done, uint8_t* stat
         OK_OR_RETURN(window_join(e, win, st));
     }
     hipLaunchKernelGGL(k_deliver, dim3(blocks(e->n, BLOCK)), dim3(BLOCK), 0, st, e->ctx, e->pend.busy, 0, 0, 1, (const float*)e->f_reward, (const u8*)e->f_done, reward, done, status);
+    enqueue_record_seal_done(e, done, status, nullptr, st);
     HIPCHK(hipGetLastError());
     pend_lockstep(e);
     e->d_it = 0;
@@ -1410,6 +1439,7 @@ int catan_set_lr_rounds(catan_env_t* e, int32_t lockstep, int32_t deferred) {
 int catan_random_rollout_timed(catan_env_t* e, uint32_t step_idx0, int64_t steps, int32_t window, catan_stream_t stream, float* kernel_ms) {
     if (!e || steps <= 0 || !kernel_ms) return fail(CATAN_EINVAL, "catan_random_rollout_timed: bad arguments");
     if (window > 0) NOT_MT(e, "catan_random_rollout_timed (deferred)");
+    if (window > 0) OK_OR_RETURN(record_not_armed(e, "catan_random_rollout_timed (deferred)", S(stream)));
     hipStream_t st = S(stream);
     const int K = EV_PER_STEP;             // see enqueue_fast / enqueue_tier1 / enqueue_slow; [5] = before the sampler
     std::vector<hipEvent_t> ev((size_t)steps * K);
@@ -2150,4 +2180,158 @@ int catan_profile_read(catan_env_t* e, uint64_t* out16) {
     return CATAN_OK;
 }
 
+
+// ---- game records (catan_record.hip).  Everything that launches one of the recorder's kernels stands here, at the end of the file, and those
+// kernels are templates: a kernel template is emitted where it is first used, so the recorder's code lands BEHIND every other kernel in the
+// code object and the existing kernels keep their places relative to each other (with the kernels in the middle of the code object
+// bench.py's pass read 36.9 instead of 36.4 us with not one of them launched: profiles/record_bench.txt).
+static void record_free(catan_env_t* e) {
+    for (void* p : { (void*)e->rec.hdr, (void*)e->rec.slot_of, (void*)e->rec.start, (void*)e->rec.fin, (void*)e->rec.log, (void*)e->rec.arm_list })
+        if (p) hipFree(p);
+    e->rec = RecordBuf{};
+    e->rec_on = 0;
+}
+// every slot's header (and guard word) on the host; synchronises st
+static int record_headers(catan_env_t* e, std::vector<u32>& hdr, hipStream_t st) {
+    const int m = e->rec.m;
+    hdr.assign((size_t)m * RECORD_HDR_WORDS, 0u);
+    std::vector<u32> guard((size_t)m, 0u);
+    HIPCHK(hipMemcpyAsync(hdr.data(), e->rec.hdr, hdr.size() * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpy2DAsync(guard.data(), sizeof(u32), e->rec.log + (size_t)e->rec.capacity * ACTION_WORDS, (size_t)e->rec.log_stride * sizeof(short),
+                            sizeof(u32), (size_t)m, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < m; s++) if (guard[s] != RECORD_GUARD) hdr[(size_t)s * RECORD_HDR_WORDS + REC_H_FLAGS] |= REC_F_GUARD_BROKEN;
+    return CATAN_OK;
+}
+// the library's own deferred loops draw their actions inside k_step: there is no action row to log
+static int record_not_armed(catan_env_t* e, const char* what, hipStream_t st) {
+    if (!e->rec_on) return CATAN_OK;
+    std::vector<u32> hdr;
+    OK_OR_RETURN(record_headers(e, hdr, st));
+    for (int s = 0; s < e->rec.m; s++) {
+        const u32 state = hdr[(size_t)s * RECORD_HDR_WORDS + REC_H_STATE];
+        if (state == REC_WAIT_DEAL || state == REC_RECORDING)
+            return fail(CATAN_EINVAL, std::string(what) + ": record slot " + std::to_string(s) + " is armed (the deferred rollout's actions never exist outside k_step)");
+    }
+    return CATAN_OK;
+}
+int catan_record_enable(catan_env_t* e, const int32_t* games, int32_t m, int32_t capacity, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_record_enable: null handle");
+    NOT_DEFERRED(e, "catan_record_enable");
+    NOT_MT(e, "catan_record_enable");
+    if (m < 0 || m > RECORD_MAX_SLOTS) return fail(CATAN_EINVAL, "catan_record_enable: m must be in 0..4096");
+    if (m > 0 && (capacity < 1 || capacity > RECORD_MAX_CAPACITY)) return fail(CATAN_EINVAL, "catan_record_enable: capacity must be in 1..65535");
+    if (m > 0 && !games) return fail(CATAN_EINVAL, "catan_record_enable: null games");
+    const hipStream_t st = S(stream);
+    // the old slots may still be written by hooks in flight on any of the handle's streams
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(e->side));
+    HIPCHK(hipStreamSynchronize(e->fstream));
+    HIPCHK(hipStreamSynchronize(e->sstream));
+    record_free(e);
+    if (m == 0) return CATAN_OK;
+    RecordBuf rb{};
+    rb.m = m; rb.capacity = capacity; rb.log_stride = (long)capacity * ACTION_WORDS + 2;
+    u32* bad = nullptr;
+    hipError_t rc = hipMalloc((void**)&rb.hdr, (size_t)m * RECORD_HDR_WORDS * sizeof(u32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&rb.slot_of, (size_t)e->N * sizeof(i32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&rb.start, (size_t)m * STATE_WORDS * sizeof(i32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&rb.fin, (size_t)m * STATE_WORDS * sizeof(i32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&rb.log, (size_t)m * rb.log_stride * sizeof(short));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&rb.arm_list, (size_t)m * sizeof(i32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&bad, sizeof(u32));
+    e->rec = rb;                                                  // (record_free below frees whatever was allocated)
+    if (rc != hipSuccess) { if (bad) hipFree(bad); record_free(e); return fail(CATAN_ENOMEM, std::string("catan_record_enable: hipMalloc: ") + hipGetErrorString(rc)); }
+    rc = hipMemsetAsync(rb.slot_of, 0xFF, (size_t)e->N * sizeof(i32), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(rb.start, 0, (size_t)m * STATE_WORDS * sizeof(i32), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(rb.fin, 0, (size_t)m * STATE_WORDS * sizeof(i32), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(bad, 0, sizeof(u32), st);
+    if (rc == hipSuccess) {
+        hipLaunchKernelGGL(k_record_bind<>, dim3(blocks(m, BLOCK)), dim3(BLOCK), 0, st, (long)e->n, games, rb, bad);
+        rc = hipGetLastError();
+    }
+    u32 nbad = 0;
+    if (rc == hipSuccess) rc = hipMemcpyAsync(&nbad, bad, sizeof(u32), hipMemcpyDeviceToHost, st);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(st);
+    hipFree(bad);
+    if (rc != hipSuccess || nbad != 0) {
+        record_free(e);
+        if (rc != hipSuccess) return fail(CATAN_EHIP, std::string("catan_record_enable: ") + hipGetErrorString(rc));
+        return fail(CATAN_EINVAL, "catan_record_enable: " + std::to_string(nbad) + " entries of games are outside [0, n) or list a game twice");
+    }
+    e->rec_on = 1;
+    return CATAN_OK;
+}
+int catan_record_arm(catan_env_t* e, const int32_t* slots, int32_t k, int32_t mode, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_record_arm: null handle");
+    if (!e->rec_on) return fail(CATAN_EINVAL, "catan_record_arm: recording is not enabled on this handle (catan_record_enable)");
+    NOT_DEFERRED(e, "catan_record_arm");
+    if (mode != CATAN_RECORD_NOW && mode != CATAN_RECORD_AT_DEAL) return fail(CATAN_EINVAL, "catan_record_arm: mode is CATAN_RECORD_NOW or CATAN_RECORD_AT_DEAL");
+    if (mode == CATAN_RECORD_AT_DEAL && !e->cfg.auto_reset) return fail(CATAN_EINVAL, "catan_record_arm: CATAN_RECORD_AT_DEAL on a handle with auto_reset = 0 (no game is re-dealt)");
+    if (!slots) k = e->rec.m;
+    if (k < 1 || k > e->rec.m) return fail(CATAN_EINVAL, "catan_record_arm: k must be in 1..m");
+    if (slots) {
+        for (int j = 0; j < k; j++)
+            if (slots[j] < 0 || slots[j] >= e->rec.m) return fail(CATAN_EINVAL, "catan_record_arm: slot " + std::to_string(slots[j]) + " is outside [0, m)");
+        // (a pageable source: the copy has left the caller's array when the call returns)
+        HIPCHK(hipMemcpyAsync(e->rec.arm_list, slots, (size_t)k * sizeof(i32), hipMemcpyHostToDevice, S(stream)));
+    }
+    hipLaunchKernelGGL(k_record_arm<>, dim3(blocks(k, 64)), dim3(64), 0, S(stream), e->ctx, e->rec, slots ? (const i32*)e->rec.arm_list : (const i32*)nullptr, (int)k,
+                       mode == CATAN_RECORD_NOW ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return CATAN_OK;
+}
+int catan_record_status(catan_env_t* e, uint32_t* out_host, catan_stream_t stream) {
+    if (!e || !out_host) return fail(CATAN_EINVAL, "catan_record_status: null argument");
+    if (!e->rec_on) return fail(CATAN_EINVAL, "catan_record_status: recording is not enabled on this handle (catan_record_enable)");
+    NOT_DEFERRED(e, "catan_record_status");           // (the side streams of an open sequence are joined by catan_step_flush)
+    std::vector<u32> hdr;
+    OK_OR_RETURN(record_headers(e, hdr, S(stream)));
+    memcpy(out_host, hdr.data(), hdr.size() * sizeof(u32));
+    return CATAN_OK;
+}
+int catan_record_read(catan_env_t* e, int32_t slot, int32_t* start_blob, int32_t* final_blob, int32_t* actions, uint32_t* out_host_header, catan_stream_t stream) {
+    if (!e || !out_host_header) return fail(CATAN_EINVAL, "catan_record_read: null argument");
+    if (!e->rec_on) return fail(CATAN_EINVAL, "catan_record_read: recording is not enabled on this handle (catan_record_enable)");
+    NOT_DEFERRED(e, "catan_record_read");
+    if (slot < 0 || slot >= e->rec.m) return fail(CATAN_EINVAL, "catan_record_read: slot is outside [0, m)");
+    const hipStream_t st = S(stream);
+    std::vector<u32> hdr;
+    OK_OR_RETURN(record_headers(e, hdr, st));
+    const u32* h = hdr.data() + (size_t)slot * RECORD_HDR_WORDS;
+    memcpy(out_host_header, h, RECORD_HDR_WORDS * sizeof(u32));
+    if (h[REC_H_STATE] != REC_SEALED && h[REC_H_STATE] != REC_RECORDING)
+        return fail(CATAN_EINVAL, "catan_record_read: slot " + std::to_string(slot) + " is neither SEALED nor RECORDING");
+    const size_t rows = h[REC_H_LENGTH] < (u32)e->rec.capacity ? h[REC_H_LENGTH] : (u32)e->rec.capacity;
+    std::vector<short> log(rows * ACTION_WORDS);
+    if (start_blob) HIPCHK(hipMemcpyAsync(start_blob, e->rec.start + (size_t)slot * STATE_WORDS, STATE_WORDS * sizeof(i32), hipMemcpyDeviceToHost, st));
+    if (final_blob && h[REC_H_STATE] == REC_SEALED)
+        HIPCHK(hipMemcpyAsync(final_blob, e->rec.fin + (size_t)slot * STATE_WORDS, STATE_WORDS * sizeof(i32), hipMemcpyDeviceToHost, st));
+    if (actions && rows) HIPCHK(hipMemcpyAsync(log.data(), e->rec.log + (size_t)slot * e->rec.log_stride, log.size() * sizeof(short), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (actions) for (size_t i = 0; i < log.size(); i++) actions[i] = (int32_t)log[i];
+    return CATAN_OK;
+}
+
 }  // extern "C"
+
+// Game records (catan_record_enable).  Seal: at the hook of the finished-game statistics, the listed games' records are still the final states.
+// Open: behind the list's consumer, on the same stream, the listed games are freshly dealt.  Off (the default): nothing is launched.
+static void enqueue_record_seal(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!e->rec_on) return;
+    hipLaunchKernelGGL(k_record_seal<>, dim3(RECORD_LIST_GRID), dim3(64), 0, st, e->ctx, e->rec, count_p, list, (const u8*)nullptr, (const u8*)nullptr, (const i32*)nullptr);
+}
+static void enqueue_record_open(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!e->rec_on) return;
+    hipLaunchKernelGGL(k_record_open<>, dim3(RECORD_LIST_GRID), dim3(64), 0, st, e->ctx, e->rec, count_p, list);
+}
+// ... the append in front of the step's first kernel that reads `actions` (busy: the deferred calls' waiting games)
+static void enqueue_record_append(catan_env_t* e, const i32* actions, const u8* busy, hipStream_t st) {
+    if (!e->rec_on) return;
+    hipLaunchKernelGGL(k_record_append<>, dim3(blocks(e->rec.m, 64)), dim3(64), 0, st, e->ctx, e->rec, actions, busy);
+}
+// ... and, on a handle without auto_reset (no re-deal list is ever consumed), the seal at the end of a stepping call over its done flags
+static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* status, const i32* actions, hipStream_t st) {
+    if (!e->rec_on || e->cfg.auto_reset) return;
+    hipLaunchKernelGGL(k_record_seal<>, dim3(blocks(e->rec.m, 64)), dim3(64), 0, st, e->ctx, e->rec, (const u32*)nullptr, (const i32*)nullptr, done, status, actions);
+}

@@ -3248,11 +3248,8 @@ struct BlobW {
     i32* p; long cnt, i; int k;
     DEVI void put(int v) { p[(long)k * cnt + i] = v; k++; }
 };
-__global__ __launch_bounds__(BLOCK) void k_export(Ctx c, const long* __restrict__ idx, long cnt, i32* __restrict__ blob) {
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= cnt) return;
-    St s(c.R, c.N, idx ? idx[i] : i);
-    BlobW o{ blob, cnt, i, 0 };
+// one game's blob (k_export; the recorder's snapshots, catan_record.hip, with cnt = 1)
+DEVI void export_game(const St& s, BlobW o) {
     for (int t = 0; t < 19; t++) o.put(s.b(B_TILE + t) & 15);
     for (int t = 0; t < 19; t++) o.put(s.b(B_TILE + t) >> 4);
     o.put(s.b(B_ROBBER));
@@ -3315,6 +3312,12 @@ __global__ __launch_bounds__(BLOCK) void k_export(Ctx c, const long* __restrict_
     for (int p = 0; p < 4; p++) o.put(s.b(B_CURVP + p));
     o.put(s.b(B_WINNER));
     o.put((int)s.w(W_RNG));
+}
+__global__ __launch_bounds__(BLOCK) void k_export(Ctx c, const long* __restrict__ idx, long cnt, i32* __restrict__ blob) {
+    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= cnt) return;
+    St s(c.R, c.N, idx ? idx[i] : i);
+    export_game(s, BlobW{ blob, cnt, i, 0 });
 }
 
 struct BlobR {

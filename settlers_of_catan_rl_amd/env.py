@@ -49,6 +49,9 @@ class VecCatanEnv(object):
         self.L = _lib.lib()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.n = int(num_envs)
+        self.seed, self.env_id0 = int(seed), int(env_id0)
+        self._reward_annealing_factor = 1.0
+        self._record_slots = 0
         cfg = _lib.CatanCfg()
         self.L.catan_cfg_default(C.byref(cfg))
         cfg.max_proposed_trades_per_turn = -1 if max_proposed_trades_per_turn is None else int(max_proposed_trades_per_turn)
@@ -184,6 +187,60 @@ class VecCatanEnv(object):
         g = None if games is None else torch.as_tensor(games, device=self.device).to(torch.int32).contiguous()
         m = int(g.numel()) if g is not None else (self.n if count is None else int(count))
         _lib.check(self.L.catan_league_stats_count(self.h, _ptr(g), m, _stream()))
+
+    # ---- game records (include/catan_hip_tuning.h "game records"; record.py)
+    def _record_call(self, name):
+        if not hasattr(self.L, name):
+            raise _lib.CatanHipError(f"the loaded library has no {name}")
+        return getattr(self.L, name)
+
+    def enable_recording(self, games, capacity=8192):
+        """Binds one record slot to each game of `games` (ids, each at most once; up to 4096) with room for `capacity` actions (up to
+        65535); the slots start idle (arm_recording).  An empty list frees everything.  Until armed, and while off, a step costs nothing."""
+        g = torch.as_tensor(games, device=self.device).to(torch.int32).contiguous().reshape(-1)
+        _lib.check(self._record_call("catan_record_enable")(self.h, _ptr(g) if g.numel() else None, int(g.numel()), int(capacity), _stream()))
+        self._record_slots, self._record_capacity, self._record_cfg = int(g.numel()), int(capacity), {}
+
+    def arm_recording(self, slots=None, at_deal=False):
+        """slots (None: all): start recording now - the current state is the start blob - or, at_deal, from the game's next re-deal
+        (auto_reset envs).  Arming discards what the slot held.  The record keeps the reward annealing factor of this moment."""
+        from . import record as _record
+        arr, k = None, 0
+        if slots is not None:
+            a = np.ascontiguousarray(np.asarray(slots).reshape(-1), dtype=np.int32)
+            arr, k = a.ctypes.data_as(C.c_void_p), int(a.size)
+        _lib.check(self._record_call("catan_record_arm")(self.h, arr, k, _record.RECORD_AT_DEAL if at_deal else _record.RECORD_NOW, _stream()))
+        cfg = _record.cfg_dict(self.cfg, self._reward_annealing_factor)
+        for s in (range(self._record_slots) if slots is None else a.tolist()):
+            self._record_cfg[int(s)] = cfg
+
+    def recording_status(self):
+        """-> int64 [m, 4] (host): state (record.IDLE / WAIT_DEAL / RECORDING / SEALED), game, length, flags per slot; waits for the stream"""
+        out = np.zeros((max(self._record_slots, 1), 4), dtype=np.uint32)
+        _lib.check(self._record_call("catan_record_status")(self.h, out.ctypes.data_as(C.c_void_p), _stream()))
+        return torch.from_numpy(out[:self._record_slots].astype(np.int64))
+
+    def recordings(self, slots=None, sealed_only=True):
+        """-> list of record.GameRecord, one per sealed slot of `slots` (None: all); sealed_only=False: also the slots still recording
+        (final_blob None).  Waits for the stream."""
+        from . import record as _record
+        status = self.recording_status().numpy()
+        out = []
+        for s in (range(self._record_slots) if slots is None else [int(x) for x in np.asarray(slots).reshape(-1)]):
+            state, game, length, flags = (int(v) for v in status[s])
+            if state != _record.SEALED and (sealed_only or state != _record.RECORDING):
+                continue
+            if flags & _record.F_GUARD_BROKEN:
+                raise _lib.CatanHipError(f"record slot {s}: the guard word behind its log was overwritten")
+            rows = min(length, self._record_capacity)
+            start, fin = np.zeros(spec.STATE_WORDS, dtype=np.int32), np.zeros(spec.STATE_WORDS, dtype=np.int32)
+            acts, hdr = np.zeros((max(rows, 1), spec.ACTION_WORDS), dtype=np.int32), np.zeros(4, dtype=np.uint32)
+            vp = lambda x: x.ctypes.data_as(C.c_void_p)
+            _lib.check(self._record_call("catan_record_read")(self.h, s, vp(start), vp(fin), vp(acts), vp(hdr), _stream()))
+            assert int(hdr[0]) == state and int(hdr[2]) == length, (hdr, status[s])      # (nothing ran in between)
+            out.append(_record.GameRecord(self.seed, self.env_id0 + game, self._record_cfg[s], start, fin if state == _record.SEALED else None,
+                                          acts[:rows], length, bool(flags & _record.F_TRUNCATED), bool(flags & _record.F_FROM_DEAL)))
+        return out
 
     def close(self):
         if getattr(self, "h", None):
@@ -434,6 +491,7 @@ class VecCatanEnv(object):
 
     def set_reward_annealing_factor(self, f):
         _lib.check(self.L.catan_set_reward_annealing(self.h, float(f)))
+        self._reward_annealing_factor = float(f)
 
 
 class _GameView(object):

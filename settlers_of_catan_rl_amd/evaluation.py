@@ -42,7 +42,7 @@ def _stats_of(res, rows, dev):
 
 @torch.no_grad()
 def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=False, generator=None, autocast_dtype=None,
-                            act_fn=None, assignment=None, stats=False, detailed=False, searchers=None):
+                            act_fn=None, assignment=None, stats=False, detailed=False, searchers=None, record=None):
     """env: freshly reset games, auto_reset off.  nets: the policies (entries may be the same object; equal objects share a
     forward); without `assignment` four of them, policy i = nets[i] in every game.  assignment int [n,4] (optional): game g's
     policy i is nets[assignment[g][i]] (the offline evaluator's opponents drawn per game).  orders int [n,4].  max_steps: the
@@ -60,8 +60,14 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
     no initial settlement, or one settlement and one road (:85-88).  A searched decision of policy 0 counts as a decision and its
     action type is tallied; its entropy, log-prob and value are 0.0 (:94-96).  LSTM nets: the planner gets all four seats' states of
     its games and returns its own next state (:90-93,108); `searcher.zero_opponent_hidden_states` and `searcher.max_thinking_time`
-    (attributes, optional) are passed on."""
+    (attributes, optional) are passed on.
+    record=k: games 0..k-1 are recorded from their reset (VecCatanEnv.enable_recording / arm_recording) and returned as "records", a list
+    of record.GameRecord in game order (a game stopped by max_steps has no final blob); the env's recorder is switched off again.
+    None: no such key."""
     n, dev = env.n, env.device
+    if record:
+        env.enable_recording(list(range(int(record))))
+        env.arm_recording()
     orders_t = torch.as_tensor(orders, device=dev).long()
     policy_of_pid = torch.empty((n, 4), dtype=torch.long, device=dev)
     policy_of_pid.scatter_(1, orders_t - 1, torch.arange(4, device=dev).expand(n, 4))
@@ -199,6 +205,9 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
            "policy_decisions": decisions.cpu().numpy()}
     if stats:
         out.update(_stats_result(decisions, ent_sum, val_sum, type_counts, trace_typ, trace_lp, trace_rec, trace_act, detailed))
+    if record:
+        out["records"] = env.recordings(sealed_only=False)
+        env.enable_recording([])
     return out
 
 
@@ -245,6 +254,8 @@ def run_evaluation_protocol(make_env, central_policy, opponent_policy, num_eval_
     res = run_evaluation_episodes(env, [central_policy, opponent_policy, opponent_policy, opponent_policy],
                                   sample_orders(num_eval_episodes, rng), **kw)
     log = {"update": update_num, "random": _protocol_entry(res)}
+    if "records" in res:                  # run_evaluation_episodes(record=k): per opponent, under the opponent's name
+        log["records"] = {"random": res["records"]}
     summary = ("\n\n---------------------- EVALUATION (after {} updates) ----------------------\n".format(update_num)
                + _protocol_paragraph("random", num_eval_episodes, res, log["random"]))
     for name, base in (baselines or {}).items():
@@ -256,17 +267,19 @@ def run_evaluation_protocol(make_env, central_policy, opponent_policy, num_eval_
             base.rebind(env)
         res = run_evaluation_episodes(env, [central_policy, base, base, base], sample_orders(num_eval_episodes, rng), **kw)
         log[name] = _protocol_entry(res)
+        if "records" in res:
+            log["records"][name] = res["records"]
         summary += _protocol_paragraph(name, num_eval_episodes, res, log[name])
     return log, summary
 
 
 def run_forward_search_evaluation(planner, other_policies, num_games, make_env=None, make_sim_env=None, seed=10, deterministic=False,
-                                  out_file="forward_policy_evaluation.pt", max_steps=2500, autocast_dtype=None):
+                                  out_file="forward_policy_evaluation.pt", max_steps=2500, autocast_dtype=None, record=None):
     """evaluation/run_forward_search_evaluation.py: policy 0 is the planner (`reference_api.ForwardSearchPolicy`), the other
     three seats are the nets `other_policies`; all num_games games run at once.  make_env(n) -> n freshly reset games without
     auto-reset (default: VecCatanEnv on the planner's device).  Prints the fraction of games the planner won and saves the
     reference's tuple (winners, game steps, victory points, planner decisions, sorted action-type counts) to out_file
-    (None: not saved).  -> the dict of run_evaluation_episodes(stats=True)."""
+    (None: not saved).  record=k: the first k games are recorded (run_evaluation_episodes).  -> the dict of run_evaluation_episodes(stats=True)."""
     if make_env is None:
         from .env import VecCatanEnv
         make_env = lambda n: VecCatanEnv(n, seed=seed, auto_reset=False, device=planner._device)  # noqa: E731
@@ -274,7 +287,7 @@ def run_forward_search_evaluation(planner, other_policies, num_games, make_env=N
     searcher = planner.make_searcher(num_games, make_sim_env)
     res = run_evaluation_episodes(env, [planner.base_policy] + list(other_policies), sample_orders(num_games, _py_random.Random(seed)),
                                   max_steps=max_steps, deterministic=deterministic, autocast_dtype=autocast_dtype, stats=True,
-                                  searchers={0: searcher})
+                                  searchers={0: searcher}, record=record)
     print("{} games finished. Fraction of games won by forward search: {}".format(num_games, float(np.mean(res["winner"] == 0))))
     if out_file is not None:
         counts = res["action_types"].sum(0)

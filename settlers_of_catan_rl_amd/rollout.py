@@ -46,6 +46,7 @@ class RolloutStorage(object):
         self.games_complete = 0
         self.episode_stats = None     # RolloutCollector(episode_stats=True): the finished games of the last gather_rollouts (env.episode_stats)
         self.league_stats = None      # RolloutCollector(league_stats=True): their results per opponent net, int64 [nets + 1, 6] (env.league_stats)
+        self.records = None           # RolloutCollector(record_games=k): the games of the k record slots that ended in the last gather_rollouts (record.GameRecord)
         self.generation = 0           # bumped by every gather_rollouts (consumers cache per-rollout derived data on it)
 
     def unpack_action_masks(self, packed):
@@ -136,7 +137,7 @@ class RolloutCollector(object):
     GRAPH_ACT_MIN_GAMES = 8192
 
     def __init__(self, env, policy, num_steps, opponents=None, seed=0, autocast_dtype=None, graph_act=None, deferred_window=None, act_buckets=None,
-                 episode_stats=False, league_stats=False):
+                 episode_stats=False, league_stats=False, record_games=0):
         """policy: central net (policy 0); opponents: list of up to 3 nets for policy slots 1..3 of every game (None =
         every seat plays the central policy).  A league (league.League.assign) installs per-game opponents instead.  An opponent
         may be a `scripted.ScriptedPolicy(env)` bound to this env: a fixed anchor beside the nets (its rows' log-probs are 0 and,
@@ -153,7 +154,10 @@ class RolloutCollector(object):
         league_stats: the env also counts, per opponent net, who won the finished games (VecCatanEnv.enable_league_stats with this
         collector's seat map and the opponent indices of set_opponents, which re-enables it - between rollouts, behind the read); every
         gather_rollouts leaves the table, a row per net in the order of set_opponents' `nets` and a totals row, in storage.league_stats
-        (None while no opponent is installed).  The same single read after the loop."""
+        (None while no opponent is installed).  The same single read after the loop.
+        record_games: games 0..k-1 are recorded whole, each from its next deal (VecCatanEnv.enable_recording / arm_recording(at_deal=True));
+        every gather_rollouts leaves the games that ended during it in storage.records (record.GameRecord: replay, describe) and arms
+        their slots again.  Read after the loop, like the statistics; the env needs auto_reset."""
         self.env, self.policy, self.T = env, policy, num_steps
         self.league_stats, self.policy_of_pid = bool(league_stats), None
         self.deferred_window = self.DEFAULT_DEFERRED_WINDOW if deferred_window is None else int(deferred_window)
@@ -198,6 +202,10 @@ class RolloutCollector(object):
         if self.episode_stats:
             env.enable_episode_stats(self.active_pid)
         self._enable_league_stats()
+        self.record_games = int(record_games)
+        if self.record_games:
+            env.enable_recording(list(range(self.record_games)))
+            env.arm_recording(at_deal=True)
         self.reset()
 
     def set_opponents(self, nets, opp_index):
@@ -321,6 +329,12 @@ class RolloutCollector(object):
                 st.episode_stats = env.episode_stats(reset=True)
             if self.league_stats:
                 st.league_stats = env.league_stats(reset=True) if self._league_on else None
+            if self.record_games:
+                from . import record as _record
+                sealed = (env.recording_status()[:, 0] == _record.SEALED).nonzero(as_tuple=True)[0].tolist()
+                st.records = env.recordings(slots=sealed) if sealed else []
+                if sealed:
+                    env.arm_recording(slots=sealed, at_deal=True)
             st.generation += 1
             self.iters = int(n_live_iters) if max_iters is None else iters
             return st

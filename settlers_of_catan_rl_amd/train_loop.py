@@ -140,6 +140,8 @@ class TrainingLoop(object):
                "hours": (time.time() - self.start_time) / 3600.0, "eval": summary}
         if getattr(st, "episode_stats", None) is not None:       # RolloutCollector(episode_stats=True): the games this rollout finished
             out["episodes"] = st.episode_stats
+        if getattr(st, "records", None) is not None:             # RolloutCollector(record_games=k): the recorded games this rollout ended
+            out["records"] = st.records
         if league_out is not None:                               # RolloutCollector(league_stats=True): the scoreboard per snapshot
             out["league"] = league_out
         if getattr(self.trainer, "diagnostics", None) is not None:   # PPOConfig(diagnostics=True): what the clipped objective did in this update
