@@ -171,6 +171,43 @@ int catan_record_status(catan_env_t* env, uint32_t* out_host, catan_stream_t str
 int catan_record_read(catan_env_t* env, int32_t slot, int32_t* start_blob, int32_t* final_blob, int32_t* actions, uint32_t* out_host_header,
                       catan_stream_t stream);
 
+/* ---- start pool ----
+ * Re-dealt games started from a pool of saved positions instead of a fresh deal (csrc/catan_start_pool.hip).  With no
+ * pool installed, the default, not one kernel more is launched and no existing kernel's code differs.
+ * catan_start_pool_set: blobs is a DEVICE int32 [736][m] (the orientation of catan_state_import), 1 <= m <= 65 536; the call keeps its own
+ *   copy in the handle's packed form - per entry the record (704 bytes) and the position's mask words under the handle's limits (48
+ *   bytes): m x (704 + 48) bytes of device memory plus (2 + m) x 8 bytes of counters (47.5 MiB at m = 65 536) - so blobs may be freed when
+ *   the call returns.  fresh_q16 in 0..65 536 is the share of deals that stay fresh, in 1/65 536ths.  The finished-position check runs on the
+ *   device and synchronises the stream once; a second set replaces the pool and zeroes the counters (and then synchronises the handle's
+ *   streams).  A call that fails leaves a previously installed pool as it was.
+ * catan_start_pool_clear: from here on every deal is fresh again, draw for draw as on a handle that never had a pool.
+ * catan_start_pool_read: out_host is a HOST uint64 [2 + m]: [0] deals that took a pool position, [1] deals that stayed fresh while the pool
+ *   was installed, [2 + k] installs of entry k; integer sums.  reset != 0 zeroes them behind the copy.  It synchronises the stream.
+ * catan_start_pool_size: m of the installed pool, 0 without one, -1 for a null handle.
+ * The install.  Every re-deal (auto_reset = 1: inside catan_step, catan_random_rollout, catan_step_deferred / catan_step_flush) and every
+ * game catan_reset deals is first dealt exactly as without a pool - the deal consumes its draws - and then, with d the game's draw counter
+ * as the deal left it, id its global id (env_id0 + game) and seed the handle's:
+ *   o = philox4x32_10(counter = (d, 0x504F4F4C, lo32(id), hi32(id)), key = (lo32(seed), hi32(seed)))
+ *   (o[1] >> 16) < fresh_q16: the fresh deal stays.  Otherwise entry k = (o[0] * m) >> 32 is installed.
+ * The game's own draws use counter word 1 = 0 and the random policy's word 1 = 1, so the block is disjoint from both and no draw is
+ * consumed.  After an install catan_state_export of the game equals pool blob k with rng_draws replaced by d: the same position in two
+ * games rolls different dice.  The pick depends on (seed, id, d) alone, so lock-step and deferred schedules of any window pick alike.
+ * catan_create's own deal precedes any pool; catan_reset_board_only never installs.
+ * Interplay.  A board-layout table (catan_set_board_configs) shapes only the deals that stay fresh: a pool position carries its own
+ * board.  The finished-game statistics and the league scoreboard count a pool-started game like any other; its `turns` include the turns
+ * the position already had.  A record armed CATAN_RECORD_AT_DEAL takes the installed position as its start blob.  The fresh deal under an
+ * install still consumes its draws, deliberately: d and everything behind it are the same whether the deal stayed or not.
+ * CATAN_EINVAL, nothing installed or changed: a null handle or null blobs (what catan_state_import refuses); m or fresh_q16 out of range; an
+ * open deferred sequence (set, clear and read); a handle under the MT19937 contract; a blob of a finished game (winner != 0); read without
+ * a pool.
+ * Not supported: handles under the MT19937 contract, and - while a pool is installed - catan_random_rollout_deferred in both of its forms
+ * and the deferred form of catan_random_rollout_timed, which return CATAN_EINVAL: there the re-deal kernel draws the fresh game's first
+ * action and its place in the next pass's lists from the state the install would then replace. */
+int catan_start_pool_set(catan_env_t* env, const int32_t* blobs, int32_t m, int32_t fresh_q16, catan_stream_t stream);
+int catan_start_pool_clear(catan_env_t* env, catan_stream_t stream);
+int catan_start_pool_read(catan_env_t* env, uint64_t* out_host, int32_t reset, catan_stream_t stream);
+int32_t catan_start_pool_size(const catan_env_t* env);
+
 /* ---- rule-based player ----
  * The "builder" bot (csrc/catan_scripted.hip): a deterministic scripted policy - the same state always gives the same
  * action, every action is legal under the game's masks, it never proposes a trade - decided by one lane-per-game kernel.  It decides for

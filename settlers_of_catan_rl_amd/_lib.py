@@ -319,12 +319,17 @@ _SIGS = {
     "catan_record_arm": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
     "catan_record_status": (C.c_int, [_vp, _vp, _vp]),
     "catan_record_read": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "catan_start_pool_set": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
+    "catan_start_pool_clear": (C.c_int, [_vp, _vp]),
+    "catan_start_pool_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, _vp]),
+    "catan_start_pool_size": (C.c_int32, [_vp]),
 }
 # bound only where the library exports them: the same callers also load oracle/libcatan_cpu.so, which implements the env ABI
 # without these
 _OPTIONAL = {"catan_set_board_configs", "catan_episode_stats_words", "catan_episode_stats_enable", "catan_episode_stats_read",
              "catan_league_stats_words", "catan_league_stats_enable", "catan_league_stats_read", "catan_league_stats_count",
-             "catan_record_enable", "catan_record_arm", "catan_record_status", "catan_record_read"}
+             "catan_record_enable", "catan_record_arm", "catan_record_status", "catan_record_read",
+             "catan_start_pool_set", "catan_start_pool_clear", "catan_start_pool_read", "catan_start_pool_size"}
 
 
 def declared_symbols():

@@ -26,6 +26,7 @@
 #include "catan_scripted.hip"
 #include "catan_league_stats.hip"
 #include "catan_record.hip"
+#include "catan_start_pool.hip"
 
 using namespace catan;
 
@@ -100,6 +101,8 @@ struct catan_env {
     unsigned long long* script_fallback;   // catan_sample_scripted_actions: decisions taken by the fall-back row (catan_scripted.hip), allocated at the first call
     RecordBuf rec;               // catan_record_enable: the recorder's slots (catan_record.hip); not in `owned`: freed and re-made by every enable
     int rec_on;
+    StartPoolBuf pool;           // catan_start_pool_set: the saved positions (catan_start_pool.hip); not in `owned`: freed and re-made by every set
+    int pool_on;
 };
 static_assert(sizeof(BoardCfg) == sizeof(catan_board_cfg_t) && sizeof(catan_board_cfg_t) == 56 &&
               offsetof(BoardCfg, terrain) == offsetof(catan_board_cfg_t, terrain) &&
@@ -420,6 +423,10 @@ static void enqueue_record_seal(catan_env_t* e, const u32* count_p, const i32* l
 static void enqueue_record_open(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
 static void enqueue_record_append(catan_env_t* e, const i32* actions, const u8* busy, hipStream_t st);
 static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* status, const i32* actions, hipStream_t st);
+// Start pool (catan_start_pool_set; defined at the end of this file): directly behind the consumer of a re-deal list, same stream, same list, in
+// front of enqueue_record_open and of the event that publishes the re-deal.  No pool installed (the default): nothing is launched.
+static void enqueue_start_pool(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
+static void enqueue_start_pool_sel(catan_env_t* e, const u8* sel, hipStream_t st);
 // k_step with G games per wave in one-wave workgroups; pend.sample (fused-sampling rollouts): actions from / to the side rows
 template <int G>
 static void launch_step(catan_env_t* e, const int32_t* actions, float* reward, uint8_t* done, hipStream_t st, const StepCfg& sc, const u32* bins) {
@@ -546,6 +553,7 @@ int catan_create(catan_env_t** out, int device, int64_t n_envs, uint64_t seed, u
 }
 
 static void record_free(catan_env_t* e);
+static void start_pool_free(catan_env_t* e);
 void catan_destroy(catan_env_t* e) {
     if (!e) return;
     hipSetDevice(e->device);
@@ -555,6 +563,7 @@ void catan_destroy(catan_env_t* e) {
     if (e->bcfg_idx_dev) hipFree(e->bcfg_idx_dev);
     if (e->lstats) hipFree(e->lstats);
     record_free(e);
+    start_pool_free(e);
     for (hipStream_t st : { e->fstream, e->sstream, e->side }) if (st) hipStreamDestroy(st);
     for (hipEvent_t ev : { e->ev_fready[0], e->ev_fready[1], e->ev_fready[2], e->ev_fdone[0], e->ev_fdone[1], e->ev_fdone[2], e->ev_sdone[0], e->ev_sdone[1],
                            e->ev_fork, e->ev_join })
@@ -579,7 +588,11 @@ int catan_reset(catan_env_t* e, const uint8_t* reset_mask, catan_stream_t stream
     if (r != CATAN_OK) return r;
     hipLaunchKernelGGL(k_reset, dim3((unsigned)(e->N < 16384 ? e->N : 16384)), dim3(64), 0, S(stream), e->ctx, reset_mask, 0);
     HIPCHK(hipGetLastError());
-    return launch_masks(e, S(stream));
+    r = launch_masks(e, S(stream));
+    if (r != CATAN_OK) return r;
+    enqueue_start_pool_sel(e, reset_mask, S(stream));            // (behind the masks of the fresh deals: an installed game takes its entry's)
+    HIPCHK(hipGetLastError());
+    return CATAN_OK;
 }
 int catan_reset_board_only(catan_env_t* e, catan_stream_t stream) {
     if (!e) return fail(CATAN_EINVAL, "catan_reset_board_only: null handle");
@@ -807,6 +820,7 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             enqueue_record_seal(e, sctr + 1, e->pend.resets[sa][0], e->side);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 1),
                                (const i32*)e->pend.resets[sa][0], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
+            enqueue_start_pool(e, sctr + 1, e->pend.resets[sa][0], e->side);
             enqueue_record_open(e, sctr + 1, e->pend.resets[sa][0], e->side);
             HIPCHK(hipEventRecord(e->ev_join, e->side));
         }
@@ -832,12 +846,14 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             enqueue_record_seal(e, sctr + 3, e->pend.resets[sa][2], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 3), (const i32*)e->pend.resets[sa][2], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
+            enqueue_start_pool(e, sctr + 3, e->pend.resets[sa][2], st);
             enqueue_record_open(e, sctr + 3, e->pend.resets[sa][2], st);
             enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_league_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_record_seal(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2), (const i32*)e->pend.resets[sa][1], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
+            enqueue_start_pool(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_record_open(e, sctr + 2, e->pend.resets[sa][1], st);
         } else {
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));
@@ -846,6 +862,7 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             enqueue_record_seal(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2),
                                (const i32*)e->pend.resets[sa][1], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
+            enqueue_start_pool(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_record_open(e, sctr + 2, e->pend.resets[sa][1], st);
         }
     }
@@ -881,6 +898,7 @@ static int step_impl(catan_env_t* e, int32_t* actions, float* reward, uint8_t* d
         hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, limits_of(e),
                            (const u32*)(e->pend.ctr + 8 + 1), (const i32*)e->pend.resets[0][0], e->pend.busy, step_cfg(e).prof,
                            (const u32*)(e->pend.ctr + 6), (const u64*)e->pend.spec, e->spec_state, e->spec_mpk, e->spec_epoch, e->pend);
+        enqueue_start_pool(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
         enqueue_record_open(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
         HIPCHK(hipEventRecord(e->ev_join, e->side));
     }
@@ -1093,6 +1111,8 @@ int catan_league_stats_count(catan_env_t* e, const int32_t* games, int64_t m, ca
 }
 
 static int record_not_armed(catan_env_t* e, const char* what, hipStream_t st);      // (game records: at the end of this file)
+// the fused deferred rollout draws a fresh game's first action inside the re-deal kernel, from the state an install would then replace
+#define NO_START_POOL(e, what) do { if ((e)->pool_on) return fail(CATAN_EINVAL, std::string(what) + ": a start pool is installed (catan_start_pool_clear first)"); } while (0)
 
 // ---- the rule-based player (catan_scripted.hip)
 int catan_sample_scripted_actions(catan_env_t* e, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
@@ -1311,6 +1331,7 @@ int catan_random_rollout_deferred(catan_env_t* e, int64_t iters, int32_t window,
     NOT_DEFERRED(e, "catan_random_rollout_deferred");
     NOT_MT(e, "catan_random_rollout_deferred");
     OK_OR_RETURN(record_not_armed(e, "catan_random_rollout_deferred", S(stream)));
+    NO_START_POOL(e, "catan_random_rollout_deferred");
     for (int64_t it = 0; it < iters; it++) {
         int r = deferred_iter(e, it, iters, window, S(stream), nullptr);
         if (r != CATAN_OK) return r;
@@ -1440,6 +1461,7 @@ int catan_random_rollout_timed(catan_env_t* e, uint32_t step_idx0, int64_t steps
     if (!e || steps <= 0 || !kernel_ms) return fail(CATAN_EINVAL, "catan_random_rollout_timed: bad arguments");
     if (window > 0) NOT_MT(e, "catan_random_rollout_timed (deferred)");
     if (window > 0) OK_OR_RETURN(record_not_armed(e, "catan_random_rollout_timed (deferred)", S(stream)));
+    if (window > 0) NO_START_POOL(e, "catan_random_rollout_timed (deferred)");
     hipStream_t st = S(stream);
     const int K = EV_PER_STEP;             // see enqueue_fast / enqueue_tier1 / enqueue_slow; [5] = before the sampler
     std::vector<hipEvent_t> ev((size_t)steps * K);
@@ -2334,4 +2356,102 @@ static void enqueue_record_append(catan_env_t* e, const i32* actions, const u8* 
 static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* status, const i32* actions, hipStream_t st) {
     if (!e->rec_on || e->cfg.auto_reset) return;
     hipLaunchKernelGGL(k_record_seal<>, dim3(blocks(e->rec.m, 64)), dim3(64), 0, st, e->ctx, e->rec, (const u32*)nullptr, (const i32*)nullptr, done, status, actions);
+}
+
+// ---- start pool (catan_start_pool.hip).  As for the recorder above: the kernels are templates first used here, behind everything else, so their
+// code follows every other kernel's in the code object and the existing kernels keep their code and their places.
+static void start_pool_free(catan_env_t* e) {
+    for (void* p : { (void*)e->pool.rec, (void*)e->pool.mask, (void*)e->pool.cnt })
+        if (p) hipFree(p);
+    e->pool = StartPoolBuf{};
+    e->pool_on = 0;
+}
+// a pool in use may still be read (and counted into) by installs in flight on any of the handle's streams
+static int start_pool_quiesce(catan_env_t* e, hipStream_t st) {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(e->side));
+    HIPCHK(hipStreamSynchronize(e->fstream));
+    HIPCHK(hipStreamSynchronize(e->sstream));
+    return CATAN_OK;
+}
+extern "C" {
+
+int catan_start_pool_set(catan_env_t* e, const int32_t* blobs, int32_t m, int32_t fresh_q16, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_start_pool_set: null handle");
+    NOT_DEFERRED(e, "catan_start_pool_set");
+    NOT_MT(e, "catan_start_pool_set");
+    if (m < 1 || m > POOL_MAX_ENTRIES) return fail(CATAN_EINVAL, "catan_start_pool_set: m must be in 1..65536");
+    if (fresh_q16 < 0 || fresh_q16 > (int32_t)POOL_Q16_ONE) return fail(CATAN_EINVAL, "catan_start_pool_set: fresh_q16 must be in 0..65536");
+    if (!blobs) return fail(CATAN_EINVAL, "catan_start_pool_set: null blobs");
+    const hipStream_t st = S(stream);
+    // the new pool is built beside the one in use, which stays installed if this call fails
+    StartPoolBuf pb{};
+    pb.m = m; pb.fresh_q16 = (u32)fresh_q16;
+    u32* bad = nullptr;
+    hipError_t rc = hipMalloc((void**)&pb.rec, (size_t)m * REC * sizeof(u32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&pb.mask, (size_t)m * POOL_MASK_STRIDE * sizeof(u32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&pb.cnt, (size_t)(2 + m) * sizeof(unsigned long long));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&bad, sizeof(u32));
+    auto drop = [&]() { for (void* p : { (void*)pb.rec, (void*)pb.mask, (void*)pb.cnt, (void*)bad }) if (p) hipFree(p); };
+    if (rc != hipSuccess) { drop(); return fail(CATAN_ENOMEM, std::string("catan_start_pool_set: hipMalloc: ") + hipGetErrorString(rc)); }
+    rc = hipMemsetAsync(pb.rec, 0, (size_t)m * REC * sizeof(u32), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(pb.cnt, 0, (size_t)(2 + m) * sizeof(unsigned long long), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(bad, 0, sizeof(u32), st);
+    if (rc == hipSuccess) {
+        // k_import itself, on the pool's records as a handle of m games: an entry's record is what catan_state_import makes of its blob
+        Ctx pc = e->ctx;
+        pc.R = pb.rec; pc.N = m; pc.n = m; pc.mt = nullptr; pc.bcfg = nullptr; pc.bcfg_idx = nullptr;
+        hipLaunchKernelGGL(k_import, dim3(blocks(m, BLOCK)), dim3(BLOCK), 0, st, pc, (const long*)nullptr, (long)m, blobs);
+        hipLaunchKernelGGL(k_pool_masks<>, dim3(blocks(m, BLOCK)), dim3(BLOCK), 0, st, pb, limits_of(e), bad);
+        rc = hipGetLastError();
+    }
+    u32 nbad = 0;
+    if (rc == hipSuccess) rc = hipMemcpyAsync(&nbad, bad, sizeof(u32), hipMemcpyDeviceToHost, st);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(st);
+    if (rc != hipSuccess || nbad != 0) {
+        drop();
+        if (rc != hipSuccess) return fail(CATAN_EHIP, std::string("catan_start_pool_set: ") + hipGetErrorString(rc));
+        return fail(CATAN_EINVAL, "catan_start_pool_set: " + std::to_string(nbad) + " blobs are positions of finished games (winner != 0)");
+    }
+    hipFree(bad);
+    bad = nullptr;
+    if (e->pool_on) {
+        const int r = start_pool_quiesce(e, st);
+        if (r != CATAN_OK) { drop(); return r; }
+    }
+    start_pool_free(e);
+    e->pool = pb;
+    e->pool_on = 1;
+    return CATAN_OK;
+}
+int catan_start_pool_clear(catan_env_t* e, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_start_pool_clear: null handle");
+    NOT_DEFERRED(e, "catan_start_pool_clear");
+    if (!e->pool_on) return CATAN_OK;
+    OK_OR_RETURN(start_pool_quiesce(e, S(stream)));
+    start_pool_free(e);
+    return CATAN_OK;
+}
+int32_t catan_start_pool_size(const catan_env_t* e) { return e ? (e->pool_on ? e->pool.m : 0) : -1; }
+int catan_start_pool_read(catan_env_t* e, uint64_t* out_host, int32_t reset, catan_stream_t stream) {
+    if (!e || !out_host) return fail(CATAN_EINVAL, "catan_start_pool_read: null argument");
+    if (!e->pool_on) return fail(CATAN_EINVAL, "catan_start_pool_read: no start pool is installed on this handle (catan_start_pool_set)");
+    NOT_DEFERRED(e, "catan_start_pool_read");          // (the side streams of an open sequence are joined by catan_step_flush)
+    const hipStream_t st = S(stream);
+    const size_t bytes = (size_t)(2 + e->pool.m) * sizeof(unsigned long long);
+    HIPCHK(hipMemcpyAsync(out_host, e->pool.cnt, bytes, hipMemcpyDeviceToHost, st));
+    if (reset) HIPCHK(hipMemsetAsync(e->pool.cnt, 0, bytes, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return CATAN_OK;
+}
+
+}  // extern "C"
+
+static void enqueue_start_pool(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!e->pool_on) return;
+    hipLaunchKernelGGL(k_pool_install_list<>, dim3(POOL_LIST_GRID), dim3(64), 0, st, e->ctx, e->mpk, e->pool, count_p, list);
+}
+static void enqueue_start_pool_sel(catan_env_t* e, const u8* sel, hipStream_t st) {
+    if (!e->pool_on) return;
+    hipLaunchKernelGGL(k_pool_install_sel<>, dim3((unsigned)(e->n < 4096 ? e->n : 4096)), dim3(64), 0, st, e->ctx, e->mpk, e->pool, sel);
 }

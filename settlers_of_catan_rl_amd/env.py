@@ -242,6 +242,43 @@ class VecCatanEnv(object):
                                           acts[:rows], length, bool(flags & _record.F_TRUNCATED), bool(flags & _record.F_FROM_DEAL)))
         return out
 
+    # ---- start pool (include/catan_hip_tuning.h "start pool"; start_pool.py)
+    def _start_pool_call(self, name):
+        if not hasattr(self.L, name):
+            raise _lib.CatanHipError(f"the loaded library has no {name}")
+        return getattr(self.L, name)
+
+    def set_start_pool(self, blobs, fresh_share=0.0):
+        """From now on a game that is re-dealt (auto_reset) or dealt by reset() starts from one of `blobs` - [m, 736], numpy or tensor, the
+        orientation of export_state, up to 65536 unfinished positions - except for the share `fresh_share` of deals, which stay fresh.
+        The game keeps its own draw counter: the same position in two games rolls different dice.  The env keeps its own copy; the
+        counters (start_pool_counts) start at zero.  A second call replaces the pool."""
+        fn = self._start_pool_call("catan_start_pool_set")
+        share = float(fresh_share)
+        if not 0.0 <= share <= 1.0:                      # (also refuses nan)
+            raise ValueError(f"fresh_share must be in [0, 1], got {fresh_share}")
+        b = blobs if torch.is_tensor(blobs) else torch.from_numpy(np.array(blobs, dtype=np.int32))      # (a copy: the source may be read-only)
+        b = b.to(device=self.device, dtype=torch.int32)
+        if b.dim() == 1:
+            b = b[None]
+        if b.dim() != 2 or b.shape[1] != spec.STATE_WORDS:
+            raise ValueError(f"start pool blobs: shape [m, {spec.STATE_WORDS}] expected, got {tuple(b.shape)}")
+        bt = b.t().contiguous()
+        _lib.check(fn(self.h, _ptr(bt) if bt.numel() else None, int(b.shape[0]), int(round(share * 65536)), _stream()))
+
+    def clear_start_pool(self):
+        """every later deal is fresh again, draw for draw as on an env that never had a pool"""
+        _lib.check(self._start_pool_call("catan_start_pool_clear")(self.h, _stream()))
+
+    def start_pool_counts(self, reset=False):
+        """-> {"pool": deals that took a pool position, "fresh": deals that stayed fresh while the pool was installed, "per_entry": int64 [m]
+        installs of each entry} since set_start_pool (or the last read with reset=True); waits for the current stream"""
+        fn = self._start_pool_call("catan_start_pool_read")
+        m = max(int(self._start_pool_call("catan_start_pool_size")(self.h)), 0)
+        out = np.zeros(2 + m, dtype=np.uint64)
+        _lib.check(fn(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), int(bool(reset)), _stream()))
+        return {"pool": int(out[0]), "fresh": int(out[1]), "per_entry": out[2:].astype(np.int64)}
+
     def close(self):
         if getattr(self, "h", None):
             self.L.catan_destroy(self.h)

@@ -42,7 +42,8 @@ def _stats_of(res, rows, dev):
 
 @torch.no_grad()
 def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=False, generator=None, autocast_dtype=None,
-                            act_fn=None, assignment=None, stats=False, detailed=False, searchers=None, record=None):
+                            act_fn=None, assignment=None, stats=False, detailed=False, searchers=None, record=None,
+                            start_blobs=None):
     """env: freshly reset games, auto_reset off.  nets: the policies (entries may be the same object; equal objects share a
     forward); without `assignment` four of them, policy i = nets[i] in every game.  assignment int [n,4] (optional): game g's
     policy i is nets[assignment[g][i]] (the offline evaluator's opponents drawn per game).  orders int [n,4].  max_steps: the
@@ -63,8 +64,19 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
     (attributes, optional) are passed on.
     record=k: games 0..k-1 are recorded from their reset (VecCatanEnv.enable_recording / arm_recording) and returned as "records", a list
     of record.GameRecord in game order (a game stopped by max_steps has no final blob); the env's recorder is switched off again.
-    None: no such key."""
+    None: no such key.
+    start_blobs [m, 736] (numpy, tensor or a start_pool.StartPool): game g starts from start_blobs[g % m] instead of its
+    deal, by env.import_state - no kernel of its own, the env runs without auto-reset.  An imported blob brings its own draw counter:
+    two runs on envs with the same seed and the same blobs see the same dice for as long as the same actions are played, which is what
+    makes a comparison of two policies from common positions a PAIRED one.  A record (record=k) then starts from the imported position.
+    None: nothing is imported."""
     n, dev = env.n, env.device
+    if start_blobs is not None:
+        b = getattr(start_blobs, "blobs", start_blobs)
+        b = (b.cpu() if torch.is_tensor(b) else torch.from_numpy(np.array(b, dtype=np.int32))).to(torch.int32).reshape(-1, spec.STATE_WORDS)
+        if b.shape[0] < 1:
+            raise ValueError("start_blobs: at least one position")
+        env.import_state(b[torch.arange(n) % b.shape[0]])
     if record:
         env.enable_recording(list(range(int(record))))
         env.arm_recording()

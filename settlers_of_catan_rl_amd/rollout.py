@@ -46,6 +46,7 @@ class RolloutStorage(object):
         self.games_complete = 0
         self.episode_stats = None     # RolloutCollector(episode_stats=True): the finished games of the last gather_rollouts (env.episode_stats)
         self.league_stats = None      # RolloutCollector(league_stats=True): their results per opponent net, int64 [nets + 1, 6] (env.league_stats)
+        self.start_pool = None        # RolloutCollector(start_pool=...): the deals of the last gather_rollouts, {"pool", "fresh", "per_entry"} (env.start_pool_counts)
         self.records = None           # RolloutCollector(record_games=k): the games of the k record slots that ended in the last gather_rollouts (record.GameRecord)
         self.generation = 0           # bumped by every gather_rollouts (consumers cache per-rollout derived data on it)
 
@@ -137,7 +138,7 @@ class RolloutCollector(object):
     GRAPH_ACT_MIN_GAMES = 8192
 
     def __init__(self, env, policy, num_steps, opponents=None, seed=0, autocast_dtype=None, graph_act=None, deferred_window=None, act_buckets=None,
-                 episode_stats=False, league_stats=False, record_games=0):
+                 episode_stats=False, league_stats=False, record_games=0, start_pool=None, start_pool_fresh=0.0):
         """policy: central net (policy 0); opponents: list of up to 3 nets for policy slots 1..3 of every game (None =
         every seat plays the central policy).  A league (league.League.assign) installs per-game opponents instead.  An opponent
         may be a `scripted.ScriptedPolicy(env)` bound to this env: a fixed anchor beside the nets (its rows' log-probs are 0 and,
@@ -157,7 +158,11 @@ class RolloutCollector(object):
         (None while no opponent is installed).  The same single read after the loop.
         record_games: games 0..k-1 are recorded whole, each from its next deal (VecCatanEnv.enable_recording / arm_recording(at_deal=True));
         every gather_rollouts leaves the games that ended during it in storage.records (record.GameRecord: replay, describe) and arms
-        their slots again.  Read after the loop, like the statistics; the env needs auto_reset."""
+        their slots again.  Read after the loop, like the statistics; the env needs auto_reset.
+        start_pool: saved positions (a start_pool.StartPool, or blobs [m, 736]) that the env's re-dealt games start from, except for the
+        share start_pool_fresh of deals, which stay fresh (VecCatanEnv.set_start_pool: installed here, in front of this collector's
+        reset(); the games the env holds at that moment are not touched - env.reset() deals them from the pool).  Every gather_rollouts
+        leaves the counts of its deals in storage.start_pool, read once after the loop like the statistics.  None: no call is made."""
         self.env, self.policy, self.T = env, policy, num_steps
         self.league_stats, self.policy_of_pid = bool(league_stats), None
         self.deferred_window = self.DEFAULT_DEFERRED_WINDOW if deferred_window is None else int(deferred_window)
@@ -206,6 +211,9 @@ class RolloutCollector(object):
         if self.record_games:
             env.enable_recording(list(range(self.record_games)))
             env.arm_recording(at_deal=True)
+        self.start_pool_on = start_pool is not None
+        if self.start_pool_on:
+            env.set_start_pool(getattr(start_pool, "blobs", start_pool), start_pool_fresh)
         self.reset()
 
     def set_opponents(self, nets, opp_index):
@@ -329,6 +337,8 @@ class RolloutCollector(object):
                 st.episode_stats = env.episode_stats(reset=True)
             if self.league_stats:
                 st.league_stats = env.league_stats(reset=True) if self._league_on else None
+            if self.start_pool_on:
+                st.start_pool = env.start_pool_counts(reset=True)
             if self.record_games:
                 from . import record as _record
                 sealed = (env.recording_status()[:, 0] == _record.SEALED).nonzero(as_tuple=True)[0].tolist()

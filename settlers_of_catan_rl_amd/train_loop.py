@@ -32,6 +32,8 @@ class TrainArgs(object):
     update_opponent_policies_every = 1
     eval_every = 25
     num_eval_episodes = 128
+    start_pool = None                    # opt-in: a start_pool.StartPool, blobs [m, 736] or the path of a saved pool - re-dealt games start from its positions
+    start_pool_fresh = 0.0               # ... except for this share of the deals, which stay fresh
     eval_scripted_baseline = False       # opt-in: the evaluation also plays the rule-based player (scripted.ScriptedPolicy) -> log["scripted"]
 
     def __init__(self, **kw):
@@ -88,6 +90,19 @@ class TrainingLoop(object):
         self.eval_logs = []
         self.start_time = time.time()
         trainer.cfg.entropy_coef = self.entropy_coef
+        if self.args.start_pool is not None:
+            # the pool on the env (unless the collector was built with one), then ONE reset: the first rollout's games already come from
+            # the pool at the configured share; the collector's per-game bookkeeping starts over with them
+            if not getattr(collector, "start_pool_on", False):
+                pool = self.args.start_pool
+                if isinstance(pool, str):
+                    from . import start_pool as _start_pool
+                    pool = _start_pool.load(pool)
+                env.set_start_pool(getattr(pool, "blobs", pool), self.args.start_pool_fresh)
+                collector.start_pool_on = True
+            env.reset()
+            env.start_pool_counts(reset=True)           # (the counts of a rollout are those of its own deals)
+            collector.reset()
         if league is not None:
             if len(league.earlier) == 0:
                 # a fresh start (robust_train.py:60-64): the deque gets the initial policy, and the FIRST rollout is played against
@@ -142,6 +157,9 @@ class TrainingLoop(object):
             out["episodes"] = st.episode_stats
         if getattr(st, "records", None) is not None:             # RolloutCollector(record_games=k): the recorded games this rollout ended
             out["records"] = st.records
+        if getattr(st, "start_pool", None) is not None:          # a start pool is installed: how this rollout's deals began
+            sp = st.start_pool
+            out["start_pool"] = {"pool": int(sp["pool"]), "fresh": int(sp["fresh"]), "per_entry": [int(x) for x in sp["per_entry"]]}
         if league_out is not None:                               # RolloutCollector(league_stats=True): the scoreboard per snapshot
             out["league"] = league_out
         if getattr(self.trainer, "diagnostics", None) is not None:   # PPOConfig(diagnostics=True): what the clipped objective did in this update

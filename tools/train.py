@@ -35,6 +35,9 @@ def main():
                     help="count on the device who won the finished games per opponent snapshot: every update's line carries \"league\"")
     ap.add_argument("--league-sampling", choices=["reference", "pfsp"], default="reference",
                     help="pfsp: draw the snapshots the central policy does badly against more often (implies --league-stats)")
+    ap.add_argument("--start-pool", metavar="FILE", default="",
+                    help="a start pool saved by start_pool.save (tools/make_start_pool.py): re-dealt games start from its positions; every update's line carries \"start_pool\"")
+    ap.add_argument("--start-pool-fresh", metavar="P", type=float, default=0.0, help="the share of deals that stay fresh with --start-pool")
     args = ap.parse_args()
     league_stats = args.league > 0 and (args.league_stats or args.league_sampling == "pfsp")
     import torch
@@ -64,7 +67,8 @@ def main():
 
     lg = League(max_distinct=args.league, seed=rank, sampling=args.league_sampling) if args.league > 0 else None
     targs = train_loop.TrainArgs(num_steps=args.num_steps, eval_every=args.eval_every, num_eval_episodes=args.num_eval_episodes,
-                                 eval_scripted_baseline=args.eval_scripted_baseline)
+                                 eval_scripted_baseline=args.eval_scripted_baseline,
+                                 **(dict(start_pool=args.start_pool, start_pool_fresh=args.start_pool_fresh) if args.start_pool else {}))
     loop = train_loop.TrainingLoop(env, net, col, tr, targs, league=lg, make_net=lambda: CatanPolicy(include_lstm=args.lstm).cuda(),
                                    evaluate=evaluate if rank == 0 else None, checkpoint_path=args.checkpoint or None)
     for _ in range(args.updates):
