@@ -208,6 +208,36 @@ int catan_start_pool_clear(catan_env_t* env, catan_stream_t stream);
 int catan_start_pool_read(catan_env_t* env, uint64_t* out_host, int32_t reset, catan_stream_t stream);
 int32_t catan_start_pool_size(const catan_env_t* env);
 
+/* ---- start pool: weighted picks and per-entry outcomes ----
+ * (csrc/catan_start_pool_weighted.hip).  Both are opt-in: with no weights set and outcomes off, no kernel of that file is
+ * launched and the install is the one described above, draw for draw.
+ * catan_start_pool_set_weights: weights_dev is a DEVICE uint32 [m] for the installed pool; NULL goes back to the uniform pick.  The call
+ *   builds the inclusive prefix sums cum[k] = w[0] + ... + w[k] on the device (summed in 64 bits), synchronises the stream once to read
+ *   their total W, and refuses W == 0 and W > 2^32 - 1 with CATAN_EINVAL, leaving the weights in force as they were.  The new table is
+ *   built beside the old one and swapped in after the handle's streams have drained.  The rule: where the deal does not stay fresh,
+ *   t = umulhi(o[0], W) and the entry is the smallest k with cum[k] > t (o, d and the freshness test are those of the install above).  An
+ *   entry of weight 0 is never installed; with every weight 1 the rule is the uniform one bit for bit.  catan_start_pool_set drops the
+ *   weights: a new pool is uniform.
+ * catan_start_pool_outcomes_enable: from now on every finished game of a handle with auto_reset is added, just before its re-deal, to a
+ *   table of 2 + (m + 1) x catan_start_pool_outcomes_words() uint64 sums, by the entry its episode started from.  focus_pid_dev is a
+ *   caller-owned DEVICE int32 [n] (PlayerId 1..4 per game, 0: none) that is read whenever a game finishes, or NULL.  The call zeroes the
+ *   table and, when it switches outcomes on, marks every game as freshly dealt: enable before the reset that deals from the pool.  It needs
+ *   a pool.  on == 0 stops the tallies.  catan_start_pool_set over a pool with outcomes on keeps them on with a zeroed table of the new
+ *   size and marks every game in flight as freshly dealt; catan_start_pool_clear switches them off.  catan_state_import and
+ *   catan_state_fork mark the games they overwrite as freshly dealt (one small launch more, only while outcomes are on).
+ * catan_start_pool_outcomes_read: out_host is a HOST uint64 [2 + (m + 1) x 8]:
+ *     [0] finished games seen   [1] of them skipped (a padding game, a winner outside 1..4, an origin outside [-1, m))
+ *   then a row of 8 per entry k < m and, as row m, for the games that were dealt fresh (the baseline):
+ *     [0] games finished   [1..4] games won by PlayerId 1..4   [5] games with a focus PlayerId in 1..4   [6] of those, won by the focus
+ *     player   [7] sum of the final turn number (the field catan_episode_stats sums as turns_sum)
+ *   All are integer sums, independent of the order of arrival.  reset != 0 zeroes the table behind the copy.  It synchronises the stream.
+ * All three refuse an open deferred sequence, and set_weights / outcomes_enable handles under the MT19937 contract.  A tally of the games
+ * of a handle without auto_reset (a _count form like catan_league_stats_count) is not built. */
+int catan_start_pool_set_weights(catan_env_t* env, const uint32_t* weights_dev, catan_stream_t stream);
+int32_t catan_start_pool_outcomes_words(void);
+int catan_start_pool_outcomes_enable(catan_env_t* env, int on, const int32_t* focus_pid_dev, catan_stream_t stream);
+int catan_start_pool_outcomes_read(catan_env_t* env, uint64_t* out_host, int32_t reset, catan_stream_t stream);
+
 /* ---- rule-based player ----
  * The "builder" bot (csrc/catan_scripted.hip): a deterministic scripted policy - the same state always gives the same
  * action, every action is legal under the game's masks, it never proposes a trade - decided by one lane-per-game kernel.  It decides for

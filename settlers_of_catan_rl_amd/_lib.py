@@ -323,13 +323,19 @@ _SIGS = {
     "catan_start_pool_clear": (C.c_int, [_vp, _vp]),
     "catan_start_pool_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, _vp]),
     "catan_start_pool_size": (C.c_int32, [_vp]),
+    "catan_start_pool_set_weights": (C.c_int, [_vp, _vp, _vp]),
+    "catan_start_pool_outcomes_words": (C.c_int32, []),
+    "catan_start_pool_outcomes_enable": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "catan_start_pool_outcomes_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, _vp]),
 }
 # bound only where the library exports them: the same callers also load oracle/libcatan_cpu.so, which implements the env ABI
 # without these
 _OPTIONAL = {"catan_set_board_configs", "catan_episode_stats_words", "catan_episode_stats_enable", "catan_episode_stats_read",
              "catan_league_stats_words", "catan_league_stats_enable", "catan_league_stats_read", "catan_league_stats_count",
              "catan_record_enable", "catan_record_arm", "catan_record_status", "catan_record_read",
-             "catan_start_pool_set", "catan_start_pool_clear", "catan_start_pool_read", "catan_start_pool_size"}
+             "catan_start_pool_set", "catan_start_pool_clear", "catan_start_pool_read", "catan_start_pool_size",
+             "catan_start_pool_set_weights", "catan_start_pool_outcomes_words", "catan_start_pool_outcomes_enable",
+             "catan_start_pool_outcomes_read"}
 
 
 def declared_symbols():

@@ -27,6 +27,7 @@
 #include "catan_league_stats.hip"
 #include "catan_record.hip"
 #include "catan_start_pool.hip"
+#include "catan_start_pool_weighted.hip"
 
 using namespace catan;
 
@@ -103,6 +104,12 @@ struct catan_env {
     int rec_on;
     StartPoolBuf pool;           // catan_start_pool_set: the saved positions (catan_start_pool.hip); not in `owned`: freed and re-made by every set
     int pool_on;
+    u32* pool_cum;               // catan_start_pool_set_weights: the inclusive prefix sums of the weights [pool.m] (catan_start_pool_weighted.hip), or NULL: the uniform pick
+    u32 pool_W;                  // ... and their sum
+    i32* pool_origin;            // catan_start_pool_outcomes_enable: per game the entry its episode started from, -1 fresh [n]
+    unsigned long long* pool_out;   // ... the table of PO_HEAD + (pool.m + 1) x PO_WORDS sums
+    const i32* pool_out_focus;   // ... the caller's focus array (device int32 [n]) or NULL
+    int pool_out_on;
 };
 static_assert(sizeof(BoardCfg) == sizeof(catan_board_cfg_t) && sizeof(catan_board_cfg_t) == 56 &&
               offsetof(BoardCfg, terrain) == offsetof(catan_board_cfg_t, terrain) &&
@@ -427,6 +434,10 @@ static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* s
 // front of enqueue_record_open and of the event that publishes the re-deal.  No pool installed (the default): nothing is launched.
 static void enqueue_start_pool(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
 static void enqueue_start_pool_sel(catan_env_t* e, const u8* sel, hipStream_t st);
+// ... its per-entry outcomes (catan_start_pool_outcomes_enable) at the hook of the league results, directly beside them, and the origins of the games
+// that catan_state_import / catan_state_fork overwrite.  Outcomes off (the default): nothing is launched.
+static void enqueue_start_pool_outcomes(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
+static void enqueue_start_pool_origin_clear(catan_env_t* e, const long* idx, long cnt, hipStream_t st);
 // k_step with G games per wave in one-wave workgroups; pend.sample (fused-sampling rollouts): actions from / to the side rows
 template <int G>
 static void launch_step(catan_env_t* e, const int32_t* actions, float* reward, uint8_t* done, hipStream_t st, const StepCfg& sc, const u32* bins) {
@@ -817,6 +828,7 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
             enqueue_episode_stats(e, sctr + 1, e->pend.resets[sa][0], e->side);
             enqueue_league_stats(e, sctr + 1, e->pend.resets[sa][0], e->side);
+            enqueue_start_pool_outcomes(e, sctr + 1, e->pend.resets[sa][0], e->side);
             enqueue_record_seal(e, sctr + 1, e->pend.resets[sa][0], e->side);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 1),
                                (const i32*)e->pend.resets[sa][0], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
@@ -843,6 +855,7 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));      // the side stream's launch of step_impl: it had the whole slow path to finish
             enqueue_episode_stats(e, sctr + 3, e->pend.resets[sa][2], st);
             enqueue_league_stats(e, sctr + 3, e->pend.resets[sa][2], st);
+            enqueue_start_pool_outcomes(e, sctr + 3, e->pend.resets[sa][2], st);
             enqueue_record_seal(e, sctr + 3, e->pend.resets[sa][2], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 3), (const i32*)e->pend.resets[sa][2], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
@@ -850,6 +863,7 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             enqueue_record_open(e, sctr + 3, e->pend.resets[sa][2], st);
             enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_league_stats(e, sctr + 2, e->pend.resets[sa][1], st);
+            enqueue_start_pool_outcomes(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_record_seal(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2), (const i32*)e->pend.resets[sa][1], busy,
                                (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
@@ -859,6 +873,7 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));
             enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_league_stats(e, sctr + 2, e->pend.resets[sa][1], st);
+            enqueue_start_pool_outcomes(e, sctr + 2, e->pend.resets[sa][1], st);
             enqueue_record_seal(e, sctr + 2, e->pend.resets[sa][1], st);
             hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2),
                                (const i32*)e->pend.resets[sa][1], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
@@ -894,6 +909,7 @@ static int step_impl(catan_env_t* e, int32_t* actions, float* reward, uint8_t* d
         e->spec_epoch++;
         enqueue_episode_stats(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);       // (the real list only: the speculative successors are no episodes)
         enqueue_league_stats(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
+        enqueue_start_pool_outcomes(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
         enqueue_record_seal(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
         hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, limits_of(e),
                            (const u32*)(e->pend.ctr + 8 + 1), (const i32*)e->pend.resets[0][0], e->pend.busy, step_cfg(e).prof,
@@ -989,6 +1005,7 @@ int catan_state_import(catan_env_t* e, const int32_t* blob, const int64_t* env_i
     if (!e || !blob || cnt <= 0 || (!env_idx && cnt > e->n)) return fail(CATAN_EINVAL, "catan_state_import: bad arguments");
     NOT_DEFERRED(e, "catan_state_import");
     hipLaunchKernelGGL(k_import, dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, S(stream), e->ctx, (const long*)env_idx, (long)cnt, blob);
+    enqueue_start_pool_origin_clear(e, (const long*)env_idx, (long)cnt, S(stream));
     HIPCHK(hipGetLastError());
     return launch_masks(e, S(stream));
 }
@@ -1007,6 +1024,7 @@ int catan_state_fork(catan_env_t* dst, const catan_env_t* src, const int64_t* sr
     const int copy_masks = ls.max_trades == ld.max_trades && ls.max_actions == ld.max_actions;
     hipLaunchKernelGGL(k_fork, dim3(blocks(cnt * FORK_SLOTS, BLOCK)), dim3(BLOCK), 0, S(stream), dst->ctx, dst->mpk, src->ctx, (const u32*)src->mpk,
                        (const long*)src_idx, (const long*)dst_idx, (const u32*)draw_offset, (long)cnt, copy_masks);
+    enqueue_start_pool_origin_clear(dst, (const long*)dst_idx, (long)cnt, S(stream));
     HIPCHK(hipGetLastError());
     if (!copy_masks) {
         hipLaunchKernelGGL(k_masks_of_list, dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, S(stream), dst->ctx, dst->mpk, ld, (const long*)dst_idx, (long)cnt);
@@ -2361,11 +2379,15 @@ static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* s
 // ---- start pool (catan_start_pool.hip).  As for the recorder above: the kernels are templates first used here, behind everything else, so their
 // code follows every other kernel's in the code object and the existing kernels keep their code and their places.
 static void start_pool_free(catan_env_t* e) {
-    for (void* p : { (void*)e->pool.rec, (void*)e->pool.mask, (void*)e->pool.cnt })
+    for (void* p : { (void*)e->pool.rec, (void*)e->pool.mask, (void*)e->pool.cnt, (void*)e->pool_cum, (void*)e->pool_origin, (void*)e->pool_out })
         if (p) hipFree(p);
     e->pool = StartPoolBuf{};
     e->pool_on = 0;
+    // weights and outcomes belong to the pool they were set on (catan_start_pool_set carries the outcomes over itself)
+    e->pool_cum = nullptr; e->pool_W = 0u;
+    e->pool_origin = nullptr; e->pool_out = nullptr; e->pool_out_focus = nullptr; e->pool_out_on = 0;
 }
+static size_t start_pool_outcome_words(int m) { return (size_t)PO_HEAD + ((size_t)m + 1) * PO_WORDS; }
 // a pool in use may still be read (and counted into) by installs in flight on any of the handle's streams
 static int start_pool_quiesce(catan_env_t* e, hipStream_t st) {
     HIPCHK(hipStreamSynchronize(st));
@@ -2388,15 +2410,19 @@ int catan_start_pool_set(catan_env_t* e, const int32_t* blobs, int32_t m, int32_
     StartPoolBuf pb{};
     pb.m = m; pb.fresh_q16 = (u32)fresh_q16;
     u32* bad = nullptr;
+    unsigned long long* out = nullptr;                // outcomes on: they stay on, with a fresh zeroed table of the new size
+    const size_t out_bytes = start_pool_outcome_words(m) * sizeof(unsigned long long);
     hipError_t rc = hipMalloc((void**)&pb.rec, (size_t)m * REC * sizeof(u32));
+    if (rc == hipSuccess && e->pool_out_on) rc = hipMalloc((void**)&out, out_bytes);
     if (rc == hipSuccess) rc = hipMalloc((void**)&pb.mask, (size_t)m * POOL_MASK_STRIDE * sizeof(u32));
     if (rc == hipSuccess) rc = hipMalloc((void**)&pb.cnt, (size_t)(2 + m) * sizeof(unsigned long long));
     if (rc == hipSuccess) rc = hipMalloc((void**)&bad, sizeof(u32));
-    auto drop = [&]() { for (void* p : { (void*)pb.rec, (void*)pb.mask, (void*)pb.cnt, (void*)bad }) if (p) hipFree(p); };
+    auto drop = [&]() { for (void* p : { (void*)pb.rec, (void*)pb.mask, (void*)pb.cnt, (void*)bad, (void*)out }) if (p) hipFree(p); };
     if (rc != hipSuccess) { drop(); return fail(CATAN_ENOMEM, std::string("catan_start_pool_set: hipMalloc: ") + hipGetErrorString(rc)); }
     rc = hipMemsetAsync(pb.rec, 0, (size_t)m * REC * sizeof(u32), st);
     if (rc == hipSuccess) rc = hipMemsetAsync(pb.cnt, 0, (size_t)(2 + m) * sizeof(unsigned long long), st);
     if (rc == hipSuccess) rc = hipMemsetAsync(bad, 0, sizeof(u32), st);
+    if (rc == hipSuccess && out) rc = hipMemsetAsync(out, 0, out_bytes, st);
     if (rc == hipSuccess) {
         // k_import itself, on the pool's records as a handle of m games: an entry's record is what catan_state_import makes of its blob
         Ctx pc = e->ctx;
@@ -2419,9 +2445,16 @@ int catan_start_pool_set(catan_env_t* e, const int32_t* blobs, int32_t m, int32_
         const int r = start_pool_quiesce(e, st);
         if (r != CATAN_OK) { drop(); return r; }
     }
+    // the origins are reset: the games in flight started from the old pool and are not booked to the new one.  The weights go: a new pool is uniform.
+    i32* const origin = e->pool_origin; const i32* const focus = e->pool_out_focus;
+    e->pool_origin = nullptr;
     start_pool_free(e);
     e->pool = pb;
     e->pool_on = 1;
+    if (out) {
+        e->pool_out = out; e->pool_origin = origin; e->pool_out_focus = focus; e->pool_out_on = 1;
+        HIPCHK(hipMemsetAsync(origin, 0xFF, (size_t)e->n * sizeof(i32), st));
+    } else if (origin) hipFree(origin);
     return CATAN_OK;
 }
 int catan_start_pool_clear(catan_env_t* e, catan_stream_t stream) {
@@ -2447,11 +2480,120 @@ int catan_start_pool_read(catan_env_t* e, uint64_t* out_host, int32_t reset, cat
 
 }  // extern "C"
 
+static void enqueue_start_pool_x(catan_env_t* e, const u32* count_p, const i32* list, const u8* sel, bool by_list, hipStream_t st);
 static void enqueue_start_pool(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
     if (!e->pool_on) return;
+    if (e->pool_cum || e->pool_out_on) { enqueue_start_pool_x(e, count_p, list, nullptr, true, st); return; }
     hipLaunchKernelGGL(k_pool_install_list<>, dim3(POOL_LIST_GRID), dim3(64), 0, st, e->ctx, e->mpk, e->pool, count_p, list);
 }
 static void enqueue_start_pool_sel(catan_env_t* e, const u8* sel, hipStream_t st) {
     if (!e->pool_on) return;
+    if (e->pool_cum || e->pool_out_on) { enqueue_start_pool_x(e, nullptr, nullptr, sel, false, st); return; }
     hipLaunchKernelGGL(k_pool_install_sel<>, dim3((unsigned)(e->n < 4096 ? e->n : 4096)), dim3(64), 0, st, e->ctx, e->mpk, e->pool, sel);
+}
+
+// ---- the start pool's weighted pick and per-entry outcomes (catan_start_pool_weighted.hip).  Behind everything above, so that the
+// kernels of catan_start_pool.hip keep their places too.
+extern "C" {
+
+int catan_start_pool_set_weights(catan_env_t* e, const uint32_t* weights_dev, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_start_pool_set_weights: null handle");
+    NOT_DEFERRED(e, "catan_start_pool_set_weights");
+    NOT_MT(e, "catan_start_pool_set_weights");
+    if (!e->pool_on) return fail(CATAN_EINVAL, "catan_start_pool_set_weights: no start pool is installed on this handle (catan_start_pool_set)");
+    const hipStream_t st = S(stream);
+    if (!weights_dev) {                                // back to the uniform kernels
+        if (!e->pool_cum) return CATAN_OK;
+        OK_OR_RETURN(start_pool_quiesce(e, st));
+        hipFree(e->pool_cum);
+        e->pool_cum = nullptr; e->pool_W = 0u;
+        return CATAN_OK;
+    }
+    // the new table is built beside the one in force, which stays if this call fails
+    const int m = e->pool.m;
+    u32* cum = nullptr;
+    unsigned long long* total = nullptr;
+    hipError_t rc = hipMalloc((void**)&cum, (size_t)m * sizeof(u32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&total, sizeof(unsigned long long));
+    auto drop = [&]() { for (void* p : { (void*)cum, (void*)total }) if (p) hipFree(p); };
+    if (rc != hipSuccess) { drop(); return fail(CATAN_ENOMEM, std::string("catan_start_pool_set_weights: hipMalloc: ") + hipGetErrorString(rc)); }
+    hipLaunchKernelGGL(k_pool_scan<>, dim3(1), dim3(POOL_SCAN_THREADS), 0, st, (const u32*)weights_dev, cum, total, m);
+    rc = hipGetLastError();
+    unsigned long long W = 0ull;
+    if (rc == hipSuccess) rc = hipMemcpyAsync(&W, total, sizeof W, hipMemcpyDeviceToHost, st);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(st);
+    if (rc != hipSuccess) { drop(); return fail(CATAN_EHIP, std::string("catan_start_pool_set_weights: ") + hipGetErrorString(rc)); }
+    if (W == 0ull || W > 0xFFFFFFFFull) {
+        drop();
+        return fail(CATAN_EINVAL, "catan_start_pool_set_weights: the weights sum to " + std::to_string(W) + " (the sum must be in 1..2^32-1)");
+    }
+    hipFree(total);
+    total = nullptr;
+    { const int r = start_pool_quiesce(e, st); if (r != CATAN_OK) { drop(); return r; } }    // installs in flight read the old table
+    if (e->pool_cum) hipFree(e->pool_cum);
+    e->pool_cum = cum; e->pool_W = (u32)W;
+    return CATAN_OK;
+}
+
+int32_t catan_start_pool_outcomes_words(void) { return PO_WORDS; }
+int catan_start_pool_outcomes_enable(catan_env_t* e, int on, const int32_t* focus_pid_dev, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_enable: null handle");
+    NOT_DEFERRED(e, "catan_start_pool_outcomes_enable");
+    NOT_MT(e, "catan_start_pool_outcomes_enable");
+    if (!e->pool_on) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_enable: no start pool is installed on this handle (catan_start_pool_set)");
+    // off: the arrays stay (installs in flight may still write the origins) until the pool goes
+    if (!on) { e->pool_out_on = 0; e->pool_out_focus = nullptr; return CATAN_OK; }
+    if (!e->cfg.auto_reset) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_enable: the handle has auto_reset = 0 (no game is re-dealt, so none would be tallied)");
+    const hipStream_t st = S(stream);
+    const size_t bytes = start_pool_outcome_words(e->pool.m) * sizeof(unsigned long long);
+    if (!e->pool_origin) {
+        const hipError_t rc = hipMalloc((void**)&e->pool_origin, (size_t)e->n * sizeof(i32));
+        if (rc != hipSuccess) { e->pool_origin = nullptr; return fail(CATAN_ENOMEM, std::string("catan_start_pool_outcomes_enable: hipMalloc: ") + hipGetErrorString(rc)); }
+    }
+    if (!e->pool_out) {
+        const hipError_t rc = hipMalloc((void**)&e->pool_out, bytes);
+        if (rc != hipSuccess) { e->pool_out = nullptr; return fail(CATAN_ENOMEM, std::string("catan_start_pool_outcomes_enable: hipMalloc: ") + hipGetErrorString(rc)); }
+    }
+    // where the origins were kept by an earlier enable they are stale by now: every game counts as freshly dealt until its next deal
+    if (!e->pool_out_on) HIPCHK(hipMemsetAsync(e->pool_origin, 0xFF, (size_t)e->n * sizeof(i32), st));
+    HIPCHK(hipMemsetAsync(e->pool_out, 0, bytes, st));
+    e->pool_out_focus = focus_pid_dev; e->pool_out_on = 1;
+    return CATAN_OK;
+}
+int catan_start_pool_outcomes_read(catan_env_t* e, uint64_t* out_host, int32_t reset, catan_stream_t stream) {
+    if (!e || !out_host) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_read: null argument");
+    if (!e->pool_on) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_read: no start pool is installed on this handle (catan_start_pool_set)");
+    if (!e->pool_out_on) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_read: outcomes are not enabled on this handle (catan_start_pool_outcomes_enable)");
+    NOT_DEFERRED(e, "catan_start_pool_outcomes_read");          // (the side streams of an open sequence are joined by catan_step_flush)
+    const hipStream_t st = S(stream);
+    const size_t bytes = start_pool_outcome_words(e->pool.m) * sizeof(unsigned long long);
+    HIPCHK(hipMemcpyAsync(out_host, e->pool_out, bytes, hipMemcpyDeviceToHost, st));
+    if (reset) HIPCHK(hipMemsetAsync(e->pool_out, 0, bytes, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return CATAN_OK;
+}
+
+}  // extern "C"
+
+static void enqueue_start_pool_outcomes(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!e->pool_out_on) return;
+    hipLaunchKernelGGL(k_pool_outcomes<>, dim3(POOL_OUTCOMES_GRID), dim3(64), 0, st, e->ctx, count_p, list, (const i32*)e->pool_origin, e->pool_out_focus, e->pool_out, e->pool.m);
+}
+static void enqueue_start_pool_origin_clear(catan_env_t* e, const long* idx, long cnt, hipStream_t st) {
+    if (!e->pool_out_on) return;
+    hipLaunchKernelGGL(k_pool_origin_clear<>, dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, st, e->pool_origin, e->n, idx, cnt);
+}
+// the install of a handle with weights set, outcomes on, or both (enqueue_start_pool / enqueue_start_pool_sel hand over)
+static void enqueue_start_pool_x(catan_env_t* e, const u32* count_p, const i32* list, const u8* sel, bool by_list, hipStream_t st) {
+    const PoolPick pp{ e->pool_cum, e->pool_W, e->pool_out_on ? e->pool_origin : nullptr };
+    const dim3 sel_grid((unsigned)(e->n < 4096 ? e->n : 4096));
+#define POOL_X(WEIGHTED, ORIGIN)                                                                                                                          \
+    do {                                                                                                                                                  \
+        if (by_list) hipLaunchKernelGGL((k_pool_install_list_x<WEIGHTED, ORIGIN>), dim3(POOL_LIST_GRID), dim3(64), 0, st, e->ctx, e->mpk, e->pool, pp, count_p, list); \
+        else hipLaunchKernelGGL((k_pool_install_sel_x<WEIGHTED, ORIGIN>), sel_grid, dim3(64), 0, st, e->ctx, e->mpk, e->pool, pp, sel);                    \
+    } while (0)
+    if (pp.cum && pp.origin) POOL_X(true, true);
+    else if (pp.cum) POOL_X(true, false);
+    else POOL_X(false, true);
+#undef POOL_X
 }

@@ -248,11 +248,12 @@ class VecCatanEnv(object):
             raise _lib.CatanHipError(f"the loaded library has no {name}")
         return getattr(self.L, name)
 
-    def set_start_pool(self, blobs, fresh_share=0.0):
+    def set_start_pool(self, blobs, fresh_share=0.0, weights=None):
         """From now on a game that is re-dealt (auto_reset) or dealt by reset() starts from one of `blobs` - [m, 736], numpy or tensor, the
         orientation of export_state, up to 65536 unfinished positions - except for the share `fresh_share` of deals, which stay fresh.
         The game keeps its own draw counter: the same position in two games rolls different dice.  The env keeps its own copy; the
-        counters (start_pool_counts) start at zero.  A second call replaces the pool."""
+        counters (start_pool_counts) start at zero.  A second call replaces the pool.  weights: see set_start_pool_weights (None: every
+        entry is equally likely; a new pool never inherits the weights of the one it replaces)."""
         fn = self._start_pool_call("catan_start_pool_set")
         share = float(fresh_share)
         if not 0.0 <= share <= 1.0:                      # (also refuses nan)
@@ -264,7 +265,64 @@ class VecCatanEnv(object):
         if b.dim() != 2 or b.shape[1] != spec.STATE_WORDS:
             raise ValueError(f"start pool blobs: shape [m, {spec.STATE_WORDS}] expected, got {tuple(b.shape)}")
         bt = b.t().contiguous()
+        w = None if weights is None else self._start_pool_weights(weights, int(b.shape[0]))      # (refused before any call)
         _lib.check(fn(self.h, _ptr(bt) if bt.numel() else None, int(b.shape[0]), int(round(share * 65536)), _stream()))
+        if w is not None:
+            _lib.check(self._start_pool_call("catan_start_pool_set_weights")(self.h, _ptr(w), _stream()))
+
+    def _start_pool_weights(self, weights, m):
+        """-> the weights as a device tensor of m uint32 values (held in int32 storage), checked on the host"""
+        self._start_pool_call("catan_start_pool_set_weights")
+        w = weights.detach().cpu().numpy() if torch.is_tensor(weights) else np.asarray(weights)
+        if w.dtype.kind not in "iu":
+            raise ValueError(f"start pool weights must be integers, got {w.dtype}")
+        if w.shape != (m,):
+            raise ValueError(f"start pool weights: one per entry ({m}), got shape {tuple(w.shape)}")
+        vals = [int(x) for x in w.tolist()]
+        if any(x < 0 or x > 0xFFFFFFFF for x in vals):
+            raise ValueError("start pool weights must be in 0..2^32-1")
+        if not 1 <= sum(vals) <= spec.START_POOL_MAX_WEIGHT_SUM:
+            raise ValueError(f"start pool weights must sum to 1..2^32-1, got {sum(vals)}")
+        return torch.from_numpy(np.array(vals, dtype=np.uint32).view(np.int32)).to(self.device)
+
+    def set_start_pool_weights(self, weights):
+        """The installed pool's entries are drawn in proportion to `weights` from now on: an integer array or tensor of m values in
+        0..2^32-1 whose sum is in 1..2^32-1 (ValueError otherwise, before any call).  An entry of weight 0 is never installed; all-ones
+        weights draw exactly what the uniform pool draws.  None: uniform again.  Waits for the env's streams."""
+        fn = self._start_pool_call("catan_start_pool_set_weights")
+        if weights is None:
+            _lib.check(fn(self.h, None, _stream()))
+            return
+        m = max(int(self._start_pool_call("catan_start_pool_size")(self.h)), 0)
+        if m == 0:
+            raise _lib.CatanHipError("set_start_pool_weights: no start pool is installed (set_start_pool)")
+        _lib.check(fn(self.h, _ptr(self._start_pool_weights(weights, m)), _stream()))
+
+    def enable_start_pool_outcomes(self, focus_pid=None, on=True):
+        """The finished games are tallied on the device from now on by the pool entry they started from (include/catan_hip_tuning.h
+        "start pool: weighted picks and per-entry outcomes"); the table starts at zero and every game the env holds counts as freshly
+        dealt until its next deal - enable in front of the reset() that deals from the pool.  focus_pid: PlayerId 1..4 per game (0:
+        none) of the seat whose own results are wanted; the env keeps an int32 copy on the device.  on=False stops the tallies."""
+        fn = self._start_pool_call("catan_start_pool_outcomes_enable")
+        focus = None
+        if on and focus_pid is not None:
+            focus = torch.as_tensor(focus_pid, device=self.device).to(torch.int32).contiguous().clone()
+            if focus.shape != (self.n,):
+                raise ValueError(f"focus_pid: one PlayerId per game ({self.n}), got shape {tuple(focus.shape)}")
+        _lib.check(fn(self.h, int(bool(on)), _ptr(focus), _stream()))
+        self._start_pool_focus = focus           # (the library reads it whenever a game finishes)
+
+    def start_pool_outcomes(self, reset=False):
+        """-> dict (spec.start_pool_outcomes_dict): "seen", "skipped", "table" (int64 [m + 1, 8]: a row per entry and the fresh deals' row),
+        the per-entry arrays by field name (spec.START_POOL_OUTCOME_FIELDS), the "fresh" row by name, and the derived win_share_by_pid
+        [m, 4] and focus_win_share [m] (NaN where no game was tallied), of the games finished since outcomes were enabled (or last read
+        with reset=True); waits for the current stream"""
+        fn = self._start_pool_call("catan_start_pool_outcomes_read")
+        assert int(self._start_pool_call("catan_start_pool_outcomes_words")()) == spec.START_POOL_OUTCOME_WORDS
+        m = max(int(self._start_pool_call("catan_start_pool_size")(self.h)), 0)
+        out = np.zeros(2 + (m + 1) * spec.START_POOL_OUTCOME_WORDS, dtype=np.uint64)
+        _lib.check(fn(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), int(bool(reset)), _stream()))
+        return spec.start_pool_outcomes_dict(out.astype(np.int64), m)
 
     def clear_start_pool(self):
         """every later deal is fresh again, draw for draw as on an env that never had a pool"""

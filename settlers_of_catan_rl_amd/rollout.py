@@ -138,7 +138,8 @@ class RolloutCollector(object):
     GRAPH_ACT_MIN_GAMES = 8192
 
     def __init__(self, env, policy, num_steps, opponents=None, seed=0, autocast_dtype=None, graph_act=None, deferred_window=None, act_buckets=None,
-                 episode_stats=False, league_stats=False, record_games=0, start_pool=None, start_pool_fresh=0.0):
+                 episode_stats=False, league_stats=False, record_games=0, start_pool=None, start_pool_fresh=0.0,
+                 start_pool_outcomes=False, start_pool_sampling="uniform"):
         """policy: central net (policy 0); opponents: list of up to 3 nets for policy slots 1..3 of every game (None =
         every seat plays the central policy).  A league (league.League.assign) installs per-game opponents instead.  An opponent
         may be a `scripted.ScriptedPolicy(env)` bound to this env: a fixed anchor beside the nets (its rows' log-probs are 0 and,
@@ -162,7 +163,16 @@ class RolloutCollector(object):
         start_pool: saved positions (a start_pool.StartPool, or blobs [m, 736]) that the env's re-dealt games start from, except for the
         share start_pool_fresh of deals, which stay fresh (VecCatanEnv.set_start_pool: installed here, in front of this collector's
         reset(); the games the env holds at that moment are not touched - env.reset() deals them from the pool).  Every gather_rollouts
-        leaves the counts of its deals in storage.start_pool, read once after the loop like the statistics.  None: no call is made."""
+        leaves the counts of its deals in storage.start_pool, read once after the loop like the statistics.  None: no call is made.
+        start_pool_outcomes: the env also tallies the finished games by the pool entry they started from, the active seat as the focus
+        player (VecCatanEnv.enable_start_pool_outcomes); every gather_rollouts leaves them in storage.start_pool["outcomes"], read once
+        beside the counts.  start_pool_sampling "balanced" (implies the outcomes): behind every rollout the tallies are added to the
+        pool (StartPool.add_outcomes; self.start_pool) and the entries' weights for the next rollout become its balanced_weights() - the
+        positions whose result is still open are drawn more often.  The defaults (False, "uniform") make no call."""
+        if start_pool_sampling not in ("uniform", "balanced"):
+            raise ValueError(f"start_pool_sampling must be 'uniform' or 'balanced', got {start_pool_sampling!r}")
+        if (start_pool_outcomes or start_pool_sampling != "uniform") and start_pool is None:
+            raise ValueError("start_pool_outcomes / start_pool_sampling need a start_pool")
         self.env, self.policy, self.T = env, policy, num_steps
         self.league_stats, self.policy_of_pid = bool(league_stats), None
         self.deferred_window = self.DEFAULT_DEFERRED_WINDOW if deferred_window is None else int(deferred_window)
@@ -214,6 +224,15 @@ class RolloutCollector(object):
         self.start_pool_on = start_pool is not None
         if self.start_pool_on:
             env.set_start_pool(getattr(start_pool, "blobs", start_pool), start_pool_fresh)
+        self.start_pool_sampling = start_pool_sampling
+        self.start_pool_outcomes = bool(start_pool_outcomes) or start_pool_sampling == "balanced"
+        self.start_pool = None
+        if self.start_pool_outcomes:
+            from . import start_pool as _start_pool
+            self.start_pool = start_pool if isinstance(start_pool, _start_pool.StartPool) else _start_pool.StartPool(start_pool)
+            env.enable_start_pool_outcomes(self.active_pid)
+            if start_pool_sampling == "balanced":
+                env.set_start_pool_weights(self.start_pool.balanced_weights())
         self.reset()
 
     def set_opponents(self, nets, opp_index):
@@ -339,6 +358,11 @@ class RolloutCollector(object):
                 st.league_stats = env.league_stats(reset=True) if self._league_on else None
             if self.start_pool_on:
                 st.start_pool = env.start_pool_counts(reset=True)
+                if self.start_pool_outcomes:
+                    st.start_pool["outcomes"] = env.start_pool_outcomes(reset=True)
+                    if self.start_pool_sampling == "balanced":
+                        self.start_pool.add_outcomes(st.start_pool["outcomes"])
+                        env.set_start_pool_weights(self.start_pool.balanced_weights())
             if self.record_games:
                 from . import record as _record
                 sealed = (env.recording_status()[:, 0] == _record.SEALED).nonzero(as_tuple=True)[0].tolist()

@@ -238,6 +238,36 @@ LEAGUE_STATS_LDS_MAX_NETS = 127                                   # up to here t
 LEAGUE_STATS_REDEALS, LEAGUE_STATS_COUNT_ONLY = 1, 2              # mode bits of catan_league_stats_enable
 
 
+# ---------------------------------------------------------------- start pool outcomes (include/catan_hip_tuning.h catan_start_pool_outcomes_*)
+# one row of uint64 sums per pool entry and a last row for the fresh deals, behind the two head words; csrc/catan_start_pool_weighted.hip
+# holds the same layout as PO_* offsets
+START_POOL_OUTCOME_HEAD = ["seen", "skipped"]
+START_POOL_OUTCOME_FIELDS = ["games", "wins_p1", "wins_p2", "wins_p3", "wins_p4", "focus_games", "focus_wins", "turns_sum"]
+START_POOL_OUTCOME_WORDS = len(START_POOL_OUTCOME_FIELDS)          # 8
+START_POOL_MAX_WEIGHT_SUM = 2 ** 32 - 1
+
+
+def start_pool_outcomes_dict(words, m):
+    """The table catan_start_pool_outcomes_read fills (2 + (m + 1) * 8 integers) -> OrderedDict: "seen", "skipped", "table" (int64 [m + 1, 8],
+    the last row the fresh deals'), every START_POOL_OUTCOME_FIELDS name -> int64 [m], "fresh" -> a dict of the same names for the last row,
+    and the derived float64 arrays "win_share_by_pid" [m, 4] and "focus_win_share" [m], NaN where no game was tallied."""
+    import numpy as np
+    t = np.asarray(words, dtype=np.int64).reshape(-1)
+    m = int(m)
+    if t.size != 2 + (m + 1) * START_POOL_OUTCOME_WORDS:
+        raise ValueError(f"an outcome table of {m} entries has {2 + (m + 1) * START_POOL_OUTCOME_WORDS} words, got {t.size}")
+    rows = t[2:].reshape(m + 1, START_POOL_OUTCOME_WORDS).copy()
+    out = OrderedDict((("seen", int(t[0])), ("skipped", int(t[1])), ("table", rows)))
+    for i, name in enumerate(START_POOL_OUTCOME_FIELDS):
+        out[name] = rows[:m, i].copy()
+    out["fresh"] = OrderedDict((name, int(rows[m, i])) for i, name in enumerate(START_POOL_OUTCOME_FIELDS))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        games, fgames = rows[:m, 0].astype(np.float64), rows[:m, 5].astype(np.float64)
+        out["win_share_by_pid"] = np.where(games[:, None] > 0, rows[:m, 1:5] / games[:, None], np.nan)
+        out["focus_win_share"] = np.where(fgames > 0, rows[:m, 6] / fgames, np.nan)
+    return out
+
+
 def league_stats_table(words, num_nets):
     """The table catan_league_stats_read fills ((num_nets + 1) * LEAGUE_STATS_WORDS integers, or anything that reshapes to
     [num_nets + 1, LEAGUE_STATS_WORDS]) -> OrderedDict: every LEAGUE_STATS_FIELDS name -> int64 array [num_nets], and "totals" -> a

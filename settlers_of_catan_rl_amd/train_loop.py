@@ -34,6 +34,8 @@ class TrainArgs(object):
     num_eval_episodes = 128
     start_pool = None                    # opt-in: a start_pool.StartPool, blobs [m, 736] or the path of a saved pool - re-dealt games start from its positions
     start_pool_fresh = 0.0               # ... except for this share of the deals, which stay fresh
+    start_pool_outcomes = False          # opt-in: the finished games are tallied per pool entry on the device -> log["start_pool"]["outcomes"]
+    start_pool_sampling = "uniform"      # "balanced": the entries whose result is still open are drawn more often (implies the outcomes)
     eval_scripted_baseline = False       # opt-in: the evaluation also plays the rule-based player (scripted.ScriptedPolicy) -> log["scripted"]
 
     def __init__(self, **kw):
@@ -100,6 +102,15 @@ class TrainingLoop(object):
                     pool = _start_pool.load(pool)
                 env.set_start_pool(getattr(pool, "blobs", pool), self.args.start_pool_fresh)
                 collector.start_pool_on = True
+                if self.args.start_pool_outcomes or self.args.start_pool_sampling != "uniform":
+                    if self.args.start_pool_sampling not in ("uniform", "balanced"):
+                        raise ValueError(f"start_pool_sampling must be 'uniform' or 'balanced', got {self.args.start_pool_sampling!r}")
+                    from . import start_pool as _start_pool
+                    collector.start_pool = pool if isinstance(pool, _start_pool.StartPool) else _start_pool.StartPool(pool)
+                    collector.start_pool_outcomes, collector.start_pool_sampling = True, self.args.start_pool_sampling
+                    env.enable_start_pool_outcomes(collector.active_pid)
+                    if self.args.start_pool_sampling == "balanced":
+                        env.set_start_pool_weights(collector.start_pool.balanced_weights())
             env.reset()
             env.start_pool_counts(reset=True)           # (the counts of a rollout are those of its own deals)
             collector.reset()
@@ -160,6 +171,10 @@ class TrainingLoop(object):
         if getattr(st, "start_pool", None) is not None:          # a start pool is installed: how this rollout's deals began
             sp = st.start_pool
             out["start_pool"] = {"pool": int(sp["pool"]), "fresh": int(sp["fresh"]), "per_entry": [int(x) for x in sp["per_entry"]]}
+            if sp.get("outcomes") is not None:                   # ... and, with start_pool_outcomes, who won the games that began at each entry
+                oc = sp["outcomes"]
+                out["start_pool"]["outcomes"] = {"seen": int(oc["seen"]), "skipped": int(oc["skipped"]), "fresh": dict(oc["fresh"]),
+                                                 "table": [[int(x) for x in row] for row in oc["table"]]}
         if league_out is not None:                               # RolloutCollector(league_stats=True): the scoreboard per snapshot
             out["league"] = league_out
         if getattr(self.trainer, "diagnostics", None) is not None:   # PPOConfig(diagnostics=True): what the clipped objective did in this update

@@ -38,6 +38,10 @@ def main():
     ap.add_argument("--start-pool", metavar="FILE", default="",
                     help="a start pool saved by start_pool.save (tools/make_start_pool.py): re-dealt games start from its positions; every update's line carries \"start_pool\"")
     ap.add_argument("--start-pool-fresh", metavar="P", type=float, default=0.0, help="the share of deals that stay fresh with --start-pool")
+    ap.add_argument("--start-pool-outcomes", action="store_true",
+                    help="with --start-pool: tally the finished games per pool entry on the device; every update's line carries them under \"start_pool\"")
+    ap.add_argument("--start-pool-sampling", choices=["uniform", "balanced"], default="uniform",
+                    help="balanced: draw the pool entries whose result is still open more often (implies --start-pool-outcomes)")
     args = ap.parse_args()
     league_stats = args.league > 0 and (args.league_stats or args.league_sampling == "pfsp")
     import torch
@@ -68,7 +72,8 @@ def main():
     lg = League(max_distinct=args.league, seed=rank, sampling=args.league_sampling) if args.league > 0 else None
     targs = train_loop.TrainArgs(num_steps=args.num_steps, eval_every=args.eval_every, num_eval_episodes=args.num_eval_episodes,
                                  eval_scripted_baseline=args.eval_scripted_baseline,
-                                 **(dict(start_pool=args.start_pool, start_pool_fresh=args.start_pool_fresh) if args.start_pool else {}))
+                                 **(dict(start_pool=args.start_pool, start_pool_fresh=args.start_pool_fresh, start_pool_outcomes=args.start_pool_outcomes,
+                                        start_pool_sampling=args.start_pool_sampling) if args.start_pool else {}))
     loop = train_loop.TrainingLoop(env, net, col, tr, targs, league=lg, make_net=lambda: CatanPolicy(include_lstm=args.lstm).cuda(),
                                    evaluate=evaluate if rank == 0 else None, checkpoint_path=args.checkpoint or None)
     for _ in range(args.updates):
