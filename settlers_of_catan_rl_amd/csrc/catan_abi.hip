@@ -430,8 +430,8 @@ static void enqueue_record_seal(catan_env_t* e, const u32* count_p, const i32* l
 static void enqueue_record_open(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
 static void enqueue_record_append(catan_env_t* e, const i32* actions, const u8* busy, hipStream_t st);
 static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* status, const i32* actions, hipStream_t st);
-// Start pool (catan_start_pool_set; defined at the end of this file): directly behind the consumer of a re-deal list, same stream, same list, in
-// front of enqueue_record_open and of the event that publishes the re-deal.  No pool installed (the default): nothing is launched.
+// Start pool (catan_start_pool_set; defined at the end of this file): directly behind the consumer of a re-deal list (enqueue_redeal has the
+// order and its reasons).  No pool installed (the default): nothing is launched.
 static void enqueue_start_pool(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
 static void enqueue_start_pool_sel(catan_env_t* e, const u8* sel, hipStream_t st);
 // ... its per-entry outcomes (catan_start_pool_outcomes_enable) at the hook of the league results, directly beside them, and the origins of the games
@@ -808,6 +808,34 @@ static int enqueue_tier1(catan_env_t* e, float* reward, uint8_t* done, hipStream
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
+// One re-deal list (its length at *count_p) and everything that hangs on the moment it is consumed, on stream st.  The order is a correctness
+// condition, and this is the one place that states it:
+//   in front of the consumer, the hooks that READ the listed games' final states, which the consumer overwrites: the finished-game
+//     statistics, the league results, the start pool's per-entry outcomes (they also read the origins the pool install rewrites) and the
+//     recorder's seal;
+//   the consumer: a fresh deal (k_reset_list), a fresh deal that also deals step_impl's speculative successors into the shadow arrays
+//     (pend.spec; they are no episodes, so the hooks see the real list only), or the install of those shadows (k_install_list);
+//   behind it, the hooks that WRITE the fresh games: the start pool's install, then the recorder's opening, whose start blob is the state
+//     the install left.
+// All of it stands in front of whatever the caller records or waits for on st to publish the re-deal.  Every hook that is off launches nothing.
+enum Redeal { REDEAL_FRESH, REDEAL_FRESH_AND_SPEC, REDEAL_INSTALL };
+static void enqueue_redeal(catan_env_t* e, Redeal how, const u32* count_p, const i32* list, u8* busy, hipStream_t st) {
+    enqueue_episode_stats(e, count_p, list, st);
+    enqueue_league_stats(e, count_p, list, st);
+    enqueue_start_pool_outcomes(e, count_p, list, st);
+    enqueue_record_seal(e, count_p, list, st);
+    if (how == REDEAL_INSTALL)
+        hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, limits_of(e), count_p, list, busy,
+                           (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
+    else if (how == REDEAL_FRESH_AND_SPEC)
+        hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, st, e->ctx, e->mpk, limits_of(e), count_p, list, busy, step_cfg(e).prof,
+                           (const u32*)(e->pend.ctr + 6), (const u64*)e->pend.spec, e->spec_state, e->spec_mpk, e->spec_epoch, e->pend);
+    else
+        hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, st, e->ctx, e->mpk, limits_of(e), count_p, list, busy, step_cfg(e).prof,
+                           (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
+    enqueue_start_pool(e, count_p, list, st);
+    enqueue_record_open(e, count_p, list, st);
+}
 // tier 2 (+ the completion of its games) and the re-deals of window slot pend.sa on stream st.
 //   deferred window: the games that ended in k_step / k_lr_finish (list 0) are re-dealt on the side stream while tier 2 runs,
 //     those that end in the tier-2 completion (list 1) afterwards.
@@ -818,7 +846,7 @@ static int enqueue_tier1(catan_env_t* e, float* reward, uint8_t* done, hipStream
 // ev (optional): [9] before k_lr_heavy, [3] / [7] after it, [4] at the end
 static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_t st, hipEvent_t* ev, int heavy_grid) {
     StepCfg sc = step_cfg(e);
-    const int sa = e->pend.sa; const Limits max_trades = limits_of(e);
+    const int sa = e->pend.sa;
     const bool lockstep = heavy_grid == LR_HEAVY_GRID;
     u32* sctr = e->pend.ctr + 8 + 4 * sa;
     u8* busy = e->pend.stag < 2 ? e->pend.busy : nullptr;       // tagged games are released by the sampler, not here
@@ -826,14 +854,7 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
         if (!lockstep) {
             HIPCHK(hipEventRecord(e->ev_fork, st));
             HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-            enqueue_episode_stats(e, sctr + 1, e->pend.resets[sa][0], e->side);
-            enqueue_league_stats(e, sctr + 1, e->pend.resets[sa][0], e->side);
-            enqueue_start_pool_outcomes(e, sctr + 1, e->pend.resets[sa][0], e->side);
-            enqueue_record_seal(e, sctr + 1, e->pend.resets[sa][0], e->side);
-            hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 1),
-                               (const i32*)e->pend.resets[sa][0], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
-            enqueue_start_pool(e, sctr + 1, e->pend.resets[sa][0], e->side);
-            enqueue_record_open(e, sctr + 1, e->pend.resets[sa][0], e->side);
+            enqueue_redeal(e, REDEAL_FRESH, sctr + 1, e->pend.resets[sa][0], busy, e->side);
             HIPCHK(hipEventRecord(e->ev_join, e->side));
         }
     }
@@ -853,32 +874,11 @@ static int enqueue_slow(catan_env_t* e, float* reward, uint8_t* done, hipStream_
     if (e->cfg.auto_reset) {
         if (lockstep) {
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));      // the side stream's launch of step_impl: it had the whole slow path to finish
-            enqueue_episode_stats(e, sctr + 3, e->pend.resets[sa][2], st);
-            enqueue_league_stats(e, sctr + 3, e->pend.resets[sa][2], st);
-            enqueue_start_pool_outcomes(e, sctr + 3, e->pend.resets[sa][2], st);
-            enqueue_record_seal(e, sctr + 3, e->pend.resets[sa][2], st);
-            hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 3), (const i32*)e->pend.resets[sa][2], busy,
-                               (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
-            enqueue_start_pool(e, sctr + 3, e->pend.resets[sa][2], st);
-            enqueue_record_open(e, sctr + 3, e->pend.resets[sa][2], st);
-            enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
-            enqueue_league_stats(e, sctr + 2, e->pend.resets[sa][1], st);
-            enqueue_start_pool_outcomes(e, sctr + 2, e->pend.resets[sa][1], st);
-            enqueue_record_seal(e, sctr + 2, e->pend.resets[sa][1], st);
-            hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2), (const i32*)e->pend.resets[sa][1], busy,
-                               (const u32*)e->spec_state, (const u32*)e->spec_mpk, e->spec_epoch, e->err);
-            enqueue_start_pool(e, sctr + 2, e->pend.resets[sa][1], st);
-            enqueue_record_open(e, sctr + 2, e->pend.resets[sa][1], st);
+            enqueue_redeal(e, REDEAL_INSTALL, sctr + 3, e->pend.resets[sa][2], busy, st);
+            enqueue_redeal(e, REDEAL_INSTALL, sctr + 2, e->pend.resets[sa][1], busy, st);
         } else {
             HIPCHK(hipStreamWaitEvent(st, e->ev_join, 0));
-            enqueue_episode_stats(e, sctr + 2, e->pend.resets[sa][1], st);
-            enqueue_league_stats(e, sctr + 2, e->pend.resets[sa][1], st);
-            enqueue_start_pool_outcomes(e, sctr + 2, e->pend.resets[sa][1], st);
-            enqueue_record_seal(e, sctr + 2, e->pend.resets[sa][1], st);
-            hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, st, e->ctx, e->mpk, max_trades, (const u32*)(sctr + 2),
-                               (const i32*)e->pend.resets[sa][1], busy, sc.prof, (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
-            enqueue_start_pool(e, sctr + 2, e->pend.resets[sa][1], st);
-            enqueue_record_open(e, sctr + 2, e->pend.resets[sa][1], st);
+            enqueue_redeal(e, REDEAL_FRESH, sctr + 2, e->pend.resets[sa][1], busy, st);
         }
     }
     if (ev) HIPCHK(hipEventRecord(ev[4], st));
@@ -907,15 +907,7 @@ static int step_impl(catan_env_t* e, int32_t* actions, float* reward, uint8_t* d
         HIPCHK(hipStreamWaitEvent(e->side, e->ev_fork, 0));
         // ... and every game on the longest-road path that this step may end (k_step's list pend.spec) gets a speculative successor
         e->spec_epoch++;
-        enqueue_episode_stats(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);       // (the real list only: the speculative successors are no episodes)
-        enqueue_league_stats(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
-        enqueue_start_pool_outcomes(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
-        enqueue_record_seal(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
-        hipLaunchKernelGGL(k_reset_list, dim3(RESET_GRID), dim3(64), 0, e->side, e->ctx, e->mpk, limits_of(e),
-                           (const u32*)(e->pend.ctr + 8 + 1), (const i32*)e->pend.resets[0][0], e->pend.busy, step_cfg(e).prof,
-                           (const u32*)(e->pend.ctr + 6), (const u64*)e->pend.spec, e->spec_state, e->spec_mpk, e->spec_epoch, e->pend);
-        enqueue_start_pool(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
-        enqueue_record_open(e, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->side);
+        enqueue_redeal(e, REDEAL_FRESH_AND_SPEC, e->pend.ctr + 8 + 1, e->pend.resets[0][0], e->pend.busy, e->side);
         HIPCHK(hipEventRecord(e->ev_join, e->side));
     }
     if (r == CATAN_OK) r = enqueue_tier1(e, reward, done, st, ev, 0, e->sched.lr_budget[0]);
@@ -1053,6 +1045,14 @@ int64_t catan_invalid_action_count(catan_env_t* e, catan_stream_t stream) {
     return (int64_t)v;
 }
 
+// The tail of every counter read: the block to the host, zeroed behind the copy if `reset`, and the stream waited for
+static int read_counters(uint64_t* out_host, unsigned long long* dev, size_t bytes, int reset, hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(out_host, dev, bytes, hipMemcpyDeviceToHost, st));
+    if (reset) HIPCHK(hipMemsetAsync(dev, 0, bytes, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return CATAN_OK;
+}
+
 // ---- finished-game statistics (catan_stats.hip)
 int32_t catan_episode_stats_words(void) { return ES_WORDS; }
 int catan_episode_stats_enable(catan_env_t* e, int on, const int32_t* focus_pid, catan_stream_t stream) {
@@ -1074,10 +1074,7 @@ int catan_episode_stats_read(catan_env_t* e, uint64_t* out_host, int reset, cata
     if (!e || !out_host) return fail(CATAN_EINVAL, "catan_episode_stats_read: null argument");
     if (!e->stats_on) return fail(CATAN_EINVAL, "catan_episode_stats_read: statistics are not enabled on this handle (catan_episode_stats_enable)");
     NOT_DEFERRED(e, "catan_episode_stats_read");      // (the side streams of an open sequence are joined by catan_step_flush)
-    HIPCHK(hipMemcpyAsync(out_host, e->stats, ES_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, S(stream)));
-    if (reset) HIPCHK(hipMemsetAsync(e->stats, 0, ES_WORDS * sizeof(unsigned long long), S(stream)));
-    HIPCHK(hipStreamSynchronize(S(stream)));
-    return CATAN_OK;
+    return read_counters(out_host, e->stats, ES_WORDS * sizeof(unsigned long long), reset, S(stream));
 }
 
 // ---- per-opponent results of a league rollout (catan_league_stats.hip)
@@ -1109,11 +1106,7 @@ int catan_league_stats_read(catan_env_t* e, uint64_t* out_host, int reset, catan
     if (!e || !out_host) return fail(CATAN_EINVAL, "catan_league_stats_read: null argument");
     if (!e->lstats_on) return fail(CATAN_EINVAL, "catan_league_stats_read: league results are not enabled on this handle (catan_league_stats_enable)");
     NOT_DEFERRED(e, "catan_league_stats_read");       // (the side streams of an open sequence are joined by catan_step_flush)
-    const size_t bytes = (size_t)(e->lstats_nets + 1) * LS_WORDS * sizeof(unsigned long long);
-    HIPCHK(hipMemcpyAsync(out_host, e->lstats, bytes, hipMemcpyDeviceToHost, S(stream)));
-    if (reset) HIPCHK(hipMemsetAsync(e->lstats, 0, bytes, S(stream)));
-    HIPCHK(hipStreamSynchronize(S(stream)));
-    return CATAN_OK;
+    return read_counters(out_host, e->lstats, (size_t)(e->lstats_nets + 1) * LS_WORDS * sizeof(unsigned long long), reset, S(stream));
 }
 int catan_league_stats_count(catan_env_t* e, const int32_t* games, int64_t m, catan_stream_t stream) {
     if (!e) return fail(CATAN_EINVAL, "catan_league_stats_count: null handle");
@@ -2470,12 +2463,7 @@ int catan_start_pool_read(catan_env_t* e, uint64_t* out_host, int32_t reset, cat
     if (!e || !out_host) return fail(CATAN_EINVAL, "catan_start_pool_read: null argument");
     if (!e->pool_on) return fail(CATAN_EINVAL, "catan_start_pool_read: no start pool is installed on this handle (catan_start_pool_set)");
     NOT_DEFERRED(e, "catan_start_pool_read");          // (the side streams of an open sequence are joined by catan_step_flush)
-    const hipStream_t st = S(stream);
-    const size_t bytes = (size_t)(2 + e->pool.m) * sizeof(unsigned long long);
-    HIPCHK(hipMemcpyAsync(out_host, e->pool.cnt, bytes, hipMemcpyDeviceToHost, st));
-    if (reset) HIPCHK(hipMemsetAsync(e->pool.cnt, 0, bytes, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return CATAN_OK;
+    return read_counters(out_host, e->pool.cnt, (size_t)(2 + e->pool.m) * sizeof(unsigned long long), reset, S(stream));
 }
 
 }  // extern "C"
@@ -2565,12 +2553,7 @@ int catan_start_pool_outcomes_read(catan_env_t* e, uint64_t* out_host, int32_t r
     if (!e->pool_on) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_read: no start pool is installed on this handle (catan_start_pool_set)");
     if (!e->pool_out_on) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_read: outcomes are not enabled on this handle (catan_start_pool_outcomes_enable)");
     NOT_DEFERRED(e, "catan_start_pool_outcomes_read");          // (the side streams of an open sequence are joined by catan_step_flush)
-    const hipStream_t st = S(stream);
-    const size_t bytes = start_pool_outcome_words(e->pool.m) * sizeof(unsigned long long);
-    HIPCHK(hipMemcpyAsync(out_host, e->pool_out, bytes, hipMemcpyDeviceToHost, st));
-    if (reset) HIPCHK(hipMemsetAsync(e->pool_out, 0, bytes, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return CATAN_OK;
+    return read_counters(out_host, e->pool_out, start_pool_outcome_words(e->pool.m) * sizeof(unsigned long long), reset, S(stream));
 }
 
 }  // extern "C"

@@ -84,6 +84,26 @@ class VecCatanEnv(object):
         elif board_config_index is not None:
             raise ValueError("board_config_index without board_config")
 
+    def _entry(self, name):
+        """-> an entry point that older builds of the library lack (_lib._OPTIONAL)"""
+        if not hasattr(self.L, name):
+            raise _lib.CatanHipError(f"the loaded library has no {name}")
+        return getattr(self.L, name)
+
+    def _per_game_i32(self, name, t, cols=None):
+        """-> the env's own int32 device copy of a per-game argument, [n] or [n, cols]: the library reads it whenever a game finishes"""
+        t = torch.as_tensor(t, device=self.device).to(torch.int32).contiguous().clone()
+        if t.shape != ((self.n,) if cols is None else (self.n, cols)):
+            raise ValueError(f"{name}: one PlayerId per game ({self.n}), got shape {tuple(t.shape)}" if cols is None
+                             else f"{name}: shape ({self.n}, {cols}) expected, got {tuple(t.shape)}")
+        return t
+
+    def _read_u64(self, name, words, reset):
+        """-> uint64 [words] (host): the counter block that entry point `name` copies out, zeroed behind the copy if `reset`; waits for the stream"""
+        out = np.zeros(words, dtype=np.uint64)
+        _lib.check(self._entry(name)(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), int(bool(reset)), _stream()))
+        return out
+
     def set_board_config(self, config_or_list, index=None):
         """Board layouts (include/catan_hip.h catan_set_board_configs): one layout or a list of up to 16, each a dict with the
         keyword names of the reference's Board (randomise_number_placement, fixed_terrain_placements - names or Terrain values -,
@@ -103,9 +123,7 @@ class VecCatanEnv(object):
             if bool(((idx < 0) | (idx >= len(cfgs))).any()):
                 raise ValueError(f"board config index: entries must be in 0..{len(cfgs) - 1}")
             idx = idx.to(torch.uint8).contiguous()
-        if not hasattr(self.L, "catan_set_board_configs"):
-            raise _lib.CatanHipError("the loaded library has no catan_set_board_configs")
-        _lib.check(self.L.catan_set_board_configs(self.h, arr, len(cfgs), _ptr(idx), _stream()))
+        _lib.check(self._entry("catan_set_board_configs")(self.h, arr, len(cfgs), _ptr(idx), _stream()))
 
     def set_step_wave_games(self, games):
         """scheduling knob of k_step: 64 / 32 / 16 games per wave (results do not depend on it)"""
@@ -125,22 +143,15 @@ class VecCatanEnv(object):
         (include/catan_hip_tuning.h catan_episode_stats_enable); the counters start at zero.  focus_pid: PlayerId 1..4 per game (0: none) of the
         seat whose own results are wanted - the env keeps an int32 copy on the device, later edits of the argument are not seen.
         on=False stops counting."""
-        if not hasattr(self.L, "catan_episode_stats_enable"):
-            raise _lib.CatanHipError("the loaded library has no catan_episode_stats_enable")
-        focus = None
-        if on and focus_pid is not None:
-            focus = torch.as_tensor(focus_pid, device=self.device).to(torch.int32).contiguous().clone()
-            if focus.shape != (self.n,):
-                raise ValueError(f"focus_pid: one PlayerId per game ({self.n}), got shape {tuple(focus.shape)}")
-        _lib.check(self.L.catan_episode_stats_enable(self.h, int(bool(on)), _ptr(focus), _stream()))
+        fn = self._entry("catan_episode_stats_enable")
+        focus = self._per_game_i32("focus_pid", focus_pid) if on and focus_pid is not None else None
+        _lib.check(fn(self.h, int(bool(on)), _ptr(focus), _stream()))
         self._episode_focus = focus              # (the library reads it whenever a game finishes)
 
     def episode_stats_words(self, reset=False):
         """-> the raw counter block (list of spec.EPISODE_STATS_WORDS ints); waits for the current stream"""
-        out = (C.c_uint64 * spec.EPISODE_STATS_WORDS)()
         assert int(self.L.catan_episode_stats_words()) == spec.EPISODE_STATS_WORDS
-        _lib.check(self.L.catan_episode_stats_read(self.h, out, int(bool(reset)), _stream()))
-        return [int(x) for x in out]
+        return [int(x) for x in self._read_u64("catan_episode_stats_read", spec.EPISODE_STATS_WORDS, reset)]
 
     def episode_stats(self, reset=False):
         """-> dict (spec.episode_stats_dict): the counters of the games finished since statistics were enabled (or last read with reset=True)
@@ -155,20 +166,14 @@ class VecCatanEnv(object):
         device (the library reads them whenever a game finishes); later edits of the arguments are not seen.
         count_only: nothing is tallied at the re-deals, only by league_stats_count (the one mode a handle without auto_reset takes).
         on=False stops counting."""
-        if not hasattr(self.L, "catan_league_stats_enable"):
-            raise _lib.CatanHipError("the loaded library has no catan_league_stats_enable")
+        fn = self._entry("catan_league_stats_enable")
         if not on:
-            _lib.check(self.L.catan_league_stats_enable(self.h, 0, None, None, 0, _stream()))
+            _lib.check(fn(self.h, 0, None, None, 0, _stream()))
             self._league_maps, self._league_nets = None, 0
             return
-        maps = []
-        for name, t, cols in (("slot_of_pid", slot_of_pid, 4), ("net_of_slot", net_of_slot, 3)):
-            t = torch.as_tensor(t, device=self.device).to(torch.int32).contiguous().clone()
-            if t.shape != (self.n, cols):
-                raise ValueError(f"{name}: shape ({self.n}, {cols}) expected, got {tuple(t.shape)}")
-            maps.append(t)
+        maps = [self._per_game_i32("slot_of_pid", slot_of_pid, 4), self._per_game_i32("net_of_slot", net_of_slot, 3)]
         mode = spec.LEAGUE_STATS_COUNT_ONLY if count_only else spec.LEAGUE_STATS_REDEALS
-        _lib.check(self.L.catan_league_stats_enable(self.h, mode, _ptr(maps[0]), _ptr(maps[1]), int(num_nets), _stream()))
+        _lib.check(fn(self.h, mode, _ptr(maps[0]), _ptr(maps[1]), int(num_nets), _stream()))
         self._league_maps, self._league_nets = maps, int(num_nets)
 
     def league_stats(self, reset=False):
@@ -177,9 +182,8 @@ class VecCatanEnv(object):
         current stream.  spec.league_stats_table names the columns."""
         rows = getattr(self, "_league_nets", 0) + 1
         assert int(self.L.catan_league_stats_words()) == spec.LEAGUE_STATS_WORDS
-        out = torch.zeros((rows, spec.LEAGUE_STATS_WORDS), dtype=torch.int64)
-        _lib.check(self.L.catan_league_stats_read(self.h, C.cast(out.data_ptr(), C.POINTER(C.c_uint64)), int(bool(reset)), _stream()))
-        return out
+        out = self._read_u64("catan_league_stats_read", rows * spec.LEAGUE_STATS_WORDS, reset)
+        return torch.from_numpy(out.astype(np.int64).reshape(rows, spec.LEAGUE_STATS_WORDS))
 
     def league_stats_count(self, games=None, count=None):
         """Adds the CURRENT records of `games` (game ids; None: games 0..count-1, count None: every game) to the league table - for
@@ -189,16 +193,11 @@ class VecCatanEnv(object):
         _lib.check(self.L.catan_league_stats_count(self.h, _ptr(g), m, _stream()))
 
     # ---- game records (include/catan_hip_tuning.h "game records"; record.py)
-    def _record_call(self, name):
-        if not hasattr(self.L, name):
-            raise _lib.CatanHipError(f"the loaded library has no {name}")
-        return getattr(self.L, name)
-
     def enable_recording(self, games, capacity=8192):
         """Binds one record slot to each game of `games` (ids, each at most once; up to 4096) with room for `capacity` actions (up to
         65535); the slots start idle (arm_recording).  An empty list frees everything.  Until armed, and while off, a step costs nothing."""
         g = torch.as_tensor(games, device=self.device).to(torch.int32).contiguous().reshape(-1)
-        _lib.check(self._record_call("catan_record_enable")(self.h, _ptr(g) if g.numel() else None, int(g.numel()), int(capacity), _stream()))
+        _lib.check(self._entry("catan_record_enable")(self.h, _ptr(g) if g.numel() else None, int(g.numel()), int(capacity), _stream()))
         self._record_slots, self._record_capacity, self._record_cfg = int(g.numel()), int(capacity), {}
 
     def arm_recording(self, slots=None, at_deal=False):
@@ -209,7 +208,7 @@ class VecCatanEnv(object):
         if slots is not None:
             a = np.ascontiguousarray(np.asarray(slots).reshape(-1), dtype=np.int32)
             arr, k = a.ctypes.data_as(C.c_void_p), int(a.size)
-        _lib.check(self._record_call("catan_record_arm")(self.h, arr, k, _record.RECORD_AT_DEAL if at_deal else _record.RECORD_NOW, _stream()))
+        _lib.check(self._entry("catan_record_arm")(self.h, arr, k, _record.RECORD_AT_DEAL if at_deal else _record.RECORD_NOW, _stream()))
         cfg = _record.cfg_dict(self.cfg, self._reward_annealing_factor)
         for s in (range(self._record_slots) if slots is None else a.tolist()):
             self._record_cfg[int(s)] = cfg
@@ -217,7 +216,7 @@ class VecCatanEnv(object):
     def recording_status(self):
         """-> int64 [m, 4] (host): state (record.IDLE / WAIT_DEAL / RECORDING / SEALED), game, length, flags per slot; waits for the stream"""
         out = np.zeros((max(self._record_slots, 1), 4), dtype=np.uint32)
-        _lib.check(self._record_call("catan_record_status")(self.h, out.ctypes.data_as(C.c_void_p), _stream()))
+        _lib.check(self._entry("catan_record_status")(self.h, out.ctypes.data_as(C.c_void_p), _stream()))
         return torch.from_numpy(out[:self._record_slots].astype(np.int64))
 
     def recordings(self, slots=None, sealed_only=True):
@@ -236,25 +235,20 @@ class VecCatanEnv(object):
             start, fin = np.zeros(spec.STATE_WORDS, dtype=np.int32), np.zeros(spec.STATE_WORDS, dtype=np.int32)
             acts, hdr = np.zeros((max(rows, 1), spec.ACTION_WORDS), dtype=np.int32), np.zeros(4, dtype=np.uint32)
             vp = lambda x: x.ctypes.data_as(C.c_void_p)
-            _lib.check(self._record_call("catan_record_read")(self.h, s, vp(start), vp(fin), vp(acts), vp(hdr), _stream()))
+            _lib.check(self._entry("catan_record_read")(self.h, s, vp(start), vp(fin), vp(acts), vp(hdr), _stream()))
             assert int(hdr[0]) == state and int(hdr[2]) == length, (hdr, status[s])      # (nothing ran in between)
             out.append(_record.GameRecord(self.seed, self.env_id0 + game, self._record_cfg[s], start, fin if state == _record.SEALED else None,
                                           acts[:rows], length, bool(flags & _record.F_TRUNCATED), bool(flags & _record.F_FROM_DEAL)))
         return out
 
     # ---- start pool (include/catan_hip_tuning.h "start pool"; start_pool.py)
-    def _start_pool_call(self, name):
-        if not hasattr(self.L, name):
-            raise _lib.CatanHipError(f"the loaded library has no {name}")
-        return getattr(self.L, name)
-
     def set_start_pool(self, blobs, fresh_share=0.0, weights=None):
         """From now on a game that is re-dealt (auto_reset) or dealt by reset() starts from one of `blobs` - [m, 736], numpy or tensor, the
         orientation of export_state, up to 65536 unfinished positions - except for the share `fresh_share` of deals, which stay fresh.
         The game keeps its own draw counter: the same position in two games rolls different dice.  The env keeps its own copy; the
         counters (start_pool_counts) start at zero.  A second call replaces the pool.  weights: see set_start_pool_weights (None: every
         entry is equally likely; a new pool never inherits the weights of the one it replaces)."""
-        fn = self._start_pool_call("catan_start_pool_set")
+        fn = self._entry("catan_start_pool_set")
         share = float(fresh_share)
         if not 0.0 <= share <= 1.0:                      # (also refuses nan)
             raise ValueError(f"fresh_share must be in [0, 1], got {fresh_share}")
@@ -268,11 +262,11 @@ class VecCatanEnv(object):
         w = None if weights is None else self._start_pool_weights(weights, int(b.shape[0]))      # (refused before any call)
         _lib.check(fn(self.h, _ptr(bt) if bt.numel() else None, int(b.shape[0]), int(round(share * 65536)), _stream()))
         if w is not None:
-            _lib.check(self._start_pool_call("catan_start_pool_set_weights")(self.h, _ptr(w), _stream()))
+            _lib.check(self._entry("catan_start_pool_set_weights")(self.h, _ptr(w), _stream()))
 
     def _start_pool_weights(self, weights, m):
         """-> the weights as a device tensor of m uint32 values (held in int32 storage), checked on the host"""
-        self._start_pool_call("catan_start_pool_set_weights")
+        self._entry("catan_start_pool_set_weights")
         w = weights.detach().cpu().numpy() if torch.is_tensor(weights) else np.asarray(weights)
         if w.dtype.kind not in "iu":
             raise ValueError(f"start pool weights must be integers, got {w.dtype}")
@@ -289,11 +283,11 @@ class VecCatanEnv(object):
         """The installed pool's entries are drawn in proportion to `weights` from now on: an integer array or tensor of m values in
         0..2^32-1 whose sum is in 1..2^32-1 (ValueError otherwise, before any call).  An entry of weight 0 is never installed; all-ones
         weights draw exactly what the uniform pool draws.  None: uniform again.  Waits for the env's streams."""
-        fn = self._start_pool_call("catan_start_pool_set_weights")
+        fn = self._entry("catan_start_pool_set_weights")
         if weights is None:
             _lib.check(fn(self.h, None, _stream()))
             return
-        m = max(int(self._start_pool_call("catan_start_pool_size")(self.h)), 0)
+        m = max(int(self._entry("catan_start_pool_size")(self.h)), 0)
         if m == 0:
             raise _lib.CatanHipError("set_start_pool_weights: no start pool is installed (set_start_pool)")
         _lib.check(fn(self.h, _ptr(self._start_pool_weights(weights, m)), _stream()))
@@ -303,12 +297,8 @@ class VecCatanEnv(object):
         "start pool: weighted picks and per-entry outcomes"); the table starts at zero and every game the env holds counts as freshly
         dealt until its next deal - enable in front of the reset() that deals from the pool.  focus_pid: PlayerId 1..4 per game (0:
         none) of the seat whose own results are wanted; the env keeps an int32 copy on the device.  on=False stops the tallies."""
-        fn = self._start_pool_call("catan_start_pool_outcomes_enable")
-        focus = None
-        if on and focus_pid is not None:
-            focus = torch.as_tensor(focus_pid, device=self.device).to(torch.int32).contiguous().clone()
-            if focus.shape != (self.n,):
-                raise ValueError(f"focus_pid: one PlayerId per game ({self.n}), got shape {tuple(focus.shape)}")
+        fn = self._entry("catan_start_pool_outcomes_enable")
+        focus = self._per_game_i32("focus_pid", focus_pid) if on and focus_pid is not None else None
         _lib.check(fn(self.h, int(bool(on)), _ptr(focus), _stream()))
         self._start_pool_focus = focus           # (the library reads it whenever a game finishes)
 
@@ -317,24 +307,20 @@ class VecCatanEnv(object):
         the per-entry arrays by field name (spec.START_POOL_OUTCOME_FIELDS), the "fresh" row by name, and the derived win_share_by_pid
         [m, 4] and focus_win_share [m] (NaN where no game was tallied), of the games finished since outcomes were enabled (or last read
         with reset=True); waits for the current stream"""
-        fn = self._start_pool_call("catan_start_pool_outcomes_read")
-        assert int(self._start_pool_call("catan_start_pool_outcomes_words")()) == spec.START_POOL_OUTCOME_WORDS
-        m = max(int(self._start_pool_call("catan_start_pool_size")(self.h)), 0)
-        out = np.zeros(2 + (m + 1) * spec.START_POOL_OUTCOME_WORDS, dtype=np.uint64)
-        _lib.check(fn(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), int(bool(reset)), _stream()))
+        assert int(self._entry("catan_start_pool_outcomes_words")()) == spec.START_POOL_OUTCOME_WORDS
+        m = max(int(self._entry("catan_start_pool_size")(self.h)), 0)
+        out = self._read_u64("catan_start_pool_outcomes_read", 2 + (m + 1) * spec.START_POOL_OUTCOME_WORDS, reset)
         return spec.start_pool_outcomes_dict(out.astype(np.int64), m)
 
     def clear_start_pool(self):
         """every later deal is fresh again, draw for draw as on an env that never had a pool"""
-        _lib.check(self._start_pool_call("catan_start_pool_clear")(self.h, _stream()))
+        _lib.check(self._entry("catan_start_pool_clear")(self.h, _stream()))
 
     def start_pool_counts(self, reset=False):
         """-> {"pool": deals that took a pool position, "fresh": deals that stayed fresh while the pool was installed, "per_entry": int64 [m]
         installs of each entry} since set_start_pool (or the last read with reset=True); waits for the current stream"""
-        fn = self._start_pool_call("catan_start_pool_read")
-        m = max(int(self._start_pool_call("catan_start_pool_size")(self.h)), 0)
-        out = np.zeros(2 + m, dtype=np.uint64)
-        _lib.check(fn(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), int(bool(reset)), _stream()))
+        m = max(int(self._entry("catan_start_pool_size")(self.h)), 0)
+        out = self._read_u64("catan_start_pool_read", 2 + m, reset)
         return {"pool": int(out[0]), "fresh": int(out[1]), "per_entry": out[2:].astype(np.int64)}
 
     def close(self):

@@ -169,11 +169,7 @@ class RolloutCollector(object):
         beside the counts.  start_pool_sampling "balanced" (implies the outcomes): behind every rollout the tallies are added to the
         pool (StartPool.add_outcomes; self.start_pool) and the entries' weights for the next rollout become its balanced_weights() - the
         positions whose result is still open are drawn more often.  The defaults (False, "uniform") make no call."""
-        if start_pool_sampling not in ("uniform", "balanced"):
-            raise ValueError(f"start_pool_sampling must be 'uniform' or 'balanced', got {start_pool_sampling!r}")
-        if (start_pool_outcomes or start_pool_sampling != "uniform") and start_pool is None:
-            raise ValueError("start_pool_outcomes / start_pool_sampling need a start_pool")
-        self.env, self.policy, self.T = env, policy, num_steps
+        self.env,self.policy, self.T = env, policy, num_steps
         self.league_stats, self.policy_of_pid = bool(league_stats), None
         self.deferred_window = self.DEFAULT_DEFERRED_WINDOW if deferred_window is None else int(deferred_window)
         self.act_buckets = None if act_buckets is None else tuple(sorted(set(int(b) for b in act_buckets) | {env.n}))
@@ -221,19 +217,31 @@ class RolloutCollector(object):
         if self.record_games:
             env.enable_recording(list(range(self.record_games)))
             env.arm_recording(at_deal=True)
-        self.start_pool_on = start_pool is not None
-        if self.start_pool_on:
-            env.set_start_pool(getattr(start_pool, "blobs", start_pool), start_pool_fresh)
-        self.start_pool_sampling = start_pool_sampling
-        self.start_pool_outcomes = bool(start_pool_outcomes) or start_pool_sampling == "balanced"
-        self.start_pool = None
-        if self.start_pool_outcomes:
-            from . import start_pool as _start_pool
-            self.start_pool = start_pool if isinstance(start_pool, _start_pool.StartPool) else _start_pool.StartPool(start_pool)
-            env.enable_start_pool_outcomes(self.active_pid)
-            if start_pool_sampling == "balanced":
-                env.set_start_pool_weights(self.start_pool.balanced_weights())
+        self.install_start_pool(start_pool, start_pool_fresh, start_pool_outcomes, start_pool_sampling)
         self.reset()
+
+    def install_start_pool(self, pool, fresh_share=0.0, outcomes=False, sampling="uniform"):
+        """The one place that puts a start pool on the env, for the constructor's start_pool arguments and for TrainingLoop (TrainArgs'):
+        `pool` as the constructor takes it, or the path of a saved pool; then the outcomes and, under "balanced", the first weights.
+        None makes no call.  The games the env holds are not touched: the caller resets."""
+        if sampling not in ("uniform", "balanced"):
+            raise ValueError(f"start_pool_sampling must be 'uniform' or 'balanced', got {sampling!r}")
+        if (outcomes or sampling != "uniform") and pool is None:
+            raise ValueError("start_pool_outcomes / start_pool_sampling need a start_pool")
+        self.start_pool_on, self.start_pool_sampling = pool is not None, sampling
+        self.start_pool_outcomes = bool(outcomes) or sampling == "balanced"
+        self.start_pool = None
+        if pool is None:
+            return
+        from . import start_pool as _start_pool
+        if isinstance(pool, str):
+            pool = _start_pool.load(pool)
+        self.env.set_start_pool(getattr(pool, "blobs", pool), fresh_share)
+        if self.start_pool_outcomes:
+            self.start_pool = pool if isinstance(pool, _start_pool.StartPool) else _start_pool.StartPool(pool)
+            self.env.enable_start_pool_outcomes(self.active_pid)
+            if sampling == "balanced":
+                self.env.set_start_pool_weights(self.start_pool.balanced_weights())
 
     def set_opponents(self, nets, opp_index):
         """nets: the distinct opponent nets in play; opp_index int64 [N,3]: which of them plays policy slots 1..3 of

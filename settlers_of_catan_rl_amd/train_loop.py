@@ -96,21 +96,7 @@ class TrainingLoop(object):
             # the pool on the env (unless the collector was built with one), then ONE reset: the first rollout's games already come from
             # the pool at the configured share; the collector's per-game bookkeeping starts over with them
             if not getattr(collector, "start_pool_on", False):
-                pool = self.args.start_pool
-                if isinstance(pool, str):
-                    from . import start_pool as _start_pool
-                    pool = _start_pool.load(pool)
-                env.set_start_pool(getattr(pool, "blobs", pool), self.args.start_pool_fresh)
-                collector.start_pool_on = True
-                if self.args.start_pool_outcomes or self.args.start_pool_sampling != "uniform":
-                    if self.args.start_pool_sampling not in ("uniform", "balanced"):
-                        raise ValueError(f"start_pool_sampling must be 'uniform' or 'balanced', got {self.args.start_pool_sampling!r}")
-                    from . import start_pool as _start_pool
-                    collector.start_pool = pool if isinstance(pool, _start_pool.StartPool) else _start_pool.StartPool(pool)
-                    collector.start_pool_outcomes, collector.start_pool_sampling = True, self.args.start_pool_sampling
-                    env.enable_start_pool_outcomes(collector.active_pid)
-                    if self.args.start_pool_sampling == "balanced":
-                        env.set_start_pool_weights(collector.start_pool.balanced_weights())
+                collector.install_start_pool(self.args.start_pool, self.args.start_pool_fresh, self.args.start_pool_outcomes, self.args.start_pool_sampling)
             env.reset()
             env.start_pool_counts(reset=True)           # (the counts of a rollout are those of its own deals)
             collector.reset()

@@ -303,9 +303,14 @@ def _episodes(finished):
     return np.array(rows, dtype=np.int64).reshape(-1, eso.COLS)
 
 
-def test_outcomes_beside_the_other_hooks(hip_lib, pools):
+@pytest.mark.parametrize("window", [None, 1, 4], ids=["lockstep", "deferred-1", "deferred-4"])
+def test_outcomes_beside_the_other_hooks(hip_lib, pools, window):
     """the finished-game statistics, the league scoreboard and the recorder run at the same hook: each table equals its own oracle over
-    the twin's finished games, the outcome table equals the twin's, and the sealed records replay to their final blobs"""
+    the twin's finished games, the outcome table equals the twin's, and the sealed records replay to their final blobs.  Lock-step steps
+    reach the re-deal of step_impl and the two installs of the slow path; step_deferred (windows 1 and 4, wr.STEP_CAP calls and the flush,
+    every hook on as well: none is refused inside an open sequence, only enabling and reading are) reaches the slow path's two fresh deals,
+    on the side stream and on the window's own.  The finished-game bound of the deferred cases is test_deferred_equals_the_twin's (same
+    pool, seed and calls); how many records seal there depends on which games wait, so one is asked for and the count is printed."""
     num_nets = 3
     env, twin = _pair(pools[64], 0, wr.weights_64())
     slot, net = lso.maps(N, num_nets, 4)
@@ -314,14 +319,19 @@ def test_outcomes_beside_the_other_hooks(hip_lib, pools):
     env.reset(); twin.reset()
     env.enable_recording(list(range(N)), capacity=wr.STEP_CAP)
     env.arm_recording(at_deal=True)
-    for t in range(150):
-        a = env.sample_scripted_actions()
-        a_h = a.cpu().numpy()
-        env.step(a); twin.step(torch.from_numpy(a_h))
-    _same_state(env, twin, "after 150 steps")
+    if window is None:
+        for t in range(150):
+            a = env.sample_scripted_actions()
+            a_h = a.cpu().numpy()
+            env.step(a); twin.step(torch.from_numpy(a_h))
+        where, min_seen, min_recs = "after 150 steps", 32, 8
+    else:
+        _deferred(env, twin, wr.STEP_CAP, window)
+        where, min_seen, min_recs = "after the flush", 16, 1
+    _same_state(env, twin, where)
     o = _same_outcomes(env, twin)
     ep = _episodes(twin.finished)
-    assert len(ep) == o["seen"] >= 32
+    assert len(ep) == o["seen"] >= min_seen and o["skipped"] == 0
     want = eso.counters(ep, 0, wr.FOCUS)
     got = env.episode_stats_words()
     assert got == want, (eso.named(got), eso.named(want))
@@ -330,7 +340,8 @@ def test_outcomes_beside_the_other_hooks(hip_lib, pools):
     assert named["episodes"] == o["games"].sum() and named["focus_episodes"] == o["focus_games"].sum() and named["focus_wins"] == o["focus_wins"].sum()
     assert named["turns_sum"] == o["turns_sum"].sum()                               # the same field: the final turn number
     recs = env.recordings()
-    assert len(recs) >= 8
+    print("driver", "lock-step" if window is None else f"deferred, window {window}", "finished", o["seen"], "sealed records", len(recs))
+    assert len(recs) >= min_recs and env.invalid_action_count() == 0
     for rec in recs[:8]:
         final, _rew, done, rejected = rr.replay_on_cpu(rec.seed, rec.game_id, rec.start_blob, rec.actions, **rec.cfg)
         assert np.array_equal(final, rec.final_blob) and done[-1] and not rejected.any()

@@ -7,9 +7,9 @@ a round and their order rotates from round to round, so that drift of the machin
 usage: bench_start_pool_weighted.py [--games N] [--calls K] [--warmup W] [--runs R] [--entries M] [--parent-library libcatan_hip.so]
                                     [--bench-runs B] [--out profiles/start_pool_weighted_bench.txt]
 
---parent-library: a libcatan_hip.so built from the parent commit; its off-path runs as one more configuration in every round, and bench.py
-runs under it in turn with this commit's.  An off case of this commit passes if its mean lies inside the spread (min..max) of the
-parent's runs (or on its better side).  The on cases are reported and not bounded.
+--parent-library: a libcatan_hip.so built from the parent commit; every configuration also runs under it, beside this commit's run in every
+round (the on cases too: they need the parent's ABI to be this commit's), and bench.py runs under it in turn with this commit's.  A case
+of this commit passes if its mean lies inside the spread (min..max) of the parent's runs (or on its better side).
 A call is: the uniform-random sampler (catan_sample_random_actions), then the step - the same in every configuration.  Timed with the
 host clock around K calls that end in a device synchronise.  The pool's entries are the unfinished states of the first M games after 600
 random steps; the weights are M seeded values in 0..65 535, every eighth of them 0."""
@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 
 
 def _use_library(path):
-    """the parent commit's library under this commit's Python (the off-path uses nothing new)"""
+    """the parent commit's library under this commit's Python"""
     os.environ["CATAN_ALLOW_STALE_LIB"] = "1"
     from settlers_of_catan_rl_amd import _lib
     _lib.LIB_PATH = os.path.abspath(path)
@@ -130,7 +130,7 @@ def main():
     configs = [("off", "off", None), (f"uniform, {a.entries} entries", "uniform", None), (f"weighted, {a.entries} entries", "weighted", None),
                ("weighted + outcomes", "weighted+outcomes", None)]
     if a.parent_library:
-        configs.insert(0, ("parent, off", "off", a.parent_library))
+        configs = [c for label, mode, _ in configs for c in ((f"parent, {label}", mode, a.parent_library), (label, mode, None))]
     rows = {c[0]: [] for c in configs}
     for r in range(a.runs):
         # (the order rotates from round to round: no configuration always runs behind the same neighbour)
@@ -142,7 +142,7 @@ def main():
                 print(text)
                 raise SystemExit(f"run {r} of {label!r} failed with exit code {rc}")      # nothing more is started on the device
             rows[label].append(json.loads(res[-1][7:]))
-            print(f"run {r} {label:28s} {res[-1][7:]}", flush=True)
+            print(f"run {r} {label:34s} {res[-1][7:]}", flush=True)
     bench = []
     for r in range(a.bench_runs):
         for label, lib in ([("parent", a.parent_library)] if a.parent_library else []) + [("change", None)]:
@@ -166,12 +166,14 @@ def main():
         lines.append(key[:-3])
         for label, _, _ in configs:
             v = [x[key] for x in rows[label]]
-            lines.append(f"  {label:28s} runs {' '.join(f'{x:8.2f}' for x in v)}   mean {sum(v) / len(v):8.2f}   min {min(v):8.2f}   max {max(v):8.2f}")
-        if a.parent_library:
-            pv, ov = [x[key] for x in rows["parent, off"]], [x[key] for x in rows["off"]]
+            lines.append(f"  {label:34s} runs {' '.join(f'{x:8.2f}' for x in v)}   mean {sum(v) / len(v):8.2f}   min {min(v):8.2f}   max {max(v):8.2f}")
+        for label, _, lib in configs if a.parent_library else []:
+            if lib:
+                continue
+            pv, ov = [x[key] for x in rows["parent, " + label]], [x[key] for x in rows[label]]
             mean = sum(ov) / len(ov)
             where = "inside" if min(pv) <= mean <= max(pv) else ("BELOW (faster than)" if mean < min(pv) else "ABOVE (slower than)")
-            lines.append(f"  off against the parent: mean {mean:.2f} {where} the parent's spread {min(pv):.2f}..{max(pv):.2f}")
+            lines.append(f"  {label} against the parent: mean {mean:.2f} {where} the parent's spread {min(pv):.2f}..{max(pv):.2f}")
         lines.append("")
     for label, mode, _ in configs:
         if mode == "off":
