@@ -1,11 +1,40 @@
 """Hand-written HIP kernels used inside the (otherwise PyTorch) policy net: fused small-sequence attention
 (csrc/catan_nn.hip).  torch is plumbing: tensors, streams, autograd registration."""
 import ctypes as C
-
+import math
 import os
+import weakref
+
+import numpy as np
 import torch
 
 from . import _lib
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The switches.  Every one is ON by default and selects the path the net trains and acts through; "off" keeps an older or a
+# plainer path alive as the oracle of a test or as one side of an A/B run (tools/ab_step_switches.py toggles them inside one
+# process).  Tests and tools set these module-level names, so they stay module-level names.
+WGRAD_BIG = True                # off: the trunk's wide weight gradient by the library's GEMM (wgrad_big_supported; ab_step_switches)
+CONCAT_ROWS = True              # off: concat_rows is torch.cat (ab_step_switches)
+GATHER_RANGES = True            # off: gather_ranges is plain indexing with autograd's index_put backward (ab_step_switches)
+FANOUT_GATHER = True            # off: fanout_gather_ranges leaves the three gradients' sum to autograd (ab_step_switches)
+fused_heads_enabled = True      # off: the acting heads through torch ops - the oracle of tests/test_gpu_ppo_pipeline.py and
+                                # tests/test_gpu_act_stats.py (tools/profile_graphed_act.py)
+chained_heads_enabled = True    # off: one fused kernel per head with torch glue between them instead of heads_chain (same tests)
+# CATAN_TE_WORKSPACE=0: every training forward of the tile encoder takes its activations from the allocator (the way out for retain_graph).
+TE_WORKSPACE = os.environ.get("CATAN_TE_WORKSPACE", "1") != "0"
+# CATAN_TE_TRAIN_UNFUSED=1: the encoder trains through its sub-layers' kernels with autograd between them - the path of unsupported
+# shapes and dtypes, and the oracle of the fused path's test (tests/test_gpu_ppo_pipeline.py), which sets the attribute.
+TE_TRAIN_UNFUSED = os.environ.get("CATAN_TE_TRAIN_UNFUSED") == "1"
+# CATAN_CATEGORICAL_BITS=0: the learner's heads read float mask rows expanded and gathered per minibatch step instead of the packed
+# mask bits (policy._evaluate_compact; ab_step_switches)
+CATEGORICAL_BITS = os.environ.get("CATAN_CATEGORICAL_BITS", "1") != "0"
+# Three more live on their objects, below:
+#   grad_arena.enabled      off: every backward accumulator is its own torch.zeros (ab_step_switches)
+#   wgrad_queue.enabled     off: each weight gradient is launched inside its layer's backward (ab_step_switches)
+#   weight_images.enabled   off (or CATAN_WEIGHT_IMAGES=0): every use of a weight casts it, as autocast does - the oracle of
+#                           tests/test_gpu_ppo_pipeline.py's test_weight_images_change_nothing
+# (policy.RECURRENT_BATCHED, the one switch of the net outside this module, is listed with policy.py's own.)
 
 SUPPORTED = {(19, 4, 16), (25, 4, 4)}
 
@@ -171,32 +200,44 @@ def grad_zeros(shape, device):
     return grad_arena.zeros(tuple(shape) if isinstance(shape, (tuple, list)) else (int(shape),), device)
 
 
+def _ln_forward(x, w, b, eps, relu):
+    """LayerNorm (+ ReLU) over the last dim of x -> (x aligned, y, and w, b as the fp32 vectors the kernels read): what a backward saves"""
+    x = _aligned(x)
+    D = x.shape[-1]
+    y = torch.empty_like(x)
+    wf, bf = w.detach().float().contiguous(), b.detach().float().contiguous()
+    _lib.check(_lib.lib().catan_layer_norm_fwd(_ptr(x), _ptr(wf), _ptr(bf), _ptr(y), x.numel() // D, D, float(eps), int(relu),
+                                               int(x.dtype == torch.bfloat16), _stream()))
+    return x, y, wf, bf
+
+
+def _ln_backward(x, wf, bf, dy, eps, relu, dres=None):
+    """-> (dx, dw, db) of _ln_forward; dres: the gradient of a residual stream that left beside the LayerNorm (_PreNorm), added
+    into dx by the kernel (catan_layer_norm_bwd_res)"""
+    D = x.shape[-1]
+    dy = _aligned(dy.to(x.dtype))
+    dx = torch.empty_like(x)
+    dw, db = grad_zeros((2, D), x.device)       # both accumulators: one fill
+    tail = (_ptr(dx), _ptr(dw), _ptr(db), x.numel() // D, D, float(eps), int(relu), int(x.dtype == torch.bfloat16), _stream())
+    if dres is None:
+        _lib.check(_lib.lib().catan_layer_norm_bwd(_ptr(x), _ptr(wf), _ptr(bf), _ptr(dy), *tail))
+    else:
+        dres = _aligned(dres.to(x.dtype))
+        _lib.check(_lib.lib().catan_layer_norm_bwd_res(_ptr(x), _ptr(wf), _ptr(bf), _ptr(dy), _ptr(dres), *tail))
+    return dx, dw, db
+
+
 class _SmallLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, eps, relu):
-        D = x.shape[-1]
-        x = _aligned(x)
-        y = torch.empty_like(x)
-        rows = x.numel() // D
-        wf, bf = w.detach().float().contiguous(), b.detach().float().contiguous()
-        _lib.check(_lib.lib().catan_layer_norm_fwd(_ptr(x), _ptr(wf), _ptr(bf), _ptr(y), rows, D, float(eps), int(relu),
-                                                   int(x.dtype == torch.bfloat16), _stream()))
+        x, y, wf, bf = _ln_forward(x, w, b, eps, relu)
         ctx.save_for_backward(x, wf, bf)
         ctx.eps, ctx.relu = eps, relu
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, wf, bf = ctx.saved_tensors
-        D = x.shape[-1]
-        rows = x.numel() // D
-        dy = _aligned(dy.to(x.dtype))
-        dx = torch.empty_like(x)
-        dwb = grad_zeros((2, D), x.device)      # both accumulators
-        dw, db = dwb[0], dwb[1]
-        _lib.check(_lib.lib().catan_layer_norm_bwd(_ptr(x), _ptr(wf), _ptr(bf), _ptr(dy), _ptr(dx), _ptr(dw), _ptr(db), rows, D,
-                                                   float(ctx.eps), int(ctx.relu), int(x.dtype == torch.bfloat16), _stream()))
-        return dx, dw, db, None, None
+        return _ln_backward(*ctx.saved_tensors, dy, ctx.eps, ctx.relu) + (None, None)
 
 
 class _PreNorm(torch.autograd.Function):
@@ -206,36 +247,16 @@ class _PreNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, eps):
-        D = x.shape[-1]
-        x = _aligned(x)
-        y = torch.empty_like(x)
-        rows = x.numel() // D
-        wf, bf = w.detach().float().contiguous(), b.detach().float().contiguous()
-        _lib.check(_lib.lib().catan_layer_norm_fwd(_ptr(x), _ptr(wf), _ptr(bf), _ptr(y), rows, D, float(eps), 0,
-                                                   int(x.dtype == torch.bfloat16), _stream()))
+        x, y, wf, bf = _ln_forward(x, w, b, eps, False)
         ctx.save_for_backward(x, wf, bf)
         ctx.eps = eps
         return y, x.view_as(x)
 
     @staticmethod
     def backward(ctx, dy, dres):
-        x, wf, bf = ctx.saved_tensors
-        D = x.shape[-1]
-        rows = x.numel() // D
-        dx = torch.empty_like(x)
-        dwb = grad_zeros((2, D), x.device)
-        L = _lib.lib()
-        if dy is None:
+        if dy is None:                          # (only the residual stream was used: its gradient is x's)
             return dres, None, None, None
-        dy = _aligned(dy.to(x.dtype))
-        if dres is None:
-            _lib.check(L.catan_layer_norm_bwd(_ptr(x), _ptr(wf), _ptr(bf), _ptr(dy), _ptr(dx), _ptr(dwb[0]), _ptr(dwb[1]), rows, D,
-                                              float(ctx.eps), 0, int(x.dtype == torch.bfloat16), _stream()))
-        else:
-            dres = _aligned(dres.to(x.dtype))
-            _lib.check(L.catan_layer_norm_bwd_res(_ptr(x), _ptr(wf), _ptr(bf), _ptr(dy), _ptr(dres), _ptr(dx), _ptr(dwb[0]), _ptr(dwb[1]),
-                                                  rows, D, float(ctx.eps), 0, int(x.dtype == torch.bfloat16), _stream()))
-        return dx, dwb[0], dwb[1], None
+        return _ln_backward(*ctx.saved_tensors, dy, ctx.eps, False, dres) + (None,)
 
 
 def pre_norm_supported(x, ln):
@@ -275,9 +296,8 @@ class _WeightImages(object):
 
     def clear(self):
         """forget every image (they are rebuilt on their next use); the sources of dropped nets are released with them"""
-        global _TE_IMAGES
         self.entries, self.by_key, self.dirty, self.table = [], {}, True, None
-        _TE_IMAGES = None
+        _TE_IMAGES.clear()
 
     def add(self, src2, dst_view, mode, out):
         """src2: 2-D fp32 view of a parameter; dst_view: a view of the image buffer indexed like src2 (any strides)"""
@@ -319,9 +339,6 @@ class _WeightImages(object):
         if not self.enabled or not self.entries:
             return
         if self.dirty:
-            import ctypes as C
-            import numpy as np
-
             class Row(C.Structure):
                 _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("s_r", C.c_int64), ("s_c", C.c_int64),
                             ("d_r", C.c_int64), ("d_c", C.c_int64), ("mode", C.c_int32), ("pad", C.c_int32)]
@@ -339,6 +356,7 @@ class _WeightImages(object):
 
 
 weight_images = _WeightImages()
+_TE_IMAGES = weakref.WeakKeyDictionary()      # tile encoder -> its _TeImages (not on the module: a deepcopy - inference_copy - must not carry them along)
 
 
 def bf16_of(w):
@@ -396,9 +414,7 @@ class _LinearTallSkinny(torch.autograd.Function):
                 return (dx,) + wgrad_queue.take(x2, dy2, w, b)      # the weight gradient joins the grouped launch at the end of the backward pass
             if ctx.window is not None and wgrad_queue.accepts(ctx.window[0], b):
                 return (dx,) + wgrad_queue.take(x2, dy2, ctx.window[0], b, col0=ctx.window[1])
-        acc = grad_zeros((O * I + O,), dy.device)          # dw and db
-        dw, db = acc[:O * I].view(O, I), (acc[O * I:] if ctx.has_bias else None)
-        _lib.check(_lib.lib().catan_linear_wgrad(_ptr(x2), _ptr(dy2), _ptr(dw), _ptr(db), x2.shape[0], I, O, _stream()))
+        dw, db = _wgrad(x2, dy2, ctx.has_bias)
         if ctx.pad:
             dw = dw[:, :I - ctx.pad]
             dx = None if dx is None else dx[..., :I - ctx.pad]
@@ -431,16 +447,20 @@ def _linear_rows(x, w, b, aux=None, mode=MODE_NONE):
     return y.reshape(x.shape[:-1] + (N,))
 
 
+def _wgrad_acc(O, I, has_bias, device, zeroed=True):
+    """(dw [O, I], db [O] or None) of a linear layer as slices of ONE fp32 buffer: zeroed (one fill) for the kernels that add into it"""
+    acc = grad_zeros((O * I + O,), device) if zeroed else torch.empty(O * I + O, dtype=torch.float32, device=device)
+    return acc[:O * I].view(O, I), (acc[O * I:] if has_bias else None)
+
+
 def _wgrad(x2, dy2, has_bias):
     O, I = dy2.shape[1], x2.shape[1]
-    acc = grad_zeros((O * I + O,), dy2.device)             # dw and db
-    dw, db = acc[:O * I].view(O, I), (acc[O * I:] if has_bias else None)
+    dw, db = _wgrad_acc(O, I, has_bias, dy2.device)
     _lib.check(_lib.lib().catan_linear_wgrad(_ptr(x2), _ptr(dy2), _ptr(dw), _ptr(db), x2.shape[0], I, O, _stream()))
     return dw, db
 
 
 _WGRAD_BIG_WS = {}
-WGRAD_BIG = True        # (tools/ab_step_switches.py)
 
 
 def wgrad_big_supported(rows, in_features, out_features):
@@ -450,7 +470,6 @@ def wgrad_big_supported(rows, in_features, out_features):
 def wgrad_big(x2, dy2, has_bias=True):
     """x2 [rows, I], dy2 [rows, O] bf16 -> (dW fp32 [O, I], db fp32 [O] or None) through catan_linear_wgrad_big: 128 x 128 output tiles, the
     row groups' partial tiles added in index order (deterministic)."""
-    import ctypes as C
     rows, I, O = x2.shape[0], x2.shape[1], dy2.shape[1]
     L = _lib.lib()
     need = int(L.catan_wgrad_big_workspace_floats(rows, I, O))
@@ -458,9 +477,8 @@ def wgrad_big(x2, dy2, has_bias=True):
     ws = _WGRAD_BIG_WS.get(key)
     if ws is None or ws.numel() < need:
         ws = _WGRAD_BIG_WS[key] = torch.empty(need, dtype=torch.float32, device=x2.device)
-    out = torch.empty(O * I + O, dtype=torch.float32, device=x2.device)
-    dw, db = out[:O * I].view(O, I), (out[O * I:] if has_bias else None)
-    _lib.check(L.catan_linear_wgrad_big(_ptr(_aligned(x2)), _ptr(_aligned(dy2)), _ptr(dw), I, _ptr(db) if has_bias else None, _ptr(ws), rows, I, O, 0, _stream()))
+    dw, db = _wgrad_acc(O, I, has_bias, x2.device, zeroed=False)        # (the kernel writes every element: nothing is added into it)
+    _lib.check(L.catan_linear_wgrad_big(_ptr(_aligned(x2)), _ptr(_aligned(dy2)), _ptr(dw), I, _ptr(db), _ptr(ws), rows, I, O, 0, _stream()))
     return dw, db
 
 
@@ -495,14 +513,12 @@ def linear_big(x, w, b):
 def wgrad_grouped(pairs, has_bias=True):
     """[(x2 [rows_k, I_k], dy2 [rows_k, O_k]) bf16] -> [(dW_k fp32 [O_k, I_k], db_k [O_k])] through catan_linear_wgrad_grouped: problems of
     the same tile shape share launches (the heads' first layers on their row segments: 44 launches -> 2)."""
-    import ctypes as C
     probs = (_lib.CatanWgradProblem * len(pairs))()
     keep, out = [], []
     for k, (x2, dy2) in enumerate(pairs):
         x2, dy2 = _aligned(x2), _aligned(dy2.to(torch.bfloat16))
         O, I = dy2.shape[1], x2.shape[1]
-        acc = grad_zeros((O * I + O,), dy2.device)
-        dw, db = acc[:O * I].view(O, I), (acc[O * I:] if has_bias else None)
+        dw, db = _wgrad_acc(O, I, has_bias, dy2.device)
         probs[k] = _lib.CatanWgradProblem(x2.data_ptr(), dy2.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None, x2.shape[0], I, O)
         keep.append((x2, dy2)); out.append((dw, db))
     _lib.check(_lib.lib().catan_linear_wgrad_grouped(probs, len(pairs), _stream()))
@@ -566,11 +582,14 @@ class _FFNResidual(torch.autograd.Function):
         return dx, dw1, db1, dw2, db2, (dy if ctx.needs_input_grad[5] else None)
 
 
+def _bf16_compute(x=None):
+    """the products run in bf16: bf16 autocast is on, or the input x (when one is given) is bf16 already"""
+    return (x is not None and x.dtype == torch.bfloat16) or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+
+
 def fused_sublayer_supported(x, dim, hidden=None):
     """training / inference on the GPU in bf16 with enough rows for the row kernels, widths they are built for"""
-    if not x.is_cuda or x.shape[-1] != dim or dim % 8 or x.numel() // dim < ROWS_KERNEL_MIN_ROWS:
-        return False
-    if not (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)):
+    if not x.is_cuda or x.shape[-1] != dim or dim % 8 or x.numel() // dim < ROWS_KERNEL_MIN_ROWS or not _bf16_compute(x):
         return False
     L = _lib.lib()
     rows = x.numel() // dim
@@ -599,9 +618,7 @@ def linear_inference(x, w, b=None):
 
 def linear_supported(x, w):
     """bf16 compute on the GPU (autocast or bf16 input), widths the kernel is built for, and enough rows to be worth it."""
-    if not x.is_cuda or w.dim() != 2:
-        return False
-    if not (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16)):
+    if not x.is_cuda or w.dim() != 2 or not _bf16_compute(x):
         return False
     O, I = w.shape
     rows = x.numel() // x.shape[-1]        # (x may be wider than w: rows already zero-padded to whole 16-byte pieces, _LinearTallSkinny)
@@ -618,7 +635,6 @@ def use_tuned_gemms():
     tunableop_gfx950.csv: rocBLAS / hipBLASLt solution indices per (transposes, m, n, k) at the rollout, minibatch and value-
     chunk widths).  Tuning itself stays off: shapes that are not in the file use the library default.  The file carries
     the library versions it was made with; TunableOp ignores it when they differ."""
-    import os
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tunableop_gfx950.csv")
     if not (torch.cuda.is_available() and os.path.exists(path)):
         return False
@@ -679,48 +695,106 @@ def _pad1(v, n):
     return out
 
 
-def tile_encoder_pack(te):
-    """The tile encoder's parameters in the layout of catan_tile_encoder_fwd (include/catan_hip.h), cached on the module and
-    re-packed when a parameter changed (optimiser step, inference-copy refresh)."""
-    params = list(te.parameters())
-    stamp = (sum(p._version for p in params), params[0].device, params[0].data_ptr())
-    cache = getattr(te, "_fused_pack", None)
-    if cache is not None and cache[0] == stamp:
-        return cache[1], cache[2]
-    def lb(bias, n):                                           # a Linear bias as bf16 autocast hands it to the GEMM (rounded once)
-        return _pad1(bias.to(torch.bfloat16), n)
+def _cached_pack(entry, params, build, extra=()):
+    """The hit / rebuild logic of every pack cache.  entry: the cache's `(stamp, *tensors)` or None; the stamp is the version counters,
+    device and address of `params` plus `extra`.  -> the entry itself on a hit (build() is not called), else `(stamp, *build())` - with
+    the new values copied INTO the entry's tensors where it has some on the same device: a captured hipGraph of the forward
+    (GraphedAct) holds their addresses.  (A build() that filled the entry's own tensors returns them and nothing is copied.)"""
+    stamp = (sum(p._version for p in params), params[0].device, params[0].data_ptr()) + tuple(extra)
+    if entry is not None and entry[0] == stamp:
+        return entry
     with torch.no_grad():
-        w = [_pad2(te.first_layer.weight, 64, 64)]
-        v = [lb(te.first_layer.bias, 64), _pad1(te.norm_2.weight, 64), _pad1(te.norm_2.bias, 64)]
-        for layer in te.encoder_layers:
-            mha, ffn = layer.multi_headed_attention, layer.pointwise_net
-            w += [_pad2(torch.cat([n.weight for n in mha.qkv_nets], 0), 192, 64), _pad2(mha.out_proj_net.weight, 64, 64),
-                  _pad2(ffn.linear1.weight, 128, 64), _pad2(ffn.linear2.weight, 64, 128)]
-            v += [_pad1(layer.sublayers[0].norm.weight, 64), _pad1(layer.sublayers[0].norm.bias, 64),
-                  lb(torch.cat([n.bias for n in mha.qkv_nets], 0), 192), lb(mha.out_proj_net.bias, 64),
-                  _pad1(layer.sublayers[1].norm.weight, 64), _pad1(layer.sublayers[1].norm.bias, 64),
-                  lb(ffn.linear1.bias, 128), lb(ffn.linear2.bias, 64)]
-        w.append(_pad2(te.out_proj.weight, 32, 64))
-        v += [lb(te.out_proj.bias, 32), _pad1(te.norm.weight, 32), _pad1(te.norm.bias, 32)]
-        wts, vecs = torch.cat(w).contiguous(), torch.cat(v).contiguous()
-    L = _lib.lib()
-    assert wts.numel() == L.catan_tile_encoder_weight_elems() and vecs.numel() == L.catan_tile_encoder_vec_elems()
-    if cache is not None and cache[1].device == wts.device:
-        # re-pack IN PLACE: a captured hipGraph of the forward (GraphedAct) holds these buffers' addresses
-        cache[1].copy_(wts); cache[2].copy_(vecs)
-        wts, vecs = cache[1], cache[2]
-    te._fused_pack = (stamp, wts, vecs)
+        new = tuple(build())
+        if entry is not None and entry[1].device == new[0].device:
+            for old, t in zip(entry[1:], new):
+                if old is not t:
+                    old.copy_(t)
+            new = entry[1:]
+    return (stamp,) + new
+
+
+def _te_blocks(te):
+    """The ONE description of catan_tile_encoder_fwd's parameter layout (include/catan_hip_nn.h), in the header's order ->
+    (weight blocks, vector blocks).  A weight block: (parameters stacked along its rows, padded rows, padded columns), bf16 row-major.
+    A vector block: (parameters one after the other, padded length, rounded), fp32 - rounded: a Linear bias, which holds the value bf16
+    autocast hands to the GEMM (rounded once); LayerNorm vectors are exact."""
+    W = lambda mods, rows, cols: ([m.weight for m in mods], rows, cols)
+    B = lambda mods, n: ([m.bias for m in mods], n, True)
+    N = lambda norm, n: [([norm.weight], n, False), ([norm.bias], n, False)]
+    wts = [W([te.first_layer], 64, 64)]
+    vecs = [B([te.first_layer], 64)] + N(te.norm_2, 64)
+    for layer in te.encoder_layers:
+        mha, ffn, qkv = layer.multi_headed_attention, layer.pointwise_net, list(layer.multi_headed_attention.qkv_nets)
+        wts += [W(qkv, 192, 64), W([mha.out_proj_net], 64, 64), W([ffn.linear1], 128, 64), W([ffn.linear2], 64, 128)]
+        vecs += N(layer.sublayers[0].norm, 64) + [B(qkv, 192), B([mha.out_proj_net], 64)] + N(layer.sublayers[1].norm, 64) \
+            + [B([ffn.linear1], 128), B([ffn.linear2], 64)]
+    wts.append(W([te.out_proj], 32, 64))
+    vecs += [B([te.out_proj], 32)] + N(te.norm, 32)
     return wts, vecs
 
 
-def tile_encoder_supported(te, tiles):
-    """inference (no autograd), GPU, bf16 compute, the reference's sizes (19 tiles x 60 features, 64 wide, 4 heads, 2 layers, 25 out)"""
-    if torch.is_grad_enabled() or not tiles.is_cuda or tiles.dim() != 3 or tuple(tiles.shape[1:]) != (19, 60):
-        return False
-    if not (tiles.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)):
-        return False
+def _te_buffers(device):
+    """zeroed (wts bf16, vecs fp32) of the kernel's sizes: the padding of _te_blocks' blocks stays zero"""
+    L = _lib.lib()
+    return (torch.zeros((L.catan_tile_encoder_weight_elems(),), dtype=torch.bfloat16, device=device),
+            torch.zeros((L.catan_tile_encoder_vec_elems(),), dtype=torch.float32, device=device))
+
+
+def _te_fill(te, wts, vecs, put):
+    """Walks _te_blocks over a (wts, vecs) pair of _te_buffers: put(parameter as a 2-D view, its view of the buffer, mode) for every
+    parameter; mode is catan_weight_images': 0 into bf16, 1 into fp32 as it is, 2 into fp32 through bf16 (the rounded vectors)."""
+    wblocks, vblocks = _te_blocks(te)
+    o = 0
+    for params, rows, cols in wblocks:
+        blk, r = wts[o:o + rows * cols].view(rows, cols), 0
+        for p in params:                                       # each in the top-left corner of its rows of the block
+            put(p, blk[r:r + p.shape[0], :p.shape[1]], 0)
+            r += p.shape[0]
+        o += rows * cols
+    assert o == wts.numel()
+    o = 0
+    for params, n, rounded in vblocks:
+        c = 0
+        for p in params:
+            put(p.view(1, -1), vecs[o + c:o + c + p.numel()].view(1, -1), 2 if rounded else 1)
+            c += p.numel()
+        o += n
+    assert o == vecs.numel()
+
+
+def _te_put_copy(src, dst, mode):
+    dst.copy_(src.to(torch.bfloat16) if mode == 2 else src)
+
+
+def tile_encoder_pack(te):
+    """The tile encoder's parameters in the layout of catan_tile_encoder_fwd (_te_blocks), cached on the module and re-packed - into
+    the same buffers - when a parameter changed (optimiser step, inference-copy refresh)."""
+    cache = getattr(te, "_fused_pack", None)
+    params = list(te.parameters())
+
+    def build():
+        same = cache is not None and cache[1].device == params[0].device
+        bufs = cache[1:] if same else _te_buffers(params[0].device)
+        _te_fill(te, *bufs, _te_put_copy)
+        return bufs
+
+    entry = _cached_pack(cache, params, build)
+    if entry is not cache:
+        te._fused_pack = entry
+    return entry[1:]
+
+
+def _te_reference_sizes(te):
+    """the reference's tile encoder: 60 features, 64 wide, 4 heads, 2 layers with a x2 pointwise net, 25 out"""
     return (te.first_layer.weight.shape == (64, 60) and len(te.encoder_layers) == 2 and te.out_proj.weight.shape == (25, 64)
             and te.encoder_layers[0].multi_headed_attention.heads == 4 and te.encoder_layers[0].pointwise_net.linear1.weight.shape == (128, 64))
+
+
+def tile_encoder_supported(te, tiles):
+    """inference (no autograd), GPU, bf16 compute, the reference's sizes (19 tiles x 60 features, _te_reference_sizes)"""
+    if torch.is_grad_enabled() or not tiles.is_cuda or tiles.dim() != 3 or tuple(tiles.shape[1:]) != (19, 60) or not _bf16_compute(tiles):
+        return False
+    return _te_reference_sizes(te)
 
 
 def tile_encoder_forward(te, tiles):
@@ -810,9 +884,6 @@ class _ConcatRows(torch.autograd.Function):
         return tuple(out)
 
 
-CONCAT_ROWS = True            # (A/B switch)
-
-
 def concat_rows(parts):
     """torch.cat(parts, -1); on the GPU for 2..4 bf16 matrices of equal row count whose rows are whole 16-byte pieces: one kernel at the
     HBM rate"""
@@ -868,10 +939,6 @@ class _FanOutGatherRanges(torch.autograd.Function):
             dy = torch.zeros((1, ctx.W), dtype=(g0 if g0 is not None else g1).dtype, device=perm.device)
             return _scatter_ranges(dy, perm, (), ctx.U, g0, g1), None, None, None
         return _scatter_ranges(dy, perm, ctx.ranges, ctx.U, g0, g1), None, None, None
-
-
-GATHER_RANGES = True          # (A/B switches)
-FANOUT_GATHER = True
 
 
 def _gather_ranges_ok(src, perm, ranges):
@@ -949,73 +1016,32 @@ def _rows_product(x2, wt):
     return y if y is not None else torch.nn.functional.linear(x2, wt)
 
 
-def _ln_backward(x, w, b, dy, eps, relu):
-    """-> (dx, dw, db) of LayerNorm (+ ReLU) over the last dim of bf16 x [rows, D]"""
-    rows, D = x.shape
-    dx = torch.empty_like(x)
-    dwb = grad_zeros((2, D), x.device)
-    wf, bf = w.detach().float().contiguous(), b.detach().float().contiguous()
-    _lib.check(_lib.lib().catan_layer_norm_bwd(_ptr(x), _ptr(wf), _ptr(bf), _ptr(dy), _ptr(dx), _ptr(dwb[0]), _ptr(dwb[1]), rows, D, float(eps), int(relu), 1, _stream()))
-    return dx, dwb[0], dwb[1]
-
-
 class _TeImages(object):
     """The training-side images of one tile encoder's parameters in weight_images: the packed weight / vector blocks of
     catan_tile_encoder_fwd (tile_encoder_pack's layout) and the transposed bf16 weights its backward chain multiplies by."""
 
     def __init__(self, te):
-        L = _lib.lib()
         dev = te.first_layer.weight.device
-        self.wts = torch.zeros((L.catan_tile_encoder_weight_elems(),), dtype=torch.bfloat16, device=dev)
-        self.vecs = torch.zeros((L.catan_tile_encoder_vec_elems(),), dtype=torch.float32, device=dev)
         self.entries = []
-        wo, vo = [0], [0]
-
-        def W(param, rows, cols):                    # a weight block [rows][cols] of the pack, the parameter in its top-left corner
-            blk = self.wts[wo[0]:wo[0] + rows * cols].view(rows, cols)
-            self.entries.append(weight_images.add(param, blk[:param.shape[0], :param.shape[1]], 0, None))
-            wo[0] += rows * cols
-
-        def Wrows(params, rows, cols):               # ... several parameters stacked along the rows (Q, K, V)
-            blk = self.wts[wo[0]:wo[0] + rows * cols].view(rows, cols)
-            r = 0
-            for prm in params:
-                self.entries.append(weight_images.add(prm, blk[r:r + prm.shape[0], :prm.shape[1]], 0, None))
-                r += prm.shape[0]
-            wo[0] += rows * cols
-
-        def V(params, n, mode):                      # a vector block of n floats; mode 2: a Linear bias as bf16 autocast rounds it
-            o = 0
-            for prm in params:
-                self.entries.append(weight_images.add(prm.view(1, -1), self.vecs[vo[0] + o:vo[0] + o + prm.numel()].view(1, -1), mode, None))
-                o += prm.numel()
-            vo[0] += n
+        register = lambda src, dst, mode: self.entries.append(weight_images.add(src, dst, mode, None))
+        self.wts, self.vecs = _te_buffers(dev)
+        _te_fill(te, self.wts, self.vecs, register)
 
         def T(params):                               # transposed bf16 [in][sum of outs]
             outs = sum(prm.shape[0] for prm in params)
             buf = torch.empty((params[0].shape[1], outs), dtype=torch.bfloat16, device=dev)
             c = 0
             for prm in params:
-                self.entries.append(weight_images.add(prm, buf[:, c:c + prm.shape[0]].t(), 0, None))
+                register(prm, buf[:, c:c + prm.shape[0]].t(), 0)
                 c += prm.shape[0]
             return buf
 
-        W(te.first_layer.weight, 64, 64)
-        V([te.first_layer.bias], 64, 2); V([te.norm_2.weight], 64, 1); V([te.norm_2.bias], 64, 1)
         self.w2t, self.w1t, self.wot, self.wqt = [], [], [], []
         for layer in te.encoder_layers:
             mha, ffn = layer.multi_headed_attention, layer.pointwise_net
-            Wrows([n.weight for n in mha.qkv_nets], 192, 64); W(mha.out_proj_net.weight, 64, 64); W(ffn.linear1.weight, 128, 64); W(ffn.linear2.weight, 64, 128)
-            V([layer.sublayers[0].norm.weight], 64, 1); V([layer.sublayers[0].norm.bias], 64, 1)
-            V([n.bias for n in mha.qkv_nets], 192, 2); V([mha.out_proj_net.bias], 64, 2)
-            V([layer.sublayers[1].norm.weight], 64, 1); V([layer.sublayers[1].norm.bias], 64, 1)
-            V([ffn.linear1.bias], 128, 2); V([ffn.linear2.bias], 64, 2)
             self.w2t.append(T([ffn.linear2.weight])); self.w1t.append(T([ffn.linear1.weight]))
             self.wot.append(T([mha.out_proj_net.weight])); self.wqt.append(T([n.weight for n in mha.qkv_nets]))
-        W(te.out_proj.weight, 32, 64)
-        V([te.out_proj.bias], 32, 2); V([te.norm.weight], 32, 1); V([te.norm.bias], 32, 1)
         self.wpt = T([te.out_proj.weight])
-        assert wo[0] == self.wts.numel() and vo[0] == self.vecs.numel()
         self.stamp = (te.first_layer.weight.data_ptr(), dev)
 
     def current(self):
@@ -1025,21 +1051,10 @@ class _TeImages(object):
         return self
 
 
-_TE_IMAGES = None
-
-
 def _te_images(te):
-    global _TE_IMAGES
-    if _TE_IMAGES is None:
-        import weakref
-        _TE_IMAGES = weakref.WeakKeyDictionary()              # (not on the module: a deepcopy - inference_copy - must not carry them along)
     im = _TE_IMAGES.get(te)
     if im is None or im.stamp != (te.first_layer.weight.data_ptr(), te.first_layer.weight.device):
-        im = _TeImages(te)
-        if _TE_IMAGES is None:                                # (the registry started over while the images were being registered)
-            import weakref
-            _TE_IMAGES = weakref.WeakKeyDictionary()
-        _TE_IMAGES[te] = im
+        im = _TE_IMAGES[te] = _TeImages(te)       # (the registry may start over while these are registered: the entry is set afterwards)
     return im.current()
 
 
@@ -1069,11 +1084,6 @@ class _TeWorkspace(object):
         return cls.Lease(cls.buf)
 
 
-# CATAN_TE_WORKSPACE=0: every training forward of the tile encoder takes its activations from the allocator (the way out for retain_graph).
-# CATAN_TE_TRAIN_UNFUSED=1: the encoder trains through its sub-layers' kernels with autograd between them - the path of unsupported
-# shapes and dtypes, and the oracle of the fused path's test, which sets the attribute.  Both are read here, once.
-TE_WORKSPACE = os.environ.get("CATAN_TE_WORKSPACE", "1") != "0"
-TE_TRAIN_UNFUSED = os.environ.get("CATAN_TE_TRAIN_UNFUSED") == "1"
 # what the training forward stores for the backward: catan_te_saves_t's fields without the LayerNorm outputs (see _TileEncoderTrain.forward)
 _TE_STORED = tuple((n, w) for n, w in _TE_SAVES if not n.startswith(("n1_", "n2_")))
 
@@ -1136,13 +1146,13 @@ class _TileEncoderTrain(torch.autograd.Function):
         def wt(*names, l=None):                 # the transposed bf16 weight(s) [in][sum of outs] as a per-use cast (weight_images off)
             return torch.cat([P[pos(n, l)] for n in names], 0).to(bf).t().contiguous()
 
-        def f32(name, l):                       # a LayerNorm vector as the kernels read it
+        def f32(name, l=None):                  # a LayerNorm vector as the kernels read it
             return P[pos(name, l)].detach().float().contiguous()
 
         with torch.autocast("cuda", enabled=False):
             # ---- the final LayerNorm (+ ReLU) and the output projection
             d = _aligned(dout[:, :475].reshape(T, 25).to(bf))
-            dp, g[pos("norm_w")], g[pos("norm_b")] = _ln_backward(sv["p"], P[pos("norm_w")], P[pos("norm_b")], d, eps, True)
+            dp, g[pos("norm_w")], g[pos("norm_b")] = _ln_backward(sv["p"], f32("norm_w"), f32("norm_b"), d, eps, True)
             dx = _rows_product(dp, im.wpt if im is not None else wt("out_w"))                     # [T, 64]
             g[pos("out_w")], g[pos("out_b")] = _wgrad(sv["xfin"], dp, True)
             for l in reversed(range(_TE_LAYERS)):
@@ -1174,7 +1184,7 @@ class _TileEncoderTrain(torch.autograd.Function):
                 for k, n in enumerate("qkv"):
                     g[pos("w" + n, l)], g[pos("b" + n, l)] = a["wqkv"][64 * k:64 * k + 64], a["bqkv"][64 * k:64 * k + 64]
             # ---- the first LayerNorm (+ ReLU) and the first layer
-            da0, g[pos("norm2_w")], g[pos("norm2_b")] = _ln_backward(sv["a0"], P[pos("norm2_w")], P[pos("norm2_b")], dx, eps, True)
+            da0, g[pos("norm2_w")], g[pos("norm2_b")] = _ln_backward(sv["a0"], f32("norm2_w"), f32("norm2_b"), dx, eps, True)
             dw0, g[pos("first_b")] = _wgrad(sv["tiles64"], da0, True)
             g[pos("first_w")] = dw0[:, :60]
         if ctx.lease is not None:
@@ -1186,13 +1196,9 @@ def tile_encoder_train_supported(te, tiles):
     """training on the GPU under bf16 autocast, the reference's sizes; TE_TRAIN_UNFUSED keeps the sub-layer kernels"""
     if not torch.is_grad_enabled() or not tiles.is_cuda or tiles.dim() != 3 or tuple(tiles.shape[1:]) != (19, 60) or tiles.requires_grad:
         return False
-    if TE_TRAIN_UNFUSED:
+    if TE_TRAIN_UNFUSED or not _bf16_compute():          # (autocast alone: bf16 tiles without it keep the sub-layers' path)
         return False
-    if not (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16):
-        return False
-    return (te.first_layer.weight.shape == (64, 60) and len(te.encoder_layers) == 2 and te.out_proj.weight.shape == (25, 64)
-            and te.encoder_layers[0].multi_headed_attention.heads == 4 and te.encoder_layers[0].pointwise_net.linear1.weight.shape == (128, 64)
-            and te.first_layer.weight.dtype == torch.float32
+    return (_te_reference_sizes(te) and te.first_layer.weight.dtype == torch.float32
             and all(abs(m.eps - 1e-5) < 1e-12 for m in [te.norm, te.norm_2] + [s.norm for l in te.encoder_layers for s in l.sublayers]))
 
 
@@ -1207,15 +1213,12 @@ def head_pack(head, trunk_dim):
     that the shared trunk product covers; the rest (conditioning columns, head 5's trade features) is W1e."""
     params = [head.mlp_1.weight, head.mlp_2.weight, head.mlp_2.bias, head.norm.weight, head.norm.bias,
               head.distribution.linear.weight, head.distribution.linear.bias]
-    stamp = (sum(p._version for p in params), params[0].device, params[0].data_ptr(), trunk_dim)
-    cache = getattr(head, "_fused_pack", None)
-    if cache is not None and cache[0] == stamp:
-        return cache[1], cache[2]
-    L = _lib.lib()
-    K = head.distribution.linear.weight.shape[0]
-    e = head.mlp_1.weight.shape[1] - trunk_dim
-    assert head.mlp_2.weight.shape == (128, 128) and K <= 80 and 0 <= e <= 32
-    with torch.no_grad():
+
+    def build():
+        L = _lib.lib()
+        K = head.distribution.linear.weight.shape[0]
+        e = head.mlp_1.weight.shape[1] - trunk_dim
+        assert head.mlp_2.weight.shape == (128, 128) and K <= 80 and 0 <= e <= 32
         w1e = torch.zeros((32, 128), dtype=torch.bfloat16, device=params[0].device)
         if e:
             w1e[:e] = head.mlp_1.weight[:, trunk_dim:].t().to(torch.bfloat16)
@@ -1223,22 +1226,20 @@ def head_pack(head, trunk_dim):
         rb = lambda b, n: _pad1(b.to(torch.bfloat16), n)             # a Linear bias as bf16 autocast hands it to the GEMM
         vec = torch.cat([_pad1(head.norm.weight, 128), _pad1(head.norm.bias, 128), rb(head.mlp_2.bias, 128),
                          rb(head.distribution.linear.bias, 80)]).contiguous()
-    assert wts.numel() == L.catan_head_weight_elems() and vec.numel() == L.catan_head_vec_elems()
-    if cache is not None and cache[1].device == wts.device:
-        cache[1].copy_(wts); cache[2].copy_(vec)
-        wts, vec = cache[1], cache[2]
-    head._fused_pack = (stamp, wts, vec)
-    return wts, vec
+        assert wts.numel() == L.catan_head_weight_elems() and vec.numel() == L.catan_head_vec_elems()
+        return wts, vec
+
+    cache = getattr(head, "_fused_pack", None)
+    entry = _cached_pack(cache, params, build, extra=(trunk_dim,))
+    if entry is not cache:
+        head._fused_pack, head._fused_trunk_dim = entry, trunk_dim       # (the trunk width by name: refresh_packs re-packs with it)
+    return entry[1:]
 
 
 def head_fused_supported(pre_all):
     """inference (no autograd) on the GPU with the trunk product in bf16"""
     return (not torch.is_grad_enabled()) and pre_all.is_cuda and pre_all.dtype == torch.bfloat16 and pre_all.stride(-1) == 1 \
         and pre_all.stride(0) % 8 == 0 and fused_heads_enabled
-
-
-fused_heads_enabled = True
-chained_heads_enabled = True       # the heads' glue inside the fused kernels (heads_chain); off: one kernel per head + torch glue
 
 
 def head_sample(head, trunk_dim, pre, cond, mask, deterministic=False, generator=None, with_entropy=False):
@@ -1262,14 +1263,13 @@ def head_sample(head, trunk_dim, pre, cond, mask, deterministic=False, generator
     assert ncond == head.mlp_1.weight.shape[1] - trunk_dim and mask.shape[1] == K
     action = torch.empty(B, dtype=torch.int64, device=pre.device)
     logp = torch.empty(B, dtype=torch.float32, device=pre.device)
+    args = (_ptr(pre), pre.stride(0), _ptr(cond), cond.stride(0) if cond is not None else 0, ncond, _ptr(wts), _ptr(vec), float(head.norm.eps), K,
+            _ptr(mask), mask.stride(0), _ptr(u), _ptr(action), _ptr(logp))
     if with_entropy:
         ent = torch.empty(B, dtype=torch.float32, device=pre.device)
-        _lib.check(_lib.lib().catan_head_fwd_entropy(_ptr(pre), pre.stride(0), _ptr(cond), cond.stride(0) if cond is not None else 0, ncond, _ptr(wts),
-                                                     _ptr(vec), float(head.norm.eps), K, _ptr(mask), mask.stride(0), _ptr(u), _ptr(action), _ptr(logp),
-                                                     _ptr(ent), B, _stream()))
+        _lib.check(_lib.lib().catan_head_fwd_entropy(*args, _ptr(ent), B, _stream()))
         return action, logp, ent
-    _lib.check(_lib.lib().catan_head_fwd(_ptr(pre), pre.stride(0), _ptr(cond), cond.stride(0) if cond is not None else 0, ncond, _ptr(wts), _ptr(vec),
-                                         float(head.norm.eps), K, _ptr(mask), mask.stride(0), _ptr(u), _ptr(action), _ptr(logp), B, _stream()))
+    _lib.check(_lib.lib().catan_head_fwd(*args, B, _stream()))
     return action, logp
 
 
@@ -1281,19 +1281,18 @@ def head5_custom_pack(head):
     """head 5's custom_mlp + custom_norm as catan_head_chain reads them (fp32 [480]; W and b rounded to bf16 as autocast hands
     them to the GEMM), cached and refreshed in place like head_pack"""
     params = [head.custom_mlp.weight, head.custom_mlp.bias, head.custom_norm.weight, head.custom_norm.bias]
-    stamp = (sum(p._version for p in params), params[0].device, params[0].data_ptr())
-    cache = getattr(head, "_custom_pack", None)
-    if cache is not None and cache[0] == stamp:
-        return cache[1]
-    with torch.no_grad():
+
+    def build():
         r = lambda t: t.to(torch.bfloat16).float().reshape(-1)
         pack = torch.cat([r(head.custom_mlp.weight), r(head.custom_mlp.bias), head.custom_norm.weight.float(), head.custom_norm.bias.float()]).contiguous()
-    assert pack.numel() == 480 and float(head.custom_norm.eps) == float(head.norm.eps)
-    if cache is not None and cache[1].device == pack.device:
-        cache[1].copy_(pack)
-        pack = cache[1]
-    head._custom_pack = (stamp, pack)
-    return pack
+        assert pack.numel() == 480 and float(head.custom_norm.eps) == float(head.norm.eps)
+        return (pack,)
+
+    cache = getattr(head, "_custom_pack", None)
+    entry = _cached_pack(cache, params, build)
+    if entry is not cache:
+        head._custom_pack = entry
+    return entry[1]
 
 
 HEAD_STATS_SLOT = 26        # include/catan_hip_nn.h catan_head_chain_ex: entropy [26], scratch [27], log record [28:32]
@@ -1405,13 +1404,11 @@ def card_summary(ids, lens, params, eps):
     return _CardSummary.apply(ids, lens.to(torch.int32).contiguous(), params, eps)
 
 
-import weakref
-_CARD_TABLES = weakref.WeakKeyDictionary()
+_CARD_TABLES = weakref.WeakKeyDictionary()      # attention module -> {id(norm): (cache entry, embedding, norm)}
 
 
 def card_summary_params(embedding, mha, norm):
     """the 544 floats catan_card_summary_* read (include/catan_hip_nn.h), from the module's weights"""
-    import math
     V, H, hd = embedding.num_embeddings, mha.heads, mha.hd
     w = torch.cat([n.weight for n in mha.qkv_nets], 0).float()
     b = torch.cat([n.bias for n in mha.qkv_nets], 0).float()
@@ -1425,22 +1422,20 @@ def card_summary_table(embedding, mha, norm):
     """(params [544], table [patterns, 16]) for inference, cached on the attention module per LayerNorm and rebuilt - IN PLACE: a
     captured hipGraph holds the addresses - when a weight changed (the inference copy is refreshed once per rollout)."""
     prm = [embedding.weight, norm.weight, norm.bias] + list(mha.parameters())
-    stamp = (sum(p._version for p in prm), prm[0].device, prm[0].data_ptr())
+
+    def build():
+        with torch.autocast(device_type="cuda", enabled=False):
+            params = card_summary_params(embedding, mha, norm).contiguous()
+            pid, plen = _pattern_lists(params.device)
+            table = torch.empty((pid.shape[0], 16), dtype=torch.float32, device=params.device)
+            _lib.check(_lib.lib().catan_card_summary_fwd(_ptr(pid), 1, pid.stride(0), _ptr(plen), _ptr(params), float(norm.eps), _ptr(table), None,
+                                                         pid.shape[0], _stream()))
+        return params, table
+
     caches = _CARD_TABLES.setdefault(mha, {})              # (not on the module: a deepcopy - inference_copy - must not carry them along)
-    cache = caches.get(id(norm))
-    if cache is not None and cache[0] == stamp:
-        return cache[1], cache[2]
-    with torch.no_grad(), torch.autocast(device_type="cuda", enabled=False):
-        params = card_summary_params(embedding, mha, norm).contiguous()
-        pid, plen = _pattern_lists(params.device)
-        table = torch.empty((pid.shape[0], 16), dtype=torch.float32, device=params.device)
-        _lib.check(_lib.lib().catan_card_summary_fwd(_ptr(pid), 1, pid.stride(0), _ptr(plen), _ptr(params), float(norm.eps), _ptr(table), None,
-                                                     pid.shape[0], _stream()))
-    if cache is not None and cache[1].device == params.device:
-        cache[1].copy_(params); cache[2].copy_(table)
-        params, table = cache[1], cache[2]
-    caches[id(norm)] = (stamp, params, table, embedding, norm)
-    return params, table
+    entry = _cached_pack(caches.get(id(norm), (None,))[0], prm, build)
+    caches[id(norm)] = (entry, embedding, norm)
+    return entry[1:]
 
 
 def card_summary_lookup(ids, lens, embedding, mha, norm):
@@ -1455,11 +1450,17 @@ def card_summary_lookup(ids, lens, embedding, mha, norm):
     return out
 
 
-def refresh_card_tables(module):
-    """brings every cached pattern table under `module` up to date in place (for captured graphs: policy.refresh_kernel_packs)"""
+def refresh_packs(module):
+    """Brings every parameter pack that EXISTS under `module` up to date, in place - the tile encoder's, the heads', head 5's custom
+    pack, the card pattern tables: what a forward does on its way and a captured hipGraph replay (GraphedAct) does not.  Builds none."""
     for m in module.modules():
-        for cache in list(_CARD_TABLES.get(m, {}).values()):
-            card_summary_table(cache[3], m, cache[4])
+        if getattr(m, "_fused_pack", None) is not None:
+            trunk_dim = getattr(m, "_fused_trunk_dim", None)         # (head_pack sets it; the tile encoder's pack has none)
+            tile_encoder_pack(m) if trunk_dim is None else head_pack(m, trunk_dim)
+        if getattr(m, "_custom_pack", None) is not None:
+            head5_custom_pack(m)
+        for _, embedding, norm in list(_CARD_TABLES.get(m, {}).values()):
+            card_summary_table(embedding, m, norm)
 
 
 class _MaskedCategorical(torch.autograd.Function):
@@ -1492,16 +1493,11 @@ class _MaskedCategorical(torch.autograd.Function):
         return dlogits, None, None, None
 
 
-# the learner's heads read packed mask bits (policy._evaluate_compact); "0": the float mask rows expanded and gathered per minibatch step
-CATEGORICAL_BITS = os.environ.get("CATAN_CATEGORICAL_BITS", "1") != "0"
-
-
 class _MaskedCategoricalBits(torch.autograd.Function):
     """k_categorical_bits_fwd / _bwd: _MaskedCategorical for given actions with the mask as bits of the packed mask rows (no float mask matrix)"""
 
     @staticmethod
     def forward(ctx, logits, packed, rows_idx, segs, given, given_ld):
-        import ctypes as C
         B, K = logits.shape
         logits = logits.contiguous()
         action = torch.empty(B, dtype=torch.int64, device=logits.device)
@@ -1517,7 +1513,6 @@ class _MaskedCategoricalBits(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _da, dlogp, dent):
-        import ctypes as C
         logits, packed, action, lse, ent = ctx.saved_tensors[:5]
         rows_idx = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
         B, K = logits.shape

@@ -1147,18 +1147,10 @@ class CatanPolicy(nn.Module):
         return c
 
     def refresh_kernel_packs(self):
-        """Brings the parameter packs the fused kernels read (the tile encoder's, nn_kernels.tile_encoder_pack) up to date, in
-        place - what a forward would do on its way; a captured hipGraph replay (GraphedAct) does not run that host code."""
-        te = self.observation_module.tile_encoder
-        if next(te.parameters()).is_cuda and getattr(te, "_fused_pack", None) is not None:
-            nn_kernels.tile_encoder_pack(te)
-        nn_kernels.refresh_card_tables(self.observation_module)
-        for h in self.action_head_module.action_heads:          # the fused head kernels' packs (nn_kernels.head_pack)
-            cache = getattr(h, "_fused_pack", None)
-            if cache is not None and h.mlp_2.weight.is_cuda:
-                nn_kernels.head_pack(h, cache[0][3])
-            if getattr(h, "_custom_pack", None) is not None and h.mlp_2.weight.is_cuda:
-                nn_kernels.head5_custom_pack(h)
+        """Brings the parameter packs the fused kernels read (nn_kernels.refresh_packs: the tile encoder's, the heads', the card
+        tables) up to date, in place - what a forward would do on its way; a captured hipGraph replay (GraphedAct) does not run
+        that host code."""
+        nn_kernels.refresh_packs(self)
 
     @torch.no_grad()
     def load_from(self, master):

@@ -26,7 +26,10 @@ and add exactly the gated dy to db; b is exactly 0 in some columns, where pre = 
 
 Further: rows do not depend on the grid (the first RPB + 1 rows of a launch equal a launch over those rows alone, bit for bit; k_lnr:
 the first 4096, its smallest launch); relu = 1 with every pre-activation > 0 equals relu = 0 bit for bit; the aligned and the misaligned
-path agree within the sum of their bounds."""
+path agree within the sum of their bounds.
+
+Last, the autograd functions nn_kernels builds on these entry points (_SmallLayerNorm, _PreNorm): what autograd returns for x, w and b
+against torch's own layer_norm differentiated in fp64, under the same rule (_judge_function)."""
 import ctypes as C
 
 import pytest
@@ -263,3 +266,100 @@ def test_aligned_and_misaligned_agree(hip_lib, D, dtype):
             for o in ("dw", "db"):
                 d = (ga[o].double() - gm[o].double()).abs()
                 assert bool((d <= ba[o] + bm[o]).all()), (D, dtype, rows, relu, o)
+
+
+# ------------------------------------------------------------------------------------- the autograd functions over these kernels
+def _torch_fp64(c, dy, relu, dres=None):
+    """torch's own layer_norm (+ relu) differentiated in fp64 on the case's inputs -> {dx, dw, db}; dres: the gradient of a second
+    use of x (the residual stream beside a pre-norm LayerNorm)"""
+    x, w, b = (c[k].double().requires_grad_() for k in ("x", "w", "b"))
+    y = torch.nn.functional.layer_norm(x, (c["D"],), w, b, EPS)
+    loss = ((torch.relu(y) if relu else y) * dy.double()).sum()
+    if dres is not None:
+        loss = loss + (x * dres.double()).sum()
+    return dict(zip(("dx", "dw", "db"), torch.autograd.grad(loss, (x, w, b))))
+
+
+def _judge_function(name, c, relu, dy, got, dres=None):
+    """this file's rule (_judge) on what an autograd function returned: the reference's dx, dw, db are torch's in fp64; the yardstick,
+    the summation terms of the column bound and the launch depth are layer_norm_reference's for the aligned path of this width.  With
+    dres the yardstick adds it to the LayerNorm term as the kernel does - that term rounded to the storage type first, then the sum."""
+    bf16 = c["x"].dtype == torch.bfloat16
+    ref = LN.ln_ref(c["x"], c["w"], c["b"], dy, EPS, relu)
+    ref.update(_torch_fp64(c, dy, relu, dres))
+    yard = LN.ln_yardstick(c["x"], c["w"], c["b"], dy, EPS, relu, bf16)
+    if dres is not None:
+        yard["dx"] = yard["dx"] + dres.float()
+        if bf16:
+            yard["dx"] = yard["dx"].to(torch.bfloat16).float()
+    got = dict(got, dw0=torch.zeros_like(got["dw"]), db0=torch.zeros_like(got["db"]))            # (fresh accumulators)
+    bad, _ = _judge(name, bf16, got, ref, yard, LN.launch_depth("aligned", c["D"], c["rows"]))
+    assert not bad, bad
+    _exact_row_checks(name, c, relu, got)
+
+
+def _layer(c):
+    ln = torch.nn.LayerNorm(c["D"], eps=EPS).cuda()
+    with torch.no_grad():
+        ln.weight.copy_(c["w"])
+        ln.bias.copy_(c["b"])
+    return ln
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
+@pytest.mark.parametrize("rows", [1, 67])
+@pytest.mark.parametrize("D", [25, 64])
+def test_small_layer_norm_function_vs_torch_fp64(hip_lib, D, rows, dtype):
+    """nn_kernels._SmallLayerNorm (small_layer_norm), with and without ReLU: y, and dx, dw, db from autograd, under the rule the kernel
+    behind it is held to above.  67 rows leave a row block partly filled; one row is the smallest launch."""
+    from settlers_of_catan_rl_amd import nn_kernels
+    c = _device_case(D, rows, "unit", LN.path_kernel("aligned", D)[1], dtype)
+    ln = _layer(c)
+    for relu in (0, 1):
+        dy = LN.gated_dy(c)[0] if relu else c["dy"]
+        x = c["x"].clone().requires_grad_()
+        assert nn_kernels.ln_supported(x, ln)
+        y = nn_kernels.small_layer_norm(x, ln, relu=bool(relu))
+        dx, dw, db = torch.autograd.grad(y, (x, ln.weight, ln.bias), dy)
+        assert dx.dtype == x.dtype and dw.dtype == db.dtype == torch.float32
+        _judge_function(f"function small D={D} {dtype} rows={rows} relu={relu}", c, relu, dy, {"y": y.detach(), "dx": dx, "dw": dw, "db": db})
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
+@pytest.mark.parametrize("rows", [1, 67])
+def test_pre_norm_function_vs_torch_fp64(hip_lib, rows, dtype):
+    """nn_kernels._PreNorm (pre_norm) at D = 64 in its three uses: both outputs consumed (x's whole gradient from
+    catan_layer_norm_bwd_res), only the normalised output, only the residual stream (x's gradient is dres, to the bit, and the LayerNorm's
+    parameters get nothing).  autograd hands a backward zeros for an output nobody used, so the `None` branches of the backward are
+    also called directly - the one for `dy is None` with no context at all: it returns before it reads or allocates anything."""
+    from types import SimpleNamespace
+    from settlers_of_catan_rl_amd import nn_kernels
+    D = 64
+    c = _device_case(D, rows, "unit", LN.path_kernel("aligned", D)[1], dtype)
+    ln = _layer(c)
+    dres = (c["dy"].float().flip(0) * 0.75 - 0.05).to(c["x"].dtype)
+    name = f"function pre_norm D={D} {dtype} rows={rows}"
+
+    def run(use_y, use_res):
+        x = c["x"].clone().requires_grad_()
+        assert nn_kernels.pre_norm_supported(x, ln)
+        y, res = nn_kernels.pre_norm(x, ln)
+        assert _same_bits(res.detach(), c["x"])
+        outs, grads = zip(*[p for p, used in (((y, c["dy"]), use_y), ((res, dres), use_res)) if used])
+        dx, dw, db = torch.autograd.grad(outs, (x, ln.weight, ln.bias), grads, allow_unused=True)
+        return y.detach(), dx, dw, db
+
+    y, dx, dw, db = run(True, True)
+    _judge_function(name + " both", c, 0, c["dy"], {"y": y, "dx": dx, "dw": dw, "db": db}, dres)
+    y, dx, dw, db = run(True, False)
+    _judge_function(name + " norm only", c, 0, c["dy"], {"y": y, "dx": dx, "dw": dw, "db": db})
+    _, dx, dw, db = run(False, True)
+    assert _same_bits(dx, dres), (name, "only the residual stream used: x's gradient is not dres")
+    assert all(g is None or not bool(g.any()) for g in (dw, db))
+    # the backward's own branches for a missing gradient
+    out = nn_kernels._PreNorm.backward(None, None, dres)
+    assert out[0] is dres and out[1:] == (None, None, None)
+    x = c["x"].clone()
+    ctx = SimpleNamespace(saved_tensors=(x, c["w"].contiguous(), c["b"].contiguous()), eps=EPS)
+    dx, dw, db, _ = nn_kernels._PreNorm.backward(ctx, c["dy"], None)
+    _judge_function(name + " dres None", c, 0, c["dy"], {"y": y, "dx": dx, "dw": dw, "db": db})
