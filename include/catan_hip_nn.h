@@ -93,6 +93,22 @@ int catan_ppo_diag(const float* logp, const float* old_logp, const float* adv, c
                    const float* returns, int64_t B, float clip, int use_norm, float norm_mean, float norm_std, const float* entropy,
                    const float* grad_norm, float max_grad_norm, double* block, double* workspace, catan_stream_t stream);
 
+/* The imitation term of kickstarting and its read-out in one launch, opt-in.  lp: device float [B], the joint log-prob
+ * of the teacher's action rows under the net; teacher: device int64 [B][18], those rows (column 0, the action type, is read).
+ * nll_i = -(double)lp_i.  loss: device float [1] = (float)(sum nll / B); dlp: device float [B] = (float)(-1.0 / B), the gradient of the
+ * loss by lp.  A row whose lp is not finite adds 0 to the loss, gets dlp 0 and is counted as skipped - expected never; the count is how
+ * a broken label shows.  ACCUMULATED into `block`: device double [catan_imitation_loss_words()] = 33, zeroed by the caller:
+ *    0 rows    1 calls    2 sum nll    3 max nll    4 rows with lp > -0.6931472f (more than half the mass on the teacher's whole action)
+ *    5 skipped rows    6..18 rows per teacher type 0..12    19..31 sum nll per teacher type    32 spare
+ * (skipped rows count in word 0 and 5 only).  Conventions of catan_ppo_diag: fp64 sums; workspace: device double
+ * [catan_imitation_loss_workspace_doubles()], ZERO before the first call and left all zero by every call; the workgroup that finishes
+ * last is the only writer of the block and adds the per-workgroup partials in index order - no atomic on the block, the same bits on
+ * every repeat; ALL CALLS INTO ONE BLOCK (and on one workspace) ON ONE STREAM.  B < 1 or a NULL pointer: CATAN_EINVAL. */
+int64_t catan_imitation_loss_words(void);
+int64_t catan_imitation_loss_workspace_doubles(void);
+int catan_imitation_loss(const float* lp, const int64_t* teacher, int64_t B, float* loss, float* dlp, double* block, double* workspace,
+                         catan_stream_t stream);
+
 /* Row gathers of the learner (RL/ppo/ppo.py:44-50 builds a minibatch with `[obs[i] for i in indices]`; here the rollout is one
  * (T + 1, N, 1 787) bf16 tensor and a minibatch 204 800 of its 3 574-byte rows).
  * catan_gather_rows: dst row j = src row idx[j]; rows of `row_bytes` (even) at any even address and pitch.

@@ -5,7 +5,8 @@
  * "finished-game statistics" (catan_episode_stats_*), which the rollout collector uses, and "rule-based player"
  * (catan_sample_scripted_actions), a fixed-strength opponent: the reference has no such interface to replace, and catan_hip.h stays the
  * reference's boundary.  "league results" (catan_league_stats_*) is a fourth: the collector's per-opponent scoreboard; "game records"
- * (catan_record_*) a fifth: whole games recorded on the device for a step-by-step replay.
+ * (catan_record_*) a fifth: whole games recorded on the device for a step-by-step replay; "teacher labels" (catan_complete_action_rows,
+ * catan_collector_label) a sixth: the rule-based player's actions as an imitation target for the learner.
  */
 #ifndef CATAN_HIP_TUNING_H
 #define CATAN_HIP_TUNING_H
@@ -253,6 +254,33 @@ int catan_start_pool_outcomes_read(catan_env_t* env, uint64_t* out_host, int32_t
  * CATAN_EINVAL, nothing launched: a null handle, null actions, n_rows <= 0, n_rows > n with games == NULL. */
 int catan_sample_scripted_actions(catan_env_t* env, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream);
 int64_t catan_scripted_fallback_count(catan_env_t* env, catan_stream_t stream);
+
+/* ---- teacher labels (csrc/catan_teacher.hip) ----
+ * catan_complete_action_rows makes any legal action row teacher-forceable through the net's heads.  The samplers (this player,
+ * catan_sample_random_actions) fill only the columns their action type uses; the heads evaluate EVERY column of every row and multiply
+ * the unused ones by 0, and column value 0 is often illegal under an unused head's mask (log-prob -inf, -inf x 0 = NaN).  The rule, per
+ * row of type t in 0..12 (head h -> column: 1 -> 1, 2 -> 2, 3 -> 3, 4 -> 4, 5 -> 5, 6 -> 6, 9 -> 15, 10 -> 16, 11 -> 17):
+ *   used, NEVER written: column 1 by Settlement / City, 2 Road, 3 MoveRobber, 4 PlayDev, 5 Respond, 6 Propose / Steal, 15 Exchange or
+ *   PlayDev with YoP / Monopoly, 16 Exchange or PlayDev with YoP, 17 Discard, 7..14 Propose;
+ *   every other column becomes the LOWEST LEGAL INDEX of the mask the head applies to the row (0 if that mask is empty): head 1 row 2 of
+ *   its (3, 54) block, head 6 row 2 of (3, 3), head 9 row 1 of (4, 5) (row 0 for Exchange; a PlayDev row ANDs row 2 for Monopoly, 3 for
+ *   YoP, else 1 - the card being column 4 after its own completion), the other heads their one row;
+ *   the trade lists of a row that is not Propose, with res = the deciding player's current_resources (obs_f[12:18]): column 7 = 0 if res
+ *   sums to 0, else the lowest r >= 1 with res[r] > 0; columns 8..10 = 0; column 11 = 0 if res sums to 0, else 1; columns 12..14 = 0.
+ * games / n_rows as for catan_sample_scripted_actions; actions: DEVICE int32 [n_rows][18], 8-BYTE ALIGNED (the 72-byte rows are read and
+ * written as 8-byte pairs; any device allocation is), edited in place.  The handle's packed masks
+ * must be current.  A row is left exactly as given when its type is outside 0..12, its game id is negative or out of range, or its game
+ * waits inside a catan_step_deferred sequence.  CATAN_EINVAL, nothing launched: as for catan_sample_scripted_actions. */
+int catan_complete_action_rows(catan_env_t* env, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream);
+/* Teacher labels in the rollout collector (catan_collector_pre / catan_collector_post of catan_hip.h).
+ * labels: int32 [n][18], a teacher's action row per game for the state the net decided in.  st_teacher: int16 [T][n][18], 4-BYTE ALIGNED
+ * (the 36-byte rows are written as nine 4-byte words); it gets the row of game g at the slot catan_collector_post stores the net's
+ * action of the same decision in - t = min(n_act[g], T - 1), for a game whose action the env consumes in this iteration and whose
+ * deciding seat is the active one.
+ * Called IN FRONT OF catan_collector_post with its counters4 / flags4 / active_pid / deciding / waiting_before: it reads n_act before
+ * the increment.  waiting_before may be NULL (catan_step); any other NULL pointer, n <= 0 or T <= 0: CATAN_EINVAL. */
+int catan_collector_label(int64_t n, int32_t T, const int64_t* counters4, const uint8_t* flags4, const int64_t* active_pid, const int32_t* deciding,
+                          const int32_t* labels, int16_t* st_teacher, const uint8_t* waiting_before, catan_stream_t stream);
 
 /* the rollout loops with a hipEvent around every kernel launch (recorded on the stream the kernel runs on); window <= 0: the
  * lock-step loop (step_idx0 as in catan_random_rollout), window > 0: the deferred loop (step_idx0 ignored).  kernel_ms is a HOST

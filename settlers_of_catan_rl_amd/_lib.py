@@ -65,23 +65,36 @@ BUILD_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 LLVM_OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
-def device_code_object(path=None):
-    """The gfx950 code object embedded in the library (clang offload bundle: magic, entry table, blobs) -> bytes"""
+# the translation units of the library, in link order: each brings a gfx950 code object of its own.  catan_abi.hip includes every other
+# kernel file; catan_teacher.hip is compiled apart so that the first code object is what it is without it
+TRANSLATION_UNITS = ("catan_abi.hip", "catan_teacher.hip")
+
+
+def device_code_objects(path=None):
+    """The gfx950 code objects embedded in the library, one per translation unit in link order (clang offload bundles: magic, entry
+    table, blobs) -> list of bytes"""
     import struct
     with open(LIB_PATH if path is None else path, "rb") as f:
         blob = f.read()
-    i = blob.find(b"__CLANG_OFFLOAD_BUNDLE__")
-    if i < 0:
-        raise CatanHipError("no offload bundle in the library")
-    n = struct.unpack_from("<Q", blob, i + 24)[0]
-    off = i + 32
-    for _ in range(n):
-        o, sz, tl = struct.unpack_from("<QQQ", blob, off)
-        triple = blob[off + 24:off + 24 + tl].decode()
-        off += 24 + tl
-        if "gfx950" in triple:
-            return blob[i + o:i + o + sz]
-    raise CatanHipError("no gfx950 code object in the library")
+    out, i = [], blob.find(b"__CLANG_OFFLOAD_BUNDLE__")
+    while i >= 0:
+        n = struct.unpack_from("<Q", blob, i + 24)[0]
+        off = i + 32
+        for _ in range(n):
+            o, sz, tl = struct.unpack_from("<QQQ", blob, off)
+            triple = blob[off + 24:off + 24 + tl].decode()
+            off += 24 + tl
+            if "gfx950" in triple:
+                out.append(blob[i + o:i + o + sz])
+        i = blob.find(b"__CLANG_OFFLOAD_BUNDLE__", i + 24)
+    if not out:
+        raise CatanHipError("no gfx950 code object in the library")
+    return out
+
+
+def device_code_object(path=None):
+    """The code object of catan_abi.hip: the first one -> bytes"""
+    return device_code_objects(path)[0]
 
 
 def check_no_packed_f32(path=None):
@@ -92,10 +105,12 @@ def check_no_packed_f32(path=None):
     import tempfile
     if not os.path.exists(LLVM_OBJDUMP):
         return None
-    with tempfile.NamedTemporaryFile(suffix=".co", dir="/tmp") as tmp:
-        tmp.write(device_code_object(path))
-        tmp.flush()
-        text = subprocess.run([LLVM_OBJDUMP, "-d", tmp.name], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout.decode("ascii", "replace")
+    text = ""
+    for co in device_code_objects(path):
+        with tempfile.NamedTemporaryFile(suffix=".co", dir="/tmp") as tmp:
+            tmp.write(co)
+            tmp.flush()
+            text += subprocess.run([LLVM_OBJDUMP, "-d", tmp.name], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout.decode("ascii", "replace")
     fn, bad = "?", {}
     for line in text.splitlines():
         m = re.match(r"^[0-9a-f]+ <(.*)>:", line)
@@ -159,7 +174,7 @@ def build_library(force=False, verbose=False):
     whenever the hash of the sources differs from the one baked into the binary - file times mean nothing on a fresh checkout
     or on a snapshot copied to the GPU box."""
     want = source_hash()
-    cmd = ["hipcc"] + BUILD_FLAGS + [f'-DCATAN_BUILD_HASH_STR="{want}"', "-o", LIB_PATH, os.path.join(CSRC, "catan_abi.hip")]
+    cmd = ["hipcc"] + BUILD_FLAGS + [f'-DCATAN_BUILD_HASH_STR="{want}"', "-o", LIB_PATH] + [os.path.join(CSRC, f) for f in TRANSLATION_UNITS]
     have = binary_hash()
     if not force and have == want:
         if verbose:
@@ -327,6 +342,11 @@ _SIGS = {
     "catan_start_pool_outcomes_words": (C.c_int32, []),
     "catan_start_pool_outcomes_enable": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "catan_start_pool_outcomes_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, _vp]),
+    "catan_complete_action_rows": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
+    "catan_collector_label": (C.c_int, [C.c_int64, C.c_int32] + [_vp] * 8),
+    "catan_imitation_loss_words": (C.c_int64, []),
+    "catan_imitation_loss_workspace_doubles": (C.c_int64, []),
+    "catan_imitation_loss": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
 }
 # bound only where the library exports them: the same callers also load oracle/libcatan_cpu.so, which implements the env ABI
 # without these

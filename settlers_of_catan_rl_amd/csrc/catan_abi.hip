@@ -2580,3 +2580,42 @@ static void enqueue_start_pool_x(catan_env_t* e, const u32* count_p, const i32* 
     else POOL_X(false, true);
 #undef POOL_X
 }
+
+// ---- kickstarting from the rule-based player.  Host code only: the kernels are catan_teacher.hip's, a translation unit and
+// a code object of their own (catan_teacher.h), so that this file's code object is what it is without them.
+#include "catan_teacher.h"
+
+extern "C" {
+
+int catan_complete_action_rows(catan_env_t* e, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_complete_action_rows: null handle");
+    if (!actions) return fail(CATAN_EINVAL, "catan_complete_action_rows: null actions");
+    if (n_rows <= 0) return fail(CATAN_EINVAL, "catan_complete_action_rows: n_rows <= 0");
+    if (!games && n_rows > e->n) return fail(CATAN_EINVAL, "catan_complete_action_rows: n_rows exceeds the handle's games (games == NULL)");
+    HIPCHK(teacher_launch_complete(e->ctx.R, e->ctx.n, (const u32*)e->mpk, games, (long)n_rows, e->d_it > 0 ? (const u8*)e->pend.busy : (const u8*)nullptr, actions,
+                                   S(stream)));
+    return CATAN_OK;
+}
+
+int catan_collector_label(int64_t n, int32_t T, const int64_t* counters4, const uint8_t* flags4, const int64_t* active_pid, const int32_t* deciding,
+                          const int32_t* labels, int16_t* st_teacher, const uint8_t* waiting_before, catan_stream_t stream) {
+    if (n <= 0 || T <= 0 || !counters4 || !flags4 || !active_pid || !deciding || !labels || !st_teacher)
+        return fail(CATAN_EINVAL, "catan_collector_label: null argument");
+    HIPCHK(teacher_launch_label((long)n, (int)T, (const long long*)counters4 + 2 * n, flags4 + 2 * n, (const long long*)active_pid, deciding, waiting_before, labels,
+                                (short*)st_teacher, S(stream)));
+    return CATAN_OK;
+}
+
+int64_t catan_imitation_loss_words(void) { return IMIT_WORDS; }
+int64_t catan_imitation_loss_workspace_doubles(void) { return IMIT_PART * IMIT_BLOCKS + 1; }
+
+int catan_imitation_loss(const float* lp, const int64_t* teacher, int64_t B, float* loss, float* dlp, double* block, double* workspace, catan_stream_t stream) {
+    if (B < 1) return fail(CATAN_EINVAL, "catan_imitation_loss: B must be at least 1");
+    if (!lp || !teacher) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL input array");
+    if (!loss || !dlp) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL output array");
+    if (!block || !workspace) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL block or workspace");
+    HIPCHK(teacher_launch_imitation(lp, (const long long*)teacher, (long)B, loss, dlp, block, workspace, S(stream)));
+    return CATAN_OK;
+}
+
+}  // extern "C"

@@ -450,6 +450,21 @@ class VecCatanEnv(object):
             _lib.check(self.L.catan_sample_scripted_actions(self.h, _ptr(games), rows, _ptr(out), _stream()))
         return out
 
+    def complete_action_rows(self, actions, games=None):
+        """catan_complete_action_rows (include/catan_hip_tuning.h): the columns of each action row that its type does
+        not use become the lowest legal index of the mask their head would apply, so that the row can be teacher-forced through
+        CatanPolicy.evaluate_actions (the samplers leave them 0, which is often illegal there: -inf x 0 = NaN).  actions: int32
+        [rows][18] on the device, edited IN PLACE and returned; games as in sample_scripted_actions.  The masks must be current."""
+        if games is not None:
+            games = games if (games.dtype == torch.int32 and games.is_contiguous() and games.device == self.device) else \
+                games.to(device=self.device, dtype=torch.int32).contiguous()
+        rows = self.n if games is None else games.numel()
+        assert actions.shape == (rows, spec.ACTION_WORDS) and actions.dtype == torch.int32 and actions.is_contiguous() and actions.is_cuda, \
+            (actions.shape, actions.dtype)
+        if rows:
+            _lib.check(self.L.catan_complete_action_rows(self.h, _ptr(games), rows, _ptr(actions), _stream()))
+        return actions
+
     def scripted_fallback_count(self):
         """decisions of sample_scripted_actions that only the rule's fall-back row could take (expected 0)"""
         return int(self.L.catan_scripted_fallback_count(self.h, _stream()))

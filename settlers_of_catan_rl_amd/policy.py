@@ -631,7 +631,8 @@ class _ActionHeads(nn.Module):
         the ~1 500 launches of a step then go out with the device waiting for each of them (the step is host-paced from there on).
         actions_all [rows, 18]; perm: the epoch's permutation.  -> list of (perm_k, ends_k (host list), None)"""
         rows = perm[:num_mini_batch * mbs]                  # (only the two columns the key is made of are gathered, not all 18)
-        typ, card = actions_all[:, 0][rows].view(num_mini_batch, mbs), actions_all[:, 4][rows].view(num_mini_batch, mbs)
+        # (.long(): the stored teacher rows are int16; nothing for the int64 actions)
+        typ, card = actions_all[:, 0][rows].long().view(num_mini_batch, mbs), actions_all[:, 4][rows].long().view(num_mini_batch, mbs)
         key = typ * 8 + torch.where(typ == T_PLAYDEV, card.clamp(0, 7), torch.zeros_like(card))
         order = torch.argsort(key, dim=1, stable=True)
         counts = torch.zeros((num_mini_batch, 13 * 8), dtype=torch.int64, device=typ.device)
@@ -1112,16 +1113,30 @@ class CatanPolicy(nn.Module):
             out += (r[3],)
         return out
 
-    def evaluate_actions(self, obs_f, lists, lens, masks, actions, hidden=None, nonterminal=None, tile_dedupe=None, grouping=None):
-        """grouping: this batch's entry of _ActionHeads.precompute_groupings (the learner computes them for a whole epoch at once)"""
+    def evaluate_actions(self, obs_f, lists, lens, masks, actions, hidden=None, nonterminal=None, tile_dedupe=None, grouping=None,
+                         teacher_actions=None, teacher_grouping=None):
+        """grouping: this batch's entry of _ActionHeads.precompute_groupings (the learner computes them for a whole epoch at once).
+        teacher_actions int64 [B, 18] (kickstarting): a teacher's COMPLETED action rows for the same states
+        (env.complete_action_rows); the heads run a second time on the same `main` - the trunk is evaluated once - and the teacher's
+        joint log-prob [B, 1] is appended to the returned tuple.  teacher_grouping: their entry of precompute_groupings.  None: the
+        call without them, bit for bit."""
         ahm = self.action_head_module
         if grouping is None or not ahm.wants_grouping(obs_f.shape[0], actions):
             grouping = ahm.start_grouping(actions) if ahm.wants_grouping(obs_f.shape[0], actions) else None    # (before the long forward)
         main, hidden = self._main(obs_f, lists, lens, hidden, nonterminal, tile_dedupe=tile_dedupe)
         cur_res, trade = self._custom(obs_f)
-        _, logp, entropy = ahm(main, masks.float(), cur_res, trade, actions, grouping=grouping, value_fn=self._value)
+        masks_f = masks.float()
+        _, logp, entropy = ahm(main, masks_f, cur_res, trade, actions, grouping=grouping, value_fn=self._value)
         value, ahm.last_value = ahm.last_value, None
-        return (value, logp[:, None], entropy, hidden) if self.include_lstm else (value, logp[:, None], entropy)
+        out = (value, logp[:, None], entropy, hidden) if self.include_lstm else (value, logp[:, None], entropy)
+        if teacher_actions is not None:
+            if teacher_grouping is None or not ahm.wants_grouping(obs_f.shape[0], teacher_actions):
+                # (only now: start_grouping hands the counts over in ONE pinned buffer, which the first pass has read by this point)
+                teacher_grouping = ahm.start_grouping(teacher_actions) if ahm.wants_grouping(obs_f.shape[0], teacher_actions) else None
+            _, t_logp, _ = ahm(main, masks_f, cur_res, trade, teacher_actions, grouping=teacher_grouping)
+            ahm.last_value = None
+            out += (t_logp[:, None],)
+        return out
 
     def get_value(self, obs_f, lists, lens, hidden=None, nonterminal=None, tile_features=None):
         return self.base(obs_f, lists, lens, hidden, nonterminal, tile_features)[0]

@@ -272,3 +272,114 @@ def reduce_diag_over_ranks(block):
     block[..., list(DIAG_MAX_WORDS)] = mx
     block[..., list(DIAG_PER_STEP_WORDS)] /= dist.get_world_size()
     return block
+
+
+# ------------------------------------------------------------------------------------------------ imitation term (kickstarting)
+# The teacher's rows under the net (k_imitation_loss, csrc/catan_teacher.hip; the words are listed in
+# include/catan_hip_nn.h): the loss -mean(lp), its gradient and the read-out from ONE launch, accumulated like the diagnostics.
+IMIT_WORDS = 33
+IMIT_MAX_WORDS = (3,)
+IMIT_PER_STEP_WORDS = (1,)               # the same on every rank (calls)
+IMIT_HALF = -0.6931472                   # lp above this (as fp32): more than half the mass on the teacher's whole composite action
+
+_IMIT_WS = {}
+
+
+def _imit_workspace(device):
+    """zeroed once; every k_imitation_loss call leaves it all zero.  One per (device, STREAM), as _loss_workspace."""
+    key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
+    if key not in _IMIT_WS:
+        _IMIT_WS[key] = torch.zeros((_lib.lib().catan_imitation_loss_workspace_doubles(),), dtype=torch.float64, device=device)
+    return _IMIT_WS[key]
+
+
+def _check_imit(lp, teacher_rows, block):
+    if block.dtype != torch.float64 or block.numel() != IMIT_WORDS or not block.is_contiguous() or block.device != lp.device:
+        raise ValueError("imitation_loss: the block is a contiguous float64 tensor of %d words on the rows' device" % IMIT_WORDS)
+    if teacher_rows.dim() != 2 or teacher_rows.shape[0] != lp.numel() or teacher_rows.shape[1] != 18 or lp.numel() < 1:
+        raise ValueError("imitation_loss: lp [B] (B >= 1) and teacher_rows [B, 18]")
+
+
+def _hip_imitation(lp, teacher_rows, block):
+    """k_imitation_loss on the current stream -> (loss [1], dlp [B])"""
+    x = lp.detach().contiguous().float().view(-1)
+    rows = teacher_rows.contiguous() if teacher_rows.dtype == torch.int64 else teacher_rows.long().contiguous()
+    loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+    dlp = torch.empty_like(x)
+    _lib.check(_lib.lib().catan_imitation_loss(_ptr(x), _ptr(rows), x.numel(), _ptr(loss), _ptr(dlp), _ptr(block),
+                                               _ptr(_imit_workspace(x.device)), _stream()))
+    return loss, dlp
+
+
+def _torch_imitation(lp, teacher_rows, block):
+    """The same arithmetic as torch operations (tensors that are not on the device: the CPU tests, a CPU learner)."""
+    x = lp.detach().reshape(-1).float()
+    B = x.numel()
+    finite = torch.isfinite(x)
+    nll = torch.where(finite, -x.double(), torch.zeros((), dtype=torch.float64, device=x.device))
+    typ = teacher_rows[:, 0].long()
+    w = torch.zeros(IMIT_WORDS, dtype=torch.float64, device=x.device)
+    w[0], w[1], w[2] = float(B), 1.0, nll.sum()
+    w[4] = (finite & (x > torch.tensor(IMIT_HALF, dtype=torch.float32, device=x.device))).sum().double()
+    w[5] = (~finite).sum().double()
+    ok = finite & (typ >= 0) & (typ <= 12)
+    w[6:19] = torch.bincount(typ[ok], minlength=13).double()
+    w[19:32] = torch.zeros(13, dtype=torch.float64, device=x.device).index_add_(0, typ[ok], nll[ok])
+    new = block + w.reshape(block.shape)
+    new.view(-1)[3] = torch.maximum(block.view(-1)[3], nll.max())
+    block.copy_(new)
+    loss = (nll.sum() / B).float().reshape(1)
+    dlp = torch.where(finite, torch.full_like(x, float(torch.tensor(-1.0 / B, dtype=torch.float64).float())), torch.zeros_like(x))
+    return loss, dlp
+
+
+class _Imitation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lp, teacher_rows, block):
+        _check_imit(lp, teacher_rows, block)
+        loss, dlp = (_hip_imitation if lp.is_cuda else _torch_imitation)(lp, teacher_rows, block)   # (rows on the device and no library: an error)
+        ctx.save_for_backward(dlp)
+        ctx.shape = lp.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlp,) = ctx.saved_tensors
+        return (g * dlp).view(ctx.shape), None, None
+
+
+def imitation_loss(lp, teacher_rows, block):
+    """-> the scalar -mean(lp) over the rows whose lp is finite (divided by ALL B rows): the imitation term of a step, differentiable
+    by lp (backward: g x dlp, dlp = -1 / B, 0 for a skipped row).  lp [B] or [B, 1]: the joint log-prob of the teacher's action rows
+    (CatanPolicy.evaluate_actions(teacher_actions=...)); teacher_rows int64 [B, 18]; the step's read-out is ADDED into `block`
+    (float64 [33] on the rows' device, zeroed by the caller; all calls into one block on one stream).  No host read;
+    `imitation_summary` turns a block into numbers once it is on the host."""
+    return _Imitation.apply(lp, teacher_rows, block)
+
+
+def imitation_summary(block):
+    """a HOST block [33] -> {"nll", "nll_max", "half_share" (rows with p > 1/2), "skipped", "rows", "steps", "rows_by_type" [13],
+    "nll_by_type" [13] (NaN for a type without rows)}; the means are over the rows that were not skipped"""
+    import numpy as np
+    w = np.asarray(block, dtype=np.float64).reshape(IMIT_WORDS)
+    nan = float("nan")
+    rows, skipped = float(w[0]), float(w[5])
+    used = rows - skipped
+    return {"nll": float(w[2]) / used if used > 0 else nan, "nll_max": float(w[3]), "half_share": float(w[4]) / used if used > 0 else nan,
+            "skipped": int(round(skipped)), "rows": int(round(rows)), "steps": int(round(float(w[1]))),
+            "rows_by_type": [int(round(float(x))) for x in w[6:19]],
+            "nll_by_type": [float(s) / float(c) if c > 0 else nan for s, c in zip(w[19:32], w[6:19])]}
+
+
+def reduce_imitation_over_ranks(block):
+    """In place, as reduce_diag_over_ranks: SUM over the default group, MAX for the maximum word, the call count divided by the world
+    size.  Nothing without > 1 rank."""
+    dist = torch.distributed
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return block
+    mx = block[..., list(IMIT_MAX_WORDS)].contiguous()
+    dist.all_reduce(block, op=dist.ReduceOp.SUM)
+    dist.all_reduce(mx, op=dist.ReduceOp.MAX)
+    block[..., list(IMIT_MAX_WORDS)] = mx
+    block[..., list(IMIT_PER_STEP_WORDS)] /= dist.get_world_size()
+    return block

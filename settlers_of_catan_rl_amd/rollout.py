@@ -30,7 +30,7 @@ class RolloutStorage(object):
         per-rollout derived data (PPOTrainer's distinct boards) key on (token, generation) and recompute"""
         self.generation += 1
 
-    def __init__(self, T, N, device, obs_dtype=torch.float32, lstm_size=0):
+    def __init__(self, T, N, device, obs_dtype=torch.float32, lstm_size=0, teacher=False):
         self.T, self.N = T, N
         self.token = next(RolloutStorage._tokens)      # process-unique: a later storage at the same address is another rollout
         # process_batch.py:53-59: the active seat's LSTM state (h, c) entering each of its stored decisions
@@ -43,6 +43,8 @@ class RolloutStorage(object):
         self.actions = torch.zeros((T, N, spec.ACTION_WORDS), dtype=torch.int64, device=device)
         self.action_log_probs = torch.zeros((T, N), dtype=torch.float32, device=device)
         self.action_masks = torch.zeros((T, N, 11), dtype=torch.int32, device=device)   # packed 325-bit masks
+        # RolloutCollector(teacher=...): the teacher's completed action row for every stored decision; allocated only then
+        self.teacher_actions = torch.zeros((T, N, spec.ACTION_WORDS), dtype=torch.int16, device=device) if teacher else None
         self.games_complete = 0
         self.episode_stats = None     # RolloutCollector(episode_stats=True): the finished games of the last gather_rollouts (env.episode_stats)
         self.league_stats = None      # RolloutCollector(league_stats=True): their results per opponent net, int64 [nets + 1, 6] (env.league_stats)
@@ -139,7 +141,7 @@ class RolloutCollector(object):
 
     def __init__(self, env, policy, num_steps, opponents=None, seed=0, autocast_dtype=None, graph_act=None, deferred_window=None, act_buckets=None,
                  episode_stats=False, league_stats=False, record_games=0, start_pool=None, start_pool_fresh=0.0,
-                 start_pool_outcomes=False, start_pool_sampling="uniform"):
+                 start_pool_outcomes=False, start_pool_sampling="uniform", teacher=None):
         """policy: central net (policy 0); opponents: list of up to 3 nets for policy slots 1..3 of every game (None =
         every seat plays the central policy).  A league (league.League.assign) installs per-game opponents instead.  An opponent
         may be a `scripted.ScriptedPolicy(env)` bound to this env: a fixed anchor beside the nets (its rows' log-probs are 0 and,
@@ -168,7 +170,14 @@ class RolloutCollector(object):
         player (VecCatanEnv.enable_start_pool_outcomes); every gather_rollouts leaves them in storage.start_pool["outcomes"], read once
         beside the counts.  start_pool_sampling "balanced" (implies the outcomes): behind every rollout the tallies are added to the
         pool (StartPool.add_outcomes; self.start_pool) and the entries' weights for the next rollout become its balanced_weights() - the
-        positions whose result is still open are drawn more often.  The defaults (False, "uniform") make no call."""
+        positions whose result is still open are drawn more often.  The defaults (False, "uniform") make no call.
+        teacher (kickstarting): any object with `label(games=None) -> int32 [N, 18]`, completed action rows for the
+        deciding player of every game - `scripted.ScriptedPolicy(env)` is the one shipped.  Every env iteration labels all N games once,
+        after the masks are read and before the step, and the label of a game goes into storage.teacher_actions (int16 [T, N, 18],
+        allocated only with a teacher) at the slot its active seat's action goes into storage.actions; opponent seats are never
+        labelled, nothing else in the storage changes.  `stop_teacher()` later stops the labelling and frees the tensor (train with
+        teacher_coef 0 from then on).  The tensor-operation loop steps with catan_step whatever `deferred_window` says, with a
+        teacher as without.  Not with LSTM policies.  None: no call is made."""
         self.env,self.policy, self.T = env, policy, num_steps
         self.league_stats, self.policy_of_pid = bool(league_stats), None
         self.deferred_window = self.DEFAULT_DEFERRED_WINDOW if deferred_window is None else int(deferred_window)
@@ -205,7 +214,12 @@ class RolloutCollector(object):
         # value is a small multiple of 1/8 (exact in bf16): the rollout tensors are kept in that dtype - half the HBM
         # (config 3: 58 instead of 116 GB) and no cast pass per minibatch.
         obs_dtype = autocast_dtype if (autocast_dtype in (torch.bfloat16, torch.float16) and torch.device(self.device).type == "cuda") else torch.float32
-        self.storage = RolloutStorage(num_steps, self.N, self.device, obs_dtype=obs_dtype, lstm_size=self.lstm_size)
+        if teacher is not None and self.recurrent:
+            raise ValueError("RolloutCollector(teacher=...) is not supported with LSTM policies")
+        if teacher is not None and not hasattr(teacher, "label"):
+            raise ValueError("RolloutCollector(teacher=...): a teacher has label(games=None) -> int32 [N, 18] (scripted.ScriptedPolicy(env))")
+        self.teacher = teacher
+        self.storage = RolloutStorage(num_steps, self.N, self.device, obs_dtype=obs_dtype, lstm_size=self.lstm_size, teacher=teacher is not None)
         # game_manager.py:94-95 sums the env's rewards (Python floats) over the other seats' moves and process_batch.py:63
         # rounds the sum to fp32: the env leaves its unrounded rewards in a float64 buffer for that
         self.reward64 = env.enable_reward64() if hasattr(env, "enable_reward64") else None
@@ -242,6 +256,12 @@ class RolloutCollector(object):
             self.env.enable_start_pool_outcomes(self.active_pid)
             if sampling == "balanced":
                 self.env.set_start_pool_weights(self.start_pool.balanced_weights())
+
+    def stop_teacher(self):
+        """No more labels from here on: the teacher goes and storage.teacher_actions (472 MB at 65 536 games x T = 200) is freed."""
+        self.teacher = None
+        if self.storage is not None:
+            self.storage.teacher_actions = None
 
     def set_opponents(self, nets, opp_index):
         """nets: the distinct opponent nets in play; opp_index int64 [N,3]: which of them plays policy slots 1..3 of
@@ -431,6 +451,7 @@ class RolloutCollector(object):
             _lib.check(_lib.lib().catan_collector_pre(N, T, _ptr(self.n_obs), _ptr(actions), _ptr(a_env), _ptr(live8), _stream()))
             n_live_iters += live8.any()
             pmasks = env.get_action_masks_packed()                                          # (before the step replaces them)
+            labels = self.teacher.label().contiguous() if self.teacher is not None else None   # (the teacher reads the games before the step too)
             if deferred:
                 wb, so = stat[sk], stat[sk ^ 1]
                 reward, done, _ = env.step_deferred(a_env, self.deferred_window, status_out=so)
@@ -438,6 +459,9 @@ class RolloutCollector(object):
             else:
                 wb = so = None
                 reward, done = env.step(a_env)                                              # :91 (auto-reset == :113)
+            if labels is not None:       # in front of catan_collector_post: the slot is n_act BEFORE its increment
+                _lib.check(_lib.lib().catan_collector_label(N, T, _ptr(self._cnt), _ptr(fl), _ptr(self.active_pid), _ptr(deciding), _ptr(labels),
+                                                            _ptr(st.teacher_actions), _ptr(wb), _stream()))
             self._collector_post(term, t_next, n_complete, deciding, env.deciding_player(), actions, logp, pmasks, reward, done, wb, so)
             live.post(iters, (self.n_obs < T + 1).sum())
             sel, t_obs = sel_next, t_next
@@ -494,11 +518,12 @@ class RolloutCollector(object):
             a_env = actions.to(torch.int32)
             a_env[:, 0] = torch.where(frozen, torch.full_like(a_env[:, 0], -1), a_env[:, 0])   # frozen games: no-op
             pmasks = env.get_action_masks_packed() if hasattr(env, "get_action_masks_packed") else pack_action_masks(masks)   # (before the step replaces them)
+            labels = self.teacher.label() if self.teacher is not None else None             # (the teacher reads the games before the step too)
             reward, done = env.step(a_env)                                                  # :91 (auto-reset == :113)
-            term = self._book_step(term, n_complete, live, deciding, actions, logp, pmasks, reward, done)
+            term = self._book_step(term, n_complete, live, deciding, actions, logp, pmasks, reward, done, labels)
         return iters
 
-    def _book_step(self, term, n_complete, live, deciding, actions, logp, pmasks, reward, done):
+    def _book_step(self, term, n_complete, live, deciding, actions, logp, pmasks, reward, done, labels=None):
         """game_manager.py:91-136 for the games that stepped (`live`), as tensor operations.  -> the new terminal masks."""
         env, st, T, ar = self.env, self.storage, self.T, self._ar
         done = done.bool() & live
@@ -509,6 +534,8 @@ class RolloutCollector(object):
         self._col_store(st.actions, actions, t, was_active)
         self._col_store(st.action_log_probs, logp, t, was_active)
         self._col_store(st.action_masks, pmasks, t, was_active)
+        if labels is not None:
+            self._col_store(st.teacher_actions, labels, t, was_active)
         self.n_act += was_active.long()
         n_deciding = env.deciding_player().long()                                       # after the step (and the reset)
         next_active = (n_deciding == self.active_pid) & live

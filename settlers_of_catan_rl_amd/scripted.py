@@ -38,3 +38,12 @@ class ScriptedPolicy(object):
         zeros = torch.zeros((rows, 1), dtype=torch.float32, device=a.device)
         return zeros, a, zeros.clone()
 
+    @torch.no_grad()
+    def label(self, games=None):
+        """The player as a TEACHER -> int32 [rows, 18]: its action for game games[j] (None: every game), completed so
+        that it can be teacher-forced through the net's heads (env.complete_action_rows).  Two launches."""
+        env = self.env
+        if env is None:
+            raise RuntimeError("ScriptedPolicy is not bound to an env (ScriptedPolicy(env) or rebind(env))")
+        return env.complete_action_rows(env.sample_scripted_actions(games=games), games=games)
+

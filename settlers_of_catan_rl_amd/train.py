@@ -38,6 +38,8 @@ class PPOConfig(object):
     truncated_seq_len = 10            # arguments.py:57-59 (LSTM policies only)
     diagnostics = False               # per-epoch KL / clip fractions / explained variance / gradient norm of an update (ppo.ppo_diag): off launches nothing
     target_kl = None                  # with diagnostics: skip an update's remaining epochs once an epoch's approx_kl exceeds this (one host read per epoch)
+    teacher_coef = 0.0                # kickstarting: > 0 adds teacher_coef x the imitation term on the rollout's teacher labels (RolloutCollector(teacher=...)); 0 launches nothing
+    teacher_only = False              # pure imitation: zero advantages (the policy-gradient term is exactly 0, the value term stays), no entropy term
     value_chunk = 1048576      # rows per forward of the value pass (swept on MI355X at 13.2 M rows: 131 072: 184 ms, 262 144: 177, 524 288: 171, 1 048 576: 164; ~4 GB of activations)
 
     def __init__(self, **kw):
@@ -87,6 +89,7 @@ class PPOTrainer(object):
         if self.cfg.target_kl is not None and not self.cfg.diagnostics:
             raise ValueError("PPOConfig.target_kl needs PPOConfig.diagnostics (the KL of an epoch is read from its diagnostics block)")
         self.diagnostics = None       # ppo.diag_summary of the last update when cfg.diagnostics, else None
+        self.teacher = None           # ppo.imitation_summary of the last update when cfg.teacher_coef > 0, else None
 
     def _autocast(self):
         if self.autocast_dtype is None:
@@ -214,12 +217,28 @@ class PPOTrainer(object):
             out[s:s + ch] = v[:, 0]
         return self.policy.denormalise(out).reshape(T1, N)
 
+    def _check_teacher(self, st):
+        """-> whether this update carries the imitation term (cfg.teacher_coef > 0); the configurations that cannot run raise"""
+        cfg = self.cfg
+        if cfg.teacher_only and cfg.target_kl is not None:
+            raise ValueError("PPOConfig.teacher_only with target_kl: pure imitation moves the policy away from the rollout's on purpose")
+        if cfg.teacher_only and not cfg.teacher_coef > 0:
+            raise ValueError("PPOConfig.teacher_only needs teacher_coef > 0")
+        if not cfg.teacher_coef > 0:
+            return False
+        if getattr(st, "teacher_actions", None) is None:
+            raise ValueError("PPOConfig.teacher_coef > 0 needs the rollout's teacher labels (RolloutCollector(teacher=...): storage.teacher_actions)")
+        if getattr(self.policy, "include_lstm", False):
+            raise ValueError("teacher labels are not supported with LSTM policies")
+        return True
+
     def update(self, st):
         """-> (value_loss, action_loss, entropy_loss) averaged over the optimiser steps, as ppo.py:70-79.  With cfg.diagnostics the
         update's read-out is left in `self.diagnostics` (ppo.diag_summary)."""
         cfg, pol = self.cfg, self.policy
         if cfg.target_kl is not None and not cfg.diagnostics:
             raise ValueError("PPOConfig.target_kl needs PPOConfig.diagnostics")
+        teach = self._check_teacher(st)
         T, N = st.T, st.N
         dev = st.obs_f.device
         total = T * N
@@ -249,6 +268,10 @@ class PPOTrainer(object):
         t_val = t_gae = t_opt = 0.0
         # one block of doubles per epoch, added to by one launch per step on this stream, copied to the host once at the end
         diag = torch.zeros((cfg.ppo_epoch, ppo_kernels.DIAG_WORDS), dtype=torch.float64, device=dev) if cfg.diagnostics else None
+        # kickstarting: the teacher's rows beside the actions, one read-out block per update on this stream, read once at the end
+        teach_all = st.teacher_actions.reshape(total, -1) if teach else None
+        tblock = torch.zeros((ppo_kernels.IMIT_WORDS,), dtype=torch.float64, device=dev) if teach else None
+        tgroupings = None
         epochs = steps = 0
         for ep in range(cfg.ppo_epoch):
             t0 = time.perf_counter()
@@ -270,11 +293,17 @@ class PPOTrainer(object):
                 groupings = None                  # the heads' row sets of every minibatch: one sort and one host read per epoch
                 if ahm is not None and hasattr(ahm, "precompute_groupings") and dev.type == "cuda" and ahm.wants_grouping(mbs, acts_all):
                     groupings = ahm.precompute_groupings(acts_all, perm, cfg.num_mini_batch, mbs)
+                    if teach:
+                        tgroupings = ahm.precompute_groupings(teach_all, perm, cfg.num_mini_batch, mbs)
             # (the packed mask rows go to the net as they are: policy.PackedActionMasks expands what the heads read)
             pam = getattr(sys.modules.get(type(pol).__module__), "PackedActionMasks", None)
             amasks = (lambda i: pam(amask_all[i], st.unpack_action_masks)) if (pam is not None and dev.type == "cuda" and amask_all.dtype == torch.int32) \
                 else (lambda i: st.unpack_action_masks(amask_all[i]))
             for bi, (idx, hidden) in enumerate(batches):
+                tkw = {}
+                if teach:                     # the heads run a second time on the teacher's rows (one trunk evaluation)
+                    t_rows = teach_all[idx].long()
+                    tkw = {"teacher_actions": t_rows} if tgroupings is None else {"teacher_actions": t_rows, "teacher_grouping": tgroupings[bi]}
                 with self._autocast():
                     if rec:
                         v, lp, ent, _ = pol.evaluate_actions(cast(f_all[idx]), lists_all[idx], lens_all[idx].long(),
@@ -285,15 +314,17 @@ class PPOTrainer(object):
                         # the rows' observations WITHOUT their tile features (64 % of a row: they come per distinct board below), gathered
                         # straight into the pieces the observation module multiplies (policy.ObsParts: no slicing / padding copies later)
                         obs_in = self._gather_obs_parts(pol, f_all, idx, o)
-                        v, lp, ent = pol.evaluate_actions(obs_in, nn_kernels.gather_rows(lists_all, idx), lens_all[idx].long(),
-                                                          amasks(idx), acts_all[idx],
-                                                          tile_dedupe=(cast(nn_kernels.gather_rows(tiles_all, first_rows[uqk])), invk, orderk, startk),
-                                                          **({} if groupings is None else {"grouping": groupings[bi]}))
+                        v, lp, ent, *tlp = pol.evaluate_actions(obs_in, nn_kernels.gather_rows(lists_all, idx), lens_all[idx].long(),
+                                                                amasks(idx), acts_all[idx],
+                                                                tile_dedupe=(cast(nn_kernels.gather_rows(tiles_all, first_rows[uqk])), invk, orderk, startk),
+                                                                **({} if groupings is None else {"grouping": groupings[bi]}), **tkw)
                     else:
-                        v, lp, ent = pol.evaluate_actions(cast(f_all[idx]), lists_all[idx], lens_all[idx].long(),
-                                                          amasks(idx), acts_all[idx],
-                                                          **({} if groupings is None else {"grouping": groupings[bi]}))
+                        v, lp, ent, *tlp = pol.evaluate_actions(cast(f_all[idx]), lists_all[idx], lens_all[idx].long(),
+                                                                amasks(idx), acts_all[idx],
+                                                                **({} if groupings is None else {"grouping": groupings[bi]}), **tkw)
                 rows4 = (old_lp_all[idx], advf[idx], vpred[idx], ret[idx])                   # (gathered once: the diagnostics read them again)
+                if teach and cfg.teacher_only:
+                    rows4 = (rows4[0], torch.zeros_like(rows4[1]), rows4[2], rows4[3])       # no policy-gradient term: its gradient is exactly 0
                 loss, parts = ppo_kernels.ppo_loss(lp.float(), v.float(), *rows4,
                                                    cfg.clip_param, cfg.value_loss_coef,
                                                    value_normaliser=(pol.VALUE_MEAN, pol.VALUE_STD))     # ppo.py:46-63
@@ -302,7 +333,11 @@ class PPOTrainer(object):
                     nn_kernels.grad_arena.begin_step(dev)                                  # the backward kernels' accumulators: one fill per step
                     nn_kernels.wgrad_queue.begin()                                         # tall-skinny weight gradients: grouped launches after the backward
                 try:
-                    (loss - ent * cfg.entropy_coef).backward()                             # ppo.py:66
+                    if teach:
+                        imit = ppo_kernels.imitation_loss(tlp[0].float(), t_rows, tblock)
+                        ((loss if cfg.teacher_only else loss - ent * cfg.entropy_coef) + cfg.teacher_coef * imit).backward()
+                    else:
+                        (loss - ent * cfg.entropy_coef).backward()                         # ppo.py:66
                 except BaseException:
                     nn_kernels.wgrad_queue.drop()      # (a flush here could raise in turn and hide the backward's own error)
                     raise
@@ -335,6 +370,9 @@ class PPOTrainer(object):
         self.diagnostics = None
         if diag is not None:
             self.diagnostics = ppo_kernels.diag_summary(ppo_kernels.reduce_diag_over_ranks(diag[:epochs].clone()).cpu().numpy())
+        self.teacher = None
+        if teach:                                         # the one host read of the update's imitation read-out, over all ranks
+            self.teacher = ppo_kernels.imitation_summary(ppo_kernels.reduce_imitation_over_ranks(tblock).cpu().numpy())
         self.timings = {"values_s": t_val, "gae_s": t_gae, "minibatches_s": t_opt}
         if timed_allreduce:                               # device time inside the gradient all-reduces (part of minibatches_s)
             self._sync()

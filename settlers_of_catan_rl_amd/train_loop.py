@@ -37,6 +37,10 @@ class TrainArgs(object):
     start_pool_outcomes = False          # opt-in: the finished games are tallied per pool entry on the device -> log["start_pool"]["outcomes"]
     start_pool_sampling = "uniform"      # "balanced": the entries whose result is still open are drawn more often (implies the outcomes)
     eval_scripted_baseline = False       # opt-in: the evaluation also plays the rule-based player (scripted.ScriptedPolicy) -> log["scripted"]
+    teacher = None                       # opt-in kickstarting: "scripted" - the rule-based player labels the rollouts (make_teacher)
+    teacher_coef = 0.0                   # ... the imitation term's coefficient at update 0
+    teacher_coef_updates = 0             # ... falling linearly to 0 over this many updates (0: constant); at 0 the collector stops labelling
+    teacher_only_updates = 0             # ... the first J updates are pure imitation (PPOConfig.teacher_only)
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -52,6 +56,28 @@ def eval_baselines(args):
         return None
     from .scripted import ScriptedPolicy
     return {"scripted": ScriptedPolicy}
+
+
+def make_teacher(args, env):
+    """The teacher `args` asks for, as RolloutCollector(teacher=...) takes it; None (the default): no teacher, no call."""
+    name = getattr(args, "teacher", None)
+    if name is None or not getattr(args, "teacher_coef", 0.0) > 0:
+        return None
+    if name != "scripted":
+        raise ValueError(f"teacher must be 'scripted' or None, got {name!r}")
+    from .scripted import ScriptedPolicy
+    return ScriptedPolicy(env)
+
+
+def teacher_coef_at(update_num, args):
+    """The imitation coefficient of update `update_num`: args.teacher_coef, falling linearly to 0 at update args.teacher_coef_updates
+    (0 updates: constant).  0 without a teacher."""
+    if getattr(args, "teacher", None) is None or not args.teacher_coef > 0:
+        return 0.0
+    k = int(args.teacher_coef_updates)
+    if k <= 0:
+        return float(args.teacher_coef)
+    return float(args.teacher_coef) * max(0.0, 1.0 - update_num / float(k))
 
 
 def linear_lr(update_num, num_updates, initial_lr):
@@ -120,6 +146,18 @@ class TrainingLoop(object):
             lr = linear_lr(u, self.num_updates, a.lr)
             for g in self.trainer.optimiser.param_groups:
                 g["lr"] = lr
+        if getattr(a, "teacher", None) is not None:       # kickstarting: this update's coefficient; once it is 0 nothing more is launched
+            coef = teacher_coef_at(u, a)
+            if coef > 0 and getattr(self.collector, "teacher", None) is None:
+                raise ValueError("TrainArgs.teacher needs a collector built with RolloutCollector(teacher=train_loop.make_teacher(args, env))")
+            self.trainer.cfg.teacher_coef = coef
+            self.trainer.cfg.teacher_only = bool(coef > 0 and u < a.teacher_only_updates)
+            if not coef > 0 and getattr(self.collector, "teacher", None) is not None:
+                stop = getattr(self.collector, "stop_teacher", None)      # (frees the label tensor too)
+                if stop is not None:
+                    stop()
+                else:
+                    self.collector.teacher = None
         st = self.collector.gather_rollouts()                                               # :101-102
         league_totals, league_out = self._record_league(st), None
         losses = self.trainer.update(st)                                                    # :104
@@ -165,6 +203,8 @@ class TrainingLoop(object):
             out["league"] = league_out
         if getattr(self.trainer, "diagnostics", None) is not None:   # PPOConfig(diagnostics=True): what the clipped objective did in this update
             out["ppo"] = self.trainer.diagnostics
+        if getattr(self.trainer, "teacher", None) is not None:       # PPOConfig(teacher_coef > 0): the update's imitation read-out
+            out["teacher"] = self.trainer.teacher
         return out
 
     def _record_league(self, st):

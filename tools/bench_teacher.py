@@ -1,0 +1,180 @@
+"""What kickstarting costs.  Off - no teacher configured, the default - against the parent commit's library: bench.py's
+env-steps/s and the PPO learner's minibatch-step time (the loop of tools/bench_ppo.py) in alternating pairs, every run a fresh process;
+the change passes where its mean lies inside the spread (min..max) of the parent's own runs, or on its better side.  On - reported only:
+rollout seconds with teacher labels and the minibatch-step time with teacher_coef > 0 (the second heads pass is the expected cost).
+
+usage: bench_teacher.py --parent-library libcatan_hip.so [--envs N] [--num-steps T] [--ppo-epoch E] [--pairs P] [--on-runs R]
+                        [--bench-pairs B] [--out profiles/teacher_bench.txt]
+
+--parent-library: a libcatan_hip.so built from the parent commit, run under this commit's Python (the teacher entry points it lacks are
+never called with no teacher configured).  A learner run is two updates of E epochs x 64 minibatches; the second update is reported
+(the first captures the policy pass).  minibatch-step ms = minibatches_s / (E x 64)."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+TEACHER_SYMBOLS = {"catan_complete_action_rows", "catan_collector_label", "catan_imitation_loss_words", "catan_imitation_loss_workspace_doubles",
+                   "catan_imitation_loss"}
+
+
+def _use_library(path):
+    """the parent commit's library under this commit's Python"""
+    os.environ["CATAN_ALLOW_STALE_LIB"] = "1"
+    from settlers_of_catan_rl_amd import _lib
+    _lib.LIB_PATH = os.path.abspath(path)
+    _lib._OPTIONAL |= TEACHER_SYMBOLS
+
+
+def ppo_child(a):
+    if a.library:
+        _use_library(a.library)
+    import torch
+    from settlers_of_catan_rl_amd.env import VecCatanEnv
+    from settlers_of_catan_rl_amd.policy import CatanPolicy
+    from settlers_of_catan_rl_amd.rollout import RolloutCollector
+    from settlers_of_catan_rl_amd.scripted import ScriptedPolicy
+    from settlers_of_catan_rl_amd.train import PPOTrainer, PPOConfig
+    torch.manual_seed(0)
+    env = VecCatanEnv(a.envs, seed=0)
+    env.random_rollout(0, 600)
+    net = CatanPolicy().cuda()
+    teach = a.teacher_coef > 0
+    col = RolloutCollector(env, net, a.num_steps, seed=0, autocast_dtype=torch.bfloat16, **(dict(teacher=ScriptedPolicy(env)) if teach else {}))
+    tr = PPOTrainer(net, PPOConfig(ppo_epoch=a.ppo_epoch, num_mini_batch=64, **(dict(teacher_coef=a.teacher_coef) if teach else {})),
+                    autocast_dtype=torch.bfloat16, seed=0)
+    out = {"library": a.library or "this commit", "teacher_coef": a.teacher_coef}
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        st = col.gather_rollouts()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        tr.update(st)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        col.after_rollouts()
+        out.update(rollout_s=t1 - t0, update_s=t2 - t1, env_iters=col.iters, minibatch_step_ms=tr.timings["minibatches_s"] / (a.ppo_epoch * 64) * 1e3,
+                   values_s=tr.timings["values_s"])
+    if tr.teacher is not None:
+        out["teacher"] = {k: tr.teacher[k] for k in ("nll", "half_share", "skipped", "rows", "steps")}
+    out["invalid_actions"] = env.invalid_action_count()
+    out["hbm_gb"] = torch.cuda.max_memory_allocated() / 2 ** 30
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def bench_child(a):
+    """bench.py as it stands, in this process, under the given library"""
+    import runpy
+    if a.library:
+        _use_library(a.library)
+    sys.argv = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(a.bench_steps), "--warmup", str(a.bench_warmup)]
+    runpy.run_path(sys.argv[0], run_name="__main__")
+
+
+def _spawn(args, timeout):
+    p = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
+    return p.returncode, p.stdout.decode("utf-8", "replace")
+
+
+def _where(mean, parent, higher_is_better):
+    if min(parent) <= mean <= max(parent):
+        return "inside"
+    better = mean > max(parent) if higher_is_better else mean < min(parent)
+    return ("ABOVE" if mean > max(parent) else "BELOW") + (" (better than)" if better else " (WORSE than)")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=65536)
+    ap.add_argument("--num-steps", type=int, default=200)
+    ap.add_argument("--ppo-epoch", type=int, default=1)
+    ap.add_argument("--pairs", type=int, default=2, help="pairs (parent, change) of learner runs with no teacher")
+    ap.add_argument("--on-runs", type=int, default=1, help="learner runs with the teacher on (this commit only)")
+    ap.add_argument("--on-coef", type=float, default=1.0)
+    ap.add_argument("--bench-pairs", type=int, default=2, help="pairs of bench.py runs (0: none)")
+    ap.add_argument("--bench-steps", type=int, default=4096)
+    ap.add_argument("--bench-warmup", type=int, default=256)
+    ap.add_argument("--parent-library")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "teacher_bench.txt"))
+    ap.add_argument("--ppo-child", action="store_true")
+    ap.add_argument("--bench-child", action="store_true")
+    ap.add_argument("--teacher-coef", type=float, default=0.0)
+    ap.add_argument("--library")
+    a = ap.parse_args()
+    if a.ppo_child:
+        return ppo_child(a)
+    if a.bench_child:
+        return bench_child(a)
+    sides = ([("parent", a.parent_library)] if a.parent_library else []) + [("change", None)]
+    common = ["--envs", str(a.envs), "--num-steps", str(a.num_steps), "--ppo-epoch", str(a.ppo_epoch)]
+    ppo, on, bench = [], [], []
+
+    def run(label, args, timeout, pick):
+        rc, text = _spawn(args, timeout)
+        res = [ln for ln in text.splitlines() if pick(ln)]
+        if rc != 0 or not res:
+            print(text)
+            raise SystemExit(f"{label} failed with exit code {rc}")      # nothing more is started on the device
+        print(label, res[-1], flush=True)
+        return res[-1]
+    for r in range(a.bench_pairs):
+        for label, lib in (sides if r % 2 == 0 else sides[::-1]):
+            j = json.loads(run(f"bench.py run {r} {label}", ["--bench-child", "--bench-steps", str(a.bench_steps), "--bench-warmup", str(a.bench_warmup)]
+                               + (["--library", lib] if lib else []), 600, lambda ln: ln.startswith("{") and '"value"' in ln))
+            bench.append((label, j.get("value"), j.get("ms_per_step"), j.get("status")))
+    for r in range(a.pairs):
+        for label, lib in (sides if r % 2 == 0 else sides[::-1]):
+            ppo.append((label, json.loads(run(f"learner run {r} {label}", ["--ppo-child"] + common + (["--library", lib] if lib else []), 900,
+                                              lambda ln: ln.startswith("RESULT "))[7:])))
+    for r in range(a.on_runs):
+        on.append(json.loads(run(f"learner run {r} teacher on", ["--ppo-child", "--teacher-coef", str(a.on_coef)] + common, 900, lambda ln: ln.startswith("RESULT "))[7:]))
+    try:
+        commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode().strip()
+    except OSError:
+        commit = ""
+    lines = ["Kickstarting from the rule-based player: what it costs off and on (tools/bench_teacher.py)",
+             f"commit {commit or 'unknown (no git checkout where it ran)'}; one MI355X, a fresh process per run, the parent's library and this commit's alternating.", ""]
+    if bench:
+        lines += [f"OFF: bench.py --gpus 1 --steps {a.bench_steps} --warmup {a.bench_warmup}: env-steps/s, ms per pass, status"]
+        lines += [f"  {label} {value} {ms} {status}" for label, value, ms, status in bench]
+        pv, cv = [b[1] for b in bench if b[0] == "parent"], [b[1] for b in bench if b[0] == "change"]
+        if pv and cv:
+            mean = sum(cv) / len(cv)
+            lines.append(f"  the change's mean {mean:.6g} lies {_where(mean, pv, True)} the parent's spread {min(pv):.6g}..{max(pv):.6g}")
+        lines.append("")
+    if ppo:
+        lines += [f"OFF: the PPO learner, {a.envs} games x T = {a.num_steps}, bf16 autocast, {a.ppo_epoch} epoch(s) x 64 minibatches of {a.envs * a.num_steps // 64} rows,",
+                  "no teacher configured; the second update of a process: minibatch-step ms, rollout s, value pass s"]
+        lines += [f"  {label} {x['minibatch_step_ms']:.3f} {x['rollout_s']:.3f} {x['values_s']:.3f}" for label, x in ppo]
+        for key, name in (("minibatch_step_ms", "minibatch-step ms"), ("rollout_s", "rollout s")):
+            pv, cv = [x[key] for l, x in ppo if l == "parent"], [x[key] for l, x in ppo if l == "change"]
+            if pv and cv:
+                mean = sum(cv) / len(cv)
+                lines.append(f"  {name}: the change's mean {mean:.4f} lies {_where(mean, pv, False)} the parent's spread {min(pv):.4f}..{max(pv):.4f}")
+        lines.append("")
+    if on:
+        lines += [f"ON (reported, not bounded): RolloutCollector(teacher=ScriptedPolicy(env)), PPOConfig(teacher_coef={a.on_coef}); the same learner run:",
+                  "minibatch-step ms, rollout s, value pass s, HBM GB; the update's read-out"]
+        lines += [f"  {x['minibatch_step_ms']:.3f} {x['rollout_s']:.3f} {x['values_s']:.3f} {x['hbm_gb']:.1f}  {json.dumps(x.get('teacher'))}  invalid actions {x['invalid_actions']}" for x in on]
+        off = [x for l, x in ppo if l == "change"]
+        if off:
+            m = lambda xs, k: sum(x[k] for x in xs) / len(xs)
+            lines.append(f"  against this commit's runs without a teacher: minibatch step {m(on, 'minibatch_step_ms'):.3f} ms vs {m(off, 'minibatch_step_ms'):.3f} ms, "
+                         f"rollout {m(on, 'rollout_s'):.3f} s vs {m(off, 'rollout_s'):.3f} s ({on[0]['env_iters']} env iterations, three more launches each: the player, the completion, the store)")
+        lines.append("")
+    lines += ["NOT timed: the three kernels on their own (hipEvents around catan_complete_action_rows / catan_collector_label / catan_imitation_loss),",
+              "more than one rank, the LSTM path (not supported), teacher_only, the league rollout with a teacher, any effect on learning."]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -4,10 +4,12 @@ import os, re, subprocess, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from settlers_of_catan_rl_amd import _lib
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-with tempfile.NamedTemporaryFile(suffix=".co") as f:
-    f.write(_lib.device_code_object(sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".so") else None)); f.flush()
-    t = subprocess.run([READELF, "--notes", f.name], stdout=subprocess.PIPE).stdout.decode()
-    syms = subprocess.run([READELF, "-sW", f.name], stdout=subprocess.PIPE).stdout.decode()
+t = syms = ""
+for co in _lib.device_code_objects(sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".so") else None):     # one per translation unit
+    with tempfile.NamedTemporaryFile(suffix=".co") as f:
+        f.write(co); f.flush()
+        t += subprocess.run([READELF, "--notes", f.name], stdout=subprocess.PIPE).stdout.decode()
+        syms += subprocess.run([READELF, "-sW", f.name], stdout=subprocess.PIPE).stdout.decode()
 code = {}                      # mangled kernel name -> bytes of its function symbol
 for line in syms.splitlines():
     p = line.split()

@@ -42,6 +42,12 @@ def main():
                     help="with --start-pool: tally the finished games per pool entry on the device; every update's line carries them under \"start_pool\"")
     ap.add_argument("--start-pool-sampling", choices=["uniform", "balanced"], default="uniform",
                     help="balanced: draw the pool entries whose result is still open more often (implies --start-pool-outcomes)")
+    ap.add_argument("--teacher", choices=["scripted"], default=None,
+                    help="kickstarting: the rule-based player labels every decision of the rollouts; every update's line carries \"teacher\"")
+    ap.add_argument("--teacher-coef", metavar="C", type=float, default=0.0, help="with --teacher: the imitation term's coefficient at update 0")
+    ap.add_argument("--teacher-coef-updates", metavar="K", type=int, default=0,
+                    help="the coefficient falls linearly to 0 over K updates (0: constant); after that the collector stops labelling")
+    ap.add_argument("--teacher-only-updates", metavar="J", type=int, default=0, help="the first J updates are pure imitation (no policy-gradient, no entropy term)")
     args = ap.parse_args()
     league_stats = args.league > 0 and (args.league_stats or args.league_sampling == "pfsp")
     import torch
@@ -59,7 +65,11 @@ def main():
     env = VecCatanEnv(n, seed=args.seed, env_id0=env_id0)          # game_manager.py:16: EnvWrapper() defaults (sparse win reward)
     net = CatanPolicy(include_lstm=args.lstm).cuda()
     cdist.broadcast_parameters(net)
-    col = RolloutCollector(env, net, args.num_steps, seed=rank, autocast_dtype=torch.bfloat16, **(dict(league_stats=True) if league_stats else {}))
+    teach = dict(teacher=args.teacher, teacher_coef=args.teacher_coef, teacher_coef_updates=args.teacher_coef_updates,
+                 teacher_only_updates=args.teacher_only_updates) if args.teacher else {}
+    teacher = train_loop.make_teacher(train_loop.TrainArgs(**teach), env)
+    col = RolloutCollector(env, net, args.num_steps, seed=rank, autocast_dtype=torch.bfloat16, **(dict(league_stats=True) if league_stats else {}),
+                           **(dict(teacher=teacher) if teacher is not None else {}))
     tr = PPOTrainer(net, PPOConfig(ppo_epoch=args.ppo_epoch, num_mini_batch=args.num_mini_batch, diagnostics=args.diagnostics), seed=rank)
     random_net = CatanPolicy(include_lstm=args.lstm).cuda().eval()                                   # robust_train.py:76-78: the evaluation opponent
 
@@ -71,7 +81,7 @@ def main():
 
     lg = League(max_distinct=args.league, seed=rank, sampling=args.league_sampling) if args.league > 0 else None
     targs = train_loop.TrainArgs(num_steps=args.num_steps, eval_every=args.eval_every, num_eval_episodes=args.num_eval_episodes,
-                                 eval_scripted_baseline=args.eval_scripted_baseline,
+                                 eval_scripted_baseline=args.eval_scripted_baseline, **teach,
                                  **(dict(start_pool=args.start_pool, start_pool_fresh=args.start_pool_fresh, start_pool_outcomes=args.start_pool_outcomes,
                                         start_pool_sampling=args.start_pool_sampling) if args.start_pool else {}))
     loop = train_loop.TrainingLoop(env, net, col, tr, targs, league=lg, make_net=lambda: CatanPolicy(include_lstm=args.lstm).cuda(),
