@@ -254,6 +254,23 @@ int catan_start_pool_outcomes_read(catan_env_t* env, uint64_t* out_host, int32_t
  * CATAN_EINVAL, nothing launched: a null handle, null actions, n_rows <= 0, n_rows > n with games == NULL. */
 int catan_sample_scripted_actions(catan_env_t* env, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream);
 int64_t catan_scripted_fallback_count(catan_env_t* env, catan_stream_t stream);
+/* The player's STYLES.  catan_sample_scripted_actions_style(env, style, ...) is catan_sample_scripted_actions with the
+ * style chosen per call:
+ *   CATAN_SCRIPTED_BUILDER (0)  the builder: the same kernel, the same bits as catan_sample_scripted_actions;
+ *   CATAN_SCRIPTED_TRADER  (1)  the "trader" (csrc/catan_trader.hip): the builder's table with its Respond row replaced (an offer is
+ *                               accepted when it brings the hand closer to the player's goal: a city, a settlement, a road or a
+ *                               development card) and two rows in front of its Exchange row (a one-for-one proposal to the weakest
+ *                               opponent holding the wanted card, at most three a turn; a bank / harbour exchange of spare cards for
+ *                               the goal).  Where none of the three fires its action is the builder's.  Deterministic, always legal.
+ * The arguments, the required state of the masks and the answer to a bad or waiting game (EndTurn) are those of
+ * catan_sample_scripted_actions.  CATAN_EINVAL, nothing launched: an unknown style, and the refusals of catan_sample_scripted_actions.
+ * catan_scripted_trade_counts: the trader's decisions since creation (or the last reset), counted on the device: out[0] decisions,
+ * [1] proposals, [2] offers decided, [3] accepted, [4] rejected because the player could not pay (accept illegal), [5] rejected by the
+ * rule, [6] goal exchanges, [7] fall-backs (expected 0).  Bad and waiting games count nothing.  Synchronises the stream; reset != 0
+ * zeroes the block behind the read.  All zero before the first trader call.  catan_scripted_fallback_count counts the builder only. */
+enum { CATAN_SCRIPTED_BUILDER = 0, CATAN_SCRIPTED_TRADER = 1 };
+int catan_sample_scripted_actions_style(catan_env_t* env, int32_t style, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream);
+int catan_scripted_trade_counts(catan_env_t* env, uint64_t out[8], int32_t reset, catan_stream_t stream);
 
 /* ---- teacher labels (csrc/catan_teacher.hip) ----
  * catan_complete_action_rows makes any legal action row teacher-forceable through the net's heads.  The samplers (this player,

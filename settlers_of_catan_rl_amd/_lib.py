@@ -66,8 +66,9 @@ LLVM_OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
 # the translation units of the library, in link order: each brings a gfx950 code object of its own.  catan_abi.hip includes every other
-# kernel file; catan_teacher.hip is compiled apart so that the first code object is what it is without it
-TRANSLATION_UNITS = ("catan_abi.hip", "catan_teacher.hip")
+# kernel file; catan_teacher.hip and catan_trader.hip (8.14) are compiled apart so that the first code object is what it
+# is without them
+TRANSLATION_UNITS = ("catan_abi.hip", "catan_teacher.hip", "catan_trader.hip")
 
 
 def device_code_objects(path=None):
@@ -260,6 +261,8 @@ _SIGS = {
     "catan_masks_of": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
     "catan_sample_scripted_actions": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
     "catan_scripted_fallback_count": (C.c_int64, [_vp, _vp]),
+    "catan_sample_scripted_actions_style": (C.c_int, [_vp, C.c_int32, _vp, C.c_int64, _vp, _vp]),
+    "catan_scripted_trade_counts": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, _vp]),
     "catan_longest_path": (C.c_int, [_vp, _vp, _vp, _vp]),
     "catan_gae_workspace_doubles": (C.c_int64, [C.c_int64]),
     "catan_gae": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp]),

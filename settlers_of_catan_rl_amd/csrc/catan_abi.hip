@@ -100,6 +100,7 @@ struct catan_env {
     int lstats_nets, lstats_cap; // rows in use (without the totals row), and allocated
     int lstats_on;               // 0 off, else the mode bits of catan_league_stats_enable
     unsigned long long* script_fallback;   // catan_sample_scripted_actions: decisions taken by the fall-back row (catan_scripted.hip), allocated at the first call
+    unsigned long long* trade_counts;      // catan_sample_scripted_actions_style, style 1: the trader's TC_WORDS counters (catan_trader.h), allocated at its first call
     RecordBuf rec;               // catan_record_enable: the recorder's slots (catan_record.hip); not in `owned`: freed and re-made by every enable
     int rec_on;
     StartPoolBuf pool;           // catan_start_pool_set: the saved positions (catan_start_pool.hip); not in `owned`: freed and re-made by every set
@@ -2616,6 +2617,44 @@ int catan_imitation_loss(const float* lp, const int64_t* teacher, int64_t B, flo
     if (!block || !workspace) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL block or workspace");
     HIPCHK(teacher_launch_imitation(lp, (const long long*)teacher, (long)B, loss, dlp, block, workspace, S(stream)));
     return CATAN_OK;
+}
+
+}  // extern "C"
+
+// ---- the rule-based player's styles.  Host code only: style 0 is catan_sample_scripted_actions itself, style 1 launches
+// k_sample_trader of catan_trader.hip, a translation unit and a code object of its own (catan_trader.h).
+#include "catan_trader.h"
+
+extern "C" {
+
+int catan_sample_scripted_actions_style(catan_env_t* e, int32_t style, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
+    if (style == CATAN_SCRIPTED_BUILDER) return catan_sample_scripted_actions(e, games, n_rows, actions, stream);
+    if (style != CATAN_SCRIPTED_TRADER) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: unknown style (0 builder, 1 trader)");
+    if (!e) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: null handle");
+    if (!actions) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: null actions");
+    if (n_rows <= 0) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: n_rows <= 0");
+    if (!games && n_rows > e->n) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: n_rows exceeds the handle's games (games == NULL)");
+    if (!e->trade_counts) {
+        hipError_t rc = hipSuccess;
+        dev_alloc(e, rc, e->trade_counts, TC_WORDS * sizeof(unsigned long long));
+        if (rc != hipSuccess) return fail(CATAN_ENOMEM, std::string("catan_sample_scripted_actions_style: hipMalloc: ") + hipGetErrorString(rc));
+        // zeroed synchronously at its allocation (once per handle): in place before a call on ANY stream can count into it
+        HIPCHK(hipMemset(e->trade_counts, 0, TC_WORDS * sizeof(unsigned long long)));
+        HIPCHK(hipStreamSynchronize(nullptr));
+    }
+    HIPCHK(trader_launch_sample(e->ctx.R, e->ctx.n, (const u32*)e->mpk, games, (long)n_rows, e->d_it > 0 ? (const u8*)e->pend.busy : (const u8*)nullptr, actions,
+                                e->trade_counts, S(stream)));
+    return CATAN_OK;
+}
+
+int catan_scripted_trade_counts(catan_env_t* e, uint64_t out[8], int32_t reset, catan_stream_t stream) {
+    static_assert(TC_WORDS == 8, "catan_scripted_trade_counts: the block is 8 words (include/catan_hip_tuning.h)");
+    if (!e || !out) return fail(CATAN_EINVAL, "catan_scripted_trade_counts: null argument");
+    if (!e->trade_counts) {                                 // no trader call yet: nothing was counted
+        for (int k = 0; k < TC_WORDS; k++) out[k] = 0;
+        return CATAN_OK;
+    }
+    return read_counters(out, e->trade_counts, TC_WORDS * sizeof(unsigned long long), reset, S(stream));
 }
 
 }  // extern "C"

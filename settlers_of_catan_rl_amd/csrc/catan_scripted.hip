@@ -239,6 +239,7 @@ DEVI int sample_scripted(const St& s, const u32 (&m)[MASK_WORDS], int (&a)[ACTIO
     return 13;
 }
 
+#ifndef CATAN_SCRIPTED_RULE_ONLY    // catan_trader.hip takes the rule above into its own code object, without the builder's kernel
 // Row j of `actions` (int32 [rows][18]) = the bot's action for game games[j] (games == nullptr: game j).  A negative or out-of-range id,
 // and a game that waits for its deferred step (busy != nullptr: an open catan_step_deferred sequence), gets EndTurn - the bot's answer
 // to the placeholder mask row catan_masks_of hands out for such a game; neither the record nor the masks of such a game are read.
@@ -264,5 +265,6 @@ __global__ __launch_bounds__(SCRIPT_BLOCK) void k_sample_scripted(Ctx c, const u
 #pragma unroll
     for (int i = 0; i < ACTION_WORDS / 2; i++) row[i] = make_uint2((u32)a[2 * i], (u32)a[2 * i + 1]);
 }
+#endif
 
 }  // namespace catan

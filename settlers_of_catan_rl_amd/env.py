@@ -435,10 +435,15 @@ class VecCatanEnv(object):
         _lib.check(self.L.catan_sample_random_actions(self.h, int(step_idx), _ptr(out), _stream()))
         return out
 
-    def sample_scripted_actions(self, games=None, out=None):
-        """catan_sample_scripted_actions (include/catan_hip_tuning.h): the rule-based "builder" player's action for the deciding player of
+    SCRIPTED_STYLES = {"builder": 0, "trader": 1}      # CATAN_SCRIPTED_* (include/catan_hip_tuning.h)
+
+    def sample_scripted_actions(self, games=None, out=None, style="builder"):
+        """catan_sample_scripted_actions (include/catan_hip_tuning.h): the rule-based player's action for the deciding player of
         every game -> int32 [rows][18].  games (int32 [k]): row j is game games[j], as in get_action_masks(games=...); None: all n games.
+        style: "builder"  or "trader" (8.14: it answers offers, proposes and exchanges for a goal).
         The masks must be current (they are after reset / step / import_state)."""
+        if style not in self.SCRIPTED_STYLES:
+            raise ValueError(f"sample_scripted_actions: style must be one of {sorted(self.SCRIPTED_STYLES)}, got {style!r}")
         if games is not None:
             games = games if (games.dtype == torch.int32 and games.is_contiguous() and games.device == self.device) else \
                 games.to(device=self.device, dtype=torch.int32).contiguous()
@@ -446,9 +451,20 @@ class VecCatanEnv(object):
         if out is None:
             out = torch.empty((rows, spec.ACTION_WORDS), dtype=torch.int32, device=self.device)
         assert out.shape == (rows, spec.ACTION_WORDS) and out.dtype == torch.int32 and out.is_contiguous(), (out.shape, out.dtype)
-        if rows:
+        if rows and style == "builder":
             _lib.check(self.L.catan_sample_scripted_actions(self.h, _ptr(games), rows, _ptr(out), _stream()))
+        elif rows:
+            _lib.check(self.L.catan_sample_scripted_actions_style(self.h, self.SCRIPTED_STYLES[style], _ptr(games), rows, _ptr(out), _stream()))
         return out
+
+    TRADE_COUNT_KEYS = ("decisions", "proposals", "responses", "accepts", "rejects_illegal", "rejects_other", "goal_exchanges", "fallbacks")
+
+    def scripted_trade_counts(self, reset=False):
+        """catan_scripted_trade_counts: what the "trader" style decided since creation (or the last reset), counted on the device ->
+        {key: int} over TRADE_COUNT_KEYS; all zero before the first trader call.  Synchronises the stream."""
+        out = (C.c_uint64 * 8)()
+        _lib.check(self.L.catan_scripted_trade_counts(self.h, out, 1 if reset else 0, _stream()))
+        return {k: int(out[i]) for i, k in enumerate(self.TRADE_COUNT_KEYS)}
 
     def complete_action_rows(self, actions, games=None):
         """catan_complete_action_rows (include/catan_hip_tuning.h): the columns of each action row that its type does

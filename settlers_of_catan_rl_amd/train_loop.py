@@ -37,7 +37,8 @@ class TrainArgs(object):
     start_pool_outcomes = False          # opt-in: the finished games are tallied per pool entry on the device -> log["start_pool"]["outcomes"]
     start_pool_sampling = "uniform"      # "balanced": the entries whose result is still open are drawn more often (implies the outcomes)
     eval_scripted_baseline = False       # opt-in: the evaluation also plays the rule-based player (scripted.ScriptedPolicy) -> log["scripted"]
-    teacher = None                       # opt-in kickstarting: "scripted" - the rule-based player labels the rollouts (make_teacher)
+    eval_trader_baseline = False         # opt-in: ... and the trading rule-based player (scripted.TraderPolicy) -> log["trader"]
+    teacher = None                       # opt-in kickstarting: "scripted" - the rule-based player labels the rollouts (make_teacher); "trader": its trading style (8.14)
     teacher_coef = 0.0                   # ... the imitation term's coefficient at update 0
     teacher_coef_updates = 0             # ... falling linearly to 0 over this many updates (0: constant); at 0 the collector stops labelling
     teacher_only_updates = 0             # ... the first J updates are pure imitation (PPOConfig.teacher_only)
@@ -52,10 +53,13 @@ class TrainArgs(object):
 def eval_baselines(args):
     """The fixed opponents `args` adds to the evaluation protocol, as evaluation.run_evaluation_protocol(baselines=...) takes them;
     None (the default): the reference's protocol alone."""
-    if not getattr(args, "eval_scripted_baseline", False):
-        return None
-    from .scripted import ScriptedPolicy
-    return {"scripted": ScriptedPolicy}
+    from .scripted import ScriptedPolicy, TraderPolicy
+    out = {}
+    if getattr(args, "eval_scripted_baseline", False):
+        out["scripted"] = ScriptedPolicy
+    if getattr(args, "eval_trader_baseline", False):
+        out["trader"] = TraderPolicy
+    return out or None
 
 
 def make_teacher(args, env):
@@ -63,10 +67,10 @@ def make_teacher(args, env):
     name = getattr(args, "teacher", None)
     if name is None or not getattr(args, "teacher_coef", 0.0) > 0:
         return None
-    if name != "scripted":
-        raise ValueError(f"teacher must be 'scripted' or None, got {name!r}")
-    from .scripted import ScriptedPolicy
-    return ScriptedPolicy(env)
+    if name not in ("scripted", "trader"):
+        raise ValueError(f"teacher must be 'scripted', 'trader' or None, got {name!r}")
+    from .scripted import ScriptedPolicy, TraderPolicy
+    return TraderPolicy(env) if name == "trader" else ScriptedPolicy(env)
 
 
 def teacher_coef_at(update_num, args):

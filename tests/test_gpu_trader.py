@@ -1,0 +1,329 @@
+"""GPU: the rule-based "trader" player - k_sample_trader against the numpy restatement of the rule
+(tests/trader_reference.py) step by step and on hand-built states, its counters, style 0 against the builder's own entry point, game
+lists and waiting games, stepping its actions, every error return, its strength against uniform-random players, and its place in the
+rollout collector as an opponent and as a teacher."""
+import ctypes as C
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import action_complete_reference as acr
+import scripted_reference as sr
+import trader_reference as tr
+from test_trader_cpu import base, _offer, _seller, _banker, _action, _put, BRICK, WOOD, ORE, SHEEP, WHEAT  # noqa: F401 (base is a fixture)
+from settlers_of_catan_rl_amd import spec
+
+pytestmark = pytest.mark.gpu
+
+N, SEED = 96, 7          # as tests/test_gpu_scripted.py: a partial wave and a partial workgroup
+ENDTURN_ROW = [sr.ENDTURN] + [0] * 17
+P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _env(n, seed, **kw):
+    from settlers_of_catan_rl_amd.env import VecCatanEnv
+    return VecCatanEnv(n, seed=seed, **kw)
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def test_kernel_equals_the_twin_over_600_steps(hip_lib):
+    """Lock-step, auto-reset on.  At every step the kernel decides all 96 games and so does the twin from export_state() +
+    get_action_masks(): all 18 words equal.  Which action a game steps rotates with the step: the uniform-random sampler's (one step
+    in four: its offers are of every shape, one or two cards each way, payable or not), the builder's (one in four) or the trader's
+    (two in four).  At the end the device's counter block equals the twin's tallies.  Every new row, every label of a proposal, every
+    rate of a goal exchange and every reason for a rejection that play reaches must have been compared: accept illegal, more asked than
+    given, a proposer at 8 points, a deficit that does not fall.  (The fifth, "no goal", needs a player without a settlement piece or a
+    city to build and an empty pile: test_hand_built_states has it.)"""
+    env = _env(N, SEED)
+    assert env.scripted_trade_counts() == dict.fromkeys(tr.COUNT_KEYS, 0)          # nothing counted, nothing allocated before the first call
+    tally = tr.Tally()
+    rows, reasons, labels, rates = {}, np.zeros(6, dtype=np.int64), np.zeros(3, dtype=np.int64), np.zeros(5, dtype=np.int64)
+    g = torch.arange(N, device="cuda")
+    for step in range(600):
+        got = env.sample_scripted_actions(style="trader")
+        blobs, masks = env.export_state().cpu().numpy(), env.get_action_masks().cpu().numpy()
+        want, row = tr.decide_all(blobs, masks, tally)
+        got_h = got.cpu().numpy()
+        bad = np.flatnonzero((got_h != want).any(1))
+        assert bad.size == 0, (step, int(bad[0]), row[bad[0]], got_h[bad[0]].tolist(), want[bad[0]].tolist())
+        for i, r in enumerate(row):
+            rows[r] = rows.get(r, 0) + 1
+            if r == "2T":
+                c = tr.respond_conditions(blobs[i], masks[i])
+                reasons[5 if all(c) else c.index(False)] += 1
+            elif r == "11P":
+                labels[want[i, 6]] += 1
+            elif r == "11E":
+                rates[tr.rate(blobs[i], sr.deciding_pid0(blobs[i]), int(want[i, 15]))] += 1
+        mix = ((g + step) % 4)[:, None]
+        env.step(torch.where(mix == 0, env.sample_random_actions(step), torch.where(mix == 1, env.sample_scripted_actions(), got)))
+    counts = env.scripted_trade_counts()
+    print("decisions per row:", rows, "first failed condition of 2T (5: accepted):", reasons.tolist(), "labels:", labels.tolist(),
+          "rates:", rates.tolist(), "counters:", counts)
+    assert env.invalid_action_count() == 0
+    assert counts == tally.c and counts["decisions"] == 600 * N and counts["fallbacks"] == 0
+    assert all(rows.get(r, 0) > 0 for r in ("2T", "11P", "11E", 11, 12)), rows
+    assert (reasons[[0, 1, 2, 4, 5]] > 0).all(), reasons.tolist()
+    assert counts["rejects_illegal"] > 0 and counts["rejects_other"] > 0 and counts["accepts"] > 0
+    assert (labels > 0).all() and (rates[[2, 3, 4]] > 0).all(), (labels.tolist(), rates.tolist())
+    assert env.scripted_fallback_count() == 0
+
+
+def test_hand_built_states(hip_lib, base):
+    """the hand-built states of tests/test_trader_cpu.py on the device: the kernel gives the hand-written answers, and the twin's"""
+    nogoal = _offer(base, [WOOD], [SHEEP])
+    _put(nogoal, "corner_bld", 0); _put(nogoal, "corner_owner", 0)
+    spec.state_field(nogoal, "edge_owner")[4] = 1
+    spec.state_field(nogoal, "settlements_left")[0] = 0
+    _put(nogoal, "pile_len", 0)
+    at8 = _offer(base, [WOOD], [SHEEP])
+    spec.state_field(at8, "curr_vps")[1] = 8
+    dev = base.copy()
+    spec.state_field(dev, "corner_bld")[0] = 1; spec.state_field(dev, "corner_owner")[0] = 1
+    _put(dev, "p1_res", [0, 0, 1, 5, 0])
+    accept, reject, end = _action(sr.RESPOND, response=tr.ACCEPT), _action(sr.RESPOND, response=sr.REJECT), _action(sr.ENDTURN)
+    propose = lambda label: _action(sr.PROPOSE, player=label, give=SHEEP + 1, want=WOOD + 1)
+    exchange = _action(sr.EXCHANGE, res_a=SHEEP, res_b=WOOD)
+    cases = [(_offer(base, [WOOD], [SHEEP]), accept), (_offer(base, [WOOD], [ORE]), reject), (_offer(base, [WOOD], [SHEEP, SHEEP]), reject),
+             (at8, reject), (_offer(base, [ORE], [SHEEP]), reject), (nogoal, reject),
+             (_seller(base, 0), propose(1)), (_seller(base, 1), propose(2)), (_seller(base, 2), propose(0)), (_seller(base, 3), end),
+             (_seller(base, 0, vps=(2, 3, 8, 2)), propose(2)), (_seller(base, 0, woods=(1, 0, 0)), propose(0)),
+             (_banker(base, 4), exchange), (_banker(base, 3), end), (_banker(base, 3, harbours=[0]), exchange),
+             (_banker(base, 2, harbours=[SHEEP + 1]), exchange), (_banker(base, 3, harbours=[WOOD + 1]), end),
+             (dev, _action(sr.EXCHANGE, res_a=SHEEP, res_b=WHEAT))]
+    env = _env(len(cases), 0)
+    env.import_state(torch.from_numpy(np.stack([b for b, _ in cases])))
+    got = env.sample_scripted_actions(style="trader").cpu().numpy()
+    twin, _ = tr.decide_all(env.export_state().cpu().numpy(), env.get_action_masks().cpu().numpy())
+    for i, (_, want) in enumerate(cases):
+        assert got[i].tolist() == want and twin[i].tolist() == want, (i, got[i].tolist(), twin[i].tolist(), want)
+    c = env.scripted_trade_counts()
+    assert c == dict(decisions=18, proposals=5, responses=6, accepts=1, rejects_illegal=1, rejects_other=4, goal_exchanges=4, fallbacks=0), c
+    env.step(torch.from_numpy(got).cuda())
+    assert env.invalid_action_count() == 0
+
+
+def test_style_builder_is_the_old_entry_point(hip_lib):
+    L = hip_lib
+    env = _env(N, SEED)
+    env.random_rollout(0, 200)
+    old = env.sample_scripted_actions()
+    assert torch.equal(env.sample_scripted_actions(style="builder"), old)
+    new = torch.full((N, 18), -3, dtype=torch.int32, device="cuda")
+    assert L.catan_sample_scripted_actions_style(env.h, 0, None, N, P(new), _stream()) == 0
+    assert torch.equal(new, old)
+    sub = torch.tensor([5, 5, -1, N, 17], dtype=torch.int32, device="cuda")
+    new = torch.full((5, 18), -3, dtype=torch.int32, device="cuda")
+    assert L.catan_sample_scripted_actions_style(env.h, 0, P(sub), 5, P(new), _stream()) == 0
+    assert torch.equal(new, env.sample_scripted_actions(games=sub))
+    assert env.scripted_trade_counts()["decisions"] == 0                               # style 0 launches nothing of the trader's
+
+
+def test_game_lists_streams_and_counter_reset(hip_lib):
+    env = _env(N, SEED)
+    g = torch.arange(N, device="cuda")
+    for s in range(200):                                                               # a mix of ages with offers open
+        mix = ((g + s) % 3)[:, None]
+        env.step(torch.where(mix == 0, env.sample_random_actions(s), env.sample_scripted_actions(style="trader")))
+    env.scripted_trade_counts(reset=True)
+    assert env.scripted_trade_counts() == dict.fromkeys(tr.COUNT_KEYS, 0)
+    full = env.sample_scripted_actions(style="trader")
+    one = env.scripted_trade_counts()
+    assert one["decisions"] == N and not torch.equal(full, env.sample_scripted_actions())          # (the styles differ on these states)
+    assert env.scripted_trade_counts(reset=True) == one and env.scripted_trade_counts()["decisions"] == 0      # (the builder's call counted nothing)
+    sub = torch.randperm(N, generator=torch.Generator().manual_seed(1))[:37].to("cuda")
+    assert torch.equal(env.sample_scripted_actions(games=sub.to(torch.int32), style="trader"), full[sub])
+    assert torch.equal(env.sample_scripted_actions(games=sub, style="trader"), full[sub])          # (an int64 list is converted)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        on_side = env.sample_scripted_actions(games=sub.to(torch.int32), style="trader")
+    torch.cuda.current_stream().wait_stream(side)
+    assert torch.equal(on_side, full[sub])
+    out = torch.full((37, 18), -5, dtype=torch.int32, device="cuda")
+    assert env.sample_scripted_actions(games=sub, out=out, style="trader") is out and torch.equal(out, full[sub])
+    assert env.scripted_trade_counts(reset=True)["decisions"] == 4 * 37
+    # duplicates, and ids outside the handle: those get EndTurn and count nothing
+    odd = torch.tensor([3, 3, -1, N, 5, 3, 1 << 30], dtype=torch.int32, device="cuda")
+    a = env.sample_scripted_actions(games=odd, style="trader")
+    assert torch.equal(a[[0, 1, 4, 5]], full[[3, 3, 5, 3]]) and all(a[k].tolist() == ENDTURN_ROW for k in (2, 3, 6))
+    c = env.scripted_trade_counts()
+    assert c["decisions"] == 4 and c["proposals"] + c["responses"] + c["goal_exchanges"] <= 4
+
+
+@pytest.mark.parametrize("deferred", [False, True])
+def test_stepping_the_traders_actions_is_always_legal(hip_lib, deferred):
+    """300 all-trader steps, lock-step and under catan_step_deferred with window 4, where a game that waits for its step gets EndTurn
+    and counts nothing"""
+    env = _env(N, SEED + 1)
+    waiting = torch.zeros(N, dtype=torch.bool, device="cuda")
+    decided = seen_waiting = 0
+    for _ in range(300):
+        a = env.sample_scripted_actions(style="trader")
+        if deferred:
+            assert bool((a[waiting] == torch.tensor(ENDTURN_ROW, dtype=torch.int32, device="cuda")).all())
+            decided += int((~waiting).sum()); seen_waiting += int(waiting.sum())
+            waiting = env.step_deferred(a, window=4)[2].bool().clone()
+        else:
+            decided += N
+            env.step(a)
+    if deferred:
+        env.step_flush()
+        assert seen_waiting > 0
+    c = env.scripted_trade_counts()
+    assert env.invalid_action_count() == 0 and c["fallbacks"] == 0 and c["decisions"] == decided, (c, decided)
+    assert c["proposals"] > 0 and c["accepts"] > 0 and c["goal_exchanges"] > 0, c
+
+
+def test_every_error_return(hip_lib):
+    L = hip_lib
+    env = _env(64, 0)
+    out = torch.full((128, 18), -9, dtype=torch.int32, device="cuda")
+    cnt = (C.c_uint64 * 8)()
+
+    def err(rc):
+        assert rc == -1                                  # CATAN_EINVAL (include/catan_hip.h)
+        return L.catan_last_error().decode()
+    name = "catan_sample_scripted_actions_style"
+    for style in (2, -1, 7):
+        assert name in err(L.catan_sample_scripted_actions_style(env.h, style, None, 64, P(out), _stream())) and "style" in L.catan_last_error().decode()
+    assert name in err(L.catan_sample_scripted_actions_style(None, 1, None, 64, P(out), _stream()))
+    assert name in err(L.catan_sample_scripted_actions_style(env.h, 1, None, 64, None, _stream()))
+    assert name in err(L.catan_sample_scripted_actions_style(env.h, 1, None, 0, P(out), _stream()))
+    assert name in err(L.catan_sample_scripted_actions_style(env.h, 1, None, 65, P(out), _stream()))
+    assert "catan_sample_scripted_actions" in err(L.catan_sample_scripted_actions_style(env.h, 0, None, 65, P(out), _stream()))     # style 0: the old call's refusals
+    assert "catan_scripted_trade_counts" in err(L.catan_scripted_trade_counts(None, cnt, 0, _stream()))
+    assert "catan_scripted_trade_counts" in err(L.catan_scripted_trade_counts(env.h, None, 0, _stream()))
+    torch.cuda.synchronize()
+    assert bool((out == -9).all())                                                     # nothing was launched
+    assert L.catan_scripted_trade_counts(env.h, cnt, 0, _stream()) == 0 and list(cnt) == [0] * 8
+    assert L.catan_sample_scripted_actions_style(env.h, 1, None, 64, P(out), _stream()) == 0
+    assert L.catan_scripted_trade_counts(env.h, cnt, 1, _stream()) == 0 and cnt[0] == 64
+    assert L.catan_scripted_trade_counts(env.h, cnt, 0, _stream()) == 0 and list(cnt) == [0] * 8
+    with pytest.raises(ValueError, match="style"):
+        env.sample_scripted_actions(style="banker")
+
+
+def test_the_trader_beats_three_uniform_random_players(hip_lib):
+    """The builder's strength test (tests/test_gpu_scripted.py) with the trader in its place: 512 evaluation games, the same env seed
+    and seat orders, and its bound: the win share above 0.25 + 5 * sqrt(0.25 * 0.75 / 512) = 0.3457."""
+    from test_gpu_scripted import UniformRandom
+    from settlers_of_catan_rl_amd import evaluation as ev
+    from settlers_of_catan_rl_amd.scripted import TraderPolicy
+    n = 512
+    env = _env(n, 21, auto_reset=False)
+    rnd = UniformRandom(env)
+    res = ev.run_evaluation_episodes(env, [TraderPolicy(env), rnd, rnd, rnd], ev.sample_orders(n, random.Random(3)), max_steps=2500)
+    share, draws = float(np.mean(res["winner"] == 0)), float(np.mean(res["winner"] == -1))
+    c = env.scripted_trade_counts()
+    print(f"trader against three uniform-random players: win share {share:.4f}, draws {draws:.4f}, mean game steps {res['game_steps'].mean():.1f}, counters {c}")
+    assert env.invalid_action_count() == 0 and c["fallbacks"] == 0
+    assert share > 0.25 + 5.0 * (0.25 * 0.75 / n) ** 0.5, share
+
+
+def test_protocol_with_the_trader_baseline_by_class(hip_lib):
+    """run_evaluation_protocol(baselines={"trader": TraderPolicy}) works like "scripted": the class is instantiated and bound to the env
+    of its games (8 games, 60 steps at most)"""
+    from settlers_of_catan_rl_amd import evaluation as ev
+    from settlers_of_catan_rl_amd.policy import CatanPolicy
+    from settlers_of_catan_rl_amd.scripted import TraderPolicy
+    torch.manual_seed(0)
+    central, opp = CatanPolicy().cuda().eval(), CatanPolicy().cuda().eval()
+    envs = []
+
+    def make_env(n):
+        envs.append(_env(n, 8, auto_reset=False))
+        return envs[-1]
+    log, summary = ev.run_evaluation_protocol(make_env, central, opp, 8, update_num=2, rng=random.Random(1), max_steps=60, baselines={"trader": TraderPolicy})
+    assert list(log) == ["update", "random", "trader"] and set(log["trader"]) == set(log["random"]) and "8 games against trader." in summary
+    assert envs[1].scripted_trade_counts()["decisions"] > 0 and envs[0].scripted_trade_counts()["decisions"] == 0
+    assert all(e.invalid_action_count() == 0 for e in envs)
+
+
+def _collect(n, T, seed, gathers, fused, **ckw):
+    import rollout_fixture as rf
+    from test_gpu_collector import SamplerPolicy
+    from settlers_of_catan_rl_amd.rollout import RolloutCollector
+    from settlers_of_catan_rl_amd.scripted import TraderPolicy
+    env = _env(n, seed)
+    env.random_rollout(0, 150)
+    cenv = rf.CountingEnv(env)
+    col = RolloutCollector(cenv, SamplerPolicy(cenv), T, opponents=[TraderPolicy(env)], seed=seed, **ckw)
+    col.fused_bookkeeping = fused
+    out = []
+    for _ in range(gathers):
+        st = col.gather_rollouts()
+        snap = {k: getattr(st, k).clone().cpu() for k in ("obs_f", "lists", "lens", "masks", "rewards", "actions", "action_log_probs", "action_masks")}
+        snap["games_complete"] = st.games_complete
+        snap["state"] = env.export_state().cpu()
+        snap["n_obs"] = col.n_obs.clone().cpu(); snap["iters"] = col.iters
+        out.append(snap)
+        col.after_rollouts()
+    c = env.scripted_trade_counts()
+    assert env.invalid_action_count() == 0 and c["fallbacks"] == 0 and c["decisions"] > 0
+    return out, c
+
+
+def test_collector_with_a_trader_opponent(hip_lib):
+    """T = 8, N = 64, the three opponent slots of every game played by the trader - RolloutCollector needs nothing but the policy
+    object: the tensor-operation loop and the device loop store identical rollouts, and so does the device loop under the default
+    deferred window; the trader answered the sampler policy's offers"""
+    from test_gpu_collector import _same
+    base_run, c = _collect(64, 8, 5, 2, False, deferred_window=0)
+    assert c["responses"] > 0
+    _same(base_run, _collect(64, 8, 5, 2, True, deferred_window=0)[0], "device loop")
+    _same(base_run, _collect(64, 8, 5, 2, True)[0], "device loop, default deferred window")
+
+
+def test_collector_with_a_trader_teacher(hip_lib):
+    """T = 8, N = 64, two rollouts with teacher=TraderPolicy(env): the stored labels are the twin's rows, completed, for the states the
+    stored decisions were taken in (the tensor-operation loop), and the device loop stores the same"""
+    import rollout_fixture as rf
+    from test_gpu_collector import SamplerPolicy
+    from test_gpu_teacher import SpyEnv
+    from settlers_of_catan_rl_amd.rollout import RolloutCollector
+    from settlers_of_catan_rl_amd.scripted import TraderPolicy
+    n, T = 64, 8
+
+    def collect(fused, spy, **ckw):
+        env = _env(n, 5)
+        env.random_rollout(0, 150)
+        inner = SpyEnv(env) if spy else env
+        cenv = rf.CountingEnv(inner)
+        col = RolloutCollector(cenv, SamplerPolicy(cenv), T, seed=5, teacher=TraderPolicy(env), **ckw)
+        col.fused_bookkeeping = fused
+        out = []
+        for _ in range(2):
+            first = len(inner.log) if spy else 0
+            st = col.gather_rollouts()
+            out.append(dict(labels=st.teacher_actions.clone().cpu(), actions=st.actions.clone().cpu(), n_act=col.n_act.clone().cpu(),
+                            log=inner.log[first:] if spy else None))
+            col.after_rollouts()
+        assert env.invalid_action_count() == 0
+        return out, col.active_pid.cpu().numpy()
+    ref, active = collect(False, True, deferred_window=0)
+    types = np.zeros(13, dtype=np.int64)
+    for snap in ref:
+        n_act, want = np.zeros(n, dtype=np.int64), np.zeros((T, n, 18), dtype=np.int64)
+        for blobs, masks, res, deciding, live in snap["log"]:
+            for g in range(n):
+                if live[g] and deciding[g] == active[g]:
+                    row = tr.decide(blobs[g], masks[g])[0]
+                    types[row[0]] += 1
+                    want[min(int(n_act[g]), T - 1), g] = acr.complete(row, masks[g], res[g])
+                    n_act[g] += 1
+        assert np.array_equal(n_act, snap["n_act"].numpy())
+        got = snap["labels"].numpy()
+        for g in range(n):
+            k = min(int(n_act[g]), T)
+            assert np.array_equal(got[:k, g], want[:k, g]), (g, got[:k, g].tolist(), want[:k, g].tolist())
+    assert types[sr.PROPOSE] > 0, types.tolist()                                       # the labels hold what the builder's never do
+    for ckw in (dict(deferred_window=0), dict(deferred_window=4)):
+        got, _ = collect(True, False, **ckw)
+        for x, y in zip(ref, got):
+            assert torch.equal(x["labels"], y["labels"]) and torch.equal(x["actions"], y["actions"]) and torch.equal(x["n_act"], y["n_act"]), ckw

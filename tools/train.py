@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--eval-max-steps", type=int, default=2500)
     ap.add_argument("--eval-scripted-baseline", action="store_true",
                     help="every evaluation also plays the rule-based player (scripted.ScriptedPolicy): log[\"scripted\"], comparable across runs")
+    ap.add_argument("--eval-trader-baseline", action="store_true",
+                    help="every evaluation also plays the trading rule-based player (scripted.TraderPolicy): log[\"trader\"]")
     ap.add_argument("--checkpoint", type=str, default="")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lstm", action="store_true", help="include_lstm (build_agent_model.py:26): LSTM policy + truncated BPTT")
@@ -42,8 +44,8 @@ def main():
                     help="with --start-pool: tally the finished games per pool entry on the device; every update's line carries them under \"start_pool\"")
     ap.add_argument("--start-pool-sampling", choices=["uniform", "balanced"], default="uniform",
                     help="balanced: draw the pool entries whose result is still open more often (implies --start-pool-outcomes)")
-    ap.add_argument("--teacher", choices=["scripted"], default=None,
-                    help="kickstarting: the rule-based player labels every decision of the rollouts; every update's line carries \"teacher\"")
+    ap.add_argument("--teacher", choices=["scripted", "trader"], default=None,
+                    help="kickstarting: the rule-based player (trader: its trading style) labels every decision of the rollouts; every update's line carries \"teacher\"")
     ap.add_argument("--teacher-coef", metavar="C", type=float, default=0.0, help="with --teacher: the imitation term's coefficient at update 0")
     ap.add_argument("--teacher-coef-updates", metavar="K", type=int, default=0,
                     help="the coefficient falls linearly to 0 over K updates (0: constant); after that the collector stops labelling")
@@ -81,7 +83,7 @@ def main():
 
     lg = League(max_distinct=args.league, seed=rank, sampling=args.league_sampling) if args.league > 0 else None
     targs = train_loop.TrainArgs(num_steps=args.num_steps, eval_every=args.eval_every, num_eval_episodes=args.num_eval_episodes,
-                                 eval_scripted_baseline=args.eval_scripted_baseline, **teach,
+                                 eval_scripted_baseline=args.eval_scripted_baseline, eval_trader_baseline=args.eval_trader_baseline, **teach,
                                  **(dict(start_pool=args.start_pool, start_pool_fresh=args.start_pool_fresh, start_pool_outcomes=args.start_pool_outcomes,
                                         start_pool_sampling=args.start_pool_sampling) if args.start_pool else {}))
     loop = train_loop.TrainingLoop(env, net, col, tr, targs, league=lg, make_net=lambda: CatanPolicy(include_lstm=args.lstm).cuda(),
