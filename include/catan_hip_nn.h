@@ -213,7 +213,8 @@ int catan_lstm_cell_bwd(const void* gx, const void* gh, const float* c_prev, con
 
 /* Masked categorical action head (RL/distributions.py:10-40; sampled / evaluated in RL/models/action_heads_module.py:202-256):
  * logp = log_softmax(logits + log(mask)) per row.  logits fp32 [rows][K] contiguous; mask fp32 rows of pitch mask_ld (> 0 =
- * legal; may be a column window of the [rows][325] mask matrix); given int64 [rows] or NULL (evaluate those actions);
+ * legal; may be a column window of the [rows][325] mask matrix); given int64 [rows] or NULL (evaluate those actions; after conversion to
+ * int32 a value outside [0, K - 1] is clamped into it, and `action` returns the clamped value; an illegal one has log-prob -inf);
  * u fp32 [rows] uniform in [0,1) or NULL: inverse-CDF sample; both NULL: arg-max.  Outputs: action int64, its log-prob,
  * the row entropy -sum p logp over p > 0, and the row's log-sum-exp (kept for the backward).
  * backward: dlogits = dlogp * (onehot(action) - p) - dent * p * (logp + entropy), 0 on masked entries. */
@@ -225,7 +226,7 @@ int catan_categorical_bwd(const float* logits, const float* mask, int64_t mask_l
  * [n][pitch_words], bit i of the flat mask = word i >> 5, bit i & 31) instead of a float window: row j of the launch uses packed row rows_idx[j]
  * (NULL: j).  segs (HOST, 8 ints): n0, n1, then (bit offset, AND offset or -1) for the rows j < n0, n0 <= j < n1 and j >= n1 - the heads whose
  * mask row depends on the action type run on rows sorted by type (build_agent_model.py:113-124); an AND offset multiplies a second mask row in.
- * given: int64, given_ld elements between consecutive rows (a column of an action matrix), or NULL (arg-max). */
+ * given: int64, given_ld elements between consecutive rows (a column of an action matrix), converted and clamped as above, or NULL (arg-max). */
 int catan_categorical_bits_fwd(const float* logits, const uint32_t* packed, int64_t pitch_words, const int64_t* rows_idx, const int32_t* segs, const int64_t* given,
                                int64_t given_ld, int64_t* action, float* logp, float* entropy, float* lse, int64_t rows, int K, catan_stream_t stream);
 int catan_categorical_bits_bwd(const float* logits, const uint32_t* packed, int64_t pitch_words, const int64_t* rows_idx, const int32_t* segs, const int64_t* action,
