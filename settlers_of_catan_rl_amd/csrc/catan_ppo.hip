@@ -8,7 +8,7 @@
 //                    action_log_probs and values in the same pass
 //   k_ppo_diag       opt-in read-out of what that loss did to a step's rows (approximate KL, clip counts, the sums behind the
 //                    explained variance, the step's entropy and gradient norm), accumulated into one block of doubles per epoch
-// fp32 recurrences are evaluated in the reference's operand order with contraction disabled (__fmul_rn/__fadd_rn)
+// fp32 recurrences are evaluated in the reference's operand order with contraction disabled (#pragma clang fp contract(off))
 // so returns match torch bit-for-bit; reductions accumulate in fp64 in a fixed order (deterministic).
 #include <hip/hip_runtime.h>
 
@@ -29,13 +29,17 @@ __global__ __launch_bounds__(GAE_BLOCK) void k_gae(const float* __restrict__ rew
         float v1 = values[T * N + n];
         for (long t = T - 1; t >= 0; t--) {
             const float m1 = masks[(t + 1) * N + n], v0 = values[t * N + n], r = rewards[t * N + n];
-            // delta = r + gamma * v1 * m1 - v0          (process_batch.py:137)
-            const float delta = __fsub_rn(__fadd_rn(r, __fmul_rn(__fmul_rn(gamma, v1), m1)), v0);
-            // gae = delta + gamma * lambda * m1 * gae   (process_batch.py:138)
-            gae = __fadd_rn(delta, __fmul_rn(__fmul_rn(gl, m1), gae));
-            const float ret = __fadd_rn(gae, v0);        // process_batch.py:139
+            float ret, a;
+            {
+                // every product rounded before it is added, as torch's separate operations do (the __fmul_rn / __fadd_rn of the HIP
+                // headers are a plain * and +, which the default -ffp-contract fuses into v_fma_f32: the pragma is what forbids it)
+#pragma clang fp contract(off)
+                const float delta = (r + (gamma * v1) * m1) - v0;       // delta = r + gamma * v1 * m1 - v0          (process_batch.py:137)
+                gae = delta + (gl * m1) * gae;                          // gae = delta + gamma * lambda * m1 * gae   (process_batch.py:138)
+                ret = gae + v0;                                         // process_batch.py:139
+                a = ret - v0;                                           // process_batch.py:141
+            }
             returns[t * N + n] = ret;
-            const float a = __fsub_rn(ret, v0);          // process_batch.py:141
             adv[t * N + n] = a;
             sum += (double)a; sumsq += (double)a * (double)a;
             v1 = v0;
@@ -95,19 +99,25 @@ __global__ __launch_bounds__(PPO_THREADS) void k_ppo_loss(const float* __restric
         const float ratio = expf(logp[i] - old_logp[i]);                    // ppo.py:54
         const float ad = adv[i];
         const float s1 = ratio * ad;                                        // :55
-        const float rc = fminf(fmaxf(ratio, lo), hi);
+        // torch.clamp / min / max pass NaN on where fminf / fmaxf return the other operand: a non-finite row reaches both the loss and
+        // its own gradient (the comparisons below are false for NaN, so the ternaries keep it); finite rows take the same values as before
+        const float rc = ratio < lo ? lo : (ratio > hi ? hi : ratio);
         const float s2 = rc * ad;                                           // :56
-        la += (double)(-fminf(s1, s2));                                     // :57
+        const float smin = (s1 != s1 || s2 != s2) ? s1 + s2 : fminf(s1, s2);
+        la += (double)(-smin);                                              // :57
         const bool inside = ratio >= lo && ratio <= hi;
-        d_logp[i] = (s1 <= s2 || inside) ? -s1 * invB : 0.0f;               // d(-min)/dlogp = -ratio * adv on the active branch
+        d_logp[i] = smin != smin ? smin : ((s1 <= s2 || inside) ? -s1 * invB : 0.0f);   // d(-min)/dlogp = -ratio * adv on the active branch
         const float v = values[i];
         const float dv = v - vp;
-        const float vc = vp + fminf(fmaxf(dv, -a.clip), a.clip);            // :59-60
+        const float vc = vp + (dv < -a.clip ? -a.clip : (dv > a.clip ? a.clip : dv));   // :59-60
         const float e1 = v - ret, e2 = vc - ret;
         const float l1 = e1 * e1, l2 = e2 * e2;                             // :61-62
-        lv += 0.5 * (double)fmaxf(l1, l2);                                  // :63
+        const float lmax = (l1 != l1 || l2 != l2) ? l1 + l2 : fmaxf(l1, l2);
+        lv += 0.5 * (double)lmax;                                           // :63
         const bool vin = dv >= -a.clip && dv <= a.clip;
-        d_values[i] = a.value_coef * invB * ((l1 >= l2) ? e1 : (vin ? e2 : 0.0f));
+        // on a tie torch's maximum hands half of the gradient to each side, and the clipped side passes its half on only inside the range
+        const float e2v = vin ? e2 : 0.0f;
+        d_values[i] = lmax != lmax ? lmax : a.value_coef * invB * (l1 > l2 ? e1 : (l1 < l2 ? e2v : 0.5f * (e1 + e2v)));
     }
     sh[0][threadIdx.x] = la; sh[1][threadIdx.x] = lv;
     __syncthreads();
