@@ -272,6 +272,50 @@ enum { CATAN_SCRIPTED_BUILDER = 0, CATAN_SCRIPTED_TRADER = 1 };
 int catan_sample_scripted_actions_style(catan_env_t* env, int32_t style, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream);
 int catan_scripted_trade_counts(catan_env_t* env, uint64_t out[8], int32_t reset, catan_stream_t stream);
 
+/* ---- the playout player (csrc/catan_playout.hip) ----
+ * A flat Monte-Carlo player that needs no net: per row it takes C candidate moves (the builder's, the trader's, `randoms` uniform-random
+ * legal ones, in this order), plays each out K times for `depth` env steps with the rule-based player of `playout_style` in every seat,
+ * on copies of the root game in a second handle, and answers with the candidate whose playouts score best for the root's deciding player p:
+ *     score of one playout = 1000 * [the game finished and p won] + 10 * (vp_p - max over q != p of vp_q)      (an integer)
+ * summed over the K playouts; ties go to the lowest candidate index.  A candidate that is bytewise equal to a lower-numbered one of its
+ * row is a duplicate: it is not played and never chosen.
+ *   root     the games that are decided; nothing of it is written, counted or drawn (it is only the source of catan_state_fork)
+ *   sim      a scratch handle on the same device, created with auto_reset = 0 and the root's max_proposed_trades_per_turn and
+ *            max_actions_per_turn, with at least n_rows * C * K games.  Slot (j*C + c)*K + k holds playout k of candidate c of row j.
+ *            Its games are overwritten by every call and its counters (catan_scripted_trade_counts, catan_invalid_action_count,
+ *            catan_inconsistent_deal_count ...) are the playouts'.  Give it a seed / env_id0 whose game ids are disjoint from the root's.
+ *   games    device int32 [n_rows] or NULL, as for catan_sample_scripted_actions: NULL = row j is game j; a game may be listed twice
+ *            (two independent rows); a negative or out-of-range id gets EndTurn, chosen -1 and an all-zero stats block
+ *   actions  device int32 [n_rows][18]: the chosen candidates' rows
+ *   chosen   device int32 [n_rows] or NULL: the chosen candidates' indices
+ *   stats    device int64 [n_rows][C][CATAN_PLAYOUT_STAT_WORDS] or NULL: per candidate valid (0: a duplicate, whose row is all zero),
+ *            sims, finished, wins, score sum, p's victory-point sum, steps really taken (spec.PLAYOUT_STAT_FIELDS)
+ * Enqueued on `stream`, in this order: the fork with draw_offset (1 + k) << 22; the candidates, sampled on the sim handle in the slots
+ * (j, c, 0); k_playout_expand; catan_randomise_uncertainty for p if `determinise`; the candidates' step; depth - 1 times the sampler of
+ * playout_style, k_playout_hold (finished, duplicate and bad slots get the no-op type -1) and catan_step; k_playout_score.  The call adds
+ * no host wait of its own; the first call on a sim handle allocates its workspace and, inside the samplers, their counters (one
+ * synchronous memset each, once per handle).  Deterministic: equal root states, handles and cfg give equal bits.
+ * Cost follows the SIM HANDLE's size, not only the call's: catan_sample_random_actions, k_playout_expand and every catan_step run over all
+ * of sim's games (the slots behind n_rows * C * K get the no-op), and the builder's and the trader's candidate samplers each run over all
+ * n_rows * C slots (j, c, 0) though each owns one column.  Size the sim handle for the passes it serves.
+ * Neither handle may be inside an open catan_step_deferred sequence (the fork would copy games that wait for their step): a caller
+ * that steps the root with catan_step_deferred flushes first, or steps with catan_step (rollout.RolloutCollector does the latter).
+ * CATAN_EINVAL, nothing launched: a null handle, cfg or actions; root == sim; handles on different devices; sim with auto_reset = 1 or
+ * with other turn / trade limits than root; n_rows <= 0, n_rows > root's games with games == NULL, or n_rows * C * K > sim's games;
+ * builder or trader outside 0..1, randoms < 0, C outside 1..8, playouts outside 1..64, depth < 1, an unknown playout_style; a handle
+ * under the MT19937 contract or inside an open catan_step_deferred sequence. */
+enum { CATAN_PLAYOUT_STAT_WORDS = 7 };
+typedef struct {
+    int32_t builder, trader, randoms;   /* candidates: C = builder + trader + randoms, 1..8 */
+    int32_t playouts;                   /* K, 1..64 */
+    int32_t depth;                      /* D >= 1: env steps per playout, the candidate's own step included */
+    int32_t playout_style;              /* CATAN_SCRIPTED_BUILDER / _TRADER: who plays every seat */
+    int32_t determinise;                /* 1: catan_randomise_uncertainty for the root's deciding player */
+    uint32_t step_idx;                  /* Philox step index of the random candidates */
+} catan_playout_cfg_t;
+int catan_playout_actions(catan_env_t* root, catan_env_t* sim, const int32_t* games, int64_t n_rows, const catan_playout_cfg_t* cfg,
+                          int32_t* actions, int32_t* chosen, int64_t* stats, catan_stream_t stream);
+
 /* ---- teacher labels (csrc/catan_teacher.hip) ----
  * catan_complete_action_rows makes any legal action row teacher-forceable through the net's heads.  The samplers (this player,
  * catan_sample_random_actions) fill only the columns their action type uses; the heads evaluate EVERY column of every row and multiply

@@ -34,6 +34,12 @@ class CatanBoardCfg(C.Structure):
                 ("terrain", C.c_int8 * 19), ("numbers", C.c_int8 * 18), ("reserved_", C.c_int8 * 7)]
 
 
+class CatanPlayoutCfg(C.Structure):
+    """catan_playout_cfg_t (include/catan_hip_tuning.h)"""
+    _fields_ = [("builder", C.c_int32), ("trader", C.c_int32), ("randoms", C.c_int32), ("playouts", C.c_int32), ("depth", C.c_int32),
+                ("playout_style", C.c_int32), ("determinise", C.c_int32), ("step_idx", C.c_uint32)]
+
+
 def _sources():
     out = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h", ".inc"))]
     inc = os.path.join(os.path.dirname(PKG_DIR), "include")
@@ -66,9 +72,9 @@ LLVM_OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
 # the translation units of the library, in link order: each brings a gfx950 code object of its own.  catan_abi.hip includes every other
-# kernel file; catan_teacher.hip and catan_trader.hip (8.14) are compiled apart so that the first code object is what it
-# is without them
-TRANSLATION_UNITS = ("catan_abi.hip", "catan_teacher.hip", "catan_trader.hip")
+# kernel file; catan_teacher.hip, catan_trader.hip (8.14) and catan_playout.hip (8.15) are compiled apart, each appended
+# behind the others, so that the code objects before it are what they are without it
+TRANSLATION_UNITS = ("catan_abi.hip", "catan_teacher.hip", "catan_trader.hip", "catan_playout.hip")
 
 
 def device_code_objects(path=None):
@@ -350,6 +356,7 @@ _SIGS = {
     "catan_imitation_loss_words": (C.c_int64, []),
     "catan_imitation_loss_workspace_doubles": (C.c_int64, []),
     "catan_imitation_loss": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "catan_playout_actions": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(CatanPlayoutCfg), _vp, _vp, _vp, _vp]),
 }
 # bound only where the library exports them: the same callers also load oracle/libcatan_cpu.so, which implements the env ABI
 # without these

@@ -101,6 +101,7 @@ struct catan_env {
     int lstats_on;               // 0 off, else the mode bits of catan_league_stats_enable
     unsigned long long* script_fallback;   // catan_sample_scripted_actions: decisions taken by the fall-back row (catan_scripted.hip), allocated at the first call
     unsigned long long* trade_counts;      // catan_sample_scripted_actions_style, style 1: the trader's TC_WORDS counters (catan_trader.h), allocated at its first call
+    void* playout_mem;           // catan_playout_actions with this handle as `sim`: the workspace (catan_playout.h PlayoutWs, carved from one allocation), allocated at its first call
     RecordBuf rec;               // catan_record_enable: the recorder's slots (catan_record.hip); not in `owned`: freed and re-made by every enable
     int rec_on;
     StartPoolBuf pool;           // catan_start_pool_set: the saved positions (catan_start_pool.hip); not in `owned`: freed and re-made by every set
@@ -2655,6 +2656,96 @@ int catan_scripted_trade_counts(catan_env_t* e, uint64_t out[8], int32_t reset, 
         return CATAN_OK;
     }
     return read_counters(out, e->trade_counts, TC_WORDS * sizeof(unsigned long long), reset, S(stream));
+}
+
+}  // extern "C"
+
+// ---- the playout player.  Host code only: the order of the launches.  The games are forked, sampled, re-dealt and stepped by the
+// entry points above; the bookkeeping kernels are catan_playout.hip's, a translation unit and a code object of their own (catan_playout.h).
+#include "catan_playout.h"
+
+// the workspace of a sim handle of n games, carved from one device allocation (8-byte arrays first, then the 72-byte rows, words, bytes)
+static PlayoutWs playout_carve(void* mem, size_t n) {
+    PlayoutWs w;
+    char* p = (char*)mem;
+    const size_t rows = n * ACTION_WORDS * sizeof(i32);
+    w.src_idx = (long long*)p; p += n * sizeof(long long);
+    w.by_builder = (i32*)p; p += rows;
+    w.by_trader = (i32*)p; p += rows;
+    w.by_random = (i32*)p; p += rows;
+    w.act = (i32*)p; p += rows;
+    w.cand = (i32*)p; p += rows;
+    w.draw_off = (u32*)p; p += n * sizeof(u32);
+    w.slot0 = (i32*)p; p += n * sizeof(i32);
+    w.ctrl = (i32*)p; p += n * sizeof(i32);
+    w.steps = (i32*)p; p += n * sizeof(i32);
+    w.rpid = (i32*)p; p += n * sizeof(i32);
+    w.held = (u8*)p; p += n;
+    w.dup = (u8*)p;
+    return w;
+}
+constexpr size_t PLAYOUT_WS_BYTES_PER_GAME = sizeof(long long) + 5 * ACTION_WORDS * sizeof(i32) + 5 * sizeof(u32) + 2;
+
+extern "C" {
+
+int catan_playout_actions(catan_env_t* root, catan_env_t* sim, const int32_t* games, int64_t n_rows, const catan_playout_cfg_t* cfg, int32_t* actions,
+                          int32_t* chosen, int64_t* stats, catan_stream_t stream) {
+    static_assert(PS_WORDS == CATAN_PLAYOUT_STAT_WORDS, "catan_playout_actions: the stats row (include/catan_hip_tuning.h)");
+    if (!root || !sim) return fail(CATAN_EINVAL, "catan_playout_actions: null handle");
+    if (!cfg) return fail(CATAN_EINVAL, "catan_playout_actions: null cfg");
+    if (!actions) return fail(CATAN_EINVAL, "catan_playout_actions: null actions");
+    if (root == sim) return fail(CATAN_EINVAL, "catan_playout_actions: root and sim are the same handle (the playouts overwrite the sim handle's games)");
+    if (root->device != sim->device) return fail(CATAN_EINVAL, "catan_playout_actions: the handles live on different devices");
+    if (sim->cfg.auto_reset) return fail(CATAN_EINVAL, "catan_playout_actions: the sim handle has auto_reset = 1 (a finished playout must keep its final state)");
+    const Limits lr = limits_of(root), ls = limits_of(sim);
+    if (lr.max_trades != ls.max_trades || lr.max_actions != ls.max_actions)
+        return fail(CATAN_EINVAL, "catan_playout_actions: max_proposed_trades_per_turn / max_actions_per_turn of the sim handle differ from the root's");
+    if ((cfg->builder != 0 && cfg->builder != 1) || (cfg->trader != 0 && cfg->trader != 1) || cfg->randoms < 0 || cfg->randoms > PLAYOUT_MAX_CANDIDATES)
+        return fail(CATAN_EINVAL, "catan_playout_actions: builder and trader are 0 or 1, randoms 0..8");
+    const int Cn = cfg->builder + cfg->trader + cfg->randoms, K = cfg->playouts;
+    if (Cn < 1 || Cn > PLAYOUT_MAX_CANDIDATES) return fail(CATAN_EINVAL, "catan_playout_actions: builder + trader + randoms must be in 1..8");
+    if (K < 1 || K > PLAYOUT_MAX_PLAYOUTS) return fail(CATAN_EINVAL, "catan_playout_actions: playouts must be in 1..64");
+    if (cfg->depth < 1) return fail(CATAN_EINVAL, "catan_playout_actions: depth must be at least 1");
+    if (cfg->playout_style != CATAN_SCRIPTED_BUILDER && cfg->playout_style != CATAN_SCRIPTED_TRADER)
+        return fail(CATAN_EINVAL, "catan_playout_actions: unknown playout_style (0 builder, 1 trader)");
+    if (n_rows <= 0) return fail(CATAN_EINVAL, "catan_playout_actions: n_rows <= 0");
+    if (!games && n_rows > root->n) return fail(CATAN_EINVAL, "catan_playout_actions: n_rows exceeds the root handle's games (games == NULL)");
+    if (n_rows > sim->n / ((int64_t)Cn * K)) return fail(CATAN_EINVAL, "catan_playout_actions: n_rows * candidates * playouts exceeds the sim handle's games");
+    NOT_MT(root, "catan_playout_actions");
+    NOT_MT(sim, "catan_playout_actions");
+    NOT_DEFERRED(root, "catan_playout_actions");
+    NOT_DEFERRED(sim, "catan_playout_actions");
+    if (!sim->playout_mem) {
+        hipError_t rc = hipSuccess;
+        dev_alloc(sim, rc, sim->playout_mem, (size_t)sim->n * PLAYOUT_WS_BYTES_PER_GAME);
+        if (rc != hipSuccess) { sim->playout_mem = nullptr; return fail(CATAN_ENOMEM, std::string("catan_playout_actions: hipMalloc: ") + hipGetErrorString(rc)); }
+    }
+    const PlayoutWs ws = playout_carve(sim->playout_mem, (size_t)sim->n);
+    PlayoutShape sh;
+    sh.rows = (long)n_rows; sh.used = (long)n_rows * Cn * K; sh.sim_n = sim->n; sh.C = Cn; sh.K = K;
+    sh.n_builder = cfg->builder; sh.n_trader = cfg->trader; sh.determinise = cfg->determinise != 0;
+    const hipStream_t st = S(stream);
+    const long cand_rows = (long)n_rows * Cn;
+    // 1. the fork: slot s = a copy of its row's root game, its draw counter moved on by (1 + k) << 22
+    HIPCHK(playout_launch_slots(sh, games, (long)root->n, ws, st));
+    OK_OR_RETURN(catan_state_fork(sim, root, (const int64_t*)ws.src_idx, nullptr, ws.draw_off, sh.used, stream));
+    // 2. the candidates, sampled on the sim handle in the slots (j, c, 0): builder, trader, random
+    if (cfg->builder) OK_OR_RETURN(catan_sample_scripted_actions_style(sim, CATAN_SCRIPTED_BUILDER, ws.slot0, cand_rows, ws.by_builder, stream));
+    if (cfg->trader) OK_OR_RETURN(catan_sample_scripted_actions_style(sim, CATAN_SCRIPTED_TRADER, ws.slot0, cand_rows, ws.by_trader, stream));
+    if (cfg->randoms) OK_OR_RETURN(catan_sample_random_actions(sim, cfg->step_idx, ws.by_random, stream));
+    // 3 - 5. candidate rows, duplicates, first actions; the re-deal of what the deciding player cannot see; the candidates' own step
+    HIPCHK(playout_launch_expand(sh, sim->ctx.R, ws, st));
+    if (sh.determinise) OK_OR_RETURN(catan_randomise_uncertainty(sim, ws.ctrl, stream));
+    OK_OR_RETURN(catan_step(sim, ws.act, sim->scratch_reward, sim->scratch_done, stream));
+    // 6. the playouts: the rule-based player in every seat, finished / duplicate / bad slots frozen
+    for (int d = 1; d < cfg->depth; d++) {
+        OK_OR_RETURN(catan_sample_scripted_actions_style(sim, cfg->playout_style, nullptr, sh.used, ws.act, stream));
+        HIPCHK(playout_launch_hold(sh, sim->scratch_done, ws, st));
+        OK_OR_RETURN(catan_step(sim, ws.act, sim->scratch_reward, sim->scratch_done, stream));
+    }
+    // 7. the scores and the pick
+    HIPCHK(playout_launch_score(sh, sim->ctx.R, ws, actions, chosen, (long long*)stats, st));
+    return CATAN_OK;
 }
 
 }  // extern "C"

@@ -131,6 +131,14 @@ static_assert(NROWS * 4 == 676 && ROWS_HOT == 112 && ROWS_HOT * 4 % 64 == 0 && R
 constexpr int F_INITIAL = 1, F_ROLLED = 2, F_PLAYED_DEV = 4, F_MUST_USE_DEV = 8, F_MUST_RESPOND = 16,
               F_RB_ACTIVE = 32, F_CAN_ROBBER = 64, F_JUST_ROBBER = 128;
 
+// The player who decides in a state, as pid0 (env/wrapper.py:53-58): the first player who still has to discard, else the target of an open
+// offer, else the player whose go it is.  Arguments: the record's B_NDISC, B_DISC (its first entry), B_FLAGS, B_TRADE_TGT and B_GO bytes.
+// (constexpr: usable in host and device code alike.  catan_playout.hip calls it; k_deciding of catan_kernels.hip and the samplers hold the
+// same three lines inline and are left as they are.)
+constexpr int deciding_pid0(int n_discard, int first_discarder, int flags, int trade_target, int players_go) {
+    return n_discard > 0 ? first_discarder : ((flags & 16 /* F_MUST_RESPOND */) ? trade_target : players_go);
+}
+
 // enums (reference game/enums.py:30-50)
 enum { C_KNIGHT = 0, C_VP = 1, C_YOP = 2, C_RB = 3, C_MONO = 4 };
 enum { T_SETTLE = 0, T_ROAD = 1, T_CITY = 2, T_BUYDEV = 3, T_PLAYDEV = 4, T_EXCHANGE = 5, T_PROPOSE = 6,

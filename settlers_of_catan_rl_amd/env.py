@@ -481,6 +481,29 @@ class VecCatanEnv(object):
             _lib.check(self.L.catan_complete_action_rows(self.h, _ptr(games), rows, _ptr(actions), _stream()))
         return actions
 
+    def playout_actions(self, sim_env, games=None, *, candidates, playouts, depth, playout_style, determinise, step_idx, return_stats=False):
+        """catan_playout_actions (include/catan_hip_tuning.h) with this env as the root: per row the candidate move whose
+        playouts on `sim_env` (a scratch VecCatanEnv with auto_reset=False and this env's limits) score best for the deciding player.
+        candidates: (builder, trader, randoms); games as in sample_scripted_actions.  -> actions int32 [rows][18], or with return_stats
+        (actions, chosen int32 [rows], stats int64 [rows][C][spec.PLAYOUT_STAT_WORDS]).  Nothing of this env changes."""
+        if playout_style not in self.SCRIPTED_STYLES:
+            raise ValueError(f"playout_actions: playout_style must be one of {sorted(self.SCRIPTED_STYLES)}, got {playout_style!r}")
+        if games is not None:
+            games = games if (games.dtype == torch.int32 and games.is_contiguous() and games.device == self.device) else \
+                games.to(device=self.device, dtype=torch.int32).contiguous()
+        rows = self.n if games is None else games.numel()
+        builder, trader, randoms = (int(x) for x in candidates)
+        cfg = _lib.CatanPlayoutCfg(builder, trader, randoms, int(playouts), int(depth), self.SCRIPTED_STYLES[playout_style], int(bool(determinise)),
+                                   int(step_idx) & 0xFFFFFFFF)
+        out = torch.empty((rows, spec.ACTION_WORDS), dtype=torch.int32, device=self.device)
+        chosen = stats = None
+        if return_stats:
+            chosen = torch.empty((rows,), dtype=torch.int32, device=self.device)
+            stats = torch.empty((rows, max(builder + trader + randoms, 0), spec.PLAYOUT_STAT_WORDS), dtype=torch.int64, device=self.device)
+        if rows:
+            _lib.check(self.L.catan_playout_actions(self.h, sim_env.h, _ptr(games), rows, C.byref(cfg), _ptr(out), _ptr(chosen), _ptr(stats), _stream()))
+        return (out, chosen, stats) if return_stats else out
+
     def scripted_fallback_count(self):
         """decisions of sample_scripted_actions that only the rule's fall-back row could take (expected 0)"""
         return int(self.L.catan_scripted_fallback_count(self.h, _stream()))

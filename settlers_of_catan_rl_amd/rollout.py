@@ -177,10 +177,13 @@ class RolloutCollector(object):
         allocated only with a teacher) at the slot its active seat's action goes into storage.actions; opponent seats are never
         labelled, nothing else in the storage changes.  `stop_teacher()` later stops the labelling and frees the tensor (train with
         teacher_coef 0 from then on).  The tensor-operation loop steps with catan_step whatever `deferred_window` says, with a
-        teacher as without.  Not with LSTM policies.  None: no call is made."""
+        teacher as without.  Not with LSTM policies.  None: no call is made.
+        A teacher or opponent with `needs_lockstep` (scripted.PlayoutPolicy) makes the default deferred_window 0 (_honour_lockstep_players)."""
         self.env,self.policy, self.T = env, policy, num_steps
         self.league_stats, self.policy_of_pid = bool(league_stats), None
         self.deferred_window = self.DEFAULT_DEFERRED_WINDOW if deferred_window is None else int(deferred_window)
+        self._window_given = deferred_window is not None
+        self.teacher = None
         self.act_buckets = None if act_buckets is None else tuple(sorted(set(int(b) for b in act_buckets) | {env.n}))
         self.N, self.device = env.n, env.device
         if torch.device(self.device).type == "cuda":
@@ -219,6 +222,7 @@ class RolloutCollector(object):
         if teacher is not None and not hasattr(teacher, "label"):
             raise ValueError("RolloutCollector(teacher=...): a teacher has label(games=None) -> int32 [N, 18] (scripted.ScriptedPolicy(env))")
         self.teacher = teacher
+        self._honour_lockstep_players()
         self.storage = RolloutStorage(num_steps, self.N, self.device, obs_dtype=obs_dtype, lstm_size=self.lstm_size, teacher=teacher is not None)
         # game_manager.py:94-95 sums the env's rewards (Python floats) over the other seats' moves and process_batch.py:63
         # rounds the sum to fp32: the env leaves its unrounded rewards in a float64 buffer for that
@@ -272,7 +276,20 @@ class RolloutCollector(object):
                                                                         and not getattr(n, "wants_games", False)
                                                                         and getattr(n, "_inference_dtype", None) is None) else n for n in nets]
         self.opp_index = opp_index.to(self.device).long().contiguous() if len(self.opponent_nets) else None
+        self._honour_lockstep_players()
         self._enable_league_stats()
+
+    def _honour_lockstep_players(self):
+        """A teacher or an opponent with `needs_lockstep` (scripted.PlayoutPolicy: it forks the env's games, which an open
+        catan_step_deferred sequence forbids) makes the collector step with catan_step from here on: deferred_window becomes 0 where it
+        was left to the default, and a window asked for by the caller is refused.  The rollouts are the same either way."""
+        who = [p for p in [self.teacher] + list(self.opponent_nets) if getattr(p, "needs_lockstep", False)]
+        if not who or not self.deferred_window:
+            return
+        if self._window_given:
+            raise ValueError(f"RolloutCollector: {type(who[0]).__name__} needs lock-step steps (it forks the env's games, which an open "
+                             f"catan_step_deferred sequence forbids): deferred_window must be 0 or None, got {self.deferred_window}")
+        self.deferred_window = 0
 
     def _enable_league_stats(self):
         """league_stats: the table for the opponents now installed, zeroed (called by set_opponents; the constructor calls it once its

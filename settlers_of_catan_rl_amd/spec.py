@@ -280,3 +280,12 @@ def league_stats_table(words, num_nets):
     out = OrderedDict((name, t[:-1, i].copy()) for i, name in enumerate(LEAGUE_STATS_FIELDS))
     out["totals"] = OrderedDict((name, int(t[-1, i])) for i, name in enumerate(LEAGUE_STATS_TOTALS))
     return out
+
+
+# ---------------------------------------------------------------- playout player (include/catan_hip_tuning.h catan_playout_actions)
+# the int64 row of one (row, candidate), in order; csrc/catan_playout.h holds the same layout as PS_* offsets
+PLAYOUT_STAT_FIELDS = ["valid", "sims", "finished", "wins", "score_sum", "vp_sum", "steps_sum"]
+PLAYOUT_STAT_WORDS = len(PLAYOUT_STAT_FIELDS)                      # 7
+PLAYOUT_MAX_CANDIDATES, PLAYOUT_MAX_PLAYOUTS = 8, 64
+PLAYOUT_WIN_SCORE, PLAYOUT_VP_SCORE = 1000, 10                    # score of a playout = 1000 [p won] + 10 (vp_p - best other vp)
+PLAYOUT_DRAW_SHIFT = 22                                           # playout k runs (1 + k) << 22 draws behind its root (forward_search.py's stride)

@@ -38,7 +38,11 @@ class TrainArgs(object):
     start_pool_sampling = "uniform"      # "balanced": the entries whose result is still open are drawn more often (implies the outcomes)
     eval_scripted_baseline = False       # opt-in: the evaluation also plays the rule-based player (scripted.ScriptedPolicy) -> log["scripted"]
     eval_trader_baseline = False         # opt-in: ... and the trading rule-based player (scripted.TraderPolicy) -> log["trader"]
-    teacher = None                       # opt-in kickstarting: "scripted" - the rule-based player labels the rollouts (make_teacher); "trader": its trading style (8.14)
+    eval_playout_baseline = False        # opt-in: ... and the playout player (scripted.PlayoutPolicy) -> log["playout"]
+    teacher = None                       # opt-in kickstarting: "scripted" - the rule-based player labels the rollouts (make_teacher); "trader": its trading style (8.14); "playout": the playout player (8.15)
+    playout_k = None                     # ... teacher "playout": PlayoutPolicy's playouts, depth and randoms (None: its defaults)
+    playout_depth = None
+    playout_randoms = None
     teacher_coef = 0.0                   # ... the imitation term's coefficient at update 0
     teacher_coef_updates = 0             # ... falling linearly to 0 over this many updates (0: constant); at 0 the collector stops labelling
     teacher_only_updates = 0             # ... the first J updates are pure imitation (PPOConfig.teacher_only)
@@ -53,12 +57,14 @@ class TrainArgs(object):
 def eval_baselines(args):
     """The fixed opponents `args` adds to the evaluation protocol, as evaluation.run_evaluation_protocol(baselines=...) takes them;
     None (the default): the reference's protocol alone."""
-    from .scripted import ScriptedPolicy, TraderPolicy
+    from .scripted import PlayoutPolicy, ScriptedPolicy, TraderPolicy
     out = {}
     if getattr(args, "eval_scripted_baseline", False):
         out["scripted"] = ScriptedPolicy
     if getattr(args, "eval_trader_baseline", False):
         out["trader"] = TraderPolicy
+    if getattr(args, "eval_playout_baseline", False):
+        out["playout"] = PlayoutPolicy
     return out or None
 
 
@@ -67,9 +73,13 @@ def make_teacher(args, env):
     name = getattr(args, "teacher", None)
     if name is None or not getattr(args, "teacher_coef", 0.0) > 0:
         return None
-    if name not in ("scripted", "trader"):
-        raise ValueError(f"teacher must be 'scripted', 'trader' or None, got {name!r}")
-    from .scripted import ScriptedPolicy, TraderPolicy
+    if name not in ("scripted", "trader", "playout"):
+        raise ValueError(f"teacher must be 'scripted', 'trader', 'playout' or None, got {name!r}")
+    from .scripted import PlayoutPolicy, ScriptedPolicy, TraderPolicy
+    if name == "playout":
+        opts = {k: getattr(args, a) for k, a in (("playouts", "playout_k"), ("depth", "playout_depth"), ("randoms", "playout_randoms"))
+                if getattr(args, a, None) is not None}
+        return PlayoutPolicy(env, **opts)
     return TraderPolicy(env) if name == "trader" else ScriptedPolicy(env)
 
 

@@ -1,0 +1,296 @@
+"""The playout player on the CPU: the restatement of its decision over the oracle (tests/playout_reference.py) against
+hand-built cases - a score table, duplicates, an all-tie row -, the legality of what it chooses on roots in mixed phases, a planted
+position that is won by one move, planted errors that the fixture must tell apart, and the host logic of scripted.PlayoutPolicy on a
+stand-in env (chunks, the games / rows errors, unbound use, parameter checks) with its wiring into the training loop's options."""
+import numpy as np
+import pytest
+import torch
+
+import oracle_lib
+import playout_reference as pr
+import scripted_reference as sr
+from settlers_of_catan_rl_amd import _lib, spec, train_loop
+from settlers_of_catan_rl_amd.scripted import PlayoutPolicy, ScriptedPolicy
+
+F = pr.FIELDS
+CFG = dict(builder=1, trader=1, randoms=3, playouts=3, depth=4, playout_style="trader", determinise=1, step_idx=3)
+
+
+@pytest.fixture(scope="module")
+def roots(oracle):
+    """the 16 fixture roots and, as game 16, the planted near-win position"""
+    return np.concatenate([pr.fixture_roots(), pr.near_win_root()[None]])
+
+
+@pytest.fixture(scope="module")
+def decided(roots):
+    """every root decided once with CFG; shared, never edited"""
+    return pr.decide(roots, None, CFG, pr.SIM_SEED, pr.SIM_ENV_ID0)
+
+
+# ---------------------------------------------------------------------------------------------- hand-built cases
+def _final(winner, vps):
+    b = np.zeros(spec.STATE_WORDS, dtype=np.int32)
+    spec.state_field(b, "winner")[0] = winner
+    for q, v in enumerate(vps):
+        spec.state_field(b, f"p{q + 1}_vp")[0] = v
+    return b
+
+
+def test_score_table_by_hand():
+    """(finished, won, score, own points) for PlayerId p: 1000 for a win of p's, 10 per point of margin over the BEST opponent"""
+    table = [((0, [2, 2, 2, 2]), 1, (0, 0, 0, 2)),
+             ((0, [5, 3, 7, 4]), 1, (0, 0, -20, 5)),
+             ((0, [5, 3, 7, 4]), 3, (0, 0, 20, 7)),
+             ((2, [4, 10, 6, 3]), 2, (1, 1, 1040, 10)),
+             ((2, [4, 10, 6, 3]), 1, (1, 0, -60, 4)),
+             ((4, [9, 2, 2, 11]), 4, (1, 1, 1020, 11)),
+             ((4, [9, 2, 2, 11]), 2, (1, 0, -90, 2))]
+    for (winner, vps), p, want in table:
+        assert pr.playout_score(_final(winner, vps), p) == want, (winner, vps, p)
+    assert spec.PLAYOUT_STAT_FIELDS[:7] == ["valid", "sims", "finished", "wins", "score_sum", "vp_sum", "steps_sum"]
+    assert spec.PLAYOUT_STAT_WORDS == 7
+
+
+def test_duplicates_are_marked_and_never_chosen_over_their_original():
+    a, b = np.arange(18, dtype=np.int32), np.arange(18, dtype=np.int32)[::-1].copy()
+    c = a.copy()
+    c[17] += 1                                   # differs in the last word only: not a duplicate
+    assert pr.mark_duplicates(np.stack([a, b, a, c, b, a])).tolist() == [False, False, True, False, True, True]
+    # a duplicate is invalid whatever its (zero) score: with the original at a negative sum the pick is still the original
+    assert pr.pick([True, False, False], [-50, 0, 0]) == 0
+    assert pr.pick([True, True, False, True], [-50, -20, 0, -20]) == 1
+    assert pr.pick([False, True, True], [900, 10, 20]) == 2
+
+
+def test_an_all_tie_row_returns_candidate_0():
+    assert pr.pick([True] * 5, [0] * 5) == 0
+    assert pr.pick([True] * 5, [7, 7, 7, 7, 7]) == 0
+    assert pr.pick([True] * 4, [1, 3, 3, 2]) == 1
+    assert pr.pick([True] * 4, [1, 3, 3, 2], variant="tie_high") == 2
+
+
+# ---------------------------------------------------------------------------------------------- the fixture and what is chosen on it
+def test_fixture_roots_cover_the_phases(roots):
+    """The coverage claim of the parity tests (tests/test_gpu_playout.py decides these very roots): a discard, an answer to an offer, an
+    initial placement and a normal turn are among them, none is over."""
+    phases = pr.root_phases(roots)
+    assert len(phases) == 17 and "over" not in phases
+    for want in ("discard", "respond", "initial", "turn"):
+        assert want in phases, (want, phases)
+
+
+def test_chosen_rows_are_legal_under_the_roots_masks(roots, decided):
+    assert decided.invalid == 0
+    for g in range(roots.shape[0]):
+        env = oracle_lib.OracleEnv(0, g)
+        env.import_(roots[g])
+        assert env.is_legal(decided.actions[g]), (g, decided.actions[g].tolist())
+        c = int(decided.chosen[g])
+        assert 0 <= c < 5 and not decided.dup[g, c] and (decided.actions[g] == decided.cand[g, c]).all()
+        assert not decided.dup[g, 0] and decided.stats[g, 0, F["valid"]] == 1
+        # a duplicate's row is all zero, a valid candidate played its K sims and took between 1 and depth steps in each
+        for k in range(5):
+            row = decided.stats[g, k]
+            if decided.dup[g, k]:
+                assert not row.any()
+            else:
+                assert row[F["sims"]] == 3 and 3 <= row[F["steps_sum"]] <= 3 * 4 and row[F["wins"]] <= row[F["finished"]] <= 3
+    assert decided.dup.any() and (decided.dup.sum(1) < 4).any()
+
+
+def test_bad_game_ids_get_endturn_and_zero_stats(roots):
+    r = pr.decide(roots, [-1, 16, 17], dict(CFG, depth=1), pr.SIM_SEED, pr.SIM_ENV_ID0)
+    assert r.actions[0].tolist() == [sr.ENDTURN] + [0] * 17 and r.actions[2].tolist() == r.actions[0].tolist()
+    assert r.chosen.tolist()[0] == -1 and r.chosen.tolist()[2] == -1 and not r.stats[0].any() and not r.stats[2].any()
+    assert r.stats[1, 0, F["valid"]] == 1
+
+
+def test_planted_win_in_one_is_found_at_depth_1(roots):
+    """Game 16: player 1 at 9 points holds a city's price and a settlement.  The builder's candidate is the city; its K playouts of one step
+    all end the game: K x (1000 + 10 x (10 - 2)).  Every other candidate leaves the margin at 10 x (9 - 2)."""
+    K = 4
+    r = pr.decide(roots, [16], dict(CFG, playouts=K, depth=1, determinise=0), pr.SIM_SEED, pr.SIM_ENV_ID0)
+    assert r.cand[0, 0].tolist() == [sr.CITY, 0] + [0] * 16 and r.chosen[0] == 0 and (r.actions[0] == r.cand[0, 0]).all()
+    assert r.stats[0, 0].tolist() == [1, K, K, K, K * (1000 + 10 * (10 - 2)), K * 10, K]
+    assert r.dup[0, 1]                                            # the trader's move is the builder's here
+    others = [c for c in range(5) if not r.dup[0, c] and c != 0]
+    assert others and all(r.stats[0, c].tolist() == [1, K, 0, 0, K * 70, K * 9, K] for c in others if r.cand[0, c, 0] != sr.CITY)
+    # ... and with the hidden cards re-dealt (nobody else holds any) the same
+    r2 = pr.decide(roots, [16], dict(CFG, playouts=K, depth=1, determinise=1), pr.SIM_SEED, pr.SIM_ENV_ID0)
+    assert (r2.stats == r.stats).all() and r2.chosen[0] == 0
+
+
+def test_planted_errors_disagree_with_the_reference_on_the_fixture(roots, decided):
+    """The fixture can tell the rule from three near misses: ties to the highest index, a hold that is not latched (a finished game goes
+    on counting steps), the margin against the weakest opponent."""
+    tie = pr.decide(roots, None, CFG, pr.SIM_SEED, pr.SIM_ENV_ID0, variant="tie_high")
+    assert (tie.stats == decided.stats).all() and (tie.chosen != decided.chosen).any()
+    games = [16, 9, 15]
+    ref = pr.decide(roots, games, CFG, pr.SIM_SEED, pr.SIM_ENV_ID0)
+    assert ref.stats[0, 0, F["finished"]] == 3 and ref.stats[0, 0, F["steps_sum"]] == 3       # won by the first step, then held
+    nl = pr.decide(roots, games, CFG, pr.SIM_SEED, pr.SIM_ENV_ID0, variant="no_latch")
+    assert nl.stats[0, 0, F["steps_sum"]] > ref.stats[0, 0, F["steps_sum"]]
+    mo = pr.decide(roots, games, CFG, pr.SIM_SEED, pr.SIM_ENV_ID0, variant="min_opponent")
+    assert (mo.stats[:, :, F["score_sum"]] != ref.stats[:, :, F["score_sum"]]).any()
+    assert (mo.stats[:, :, F["steps_sum"]] == ref.stats[:, :, F["steps_sum"]]).all()
+
+
+def test_same_inputs_same_decision_and_step_idx_moves_only_the_random_candidates(roots, decided):
+    again = pr.decide(roots, None, CFG, pr.SIM_SEED, pr.SIM_ENV_ID0)
+    assert all((x == y).all() for x, y in zip(again[:5], decided[:5]))
+    other = pr.decide(roots, None, dict(CFG, step_idx=4), pr.SIM_SEED, pr.SIM_ENV_ID0)
+    assert (other.cand[:, :2] == decided.cand[:, :2]).all() and (other.cand[:, 2:] != decided.cand[:, 2:]).any()
+
+
+# ---------------------------------------------------------------------------------------------- scripted.PlayoutPolicy on a stand-in env
+class _Cfg(object):
+    max_proposed_trades_per_turn, max_actions_per_turn = 4, -1
+
+
+class _StandInEnv(object):
+    """an env that records what PlayoutPolicy asks of it: row j of a call answers with its game id in column 1"""
+
+    def __init__(self, n):
+        self.n, self.env_id0, self.device, self.cfg = n, 7, torch.device("cpu"), _Cfg()
+        self.calls, self.completed = [], 0
+
+    def playout_actions(self, sim_env, games=None, *, candidates, playouts, depth, playout_style, determinise, step_idx, return_stats=False):
+        g = torch.arange(self.n, dtype=torch.int32) if games is None else games.to(torch.int32).reshape(-1)
+        assert return_stats and g.numel() * sum(candidates) * playouts <= sim_env.n
+        self.calls.append(dict(sim=sim_env, games=g.tolist(), implicit=games is None, candidates=candidates, playouts=playouts, depth=depth,
+                               playout_style=playout_style, determinise=determinise, step_idx=step_idx))
+        a = torch.zeros((g.numel(), 18), dtype=torch.int32)
+        a[:, 0], a[:, 1] = sr.ENDTURN, g
+        C = sum(candidates)
+        return a, torch.zeros(g.numel(), dtype=torch.int32), g.long()[:, None, None].expand(g.numel(), C, spec.PLAYOUT_STAT_WORDS).clone()
+
+    def complete_action_rows(self, actions, games=None):
+        self.completed += 1
+        actions[:, 17] = 3
+        return actions
+
+
+class _Sim(object):
+    def __init__(self, n, env_id0):
+        self.n, self.env_id0 = n, env_id0
+
+
+class _Policy(PlayoutPolicy):
+    def _make_sim(self, env, games):
+        return _Sim(games, int(env.env_id0) + self.SIM_ID_OFFSET)
+
+
+def _obs(rows):
+    return torch.zeros(rows, 4), None, None, None
+
+
+def test_policy_chunks_a_pass_that_exceeds_the_sim_rows():
+    env = _StandInEnv(10)
+    pol = _Policy(env, randoms=1, playouts=2, depth=5, sim_games=3 * 6 + 5)      # C*K = 6: three rows per call, 5 games left over
+    assert pol.wants_games and not pol.include_lstm and pol.sims_per_row == 6
+    v, a, lp = pol.act(*_obs(10))
+    assert [c["games"] for c in env.calls] == [[0, 1, 2], [3, 4, 5], [6, 7, 8], [9]]
+    assert [c["step_idx"] for c in env.calls] == [0, 1, 2, 3] and pol.step_idx == 4       # a step index per chunk: the chunks share the slots
+    assert a.dtype == torch.int64 and a[:, 1].tolist() == list(range(10)) and v.shape == (10, 1) and lp.shape == (10, 1) and not v.any() and not lp.any()
+    assert pol.last_stats.shape == (10, 3, 7) and pol.last_stats[:, 0, 0].tolist() == list(range(10)) and pol.last_chosen.shape == (10,)
+    assert env.calls[0]["sim"].n == 23 and env.calls[0]["sim"].env_id0 == 7 + (1 << 40)
+    assert env.calls[0]["candidates"] == (1, 1, 1) and env.calls[0]["playouts"] == 2 and env.calls[0]["depth"] == 5
+    assert env.calls[0]["playout_style"] == "trader" and env.calls[0]["determinise"] is True
+    # a listed pass: the same chunks of the list, the next step index, the same sim handle
+    env.calls.clear()
+    games = torch.tensor([9, 9, 4, 0, 2], dtype=torch.int64)
+    _, a, _ = pol.act(*_obs(5), games=games)
+    assert [c["games"] for c in env.calls] == [[9, 9, 4], [0, 2]] and [c["step_idx"] for c in env.calls] == [4, 5] and a[:, 1].tolist() == [9, 9, 4, 0, 2]
+    # a pass that fits is one call with the caller's own `games` (None stays None)
+    env.calls.clear()
+    small = _Policy(env, randoms=0, playouts=1, depth=1)
+    small.act(*_obs(10))
+    assert len(env.calls) == 1 and env.calls[0]["implicit"] and env.calls[0]["sim"].n == 2 * 10
+
+
+def test_policy_label_completes_the_chosen_rows():
+    env = _StandInEnv(4)
+    pol = _Policy(env, playouts=1, depth=1)
+    lab = pol.label()
+    assert lab.dtype == torch.int32 and lab.shape == (4, 18) and env.completed == 1 and lab[:, 17].tolist() == [3] * 4
+    lab = pol.label(games=torch.tensor([2, 1]))
+    assert lab[:, 1].tolist() == [2, 1] and env.completed == 2 and pol.step_idx == 2
+
+
+def test_policy_games_rows_mismatch_and_unbound_use_raise():
+    env = _StandInEnv(4)
+    pol = _Policy(env, playouts=1, depth=1)
+    with pytest.raises(ValueError, match="decides all 4 games"):
+        pol.act(*_obs(3))
+    with pytest.raises(ValueError, match="2 games for 3 rows"):
+        pol.act(*_obs(3), games=torch.tensor([0, 1]))
+    # the messages are ScriptedPolicy's, with the class's own name
+    with pytest.raises(ValueError, match="decides all 4 games"):
+        ScriptedPolicy(env).act(*_obs(3))
+    unbound = _Policy()
+    with pytest.raises(RuntimeError, match="not bound"):
+        unbound.act(*_obs(4))
+    with pytest.raises(RuntimeError, match="not bound"):
+        unbound.label()
+    assert unbound.rebind(env) is unbound and unbound.act(*_obs(4))[1].shape == (4, 18)
+    sim = unbound.sim
+    assert unbound.rebind(env).sim is sim and unbound.rebind(_StandInEnv(4)).sim is None      # another env: another scratch handle
+
+
+def test_policy_parameter_validation():
+    for kw in (dict(builder=False, trader=False, randoms=0), dict(randoms=7), dict(randoms=-1), dict(playouts=0), dict(playouts=65),
+               dict(depth=0), dict(playout_style="banker"), dict(sim_games=31)):
+        with pytest.raises(ValueError):
+            PlayoutPolicy(**kw)
+    p = PlayoutPolicy()
+    assert (p.candidates, p.playouts, p.depth, p.playout_style, p.determinise, p.sim_games, p.seed) == ((1, 1, 2), 8, 120, "trader", True, None, 0)
+    assert PlayoutPolicy(builder=False, trader=False, randoms=8, playouts=64, sim_games=512).sims_per_row == 512
+
+
+def test_make_teacher_eval_baselines_and_the_library_know_the_player():
+    A = train_loop.TrainArgs
+    assert train_loop.eval_baselines(A()) is None
+    assert train_loop.eval_baselines(A(eval_playout_baseline=True)) == {"playout": PlayoutPolicy}
+    env = _StandInEnv(4)
+    assert train_loop.make_teacher(A(teacher="playout"), env) is None                              # coefficient 0: no teacher, no call
+    t = train_loop.make_teacher(A(teacher="playout", teacher_coef=0.5, playout_k=3, playout_depth=9, playout_randoms=1), env)
+    assert isinstance(t, PlayoutPolicy) and (t.playouts, t.depth, t.candidates) == (3, 9, (1, 1, 1)) and t.env is env
+    t = train_loop.make_teacher(A(teacher="playout", teacher_coef=0.5), env)
+    assert (t.playouts, t.depth, t.candidates) == (8, 120, (1, 1, 2))
+    assert "catan_playout_actions" in _lib.declared_symbols() and _lib.TRANSLATION_UNITS[-1] == "catan_playout.hip"
+    assert _lib.TRANSLATION_UNITS[:3] == ("catan_abi.hip", "catan_teacher.hip", "catan_trader.hip")
+    import ctypes as C
+    assert C.sizeof(_lib.CatanPlayoutCfg) == 32
+
+
+def test_collector_steps_lockstep_for_a_player_that_needs_it(oracle):
+    """RolloutCollector reads `needs_lockstep` from its teacher and its opponents: a default window becomes 0, an explicit one is refused
+    with the reason; players without the attribute keep the default"""
+    from oracle_vec_env import OracleVecEnv
+    from oracle_vec_env import ScriptedPolicy as OraclePolicy
+    from settlers_of_catan_rl_amd.rollout import RolloutCollector
+    env = OracleVecEnv(4, seed=1)
+
+    class Teacher(object):
+        def __init__(self, lockstep):
+            self.needs_lockstep = lockstep
+
+        def label(self, games=None):
+            return torch.zeros((4, 18), dtype=torch.int32)
+    assert PlayoutPolicy.needs_lockstep and not getattr(ScriptedPolicy, "needs_lockstep", False)
+    default = RolloutCollector.DEFAULT_DEFERRED_WINDOW
+    assert RolloutCollector(env, OraclePolicy(env), 4).deferred_window == default
+    assert RolloutCollector(env, OraclePolicy(env), 4, teacher=Teacher(False)).deferred_window == default
+    assert RolloutCollector(env, OraclePolicy(env), 4, teacher=Teacher(True)).deferred_window == 0
+    assert RolloutCollector(env, OraclePolicy(env), 4, teacher=Teacher(True), deferred_window=0).deferred_window == 0
+    with pytest.raises(ValueError, match="lock-step"):
+        RolloutCollector(env, OraclePolicy(env), 4, teacher=Teacher(True), deferred_window=4)
+    opp = OraclePolicy(env)
+    opp.needs_lockstep = True
+    assert RolloutCollector(env, OraclePolicy(env), 4, opponents=[opp]).deferred_window == 0
+    with pytest.raises(ValueError, match="lock-step"):
+        RolloutCollector(env, OraclePolicy(env), 4, opponents=[opp], deferred_window=8)
+    col = RolloutCollector(env, OraclePolicy(env), 4)
+    col.set_opponents([opp], torch.zeros((4, 3), dtype=torch.int64))              # installed later (a league): the same rule
+    assert col.deferred_window == 0

@@ -28,6 +28,8 @@ def main():
                     help="every evaluation also plays the rule-based player (scripted.ScriptedPolicy): log[\"scripted\"], comparable across runs")
     ap.add_argument("--eval-trader-baseline", action="store_true",
                     help="every evaluation also plays the trading rule-based player (scripted.TraderPolicy): log[\"trader\"]")
+    ap.add_argument("--eval-playout-baseline", action="store_true",
+                    help="every evaluation also plays the playout player (scripted.PlayoutPolicy, at its defaults): log[\"playout\"]")
     ap.add_argument("--checkpoint", type=str, default="")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lstm", action="store_true", help="include_lstm (build_agent_model.py:26): LSTM policy + truncated BPTT")
@@ -44,8 +46,11 @@ def main():
                     help="with --start-pool: tally the finished games per pool entry on the device; every update's line carries them under \"start_pool\"")
     ap.add_argument("--start-pool-sampling", choices=["uniform", "balanced"], default="uniform",
                     help="balanced: draw the pool entries whose result is still open more often (implies --start-pool-outcomes)")
-    ap.add_argument("--teacher", choices=["scripted", "trader"], default=None,
-                    help="kickstarting: the rule-based player (trader: its trading style) labels every decision of the rollouts; every update's line carries \"teacher\"")
+    ap.add_argument("--teacher", choices=["scripted", "trader", "playout"], default=None,
+                    help="kickstarting: the rule-based player (trader: its trading style; playout: the playout player, whose rollouts are stepped lock-step) labels every decision of the rollouts; every update's line carries \"teacher\"")
+    ap.add_argument("--playout-k", metavar="K", type=int, default=None, help="with --teacher playout: playouts per candidate (default: PlayoutPolicy's)")
+    ap.add_argument("--playout-depth", metavar="D", type=int, default=None, help="with --teacher playout: env steps per playout")
+    ap.add_argument("--playout-randoms", metavar="R", type=int, default=None, help="with --teacher playout: uniform-random candidates beside the builder's and the trader's")
     ap.add_argument("--teacher-coef", metavar="C", type=float, default=0.0, help="with --teacher: the imitation term's coefficient at update 0")
     ap.add_argument("--teacher-coef-updates", metavar="K", type=int, default=0,
                     help="the coefficient falls linearly to 0 over K updates (0: constant); after that the collector stops labelling")
@@ -69,6 +74,8 @@ def main():
     cdist.broadcast_parameters(net)
     teach = dict(teacher=args.teacher, teacher_coef=args.teacher_coef, teacher_coef_updates=args.teacher_coef_updates,
                  teacher_only_updates=args.teacher_only_updates) if args.teacher else {}
+    if args.teacher == "playout":
+        teach.update(playout_k=args.playout_k, playout_depth=args.playout_depth, playout_randoms=args.playout_randoms)
     teacher = train_loop.make_teacher(train_loop.TrainArgs(**teach), env)
     col = RolloutCollector(env, net, args.num_steps, seed=rank, autocast_dtype=torch.bfloat16, **(dict(league_stats=True) if league_stats else {}),
                            **(dict(teacher=teacher) if teacher is not None else {}))
@@ -83,7 +90,8 @@ def main():
 
     lg = League(max_distinct=args.league, seed=rank, sampling=args.league_sampling) if args.league > 0 else None
     targs = train_loop.TrainArgs(num_steps=args.num_steps, eval_every=args.eval_every, num_eval_episodes=args.num_eval_episodes,
-                                 eval_scripted_baseline=args.eval_scripted_baseline, eval_trader_baseline=args.eval_trader_baseline, **teach,
+                                 eval_scripted_baseline=args.eval_scripted_baseline, eval_trader_baseline=args.eval_trader_baseline,
+                                 eval_playout_baseline=args.eval_playout_baseline, **teach,
                                  **(dict(start_pool=args.start_pool, start_pool_fresh=args.start_pool_fresh, start_pool_outcomes=args.start_pool_outcomes,
                                         start_pool_sampling=args.start_pool_sampling) if args.start_pool else {}))
     loop = train_loop.TrainingLoop(env, net, col, tr, targs, league=lg, make_net=lambda: CatanPolicy(include_lstm=args.lstm).cuda(),
