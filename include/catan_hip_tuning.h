@@ -257,7 +257,7 @@ int64_t catan_scripted_fallback_count(catan_env_t* env, catan_stream_t stream);
 /* The player's STYLES.  catan_sample_scripted_actions_style(env, style, ...) is catan_sample_scripted_actions with the
  * style chosen per call:
  *   CATAN_SCRIPTED_BUILDER (0)  the builder: the same kernel, the same bits as catan_sample_scripted_actions;
- *   CATAN_SCRIPTED_TRADER  (1)  the "trader" (csrc/catan_trader.hip): the builder's table with its Respond row replaced (an offer is
+ *   CATAN_SCRIPTED_TRADER  (1)  the "trader" (csrc/catan_players.hip): the builder's table with its Respond row replaced (an offer is
  *                               accepted when it brings the hand closer to the player's goal: a city, a settlement, a road or a
  *                               development card) and two rows in front of its Exchange row (a one-for-one proposal to the weakest
  *                               opponent holding the wanted card, at most three a turn; a bank / harbour exchange of spare cards for
@@ -272,7 +272,7 @@ enum { CATAN_SCRIPTED_BUILDER = 0, CATAN_SCRIPTED_TRADER = 1 };
 int catan_sample_scripted_actions_style(catan_env_t* env, int32_t style, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream);
 int catan_scripted_trade_counts(catan_env_t* env, uint64_t out[8], int32_t reset, catan_stream_t stream);
 
-/* ---- the playout player (csrc/catan_playout.hip) ----
+/* ---- the playout player (csrc/catan_players.hip) ----
  * A flat Monte-Carlo player that needs no net: per row it takes C candidate moves (the builder's, the trader's, `randoms` uniform-random
  * legal ones, in this order), plays each out K times for `depth` env steps with the rule-based player of `playout_style` in every seat,
  * on copies of the root game in a second handle, and answers with the candidate whose playouts score best for the root's deciding player p:
@@ -316,7 +316,7 @@ typedef struct {
 int catan_playout_actions(catan_env_t* root, catan_env_t* sim, const int32_t* games, int64_t n_rows, const catan_playout_cfg_t* cfg,
                           int32_t* actions, int32_t* chosen, int64_t* stats, catan_stream_t stream);
 
-/* ---- teacher labels (csrc/catan_teacher.hip) ----
+/* ---- teacher labels (csrc/catan_players.hip) ----
  * catan_complete_action_rows makes any legal action row teacher-forceable through the net's heads.  The samplers (this player,
  * catan_sample_random_actions) fill only the columns their action type uses; the heads evaluate EVERY column of every row and multiply
  * the unused ones by 0, and column value 0 is often illegal under an unused head's mask (log-prob -inf, -inf x 0 = NaN).  The rule, per

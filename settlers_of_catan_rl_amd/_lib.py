@@ -71,10 +71,9 @@ BUILD_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 LLVM_OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
-# the translation units of the library, in link order: each brings a gfx950 code object of its own.  catan_abi.hip includes every other
-# kernel file; catan_teacher.hip, catan_trader.hip (8.14) and catan_playout.hip (8.15) are compiled apart, each appended
-# behind the others, so that the code objects before it are what they are without it
-TRANSLATION_UNITS = ("catan_abi.hip", "catan_teacher.hip", "catan_trader.hip", "catan_playout.hip")
+# the translation units of the library, in link order: each brings a gfx950 code object of its own.  catan_abi.hip includes every kernel
+# file but catan_players.hip, whose top says why it is compiled apart
+TRANSLATION_UNITS = ("catan_abi.hip", "catan_players.hip")
 
 
 def device_code_objects(path=None):

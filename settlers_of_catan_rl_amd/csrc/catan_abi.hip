@@ -28,6 +28,7 @@
 #include "catan_record.hip"
 #include "catan_start_pool.hip"
 #include "catan_start_pool_weighted.hip"
+#include "catan_players.h"
 
 using namespace catan;
 
@@ -100,8 +101,8 @@ struct catan_env {
     int lstats_nets, lstats_cap; // rows in use (without the totals row), and allocated
     int lstats_on;               // 0 off, else the mode bits of catan_league_stats_enable
     unsigned long long* script_fallback;   // catan_sample_scripted_actions: decisions taken by the fall-back row (catan_scripted.hip), allocated at the first call
-    unsigned long long* trade_counts;      // catan_sample_scripted_actions_style, style 1: the trader's TC_WORDS counters (catan_trader.h), allocated at its first call
-    void* playout_mem;           // catan_playout_actions with this handle as `sim`: the workspace (catan_playout.h PlayoutWs, carved from one allocation), allocated at its first call
+    unsigned long long* trade_counts;      // catan_sample_scripted_actions_style, style 1: the trader's TC_WORDS counters (catan_players.h), allocated at its first call
+    void* playout_mem;           // catan_playout_actions with this handle as `sim`: the workspace (catan_players.h PlayoutWs, carved from one allocation), allocated at its first call
     RecordBuf rec;               // catan_record_enable: the recorder's slots (catan_record.hip); not in `owned`: freed and re-made by every enable
     int rec_on;
     StartPoolBuf pool;           // catan_start_pool_set: the saved positions (catan_start_pool.hip); not in `owned`: freed and re-made by every set
@@ -1126,34 +1127,6 @@ int catan_league_stats_count(catan_env_t* e, const int32_t* games, int64_t m, ca
 static int record_not_armed(catan_env_t* e, const char* what, hipStream_t st);      // (game records: at the end of this file)
 // the fused deferred rollout draws a fresh game's first action inside the re-deal kernel, from the state an install would then replace
 #define NO_START_POOL(e, what) do { if ((e)->pool_on) return fail(CATAN_EINVAL, std::string(what) + ": a start pool is installed (catan_start_pool_clear first)"); } while (0)
-
-// ---- the rule-based player (catan_scripted.hip)
-int catan_sample_scripted_actions(catan_env_t* e, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
-    if (!e) return fail(CATAN_EINVAL, "catan_sample_scripted_actions: null handle");
-    if (!actions) return fail(CATAN_EINVAL, "catan_sample_scripted_actions: null actions");
-    if (n_rows <= 0) return fail(CATAN_EINVAL, "catan_sample_scripted_actions: n_rows <= 0");
-    if (!games && n_rows > e->n) return fail(CATAN_EINVAL, "catan_sample_scripted_actions: n_rows exceeds the handle's games (games == NULL)");
-    if (!e->script_fallback) {
-        hipError_t rc = hipSuccess;
-        dev_alloc(e, rc, e->script_fallback, sizeof(unsigned long long));
-        if (rc != hipSuccess) return fail(CATAN_ENOMEM, std::string("catan_sample_scripted_actions: hipMalloc: ") + hipGetErrorString(rc));
-        // zeroed synchronously at its allocation (once per handle): in place before a call on ANY stream can count into it
-        HIPCHK(hipMemset(e->script_fallback, 0, sizeof(unsigned long long)));
-        HIPCHK(hipStreamSynchronize(nullptr));
-    }
-    hipLaunchKernelGGL(k_sample_scripted, dim3(blocks(n_rows, SCRIPT_BLOCK)), dim3(SCRIPT_BLOCK), 0, S(stream), e->ctx, (const u32*)e->mpk, games, (long)n_rows,
-                       e->d_it > 0 ? (const u8*)e->pend.busy : (const u8*)nullptr, actions, e->script_fallback);
-    HIPCHK(hipGetLastError());
-    return CATAN_OK;
-}
-int64_t catan_scripted_fallback_count(catan_env_t* e, catan_stream_t stream) {
-    if (!e) return -1;
-    if (!e->script_fallback) return 0;
-    unsigned long long v = 0;
-    if (hipMemcpyAsync(&v, e->script_fallback, sizeof v, hipMemcpyDeviceToHost, S(stream)) != hipSuccess) return -1;
-    if (hipStreamSynchronize(S(stream)) != hipSuccess) return -1;
-    return (int64_t)v;
-}
 
 int catan_random_rollout(catan_env_t* e, uint32_t step_idx0, int64_t steps, catan_stream_t stream) {
     if (!e || steps < 0) return fail(CATAN_EINVAL, "catan_random_rollout: bad arguments");
@@ -2348,8 +2321,6 @@ int catan_record_read(catan_env_t* e, int32_t slot, int32_t* start_blob, int32_t
     return CATAN_OK;
 }
 
-}  // extern "C"
-
 // Game records (catan_record_enable).  Seal: at the hook of the finished-game statistics, the listed games' records are still the final states.
 // Open: behind the list's consumer, on the same stream, the listed games are freshly dealt.  Off (the default): nothing is launched.
 static void enqueue_record_seal(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
@@ -2391,8 +2362,6 @@ static int start_pool_quiesce(catan_env_t* e, hipStream_t st) {
     HIPCHK(hipStreamSynchronize(e->sstream));
     return CATAN_OK;
 }
-extern "C" {
-
 int catan_start_pool_set(catan_env_t* e, const int32_t* blobs, int32_t m, int32_t fresh_q16, catan_stream_t stream) {
     if (!e) return fail(CATAN_EINVAL, "catan_start_pool_set: null handle");
     NOT_DEFERRED(e, "catan_start_pool_set");
@@ -2468,8 +2437,6 @@ int catan_start_pool_read(catan_env_t* e, uint64_t* out_host, int32_t reset, cat
     return read_counters(out_host, e->pool.cnt, (size_t)(2 + e->pool.m) * sizeof(unsigned long long), reset, S(stream));
 }
 
-}  // extern "C"
-
 static void enqueue_start_pool_x(catan_env_t* e, const u32* count_p, const i32* list, const u8* sel, bool by_list, hipStream_t st);
 static void enqueue_start_pool(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
     if (!e->pool_on) return;
@@ -2484,8 +2451,6 @@ static void enqueue_start_pool_sel(catan_env_t* e, const u8* sel, hipStream_t st
 
 // ---- the start pool's weighted pick and per-entry outcomes (catan_start_pool_weighted.hip).  Behind everything above, so that the
 // kernels of catan_start_pool.hip keep their places too.
-extern "C" {
-
 int catan_start_pool_set_weights(catan_env_t* e, const uint32_t* weights_dev, catan_stream_t stream) {
     if (!e) return fail(CATAN_EINVAL, "catan_start_pool_set_weights: null handle");
     NOT_DEFERRED(e, "catan_start_pool_set_weights");
@@ -2558,8 +2523,6 @@ int catan_start_pool_outcomes_read(catan_env_t* e, uint64_t* out_host, int32_t r
     return read_counters(out_host, e->pool_out, start_pool_outcome_words(e->pool.m) * sizeof(unsigned long long), reset, S(stream));
 }
 
-}  // extern "C"
-
 static void enqueue_start_pool_outcomes(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
     if (!e->pool_out_on) return;
     hipLaunchKernelGGL(k_pool_outcomes<>, dim3(POOL_OUTCOMES_GRID), dim3(64), 0, st, e->ctx, count_p, list, (const i32*)e->pool_origin, e->pool_out_focus, e->pool_out, e->pool.m);
@@ -2583,71 +2546,58 @@ static void enqueue_start_pool_x(catan_env_t* e, const u32* count_p, const i32* 
 #undef POOL_X
 }
 
-// ---- kickstarting from the rule-based player.  Host code only: the kernels are catan_teacher.hip's, a translation unit and
-// a code object of their own (catan_teacher.h), so that this file's code object is what it is without them.
-#include "catan_teacher.h"
+// ---- the players that read the games themselves.  Host code only, but for k_sample_scripted (catan_scripted.hip,
+// this file's code object): every other kernel is catan_players.hip's, the library's second translation unit and code object (catan_players.h).
 
-extern "C" {
-
-int catan_complete_action_rows(catan_env_t* e, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
-    if (!e) return fail(CATAN_EINVAL, "catan_complete_action_rows: null handle");
-    if (!actions) return fail(CATAN_EINVAL, "catan_complete_action_rows: null actions");
-    if (n_rows <= 0) return fail(CATAN_EINVAL, "catan_complete_action_rows: n_rows <= 0");
-    if (!games && n_rows > e->n) return fail(CATAN_EINVAL, "catan_complete_action_rows: n_rows exceeds the handle's games (games == NULL)");
-    HIPCHK(teacher_launch_complete(e->ctx.R, e->ctx.n, (const u32*)e->mpk, games, (long)n_rows, e->d_it > 0 ? (const u8*)e->pend.busy : (const u8*)nullptr, actions,
-                                   S(stream)));
+// What every call over rows of games checks first; `whose`: whose games the rows are, as the message says it
+static int check_row_call(const char* what, const catan_env_t* e, const int32_t* games, int64_t n_rows, const int32_t* actions, const char* whose = "handle's") {
+    const std::string w(what);
+    if (!e) return fail(CATAN_EINVAL, w + ": null handle");
+    if (!actions) return fail(CATAN_EINVAL, w + ": null actions");
+    if (n_rows <= 0) return fail(CATAN_EINVAL, w + ": n_rows <= 0");
+    if (!games && n_rows > e->n) return fail(CATAN_EINVAL, w + ": n_rows exceeds the " + whose + " games (games == NULL)");
     return CATAN_OK;
 }
-
-int catan_collector_label(int64_t n, int32_t T, const int64_t* counters4, const uint8_t* flags4, const int64_t* active_pid, const int32_t* deciding,
-                          const int32_t* labels, int16_t* st_teacher, const uint8_t* waiting_before, catan_stream_t stream) {
-    if (n <= 0 || T <= 0 || !counters4 || !flags4 || !active_pid || !deciding || !labels || !st_teacher)
-        return fail(CATAN_EINVAL, "catan_collector_label: null argument");
-    HIPCHK(teacher_launch_label((long)n, (int)T, (const long long*)counters4 + 2 * n, flags4 + 2 * n, (const long long*)active_pid, deciding, waiting_before, labels,
-                                (short*)st_teacher, S(stream)));
+// A block of device counters owned by the handle, allocated and zeroed at its first use.  Zeroed synchronously (once per handle): in place before
+// a call on ANY stream can count into it
+static int counter_block(catan_env_t* e, const char* what, unsigned long long*& block, size_t words) {
+    if (block) return CATAN_OK;
+    hipError_t rc = hipSuccess;
+    dev_alloc(e, rc, block, words * sizeof(unsigned long long));
+    if (rc != hipSuccess) return fail(CATAN_ENOMEM, std::string(what) + ": hipMalloc: " + hipGetErrorString(rc));
+    HIPCHK(hipMemset(block, 0, words * sizeof(unsigned long long)));
+    HIPCHK(hipStreamSynchronize(nullptr));
     return CATAN_OK;
 }
+static const u8* busy_of(const catan_env_t* e) { return e->d_it > 0 ? (const u8*)e->pend.busy : (const u8*)nullptr; }
 
-int64_t catan_imitation_loss_words(void) { return IMIT_WORDS; }
-int64_t catan_imitation_loss_workspace_doubles(void) { return IMIT_PART * IMIT_BLOCKS + 1; }
-
-int catan_imitation_loss(const float* lp, const int64_t* teacher, int64_t B, float* loss, float* dlp, double* block, double* workspace, catan_stream_t stream) {
-    if (B < 1) return fail(CATAN_EINVAL, "catan_imitation_loss: B must be at least 1");
-    if (!lp || !teacher) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL input array");
-    if (!loss || !dlp) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL output array");
-    if (!block || !workspace) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL block or workspace");
-    HIPCHK(teacher_launch_imitation(lp, (const long long*)teacher, (long)B, loss, dlp, block, workspace, S(stream)));
+// the rule-based player, style 0: the builder (catan_scripted.hip)
+int catan_sample_scripted_actions(catan_env_t* e, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
+    OK_OR_RETURN(check_row_call("catan_sample_scripted_actions", e, games, n_rows, actions));
+    OK_OR_RETURN(counter_block(e, "catan_sample_scripted_actions", e->script_fallback, 1));
+    hipLaunchKernelGGL(k_sample_scripted, dim3(blocks(n_rows, SCRIPT_BLOCK)), dim3(SCRIPT_BLOCK), 0, S(stream), e->ctx, (const u32*)e->mpk, games, (long)n_rows,
+                       busy_of(e), actions, e->script_fallback);
+    HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
+int64_t catan_scripted_fallback_count(catan_env_t* e, catan_stream_t stream) {
+    if (!e) return -1;
+    if (!e->script_fallback) return 0;
+    unsigned long long v = 0;
+    if (hipMemcpyAsync(&v, e->script_fallback, sizeof v, hipMemcpyDeviceToHost, S(stream)) != hipSuccess) return -1;
+    if (hipStreamSynchronize(S(stream)) != hipSuccess) return -1;
+    return (int64_t)v;
+}
 
-}  // extern "C"
-
-// ---- the rule-based player's styles.  Host code only: style 0 is catan_sample_scripted_actions itself, style 1 launches
-// k_sample_trader of catan_trader.hip, a translation unit and a code object of its own (catan_trader.h).
-#include "catan_trader.h"
-
-extern "C" {
-
+// its styles: style 0 is the call above, style 1 the trader
 int catan_sample_scripted_actions_style(catan_env_t* e, int32_t style, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
     if (style == CATAN_SCRIPTED_BUILDER) return catan_sample_scripted_actions(e, games, n_rows, actions, stream);
     if (style != CATAN_SCRIPTED_TRADER) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: unknown style (0 builder, 1 trader)");
-    if (!e) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: null handle");
-    if (!actions) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: null actions");
-    if (n_rows <= 0) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: n_rows <= 0");
-    if (!games && n_rows > e->n) return fail(CATAN_EINVAL, "catan_sample_scripted_actions_style: n_rows exceeds the handle's games (games == NULL)");
-    if (!e->trade_counts) {
-        hipError_t rc = hipSuccess;
-        dev_alloc(e, rc, e->trade_counts, TC_WORDS * sizeof(unsigned long long));
-        if (rc != hipSuccess) return fail(CATAN_ENOMEM, std::string("catan_sample_scripted_actions_style: hipMalloc: ") + hipGetErrorString(rc));
-        // zeroed synchronously at its allocation (once per handle): in place before a call on ANY stream can count into it
-        HIPCHK(hipMemset(e->trade_counts, 0, TC_WORDS * sizeof(unsigned long long)));
-        HIPCHK(hipStreamSynchronize(nullptr));
-    }
-    HIPCHK(trader_launch_sample(e->ctx.R, e->ctx.n, (const u32*)e->mpk, games, (long)n_rows, e->d_it > 0 ? (const u8*)e->pend.busy : (const u8*)nullptr, actions,
-                                e->trade_counts, S(stream)));
+    OK_OR_RETURN(check_row_call("catan_sample_scripted_actions_style", e, games, n_rows, actions));
+    OK_OR_RETURN(counter_block(e, "catan_sample_scripted_actions_style", e->trade_counts, TC_WORDS));
+    HIPCHK(trader_launch_sample(e->ctx.R, e->ctx.n, (const u32*)e->mpk, games, (long)n_rows, busy_of(e), actions, e->trade_counts, S(stream)));
     return CATAN_OK;
 }
-
 int catan_scripted_trade_counts(catan_env_t* e, uint64_t out[8], int32_t reset, catan_stream_t stream) {
     static_assert(TC_WORDS == 8, "catan_scripted_trade_counts: the block is 8 words (include/catan_hip_tuning.h)");
     if (!e || !out) return fail(CATAN_EINVAL, "catan_scripted_trade_counts: null argument");
@@ -2658,13 +2608,33 @@ int catan_scripted_trade_counts(catan_env_t* e, uint64_t out[8], int32_t reset, 
     return read_counters(out, e->trade_counts, TC_WORDS * sizeof(unsigned long long), reset, S(stream));
 }
 
-}  // extern "C"
+// kickstarting from a player: its rows made teacher-forceable, stored beside the net's, and the imitation term
+int catan_complete_action_rows(catan_env_t* e, const int32_t* games, int64_t n_rows, int32_t* actions, catan_stream_t stream) {
+    OK_OR_RETURN(check_row_call("catan_complete_action_rows", e, games, n_rows, actions));
+    HIPCHK(teacher_launch_complete(e->ctx.R, e->ctx.n, (const u32*)e->mpk, games, (long)n_rows, busy_of(e), actions, S(stream)));
+    return CATAN_OK;
+}
+int catan_collector_label(int64_t n, int32_t T, const int64_t* counters4, const uint8_t* flags4, const int64_t* active_pid, const int32_t* deciding,
+                          const int32_t* labels, int16_t* st_teacher, const uint8_t* waiting_before, catan_stream_t stream) {
+    if (n <= 0 || T <= 0 || !counters4 || !flags4 || !active_pid || !deciding || !labels || !st_teacher)
+        return fail(CATAN_EINVAL, "catan_collector_label: null argument");
+    HIPCHK(teacher_launch_label((long)n, (int)T, (const long long*)counters4 + 2 * n, flags4 + 2 * n, (const long long*)active_pid, deciding, waiting_before, labels,
+                                (short*)st_teacher, S(stream)));
+    return CATAN_OK;
+}
+int64_t catan_imitation_loss_words(void) { return IMIT_WORDS; }
+int64_t catan_imitation_loss_workspace_doubles(void) { return IMIT_PART * IMIT_BLOCKS + 1; }
+int catan_imitation_loss(const float* lp, const int64_t* teacher, int64_t B, float* loss, float* dlp, double* block, double* workspace, catan_stream_t stream) {
+    if (B < 1) return fail(CATAN_EINVAL, "catan_imitation_loss: B must be at least 1");
+    if (!lp || !teacher) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL input array");
+    if (!loss || !dlp) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL output array");
+    if (!block || !workspace) return fail(CATAN_EINVAL, "catan_imitation_loss: a NULL block or workspace");
+    HIPCHK(teacher_launch_imitation(lp, (const long long*)teacher, (long)B, loss, dlp, block, workspace, S(stream)));
+    return CATAN_OK;
+}
 
-// ---- the playout player.  Host code only: the order of the launches.  The games are forked, sampled, re-dealt and stepped by the
-// entry points above; the bookkeeping kernels are catan_playout.hip's, a translation unit and a code object of their own (catan_playout.h).
-#include "catan_playout.h"
-
-// the workspace of a sim handle of n games, carved from one device allocation (8-byte arrays first, then the 72-byte rows, words, bytes)
+// the playout player: the order of the launches.  The games are forked, sampled, re-dealt and stepped by the entry points above.
+// The workspace of a sim handle of n games, carved from one device allocation (8-byte arrays first, then the 72-byte rows, words, bytes)
 static PlayoutWs playout_carve(void* mem, size_t n) {
     PlayoutWs w;
     char* p = (char*)mem;
@@ -2686,8 +2656,6 @@ static PlayoutWs playout_carve(void* mem, size_t n) {
 }
 constexpr size_t PLAYOUT_WS_BYTES_PER_GAME = sizeof(long long) + 5 * ACTION_WORDS * sizeof(i32) + 5 * sizeof(u32) + 2;
 
-extern "C" {
-
 int catan_playout_actions(catan_env_t* root, catan_env_t* sim, const int32_t* games, int64_t n_rows, const catan_playout_cfg_t* cfg, int32_t* actions,
                           int32_t* chosen, int64_t* stats, catan_stream_t stream) {
     static_assert(PS_WORDS == CATAN_PLAYOUT_STAT_WORDS, "catan_playout_actions: the stats row (include/catan_hip_tuning.h)");
@@ -2708,8 +2676,8 @@ int catan_playout_actions(catan_env_t* root, catan_env_t* sim, const int32_t* ga
     if (cfg->depth < 1) return fail(CATAN_EINVAL, "catan_playout_actions: depth must be at least 1");
     if (cfg->playout_style != CATAN_SCRIPTED_BUILDER && cfg->playout_style != CATAN_SCRIPTED_TRADER)
         return fail(CATAN_EINVAL, "catan_playout_actions: unknown playout_style (0 builder, 1 trader)");
-    if (n_rows <= 0) return fail(CATAN_EINVAL, "catan_playout_actions: n_rows <= 0");
-    if (!games && n_rows > root->n) return fail(CATAN_EINVAL, "catan_playout_actions: n_rows exceeds the root handle's games (games == NULL)");
+    // (the two checks above it found root and actions set: what it still tests are the rows, where this call has always tested them)
+    OK_OR_RETURN(check_row_call("catan_playout_actions", root, games, n_rows, actions, "root handle's"));
     if (n_rows > sim->n / ((int64_t)Cn * K)) return fail(CATAN_EINVAL, "catan_playout_actions: n_rows * candidates * playouts exceeds the sim handle's games");
     NOT_MT(root, "catan_playout_actions");
     NOT_MT(sim, "catan_playout_actions");

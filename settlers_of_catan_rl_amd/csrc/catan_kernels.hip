@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "catan_state.h"
+#include "catan_view.h"
 
 #define CATAN_TABLE static __device__ __constant__ const
 #define CATAN_FN static __device__ __forceinline__
@@ -33,10 +34,7 @@
 
 namespace catan {
 
-#define DEVI __device__ __forceinline__
-
 constexpr int BLOCK = 256;
-constexpr u64 ALL54 = (1ull << 54) - 1;
 
 // ------------------------------------------------------------------------------------------------ state view
 // RNG contract (A) on the device (single-game handles, catan_seed_mt19937): the two process-global Mersenne Twisters of the
@@ -71,29 +69,7 @@ struct Ctx {          // launch-invariant handle fields
     const u8* bcfg_idx;     // [N] layout of each game (read only when bcfg != null)
 };
 
-// Derived helpers shared by the two state views (CRTP).
-template <class D>
-struct StOps {
-    DEVI const D& self() const { return *static_cast<const D*>(this); }
-    DEVI int pb(int p, int f) const { return self().b(B_PLAYER + p * PB + f); }
-    DEVI void spb(int p, int f, int v) const { self().sb(B_PLAYER + p * PB + f, v); }
-    DEVI u64 settle(int p) const { return (u64)self().w(W_SETTLE_LO + p) | ((u64)self().w(W_SETTLE_HI + p) << 32); }
-    DEVI u64 city(int p) const { return (u64)self().w(W_CITY_LO + p) | ((u64)self().w(W_CITY_HI + p) << 32); }
-    DEVI void set_settle(int p, u64 v) const { self().sw(W_SETTLE_LO + p, (u32)v); self().sw(W_SETTLE_HI + p, (u32)(v >> 32)); }
-    DEVI void set_city(int p, u64 v) const { self().sw(W_CITY_LO + p, (u32)v); self().sw(W_CITY_HI + p, (u32)(v >> 32)); }
-    DEVI u64 road_lo(int p) const { return (u64)self().w(W_ROAD0 + p) | ((u64)self().w(W_ROAD1 + p) << 32); }
-    DEVI u32 road_hi(int p) const { return self().w(W_ROAD2 + p); }
-    DEVI int flags() const { return self().b(B_FLAGS); }
-    DEVI int res(int p, int r0) const { return pb(p, P_RES + r0); }
-    DEVI int total(int p) const { return res(p, 0) + res(p, 1) + res(p, 2) + res(p, 3) + res(p, 4); }
-    // cold byte fields (always global): ordered card lists and the pile
-    DEVI int hidden(int p, int i) const { return self().cold(B_CARDS + p * 50 + i); }
-    DEVI void set_hidden(int p, int i, int v) const { self().scold(B_CARDS + p * 50 + i, v); }
-    DEVI int played(int p, int i) const { return self().cold(B_CARDS + p * 50 + 25 + i); }
-    DEVI void set_played(int p, int i, int v) const { self().scold(B_CARDS + p * 50 + 25 + i, v); }
-    DEVI int pile(int i) const { return self().cold(B_PILE + i); }
-    DEVI void set_pile(int i, int v) const { self().scold(B_PILE + i, v); }
-};
+// (StOps, the accessors both views derive from the layout, is catan_view.h's)
 // view 1: the game's record in HBM (k_masks, k_reset, k_sample_random, export/import, k_obs_rows, tier-2 longest road)
 struct St : StOps<St> {
     u32* P;           // the game's record
@@ -287,11 +263,6 @@ DEVI void stage_out_masks(u32* tile, u32* __restrict__ mpk, int e, int lane, con
     }
 }
 
-DEVI int seat_of(int seatof, int p) { return (seatof >> (2 * p)) & 3; }
-DEVI int pid_at(int order, int seat) { return (order >> (2 * (seat & 3))) & 3; }
-// ref: game/components/player.py:12-20
-DEVI int label_of(int seatof, int me, int other) { return ((seat_of(seatof, other) - seat_of(seatof, me)) & 3) - 1; }
-DEVI int player_at_label(int order, int seatof, int me, int label) { return pid_at(order, seat_of(seatof, me) + 1 + label); }
 DEVI int clipi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // ------------------------------------------------------------------------------------------------ RNG
@@ -1066,26 +1037,6 @@ DEVI void setr(u32 (&m)[MASK_WORDS], u64 v) {      // overwrite bit range [OFF, 
     m[w0] = (m[w0] & ~(u32)(full << sh)) | (u32)(v << sh);
     if constexpr (sh + NBITS > 32) m[w0 + 1] = (m[w0 + 1] & ~(u32)(full >> (32 - sh))) | (u32)(v >> (32 - sh));
     if constexpr (sh + NBITS > 64) m[w0 + 2] = (m[w0 + 2] & ~(u32)(full >> (64 - sh))) | (u32)(v >> (64 - sh));
-}
-template <int OFF, int NBITS>
-DEVI u64 getr(const u32 (&m)[MASK_WORDS]) {
-    constexpr int w0 = OFF >> 5, sh = OFF & 31;
-    constexpr u64 full = NBITS >= 64 ? ~0ull : ((1ull << NBITS) - 1);
-    u64 v = (u64)m[w0] >> sh;
-    if constexpr (sh + NBITS > 32) v |= (u64)m[w0 + 1] << (32 - sh);
-    if constexpr (sh + NBITS > 64) v |= (u64)m[w0 + 2] << (64 - sh);
-    return v & full;
-}
-struct Boards { u64 occ, own_bld, own_set, own_rlo, all_rlo; u32 own_rhi, all_rhi; };
-template <class S>
-DEVI void load_boards(const S& s, int pid, Boards& b) {
-    b.occ = 0; b.own_bld = 0; b.own_set = 0; b.own_rlo = 0; b.all_rlo = 0; b.own_rhi = 0; b.all_rhi = 0;
-    for (int p = 0; p < 4; p++) {
-        u64 st = s.settle(p), ct = s.city(p), rl = s.road_lo(p);
-        u32 rh = s.road_hi(p);
-        b.occ |= st | ct; b.all_rlo |= rl; b.all_rhi |= rh;
-        if (p == pid) { b.own_bld = st | ct; b.own_set = st; b.own_rlo = rl; b.own_rhi = rh; }
-    }
 }
 // ref: game/components/corner.py:24-39 over all corners.  initial=true ignores the own-road requirement.
 DEVI u64 settle_spots(const Boards& b, bool initial) {

@@ -1,15 +1,35 @@
-// catan_playout.h - what catan_abi.hip sees of catan_playout.hip (the flat Monte-Carlo playout player).
-//
-// catan_playout.hip is a translation unit of its own, as catan_teacher.hip and catan_trader.hip are: its kernels live in a gfx950 code
-// object of their own inside libcatan_hip.so, and the code objects of the three units before it stay what they are without it.  The
-// ABI's entry point (argument checks, the order of the launches, the sim handle's workspace) stands in catan_abi.hip and launches
-// through this.
+// catan_players.h - what catan_abi.hip sees of catan_players.hip: the launch functions of the teacher's kernels, the
+// trader (8.14) and the playout player (8.15), and the layouts both sides share.  catan_players.hip is the library's second translation
+// unit and second gfx950 code object (the reason stands at its top); the ABI's entry points - argument checks, the handles' fields, the
+// order of the launches - stand in catan_abi.hip and launch through these functions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace catan {
 
+// ---- teacher
+constexpr int IMIT_WORDS = 33, IMIT_PART = 30;       // the read-out block of k_imitation_loss; partial q of a workgroup = word q + 2
+constexpr int IMIT_BLOCKS = 256, IMIT_THREADS = 256; // its grid is capped at IMIT_BLOCKS workgroups; workspace = IMIT_PART * IMIT_BLOCKS + 1 doubles
+
+// records: the handle's game records (Ctx::R), n its games, mpk its side rows; busy: null outside a deferred sequence
+hipError_t teacher_launch_complete(const uint32_t* records, long n, const uint32_t* mpk, const int32_t* games, long rows, const uint8_t* busy,
+                                   int32_t* actions, hipStream_t stream);
+hipError_t teacher_launch_label(long n, int T, const long long* n_act, const uint8_t* live, const long long* active_pid, const int32_t* deciding,
+                                const uint8_t* waiting_before, const int32_t* labels, short* st_teacher, hipStream_t stream);
+hipError_t teacher_launch_imitation(const float* lp, const long long* teacher, long B, float* loss, float* dlp, double* block, double* workspace,
+                                    hipStream_t stream);
+
+// ---- trader
+// the counter block of the trader (catan_scripted_trade_counts): one uint64 each
+enum { TC_DECISIONS = 0, TC_PROPOSALS = 1, TC_RESPONSES = 2, TC_ACCEPTS = 3, TC_REJECT_ILLEGAL = 4, TC_REJECT_OTHER = 5, TC_EXCHANGES = 6,
+       TC_FALLBACKS = 7, TC_WORDS = 8 };
+
+// records, n, mpk, busy: as above; counts: device uint64 [TC_WORDS]
+hipError_t trader_launch_sample(const uint32_t* records, long n, const uint32_t* mpk, const int32_t* games, long rows, const uint8_t* busy,
+                                int32_t* actions, unsigned long long* counts, hipStream_t stream);
+
+// ---- playout player
 // the int64 row of one (row, candidate): restated in include/catan_hip_tuning.h and spec.PLAYOUT_STAT_FIELDS
 enum { PS_VALID = 0, PS_SIMS = 1, PS_FINISHED = 2, PS_WINS = 3, PS_SCORE_SUM = 4, PS_VP_SUM = 5, PS_STEPS_SUM = 6, PS_WORDS = 7 };
 constexpr int PLAYOUT_MAX_CANDIDATES = 8, PLAYOUT_MAX_PLAYOUTS = 64;

@@ -12,7 +12,8 @@
 // profiles/scripted_policy_kernel_resources.txt is where that is checked (scratch 0).  The branches diverge by action type within a wave,
 // as in k_sample_random.
 //
-// Included behind every other kernel file: no existing kernel's code changes with it.
+// Included behind every other kernel file of catan_abi.hip: no existing kernel's code changes with it.  catan_players.hip includes it
+// too, for the rule alone (CATAN_SCRIPTED_RULE_ONLY); the views and helpers it reads a game through are catan_view.h's.
 #pragma once
 
 namespace catan {
@@ -22,7 +23,8 @@ constexpr int SCRIPT_ROWS = 13;          // rows of the table in DESIGN.md 8.8 (
 
 // the 19 tiles in two 64-bit words, 3 bits per tile: pips = 6 - |7 - value| (0 for the desert) and the resource (Terrain value, 0 = desert)
 struct ScriptTiles { u64 pips, res; };
-DEVI ScriptTiles script_tiles(const St& s) {
+template <class S>
+DEVI ScriptTiles script_tiles(const S& s) {
     u32 w[5];
 #pragma unroll
     for (int k = 0; k < 5; k++) w[k] = s.w(NW + B_TILE / 4 + k);
@@ -78,20 +80,14 @@ DEVI int script_pick_res(u32 legal, const int (&key)[5], bool most) {
     }
     return best;
 }
-DEVI int script_lowest(u64 v) { return v ? __ffsll((unsigned long long)v) - 1 : 0; }
 
-// -> the row of the table that fired (1..13); a[] = the action
-DEVI int sample_scripted(const St& s, const u32 (&m)[MASK_WORDS], int (&a)[ACTION_WORDS]) {
+// -> the row of the table that fired (1..13); a[] = the action.  S: a view of the game's record (catan_view.h)
+template <class S>
+DEVI int sample_scripted(const S& s, const u32 (&m)[MASK_WORDS], int (&a)[ACTION_WORDS]) {
 #pragma unroll
     for (int i = 0; i < ACTION_WORDS; i++) a[i] = 0;
     const u32 types = (u32)getr<M0, 13>(m);
-    const int flags = s.flags();
-    // the deciding player: discarder, then trade target, then players_go (k_deciding)
-    int me;
-    if (s.b(B_NDISC) > 0) me = s.b(B_DISC);
-    else if (flags & F_MUST_RESPOND) me = s.b(B_TRADE_TGT);
-    else me = s.b(B_GO);
-    me &= 3;
+    const int me = deciding(s) & 3;
     int hand[5];
 #pragma unroll
     for (int r = 0; r < 5; r++) hand[r] = s.res(me, r);
@@ -239,7 +235,7 @@ DEVI int sample_scripted(const St& s, const u32 (&m)[MASK_WORDS], int (&a)[ACTIO
     return 13;
 }
 
-#ifndef CATAN_SCRIPTED_RULE_ONLY    // catan_trader.hip takes the rule above into its own code object, without the builder's kernel
+#ifndef CATAN_SCRIPTED_RULE_ONLY    // catan_players.hip takes the rule above into its own code object, without the builder's kernel
 // Row j of `actions` (int32 [rows][18]) = the bot's action for game games[j] (games == nullptr: game j).  A negative or out-of-range id,
 // and a game that waits for its deferred step (busy != nullptr: an open catan_step_deferred sequence), gets EndTurn - the bot's answer
 // to the placeholder mask row catan_masks_of hands out for such a game; neither the record nor the masks of such a game are read.
@@ -261,9 +257,7 @@ __global__ __launch_bounds__(SCRIPT_BLOCK) void k_sample_scripted(Ctx c, const u
         for (int i = 0; i < MASK_WORDS; i++) m[i] = mpk[e * MPK_STRIDE + i];
         if (sample_scripted(s, m, a) == SCRIPT_ROWS) atomicAdd(fallback, 1ull);
     }
-    uint2* row = reinterpret_cast<uint2*>(actions + j * ACTION_WORDS);    // 72 B rows: 8 B aligned
-#pragma unroll
-    for (int i = 0; i < ACTION_WORDS / 2; i++) row[i] = make_uint2((u32)a[2 * i], (u32)a[2 * i + 1]);
+    store_action_row(actions, j, a);
 }
 #endif
 

@@ -133,8 +133,8 @@ constexpr int F_INITIAL = 1, F_ROLLED = 2, F_PLAYED_DEV = 4, F_MUST_USE_DEV = 8,
 
 // The player who decides in a state, as pid0 (env/wrapper.py:53-58): the first player who still has to discard, else the target of an open
 // offer, else the player whose go it is.  Arguments: the record's B_NDISC, B_DISC (its first entry), B_FLAGS, B_TRADE_TGT and B_GO bytes.
-// (constexpr: usable in host and device code alike.  catan_playout.hip calls it; k_deciding of catan_kernels.hip and the samplers hold the
-// same three lines inline and are left as they are.)
+// (constexpr: usable in host and device code alike.  Device code reads it off a view through catan_view.h's deciding(); k_playout_expand
+// of catan_players.hip calls it directly, k_deciding of catan_kernels.hip holds the same three lines with its ignore_discard switch.)
 constexpr int deciding_pid0(int n_discard, int first_discarder, int flags, int trade_target, int players_go) {
     return n_discard > 0 ? first_discarder : ((flags & 16 /* F_MUST_RESPOND */) ? trade_target : players_go);
 }

@@ -275,7 +275,7 @@ def reduce_diag_over_ranks(block):
 
 
 # ------------------------------------------------------------------------------------------------ imitation term (kickstarting)
-# The teacher's rows under the net (k_imitation_loss, csrc/catan_teacher.hip; the words are listed in
+# The teacher's rows under the net (k_imitation_loss, csrc/catan_players.hip; the words are listed in
 # include/catan_hip_nn.h): the loss -mean(lp), its gradient and the read-out from ONE launch, accumulated like the diagnostics.
 IMIT_WORDS = 33
 IMIT_MAX_WORDS = (3,)

@@ -1,6 +1,6 @@
 """The rule-based players as policy objects: the "builder" (csrc/catan_scripted.hip) and the "trader" (8.14;
-csrc/catan_trader.hip), which is the builder plus answers to offers, proposals and exchanges for a goal; and the playout player (8.15;
-csrc/catan_playout.hip), which picks among their moves and a few random ones by playing each out on the device.
+csrc/catan_players.hip), which is the builder plus answers to offers, proposals and exchanges for a goal; and the playout player (8.15;
+csrc/catan_players.hip), which picks among their moves and a few random ones by playing each out on the device.
 
 A fixed-strength opponent: the same on every run and every checkpoint, far stronger than uniform-random play (DESIGN.md 8.8 has the
 measured win share), one kernel launch per pass where a net's pass is a whole forward.  It sits wherever a net does - a seat of `evaluation.run_evaluation_episodes`, an opponent of
@@ -11,9 +11,52 @@ import torch
 STYLES = ("builder", "trader")
 
 
-class ScriptedPolicy(object):
+class GamesPolicy(object):
+    """A player that reads the games themselves: bound to an env, it answers a pass with int32 [rows, 18] actions.  A subclass supplies
+    `_rows(env, games)`, the call that yields them."""
     wants_games = True            # the callers hand over which game each row of a pass is
     include_lstm = False
+
+    def rebind(self, env):
+        self.env = env
+        return self
+
+    def _bound_env(self):
+        if self.env is None:
+            name = type(self).__name__
+            raise RuntimeError(f"{name} is not bound to an env ({name}(env) or rebind(env))")
+        return self.env
+
+    def _rows(self, env, games):
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def act(self, f, lists, lens, masks, games=None, deterministic=False, generator=None, **ignored):
+        """-> (value zeros [rows,1], actions int64 [rows,18], log-prob zeros [rows,1]): the tuple acting.act's callers index.  The
+        observation tensors only say how many rows the pass has; row j is game games[j] (None: game j, and the pass must then hold
+        all of the env's games)."""
+        env = self._bound_env()
+        name = type(self).__name__
+        rows = int(f.shape[0])
+        if games is None:
+            if rows != env.n:
+                raise ValueError(f"{name}.act without `games` decides all {env.n} games of its env, the pass has {rows} rows")
+        elif int(games.numel()) != rows:
+            raise ValueError(f"{name}.act: {int(games.numel())} games for {rows} rows")
+        a = self._rows(env, games).long()
+        zeros = torch.zeros((rows, 1), dtype=torch.float32, device=a.device)
+        return zeros, a, zeros.clone()
+
+    @torch.no_grad()
+    def label(self, games=None):
+        """The player as a TEACHER (DESIGN.md 8.13) -> int32 [rows, 18]: its action for game games[j] (None: every game), completed so
+        that it can be teacher-forced through the net's heads (env.complete_action_rows)."""
+        env = self._bound_env()
+        return env.complete_action_rows(self._rows(env, games), games=games)
+
+
+class ScriptedPolicy(GamesPolicy):
+    """The rule-based player.  As a teacher, two launches; the trader's labels hold Propose rows and accepts."""
     default_style = "builder"
 
     def __init__(self, env=None, style=None):
@@ -26,43 +69,9 @@ class ScriptedPolicy(object):
         self.env = env
         self.style = style
 
-    def rebind(self, env):
-        self.env = env
-        return self
-
-    def _sample(self, env, games):
+    def _rows(self, env, games):
         # (the builder's call is the one it always was: an env stand-in that knows no styles still serves it)
         return env.sample_scripted_actions(games=games) if self.style == "builder" else env.sample_scripted_actions(games=games, style=self.style)
-
-    @torch.no_grad()
-    def act(self, f, lists, lens, masks, games=None, deterministic=False, generator=None, **ignored):
-        """-> (value zeros [rows,1], actions int64 [rows,18], log-prob zeros [rows,1]): the tuple acting.act's callers index.  The
-        observation tensors only say how many rows the pass has; row j is game games[j] (None: game j, and the pass must then hold
-        all of the env's games)."""
-        env = self.env
-        name = type(self).__name__
-        if env is None:
-            raise RuntimeError(f"{name} is not bound to an env ({name}(env) or rebind(env))")
-        rows = int(f.shape[0])
-        if games is None:
-            if rows != env.n:
-                raise ValueError(f"{name}.act without `games` decides all {env.n} games of its env, the pass has {rows} rows")
-        elif int(games.numel()) != rows:
-            raise ValueError(f"{name}.act: {int(games.numel())} games for {rows} rows")
-        a = self._sample(env, games).long()
-        zeros = torch.zeros((rows, 1), dtype=torch.float32, device=a.device)
-        return zeros, a, zeros.clone()
-
-    @torch.no_grad()
-    def label(self, games=None):
-        """The player as a TEACHER (DESIGN.md 8.13) -> int32 [rows, 18]: its action for game games[j] (None: every game), completed so
-        that it can be teacher-forced through the net's heads (env.complete_action_rows).  Two launches.  The trader's labels hold
-        Propose rows and accepts (8.14)."""
-        env = self.env
-        name = type(self).__name__
-        if env is None:
-            raise RuntimeError(f"{name} is not bound to an env ({name}(env) or rebind(env))")
-        return env.complete_action_rows(self._sample(env, games), games=games)
 
 
 class TraderPolicy(ScriptedPolicy):
@@ -71,7 +80,7 @@ class TraderPolicy(ScriptedPolicy):
     default_style = "trader"
 
 
-class PlayoutPolicy(object):
+class PlayoutPolicy(GamesPolicy):
     """The flat Monte-Carlo playout player (env.playout_actions): per decision it takes the builder's move, the trader's
     and `randoms` uniform-random legal ones, plays each out `playouts` times for `depth` env steps with the rule-based player of
     `playout_style` in every seat - on forked copies of the game in a scratch env of its own, re-dealt for what the deciding player cannot
@@ -85,8 +94,6 @@ class PlayoutPolicy(object):
     its own, since the chunks reuse the same scratch slots -: equal root states and an equal step_idx give equal bits.
     The root env must not be inside an open `step_deferred` sequence (the fork is refused there): `needs_lockstep` tells
     `RolloutCollector`, which then steps with `catan_step` (its default window becomes 0; an explicit window is refused)."""
-    wants_games = True
-    include_lstm = False
     needs_lockstep = True             # it forks the env's games: not inside an open catan_step_deferred sequence (RolloutCollector steps lock-step for it)
     DEFAULT_SIM_ROWS = 1024
     SIM_ID_OFFSET = 1 << 40           # the scratch env's game ids start this far behind the root's: disjoint Philox streams
@@ -140,13 +147,8 @@ class PlayoutPolicy(object):
             self._sim_rows = games // self.sims_per_row
         return self.sim
 
-    @torch.no_grad()
-    def _decide(self, games):
+    def _rows(self, env, games):
         """-> int32 [rows, 18]; fills last_stats / last_chosen; one call per chunk of the scratch env's rows"""
-        env = self.env
-        name = type(self).__name__
-        if env is None:
-            raise RuntimeError(f"{name} is not bound to an env ({name}(env) or rebind(env))")
         sim = self._sim_for(env)
         rows, cap = int(env.n) if games is None else int(games.numel()), self._sim_rows
         kw = dict(candidates=self.candidates, playouts=self.playouts, depth=self.depth, playout_style=self.playout_style, determinise=self.determinise,
@@ -155,33 +157,10 @@ class PlayoutPolicy(object):
         if rows <= cap:
             self.step_idx += 1
             a, self.last_chosen, self.last_stats = env.playout_actions(sim, games, step_idx=first, **kw)
-            return a
+            return a.contiguous()
         g = torch.arange(rows, dtype=torch.int32, device=env.device) if games is None else games.reshape(-1)
         # every chunk runs in the same slots: its own step index keeps the chunks' random candidates on different Philox blocks
         parts = [env.playout_actions(sim, g[lo:lo + cap], step_idx=first + i, **kw) for i, lo in enumerate(range(0, rows, cap))]
         self.step_idx += len(parts)
         a, self.last_chosen, self.last_stats = (torch.cat([p[i] for p in parts], 0) for i in range(3))
-        return a
-
-    @torch.no_grad()
-    def act(self, f, lists, lens, masks, games=None, deterministic=False, generator=None, **ignored):
-        """-> (value zeros [rows,1], actions int64 [rows,18], log-prob zeros [rows,1]), as ScriptedPolicy.act"""
-        env = self.env
-        name = type(self).__name__
-        if env is None:
-            raise RuntimeError(f"{name} is not bound to an env ({name}(env) or rebind(env))")
-        rows = int(f.shape[0])
-        if games is None:
-            if rows != env.n:
-                raise ValueError(f"{name}.act without `games` decides all {env.n} games of its env, the pass has {rows} rows")
-        elif int(games.numel()) != rows:
-            raise ValueError(f"{name}.act: {int(games.numel())} games for {rows} rows")
-        a = self._decide(games).long()
-        zeros = torch.zeros((rows, 1), dtype=torch.float32, device=a.device)
-        return zeros, a, zeros.clone()
-
-    @torch.no_grad()
-    def label(self, games=None):
-        """The player as a TEACHER -> int32 [rows, 18]: the chosen rows, completed by env.complete_action_rows"""
-        a = self._decide(games)              # (raises when unbound)
-        return self.env.complete_action_rows(a.contiguous(), games=games)
+        return a.contiguous()

@@ -283,7 +283,7 @@ def league_stats_table(words, num_nets):
 
 
 # ---------------------------------------------------------------- playout player (include/catan_hip_tuning.h catan_playout_actions)
-# the int64 row of one (row, candidate), in order; csrc/catan_playout.h holds the same layout as PS_* offsets
+# the int64 row of one (row, candidate), in order; csrc/catan_players.h holds the same layout as PS_* offsets
 PLAYOUT_STAT_FIELDS = ["valid", "sims", "finished", "wins", "score_sum", "vp_sum", "steps_sum"]
 PLAYOUT_STAT_WORDS = len(PLAYOUT_STAT_FIELDS)                      # 7
 PLAYOUT_MAX_CANDIDATES, PLAYOUT_MAX_PLAYOUTS = 8, 64

@@ -1,4 +1,4 @@
-"""GPU: the playout player (csrc/catan_playout.hip) - catan_playout_actions against the restatement of its decision over
+"""GPU: the playout player (csrc/catan_players.hip) - catan_playout_actions against the restatement of its decision over
 the CPU oracle (tests/playout_reference.py), integer for integer, on the roots of tests/test_playout_reference_cpu.py (initial
 placements, turns, answers to offers, a discard, a planted win in one); the root handle untouched; determinism; the forms of `games`;
 every refusal; legal and teacher-forceable rows; the player in evaluation games and as a collector's teacher."""

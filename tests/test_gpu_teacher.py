@@ -1,4 +1,4 @@
-"""GPU: kickstarting from the rule-based player (csrc/catan_teacher.hip) - catan_complete_action_rows against its numpy
+"""GPU: kickstarting from the rule-based player (csrc/catan_players.hip) - catan_complete_action_rows against its numpy
 twin (tests/action_complete_reference.py), teacher labels in the rollout collector's loops, catan_imitation_loss against fp64,
 evaluate_actions(teacher_actions=) against the CPU, and one PPO update with the imitation term."""
 import copy

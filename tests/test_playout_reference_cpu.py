@@ -258,8 +258,8 @@ def test_make_teacher_eval_baselines_and_the_library_know_the_player():
     assert isinstance(t, PlayoutPolicy) and (t.playouts, t.depth, t.candidates) == (3, 9, (1, 1, 1)) and t.env is env
     t = train_loop.make_teacher(A(teacher="playout", teacher_coef=0.5), env)
     assert (t.playouts, t.depth, t.candidates) == (8, 120, (1, 1, 2))
-    assert "catan_playout_actions" in _lib.declared_symbols() and _lib.TRANSLATION_UNITS[-1] == "catan_playout.hip"
-    assert _lib.TRANSLATION_UNITS[:3] == ("catan_abi.hip", "catan_teacher.hip", "catan_trader.hip")
+    assert "catan_playout_actions" in _lib.declared_symbols()
+    assert _lib.TRANSLATION_UNITS == ("catan_abi.hip", "catan_players.hip")
     import ctypes as C
     assert C.sizeof(_lib.CatanPlayoutCfg) == 32
 
