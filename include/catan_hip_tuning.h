@@ -128,7 +128,7 @@ int catan_league_stats_read(catan_env_t* env, uint64_t* out_host, int reset, cat
 int catan_league_stats_count(catan_env_t* env, const int32_t* games, int64_t m, catan_stream_t stream);
 
 /* ---- game records ----
- * Whole games recorded on the device and replayed step by step (csrc/catan_record.hip).  A game's draws come from Philox
+ * Whole games recorded on the device and replayed step by step (csrc/catan_hooks.hip).  A game's draws come from Philox
  * keyed by (seed, global game id) and counted in the state itself (blob word rng_draws), so a start blob, the applied actions, the seed,
  * the game id and catan_cfg_t reproduce the game bit for bit on a fresh one-game handle (settlers_of_catan_rl_amd/record.py: replay).
  * Off, the default, not one kernel more is launched and no existing kernel's code differs.
@@ -173,11 +173,11 @@ int catan_record_read(catan_env_t* env, int32_t slot, int32_t* start_blob, int32
                       catan_stream_t stream);
 
 /* ---- start pool ----
- * Re-dealt games started from a pool of saved positions instead of a fresh deal (csrc/catan_start_pool.hip).  With no
+ * Re-dealt games started from a pool of saved positions instead of a fresh deal (csrc/catan_hooks.hip).  With no
  * pool installed, the default, not one kernel more is launched and no existing kernel's code differs.
  * catan_start_pool_set: blobs is a DEVICE int32 [736][m] (the orientation of catan_state_import), 1 <= m <= 65 536; the call keeps its own
- *   copy in the handle's packed form - per entry the record (704 bytes) and the position's mask words under the handle's limits (48
- *   bytes): m x (704 + 48) bytes of device memory plus (2 + m) x 8 bytes of counters (47.5 MiB at m = 65 536) - so blobs may be freed when
+ *   copy in the handle's packed form - per entry the record (704 bytes) and the position's side row under the handle's limits (128
+ *   bytes): m x (704 + 128) bytes of device memory plus (2 + m) x 8 bytes of counters (52.5 MiB at m = 65 536) - so blobs may be freed when
  *   the call returns.  fresh_q16 in 0..65 536 is the share of deals that stay fresh, in 1/65 536ths.  The finished-position check runs on the
  *   device and synchronises the stream once; a second set replaces the pool and zeroes the counters (and then synchronises the handle's
  *   streams).  A call that fails leaves a previously installed pool as it was.
@@ -210,8 +210,8 @@ int catan_start_pool_read(catan_env_t* env, uint64_t* out_host, int32_t reset, c
 int32_t catan_start_pool_size(const catan_env_t* env);
 
 /* ---- start pool: weighted picks and per-entry outcomes ----
- * (csrc/catan_start_pool_weighted.hip).  Both are opt-in: with no weights set and outcomes off, no kernel of that file is
- * launched and the install is the one described above, draw for draw.
+ * (csrc/catan_hooks.hip).  Both are opt-in: with no weights set and outcomes off the install is the one described above,
+ * draw for draw.
  * catan_start_pool_set_weights: weights_dev is a DEVICE uint32 [m] for the installed pool; NULL goes back to the uniform pick.  The call
  *   builds the inclusive prefix sums cum[k] = w[0] + ... + w[k] on the device (summed in 64 bits), synchronises the stream once to read
  *   their total W, and refuses W == 0 and W > 2^32 - 1 with CATAN_EINVAL, leaving the weights in force as they were.  The new table is

@@ -72,8 +72,8 @@ LLVM_OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
 # the translation units of the library, in link order: each brings a gfx950 code object of its own.  catan_abi.hip includes every kernel
-# file but catan_players.hip, whose top says why it is compiled apart
-TRANSLATION_UNITS = ("catan_abi.hip", "catan_players.hip")
+# file but the two whose kernels are opt-in: catan_players.hip (its top says why it is compiled apart) and catan_hooks.hip
+TRANSLATION_UNITS = ("catan_abi.hip", "catan_players.hip", "catan_hooks.hip")
 
 
 def device_code_objects(path=None):

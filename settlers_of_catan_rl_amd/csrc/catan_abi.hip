@@ -25,10 +25,8 @@
 #include "catan_stats.hip"
 #include "catan_scripted.hip"
 #include "catan_league_stats.hip"
-#include "catan_record.hip"
-#include "catan_start_pool.hip"
-#include "catan_start_pool_weighted.hip"
 #include "catan_players.h"
+#include "catan_hooks.h"
 
 using namespace catan;
 
@@ -103,11 +101,11 @@ struct catan_env {
     unsigned long long* script_fallback;   // catan_sample_scripted_actions: decisions taken by the fall-back row (catan_scripted.hip), allocated at the first call
     unsigned long long* trade_counts;      // catan_sample_scripted_actions_style, style 1: the trader's TC_WORDS counters (catan_players.h), allocated at its first call
     void* playout_mem;           // catan_playout_actions with this handle as `sim`: the workspace (catan_players.h PlayoutWs, carved from one allocation), allocated at its first call
-    RecordBuf rec;               // catan_record_enable: the recorder's slots (catan_record.hip); not in `owned`: freed and re-made by every enable
+    RecordBuf rec;               // catan_record_enable: the recorder's slots (catan_hooks.h); not in `owned`: freed and re-made by every enable
     int rec_on;
-    StartPoolBuf pool;           // catan_start_pool_set: the saved positions (catan_start_pool.hip); not in `owned`: freed and re-made by every set
+    StartPoolBuf pool;           // catan_start_pool_set: the saved positions (catan_hooks.h); not in `owned`: freed and re-made by every set
     int pool_on;
-    u32* pool_cum;               // catan_start_pool_set_weights: the inclusive prefix sums of the weights [pool.m] (catan_start_pool_weighted.hip), or NULL: the uniform pick
+    u32* pool_cum;               // catan_start_pool_set_weights: the inclusive prefix sums of the weights [pool.m], or NULL: the uniform pick
     u32 pool_W;                  // ... and their sum
     i32* pool_origin;            // catan_start_pool_outcomes_enable: per game the entry its episode started from, -1 fresh [n]
     unsigned long long* pool_out;   // ... the table of PO_HEAD + (pool.m + 1) x PO_WORDS sums
@@ -427,20 +425,50 @@ static void enqueue_league_stats(catan_env_t* e, const u32* count_p, const i32* 
     if (!(e->lstats_on & CATAN_LEAGUE_STATS_REDEALS)) return;
     launch_league_stats(e, count_p, 0u, list, LEAGUE_STATS_GRID, st);
 }
-// Game records (catan_record_enable; defined at the end of this file, see there): seal in front of a re-deal list's consumer, open behind
-// it, the append in front of the step, the seal over the done flags of a handle without auto_reset.  Off (the default): nothing is launched.
-static void enqueue_record_seal(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
-static void enqueue_record_open(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
-static void enqueue_record_append(catan_env_t* e, const i32* actions, const u8* busy, hipStream_t st);
-static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* status, const i32* actions, hipStream_t st);
-// Start pool (catan_start_pool_set; defined at the end of this file): directly behind the consumer of a re-deal list (enqueue_redeal has the
-// order and its reasons).  No pool installed (the default): nothing is launched.
-static void enqueue_start_pool(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
-static void enqueue_start_pool_sel(catan_env_t* e, const u8* sel, hipStream_t st);
+// Game records (catan_record_enable; the kernels of this and the next hooks are catan_hooks.hip's, and a launch's status stays pending for the
+// hipGetLastError at the end of the caller's sequence: catan_hooks.h).  Seal: at the hook of the finished-game statistics, the listed games'
+// records are still the final states.  Open: behind the list's consumer, on the same stream, the listed games are freshly dealt.  Off (the
+// default): nothing is launched.
+static void enqueue_record_seal(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!e->rec_on) return;
+    (void)record_launch_seal(e->ctx, e->rec, count_p, list, nullptr, nullptr, nullptr, st);
+}
+static void enqueue_record_open(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!e->rec_on) return;
+    (void)record_launch_open(e->ctx, e->rec, count_p, list, st);
+}
+// ... the append in front of the step's first kernel that reads `actions` (busy: the deferred calls' waiting games)
+static void enqueue_record_append(catan_env_t* e, const i32* actions, const u8* busy, hipStream_t st) {
+    if (!e->rec_on) return;
+    (void)record_launch_append(e->ctx, e->rec, actions, busy, st);
+}
+// ... and, on a handle without auto_reset (no re-deal list is ever consumed), the seal at the end of a stepping call over its done flags
+static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* status, const i32* actions, hipStream_t st) {
+    if (!e->rec_on || e->cfg.auto_reset) return;
+    (void)record_launch_seal(e->ctx, e->rec, nullptr, nullptr, done, status, actions, st);
+}
+// Start pool (catan_start_pool_set): directly behind the consumer of a re-deal list (enqueue_redeal has the order and its reasons), or
+// behind catan_reset's deal over the games with sel[g] != 0 (sel == nullptr: every game).  Weights set: the weighted pick; outcomes on:
+// the origin word is written.  No pool installed (the default): nothing is launched.
+static PoolPick pool_pick_of(const catan_env_t* e) { return PoolPick{ e->pool_cum, e->pool_W, e->pool_out_on ? e->pool_origin : nullptr }; }
+static void enqueue_start_pool(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!e->pool_on) return;
+    (void)pool_launch_install(e->ctx, e->mpk, e->pool, pool_pick_of(e), count_p, list, nullptr, st);
+}
+static void enqueue_start_pool_sel(catan_env_t* e, const u8* sel, hipStream_t st) {
+    if (!e->pool_on) return;
+    (void)pool_launch_install(e->ctx, e->mpk, e->pool, pool_pick_of(e), nullptr, nullptr, sel, st);
+}
 // ... its per-entry outcomes (catan_start_pool_outcomes_enable) at the hook of the league results, directly beside them, and the origins of the games
 // that catan_state_import / catan_state_fork overwrite.  Outcomes off (the default): nothing is launched.
-static void enqueue_start_pool_outcomes(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st);
-static void enqueue_start_pool_origin_clear(catan_env_t* e, const long* idx, long cnt, hipStream_t st);
+static void enqueue_start_pool_outcomes(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
+    if (!e->pool_out_on) return;
+    (void)pool_launch_outcomes(e->ctx, count_p, list, e->pool_origin, e->pool_out_focus, e->pool_out, e->pool.m, st);
+}
+static void enqueue_start_pool_origin_clear(catan_env_t* e, const long* idx, long cnt, hipStream_t st) {
+    if (!e->pool_out_on) return;
+    (void)pool_launch_origin_clear(e->pool_origin, e->n, idx, cnt, st);
+}
 // k_step with G games per wave in one-wave workgroups; pend.sample (fused-sampling rollouts): actions from / to the side rows
 template <int G>
 static void launch_step(catan_env_t* e, const int32_t* actions, float* reward, uint8_t* done, hipStream_t st, const StepCfg& sc, const u32* bins) {
@@ -1124,7 +1152,7 @@ int catan_league_stats_count(catan_env_t* e, const int32_t* games, int64_t m, ca
     return CATAN_OK;
 }
 
-static int record_not_armed(catan_env_t* e, const char* what, hipStream_t st);      // (game records: at the end of this file)
+static int record_not_armed(catan_env_t* e, const char* what, hipStream_t st);      // (game records: below)
 // the fused deferred rollout draws a fresh game's first action inside the re-deal kernel, from the state an install would then replace
 #define NO_START_POOL(e, what) do { if ((e)->pool_on) return fail(CATAN_EINVAL, std::string(what) + ": a start pool is installed (catan_start_pool_clear first)"); } while (0)
 
@@ -2189,10 +2217,17 @@ int catan_profile_read(catan_env_t* e, uint64_t* out16) {
 }
 
 
-// ---- game records (catan_record.hip).  Everything that launches one of the recorder's kernels stands here, at the end of the file, and those
-// kernels are templates: a kernel template is emitted where it is first used, so the recorder's code lands BEHIND every other kernel in the
-// code object and the existing kernels keep their places relative to each other (with the kernels in the middle of the code object
-// bench.py's pass read 36.9 instead of 36.4 us with not one of them launched: profiles/record_bench.txt).
+// Hooks in flight on any of the handle's streams may still read or write what a call is about to free or replace (the recorder's slots, a
+// pool in use and its counters, the table of weights): all four streams are waited for
+static int sync_hook_streams(catan_env_t* e, hipStream_t st) {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(e->side));
+    HIPCHK(hipStreamSynchronize(e->fstream));
+    HIPCHK(hipStreamSynchronize(e->sstream));
+    return CATAN_OK;
+}
+
+// ---- game records (the kernels are catan_hooks.hip's, the hooks that launch them stand beside enqueue_episode_stats)
 static void record_free(catan_env_t* e) {
     for (void* p : { (void*)e->rec.hdr, (void*)e->rec.slot_of, (void*)e->rec.start, (void*)e->rec.fin, (void*)e->rec.log, (void*)e->rec.arm_list })
         if (p) hipFree(p);
@@ -2231,11 +2266,7 @@ int catan_record_enable(catan_env_t* e, const int32_t* games, int32_t m, int32_t
     if (m > 0 && (capacity < 1 || capacity > RECORD_MAX_CAPACITY)) return fail(CATAN_EINVAL, "catan_record_enable: capacity must be in 1..65535");
     if (m > 0 && !games) return fail(CATAN_EINVAL, "catan_record_enable: null games");
     const hipStream_t st = S(stream);
-    // the old slots may still be written by hooks in flight on any of the handle's streams
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipStreamSynchronize(e->side));
-    HIPCHK(hipStreamSynchronize(e->fstream));
-    HIPCHK(hipStreamSynchronize(e->sstream));
+    OK_OR_RETURN(sync_hook_streams(e, st));                       // the old slots may still be written
     record_free(e);
     if (m == 0) return CATAN_OK;
     RecordBuf rb{};
@@ -2254,10 +2285,7 @@ int catan_record_enable(catan_env_t* e, const int32_t* games, int32_t m, int32_t
     if (rc == hipSuccess) rc = hipMemsetAsync(rb.start, 0, (size_t)m * STATE_WORDS * sizeof(i32), st);
     if (rc == hipSuccess) rc = hipMemsetAsync(rb.fin, 0, (size_t)m * STATE_WORDS * sizeof(i32), st);
     if (rc == hipSuccess) rc = hipMemsetAsync(bad, 0, sizeof(u32), st);
-    if (rc == hipSuccess) {
-        hipLaunchKernelGGL(k_record_bind<>, dim3(blocks(m, BLOCK)), dim3(BLOCK), 0, st, (long)e->n, games, rb, bad);
-        rc = hipGetLastError();
-    }
+    if (rc == hipSuccess) rc = record_launch_bind((long)e->n, games, rb, bad, st);
     u32 nbad = 0;
     if (rc == hipSuccess) rc = hipMemcpyAsync(&nbad, bad, sizeof(u32), hipMemcpyDeviceToHost, st);
     if (rc == hipSuccess) rc = hipStreamSynchronize(st);
@@ -2284,9 +2312,7 @@ int catan_record_arm(catan_env_t* e, const int32_t* slots, int32_t k, int32_t mo
         // (a pageable source: the copy has left the caller's array when the call returns)
         HIPCHK(hipMemcpyAsync(e->rec.arm_list, slots, (size_t)k * sizeof(i32), hipMemcpyHostToDevice, S(stream)));
     }
-    hipLaunchKernelGGL(k_record_arm<>, dim3(blocks(k, 64)), dim3(64), 0, S(stream), e->ctx, e->rec, slots ? (const i32*)e->rec.arm_list : (const i32*)nullptr, (int)k,
-                       mode == CATAN_RECORD_NOW ? 1 : 0);
-    HIPCHK(hipGetLastError());
+    HIPCHK(record_launch_arm(e->ctx, e->rec, slots ? (const i32*)e->rec.arm_list : (const i32*)nullptr, (int)k, mode == CATAN_RECORD_NOW ? 1 : 0, S(stream)));
     return CATAN_OK;
 }
 int catan_record_status(catan_env_t* e, uint32_t* out_host, catan_stream_t stream) {
@@ -2321,29 +2347,7 @@ int catan_record_read(catan_env_t* e, int32_t slot, int32_t* start_blob, int32_t
     return CATAN_OK;
 }
 
-// Game records (catan_record_enable).  Seal: at the hook of the finished-game statistics, the listed games' records are still the final states.
-// Open: behind the list's consumer, on the same stream, the listed games are freshly dealt.  Off (the default): nothing is launched.
-static void enqueue_record_seal(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
-    if (!e->rec_on) return;
-    hipLaunchKernelGGL(k_record_seal<>, dim3(RECORD_LIST_GRID), dim3(64), 0, st, e->ctx, e->rec, count_p, list, (const u8*)nullptr, (const u8*)nullptr, (const i32*)nullptr);
-}
-static void enqueue_record_open(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
-    if (!e->rec_on) return;
-    hipLaunchKernelGGL(k_record_open<>, dim3(RECORD_LIST_GRID), dim3(64), 0, st, e->ctx, e->rec, count_p, list);
-}
-// ... the append in front of the step's first kernel that reads `actions` (busy: the deferred calls' waiting games)
-static void enqueue_record_append(catan_env_t* e, const i32* actions, const u8* busy, hipStream_t st) {
-    if (!e->rec_on) return;
-    hipLaunchKernelGGL(k_record_append<>, dim3(blocks(e->rec.m, 64)), dim3(64), 0, st, e->ctx, e->rec, actions, busy);
-}
-// ... and, on a handle without auto_reset (no re-deal list is ever consumed), the seal at the end of a stepping call over its done flags
-static void enqueue_record_seal_done(catan_env_t* e, const u8* done, const u8* status, const i32* actions, hipStream_t st) {
-    if (!e->rec_on || e->cfg.auto_reset) return;
-    hipLaunchKernelGGL(k_record_seal<>, dim3(blocks(e->rec.m, 64)), dim3(64), 0, st, e->ctx, e->rec, (const u32*)nullptr, (const i32*)nullptr, done, status, actions);
-}
-
-// ---- start pool (catan_start_pool.hip).  As for the recorder above: the kernels are templates first used here, behind everything else, so their
-// code follows every other kernel's in the code object and the existing kernels keep their code and their places.
+// ---- start pool (the kernels are catan_hooks.hip's but for k_import and k_masks)
 static void start_pool_free(catan_env_t* e) {
     for (void* p : { (void*)e->pool.rec, (void*)e->pool.mask, (void*)e->pool.cnt, (void*)e->pool_cum, (void*)e->pool_origin, (void*)e->pool_out })
         if (p) hipFree(p);
@@ -2354,14 +2358,6 @@ static void start_pool_free(catan_env_t* e) {
     e->pool_origin = nullptr; e->pool_out = nullptr; e->pool_out_focus = nullptr; e->pool_out_on = 0;
 }
 static size_t start_pool_outcome_words(int m) { return (size_t)PO_HEAD + ((size_t)m + 1) * PO_WORDS; }
-// a pool in use may still be read (and counted into) by installs in flight on any of the handle's streams
-static int start_pool_quiesce(catan_env_t* e, hipStream_t st) {
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipStreamSynchronize(e->side));
-    HIPCHK(hipStreamSynchronize(e->fstream));
-    HIPCHK(hipStreamSynchronize(e->sstream));
-    return CATAN_OK;
-}
 int catan_start_pool_set(catan_env_t* e, const int32_t* blobs, int32_t m, int32_t fresh_q16, catan_stream_t stream) {
     if (!e) return fail(CATAN_EINVAL, "catan_start_pool_set: null handle");
     NOT_DEFERRED(e, "catan_start_pool_set");
@@ -2378,7 +2374,7 @@ int catan_start_pool_set(catan_env_t* e, const int32_t* blobs, int32_t m, int32_
     const size_t out_bytes = start_pool_outcome_words(m) * sizeof(unsigned long long);
     hipError_t rc = hipMalloc((void**)&pb.rec, (size_t)m * REC * sizeof(u32));
     if (rc == hipSuccess && e->pool_out_on) rc = hipMalloc((void**)&out, out_bytes);
-    if (rc == hipSuccess) rc = hipMalloc((void**)&pb.mask, (size_t)m * POOL_MASK_STRIDE * sizeof(u32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&pb.mask, (size_t)m * MPK_STRIDE * sizeof(u32));
     if (rc == hipSuccess) rc = hipMalloc((void**)&pb.cnt, (size_t)(2 + m) * sizeof(unsigned long long));
     if (rc == hipSuccess) rc = hipMalloc((void**)&bad, sizeof(u32));
     auto drop = [&]() { for (void* p : { (void*)pb.rec, (void*)pb.mask, (void*)pb.cnt, (void*)bad, (void*)out }) if (p) hipFree(p); };
@@ -2388,12 +2384,13 @@ int catan_start_pool_set(catan_env_t* e, const int32_t* blobs, int32_t m, int32_
     if (rc == hipSuccess) rc = hipMemsetAsync(bad, 0, sizeof(u32), st);
     if (rc == hipSuccess && out) rc = hipMemsetAsync(out, 0, out_bytes, st);
     if (rc == hipSuccess) {
-        // k_import itself, on the pool's records as a handle of m games: an entry's record is what catan_state_import makes of its blob
+        // k_import and k_masks themselves, on the pool's records as a handle of m games: an entry's record is what catan_state_import makes of
+        // its blob, and its mask row what catan_reset's masks would be under the handle's limits
         Ctx pc = e->ctx;
         pc.R = pb.rec; pc.N = m; pc.n = m; pc.mt = nullptr; pc.bcfg = nullptr; pc.bcfg_idx = nullptr;
         hipLaunchKernelGGL(k_import, dim3(blocks(m, BLOCK)), dim3(BLOCK), 0, st, pc, (const long*)nullptr, (long)m, blobs);
-        hipLaunchKernelGGL(k_pool_masks<>, dim3(blocks(m, BLOCK)), dim3(BLOCK), 0, st, pb, limits_of(e), bad);
-        rc = hipGetLastError();
+        hipLaunchKernelGGL(k_masks, dim3(blocks(m, BLOCK)), dim3(BLOCK), 0, st, pc, pb.mask, limits_of(e));
+        rc = pool_launch_count_finished(pb.rec, m, bad, st);
     }
     u32 nbad = 0;
     if (rc == hipSuccess) rc = hipMemcpyAsync(&nbad, bad, sizeof(u32), hipMemcpyDeviceToHost, st);
@@ -2406,7 +2403,7 @@ int catan_start_pool_set(catan_env_t* e, const int32_t* blobs, int32_t m, int32_
     hipFree(bad);
     bad = nullptr;
     if (e->pool_on) {
-        const int r = start_pool_quiesce(e, st);
+        const int r = sync_hook_streams(e, st);
         if (r != CATAN_OK) { drop(); return r; }
     }
     // the origins are reset: the games in flight started from the old pool and are not booked to the new one.  The weights go: a new pool is uniform.
@@ -2425,7 +2422,7 @@ int catan_start_pool_clear(catan_env_t* e, catan_stream_t stream) {
     if (!e) return fail(CATAN_EINVAL, "catan_start_pool_clear: null handle");
     NOT_DEFERRED(e, "catan_start_pool_clear");
     if (!e->pool_on) return CATAN_OK;
-    OK_OR_RETURN(start_pool_quiesce(e, S(stream)));
+    OK_OR_RETURN(sync_hook_streams(e, S(stream)));
     start_pool_free(e);
     return CATAN_OK;
 }
@@ -2437,29 +2434,16 @@ int catan_start_pool_read(catan_env_t* e, uint64_t* out_host, int32_t reset, cat
     return read_counters(out_host, e->pool.cnt, (size_t)(2 + e->pool.m) * sizeof(unsigned long long), reset, S(stream));
 }
 
-static void enqueue_start_pool_x(catan_env_t* e, const u32* count_p, const i32* list, const u8* sel, bool by_list, hipStream_t st);
-static void enqueue_start_pool(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
-    if (!e->pool_on) return;
-    if (e->pool_cum || e->pool_out_on) { enqueue_start_pool_x(e, count_p, list, nullptr, true, st); return; }
-    hipLaunchKernelGGL(k_pool_install_list<>, dim3(POOL_LIST_GRID), dim3(64), 0, st, e->ctx, e->mpk, e->pool, count_p, list);
-}
-static void enqueue_start_pool_sel(catan_env_t* e, const u8* sel, hipStream_t st) {
-    if (!e->pool_on) return;
-    if (e->pool_cum || e->pool_out_on) { enqueue_start_pool_x(e, nullptr, nullptr, sel, false, st); return; }
-    hipLaunchKernelGGL(k_pool_install_sel<>, dim3((unsigned)(e->n < 4096 ? e->n : 4096)), dim3(64), 0, st, e->ctx, e->mpk, e->pool, sel);
-}
-
-// ---- the start pool's weighted pick and per-entry outcomes (catan_start_pool_weighted.hip).  Behind everything above, so that the
-// kernels of catan_start_pool.hip keep their places too.
+// the weighted pick and the per-entry outcomes
 int catan_start_pool_set_weights(catan_env_t* e, const uint32_t* weights_dev, catan_stream_t stream) {
     if (!e) return fail(CATAN_EINVAL, "catan_start_pool_set_weights: null handle");
     NOT_DEFERRED(e, "catan_start_pool_set_weights");
     NOT_MT(e, "catan_start_pool_set_weights");
     if (!e->pool_on) return fail(CATAN_EINVAL, "catan_start_pool_set_weights: no start pool is installed on this handle (catan_start_pool_set)");
     const hipStream_t st = S(stream);
-    if (!weights_dev) {                                // back to the uniform kernels
+    if (!weights_dev) {                                // back to the uniform pick
         if (!e->pool_cum) return CATAN_OK;
-        OK_OR_RETURN(start_pool_quiesce(e, st));
+        OK_OR_RETURN(sync_hook_streams(e, st));
         hipFree(e->pool_cum);
         e->pool_cum = nullptr; e->pool_W = 0u;
         return CATAN_OK;
@@ -2472,8 +2456,7 @@ int catan_start_pool_set_weights(catan_env_t* e, const uint32_t* weights_dev, ca
     if (rc == hipSuccess) rc = hipMalloc((void**)&total, sizeof(unsigned long long));
     auto drop = [&]() { for (void* p : { (void*)cum, (void*)total }) if (p) hipFree(p); };
     if (rc != hipSuccess) { drop(); return fail(CATAN_ENOMEM, std::string("catan_start_pool_set_weights: hipMalloc: ") + hipGetErrorString(rc)); }
-    hipLaunchKernelGGL(k_pool_scan<>, dim3(1), dim3(POOL_SCAN_THREADS), 0, st, (const u32*)weights_dev, cum, total, m);
-    rc = hipGetLastError();
+    rc = pool_launch_scan((const u32*)weights_dev, cum, total, m, st);
     unsigned long long W = 0ull;
     if (rc == hipSuccess) rc = hipMemcpyAsync(&W, total, sizeof W, hipMemcpyDeviceToHost, st);
     if (rc == hipSuccess) rc = hipStreamSynchronize(st);
@@ -2484,7 +2467,7 @@ int catan_start_pool_set_weights(catan_env_t* e, const uint32_t* weights_dev, ca
     }
     hipFree(total);
     total = nullptr;
-    { const int r = start_pool_quiesce(e, st); if (r != CATAN_OK) { drop(); return r; } }    // installs in flight read the old table
+    { const int r = sync_hook_streams(e, st); if (r != CATAN_OK) { drop(); return r; } }    // installs in flight read the old table
     if (e->pool_cum) hipFree(e->pool_cum);
     e->pool_cum = cum; e->pool_W = (u32)W;
     return CATAN_OK;
@@ -2521,29 +2504,6 @@ int catan_start_pool_outcomes_read(catan_env_t* e, uint64_t* out_host, int32_t r
     if (!e->pool_out_on) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_read: outcomes are not enabled on this handle (catan_start_pool_outcomes_enable)");
     NOT_DEFERRED(e, "catan_start_pool_outcomes_read");          // (the side streams of an open sequence are joined by catan_step_flush)
     return read_counters(out_host, e->pool_out, start_pool_outcome_words(e->pool.m) * sizeof(unsigned long long), reset, S(stream));
-}
-
-static void enqueue_start_pool_outcomes(catan_env_t* e, const u32* count_p, const i32* list, hipStream_t st) {
-    if (!e->pool_out_on) return;
-    hipLaunchKernelGGL(k_pool_outcomes<>, dim3(POOL_OUTCOMES_GRID), dim3(64), 0, st, e->ctx, count_p, list, (const i32*)e->pool_origin, e->pool_out_focus, e->pool_out, e->pool.m);
-}
-static void enqueue_start_pool_origin_clear(catan_env_t* e, const long* idx, long cnt, hipStream_t st) {
-    if (!e->pool_out_on) return;
-    hipLaunchKernelGGL(k_pool_origin_clear<>, dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, st, e->pool_origin, e->n, idx, cnt);
-}
-// the install of a handle with weights set, outcomes on, or both (enqueue_start_pool / enqueue_start_pool_sel hand over)
-static void enqueue_start_pool_x(catan_env_t* e, const u32* count_p, const i32* list, const u8* sel, bool by_list, hipStream_t st) {
-    const PoolPick pp{ e->pool_cum, e->pool_W, e->pool_out_on ? e->pool_origin : nullptr };
-    const dim3 sel_grid((unsigned)(e->n < 4096 ? e->n : 4096));
-#define POOL_X(WEIGHTED, ORIGIN)                                                                                                                          \
-    do {                                                                                                                                                  \
-        if (by_list) hipLaunchKernelGGL((k_pool_install_list_x<WEIGHTED, ORIGIN>), dim3(POOL_LIST_GRID), dim3(64), 0, st, e->ctx, e->mpk, e->pool, pp, count_p, list); \
-        else hipLaunchKernelGGL((k_pool_install_sel_x<WEIGHTED, ORIGIN>), sel_grid, dim3(64), 0, st, e->ctx, e->mpk, e->pool, pp, sel);                    \
-    } while (0)
-    if (pp.cum && pp.origin) POOL_X(true, true);
-    else if (pp.cum) POOL_X(true, false);
-    else POOL_X(false, true);
-#undef POOL_X
 }
 
 // ---- the players that read the games themselves.  Host code only, but for k_sample_scripted (catan_scripted.hip,

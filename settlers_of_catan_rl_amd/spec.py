@@ -239,7 +239,7 @@ LEAGUE_STATS_REDEALS, LEAGUE_STATS_COUNT_ONLY = 1, 2              # mode bits of
 
 
 # ---------------------------------------------------------------- start pool outcomes (include/catan_hip_tuning.h catan_start_pool_outcomes_*)
-# one row of uint64 sums per pool entry and a last row for the fresh deals, behind the two head words; csrc/catan_start_pool_weighted.hip
+# one row of uint64 sums per pool entry and a last row for the fresh deals, behind the two head words; csrc/catan_hooks.h
 # holds the same layout as PO_* offsets
 START_POOL_OUTCOME_HEAD = ["seen", "skipped"]
 START_POOL_OUTCOME_FIELDS = ["games", "wins_p1", "wins_p2", "wins_p3", "wins_p4", "focus_games", "focus_wins", "turns_sum"]

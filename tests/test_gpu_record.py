@@ -1,4 +1,4 @@
-"""GPU: whole games recorded on the device (csrc/catan_record.hip) - 64 games, 16 slots on both 32-game tiles of k_step
+"""GPU: whole games recorded on the device (csrc/catan_hooks.hip) - 64 games, 16 slots on both 32-game tiles of k_step
 (games 0, 31, 32 and 63 among them), the rule-based player in every seat.  Everything is compared with integer equality; a replay steps the
 record's start blob through oracle/libcatan_cpu.so created with n = 1, the record's seed and env_id0 = the game id.  The seed and the
 step caps come from tests/record_reference.py and are checked on the CPU by tests/test_record_cpu.py, so every armed slot must seal."""

@@ -1,4 +1,4 @@
-"""GPU: re-dealt games started from a pool of saved positions (csrc/catan_start_pool.hip) - 64 games, so both 32-game
+"""GPU: re-dealt games started from a pool of saved positions (csrc/catan_hooks.hip) - 64 games, so both 32-game
 tiles of k_step with games 0, 31, 32 and 63, a global id base whose high and low words are both non-zero, the rule-based player in
 every seat.  The twin is tests/start_pool_reference.py: the CPU oracle with the pick rule applied by export / import.  Every comparison
 is integer (or bit) equality.  Seeds, pools and caps come from the reference module and are checked on the CPU by

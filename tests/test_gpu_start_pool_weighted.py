@@ -1,4 +1,4 @@
-"""GPU: the start pool's weighted pick and per-entry outcome tallies (csrc/catan_start_pool_weighted.hip) - 64 games, the
+"""GPU: the start pool's weighted pick and per-entry outcome tallies (csrc/catan_hooks.hip) - 64 games, the
 scenario of tests/test_gpu_start_pool.py (both 32-game tiles of k_step, a global id base whose words are both non-zero, the rule-based
 player in every seat).  The twin is tests/start_pool_weighted_reference.py: the CPU oracle with the weighted rule applied by export /
 import and the outcome table kept in Python integers.  Every comparison is integer (or bit) equality.  Weights, seeds and caps come from

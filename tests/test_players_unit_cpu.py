@@ -1,8 +1,10 @@
-"""CPU: the two-unit layout of the library (csrc/catan_players.hip beside csrc/catan_abi.hip) and the players' shared policy base class.
+"""CPU: the three-unit layout of the library (csrc/catan_players.hip and csrc/catan_hooks.hip beside csrc/catan_abi.hip) and the players'
+shared policy base class.
 
-The library carries two gfx950 code objects.  k_sample_scripted, the builder's kernel, is a function of the first - the one that holds
-k_step and the learner's kernels, and that must stay what it is without the other players -, and the kernels of the teacher, the trader
-and the playout player are functions of the second and of the second only.  Read off the code objects' symbol tables (llvm-readelf, as
+The library carries three gfx950 code objects.  k_sample_scripted, the builder's kernel, is a function of the first - the one that holds
+k_step and the learner's kernels, and that must stay what it is without the other players and without the opt-in hooks -, the kernels of
+the teacher, the trader and the playout player are functions of the second and of the second only, and the kernels of the recorder and of
+the start pool are functions of the third and of the third only.  Read off the code objects' symbol tables (llvm-readelf, as
 tools/kernel_resources.py reads them); no GPU needed."""
 import os
 import re
@@ -17,8 +19,12 @@ from settlers_of_catan_rl_amd.scripted import PlayoutPolicy, ScriptedPolicy, Tra
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 FIRST = ("k_sample_scripted",)
+FIRST_ENV = ("k_step", "k_masks", "k_export", "k_import", "k_episode_stats", "k_league_stats", "k_sample_scripted")
 SECOND = ("k_sample_trader", "k_complete_action_rows", "k_collector_label", "k_imitation_loss", "k_playout_slots", "k_playout_expand",
           "k_playout_hold", "k_playout_score")
+THIRD = ("k_record_bind", "k_record_arm", "k_record_append", "k_record_seal", "k_record_open", "k_pool_count_finished", "k_pool_scan",
+         "k_pool_install_list_x", "k_pool_install_sel_x", "k_pool_origin_clear", "k_pool_outcomes")
+GONE = ("k_pool_masks", "k_pool_install_list", "k_pool_install_sel")
 
 
 @pytest.fixture(scope="module")
@@ -46,8 +52,8 @@ def kernels_per_code_object():
 
 
 def test_the_library_has_two_code_objects(kernels_per_code_object):
-    assert _lib.TRANSLATION_UNITS == ("catan_abi.hip", "catan_players.hip")
-    assert len(kernels_per_code_object) == 2
+    assert _lib.TRANSLATION_UNITS == ("catan_abi.hip", "catan_players.hip", "catan_hooks.hip")
+    assert len(kernels_per_code_object) == 3
 
 
 def test_the_builder_kernel_is_in_the_first_code_object(kernels_per_code_object):
@@ -57,10 +63,19 @@ def test_the_builder_kernel_is_in_the_first_code_object(kernels_per_code_object)
 
 
 def test_the_players_kernels_are_in_the_second_code_object_only(kernels_per_code_object):
-    first, second = kernels_per_code_object
+    first, second, third = kernels_per_code_object
     assert all(k in second for k in SECOND), sorted(k for k in SECOND if k not in second)
-    assert not any(k in first for k in SECOND), sorted(k for k in SECOND if k in first)
+    assert not any(k in first | third for k in SECOND), sorted(k for k in SECOND if k in first | third)
     assert not any(k in second for k in FIRST)
+
+
+def test_the_hooks_kernels_are_in_the_third_code_object_only(kernels_per_code_object):
+    first, second, third = kernels_per_code_object
+    hooks = {k for names in kernels_per_code_object for k in names if k.startswith(("k_record_", "k_pool_"))}
+    assert hooks == set(THIRD), sorted(hooks ^ set(THIRD))
+    assert hooks <= third and not hooks & (first | second), sorted(hooks & (first | second))
+    assert all(k in first for k in FIRST_ENV), sorted(k for k in FIRST_ENV if k not in first)
+    assert not any(k in names for k in GONE for names in kernels_per_code_object)
 
 
 # ---- the base class of scripted.py: rebind, the bound-env check, act and label, for every player

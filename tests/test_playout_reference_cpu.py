@@ -259,7 +259,7 @@ def test_make_teacher_eval_baselines_and_the_library_know_the_player():
     t = train_loop.make_teacher(A(teacher="playout", teacher_coef=0.5), env)
     assert (t.playouts, t.depth, t.candidates) == (8, 120, (1, 1, 2))
     assert "catan_playout_actions" in _lib.declared_symbols()
-    assert _lib.TRANSLATION_UNITS == ("catan_abi.hip", "catan_players.hip")
+    assert _lib.TRANSLATION_UNITS == ("catan_abi.hip", "catan_players.hip", "catan_hooks.hip")
     import ctypes as C
     assert C.sizeof(_lib.CatanPlayoutCfg) == 32
 

@@ -137,7 +137,7 @@ def test_npz_round_trip_with_and_without_the_new_keys(tmp_path):
 def test_the_outcome_fields_are_restated_alike():
     assert spec.START_POOL_OUTCOME_FIELDS == wr.FIELDS and spec.START_POOL_OUTCOME_WORDS == 8 and spec.START_POOL_MAX_WEIGHT_SUM == wr.MAX_SUM
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "settlers_of_catan_rl_amd", "csrc", "catan_start_pool_weighted.hip")).read()
+    src = open(os.path.join(root, "settlers_of_catan_rl_amd", "csrc", "catan_hooks.h")).read()
     offs = {name: int(v) for name, v in re.findall(r"constexpr int (PO_[A-Z_]+) = (\d+);", src)}
     assert (offs["PO_GAMES"], offs["PO_WINS_PLAYER"], offs["PO_FOCUS_GAMES"], offs["PO_FOCUS_WINS"], offs["PO_TURNS_SUM"], offs["PO_WORDS"]) == (0, 1, 5, 6, 7, 8)
     # spec's reading of a table against the twin's own

@@ -367,4 +367,4 @@ def test_make_teacher_and_eval_baselines():
 def test_the_library_declares_the_new_entry_points():
     from settlers_of_catan_rl_amd import _lib
     assert {"catan_sample_scripted_actions_style", "catan_scripted_trade_counts"} <= set(_lib.declared_symbols())
-    assert _lib.TRANSLATION_UNITS == ("catan_abi.hip", "catan_players.hip")
+    assert _lib.TRANSLATION_UNITS == ("catan_abi.hip", "catan_players.hip", "catan_hooks.hip")
