@@ -41,6 +41,26 @@ TRAJS = ["traj_s3_e0.npz", "traj_s3_e1.npz", "traj_s17_e4.npz", "traj_dense037_t
          "traj_maxact2_s7_e1.npz"]
 
 
+# rule-case trajectories (tools/gen_golden.py gen_rule_trajs): games whose action lists were scouted in the CPU oracle so that they
+# reach a rule branch the random trajectories above never take, replayed and recorded by the reference; `event` names the case,
+# `event_step` is the step whose action triggers it (for city_none_left: whose masks show it)
+RULE_TRAJS = ["traj_rule_lr_takeover.npz", "traj_rule_lr_tie_keep.npz", "traj_rule_lr_tie_vacate.npz", "traj_rule_lr_none_vacate.npz",
+              "traj_rule_lr_takeover_order.npz", "traj_rule_lr_takeover_after_tie.npz", "traj_rule_rb_dummy_edge.npz",
+              "traj_rule_yop_bank_short.npz", "traj_rule_city_none_left.npz"]
+
+
+def traj_event(t):
+    """-> (event, event_step) of a rule-case trajectory"""
+    return str(t["event"]), int(t["event_step"])
+
+
+def traj_sample(t, step):
+    """-> the reference's state blob (int32) a trajectory stores for `step`"""
+    k = np.flatnonzero(t["sample_idx"] == step)
+    assert len(k) == 1, f"step {step} is not sampled"
+    return t["sample_blob"][int(k[0])].astype(np.int32)
+
+
 def traj_kwargs(t):
     """-> (dense_reward, reward_annealing_factor, max_proposed_trades_per_turn, max_actions_per_turn) a trajectory was generated with"""
     ma = None if ("max_actions" not in t.files or int(t["max_actions"]) < 0) else int(t["max_actions"])

@@ -23,7 +23,7 @@ def test_reset_states_vs_reference(hip_lib):
     assert np.array_equal(got, g["blobs"]), spec.describe_state_diff(g["blobs"][0], got[0])
 
 
-@pytest.mark.parametrize("name", gu.TRAJS)
+@pytest.mark.parametrize("name", gu.TRAJS + gu.RULE_TRAJS)
 def test_trajectory_vs_reference(hip_lib, name):
     import torch
     t = gu.load(name)
@@ -55,7 +55,7 @@ def test_reference_states_masks(hip_lib):
     """Import every sampled reference state of every golden trajectory into the device and compare the masks (one env per
     trade limit the trajectories were generated with: the propose-trade mask bit depends on it, wrapper.py:284-289)."""
     groups = {}
-    for name in gu.TRAJS:
+    for name in gu.TRAJS + gu.RULE_TRAJS:
         t = gu.load(name)
         _, _, trades, max_actions = gu.traj_kwargs(t)
         blobs, masks = groups.setdefault((trades, max_actions), ([], []))

@@ -116,7 +116,83 @@ def test_reset_states(oracle):
         assert np.array_equal(ob, blob), spec.describe_state_diff(blob, ob)
 
 
-@pytest.mark.parametrize("name", gu.TRAJS)
+def _assert_rule_event(t):
+    """The case a rule-case trajectory was recorded for, read off the REFERENCE's own data around `event_step` (its blobs before and
+    after the step, its masks, the action): a regenerated fixture that no longer holds its case fails here."""
+    f = spec.state_field
+    event, s = gu.traj_event(t)
+    before, after = gu.traj_sample(t, s), gu.traj_sample(t, s + 1)
+    a = t["actions"][s].astype(np.int32)
+    m = gu.unpack_masks(t["masks"][s])
+    M = spec.MASK_OFFSETS
+    actor = int(f(before, "players_go")[0])
+    vp = lambda b: np.array([int(f(b, f"p{q}_vp")[0]) for q in (1, 2, 3, 4)])
+    if event.startswith("lr_"):
+        # a settlement on the title holder's road (game.py:880-912); the builder's own +1 VP is taken out of the VP change
+        p, n = int(f(before, "lr_player")[0]), int(f(before, "lr_count")[0])
+        q, n2 = int(f(after, "lr_player")[0]), int(f(after, "lr_count")[0])
+        assert p != 0 and a[0] == 0 and not f(before, "initial_phase")[0] and actor != p
+        dvp = vp(after) - vp(before)
+        dvp[actor - 1] -= 1
+        paths = [int(x) for x in f(after, "cur_longest_path")]
+        mine, others = paths[p - 1], [paths[o - 1] for o in (1, 2, 3, 4) if o != p]
+        assert mine < n, "the holder's road was not cut"
+        want = [0, 0, 0, 0]
+        if event in ("lr_takeover", "lr_takeover_order", "lr_takeover_after_tie"):
+            assert q not in (0, p) and n2 == paths[q - 1] == max(others) > mine and n2 >= 5 and others.count(n2) == 1
+            if event == "lr_takeover":
+                assert sum(x > mine for x in others) == 1
+            elif event == "lr_takeover_order":
+                assert sum(x > mine for x in others) >= 2
+            else:       # in the order of game.py:886 a player level with the holder comes before the new holder: the tie flag is set, then dropped
+                order = [o for o in (1, 2, 3, 4) if o != p]
+                assert any(paths[o - 1] == mine for o in order[:order.index(q)])
+            want[p - 1], want[q - 1] = -2, 2
+        elif event == "lr_tie_keep":
+            assert q == p and n2 == mine >= 5 and max(others) == mine
+        elif event == "lr_tie_vacate":
+            assert q == 0 and n2 == 0 and max(others) >= 5 and max(others) > mine and others.count(max(others)) >= 2
+            want[p - 1] = -2
+        else:
+            assert event == "lr_none_vacate" and q == 0 and n2 == 0 and max(others + [mine]) < 5
+            want[p - 1] = -2
+        assert dvp.tolist() == want, (event, dvp.tolist())
+        if q == 0:      # somebody claims the vacant title again inside the replay, with a road (game.py:874-878)
+            c = int(t["claim_step"])
+            b0, b1 = gu.traj_sample(t, c), gu.traj_sample(t, c + 1)
+            who = int(f(b0, "players_go")[0])
+            assert s < c < len(t["actions"]) - 1 and t["actions"][c][0] == 1 and int(f(b0, "lr_player")[0]) == 0
+            assert int(f(b1, "lr_player")[0]) == who and int(f(b1, "lr_count")[0]) == int(f(b1, "cur_longest_path")[who - 1]) >= 5
+            assert (vp(b1) - vp(b0)).tolist() == [2 * (o == who) for o in (1, 2, 3, 4)]
+    elif event == "rb_dummy_edge":
+        # road building with no legal edge: only the dummy edge 72 is offered, and taking it places nothing
+        assert f(before, "road_building_active")[0] == 1 and m[:13].tolist() == [0, 1] + [0] * 11
+        assert np.flatnonzero(m[M[2]:M[2] + 73]).tolist() == [72] and a[0] == 1 and a[2] == 72
+        assert np.array_equal(f(before, "edge_owner"), f(after, "edge_owner"))
+        cnt = int(f(before, "road_building_count")[0])
+        assert (int(f(after, "road_building_active")[0]), int(f(after, "road_building_count")[0])) == ((1, 1) if cnt == 0 else (0, 0))
+    elif event == "yop_bank_short":
+        # Year of Plenty offered while the bank lacks a resource: that resource's bit is 0 in both resource heads
+        # (wrapper.py:267-269), and a pick of it (accepted by validate_action only) is skipped (game.py:684-689)
+        bank = f(before, "bank_res")
+        r1, r2 = int(a[15]), int(a[16])
+        assert a[0] == 4 and a[4] == 2 and m[4] == 1 and m[M[4] + 2] == 1
+        assert bank[r1] == 0 and bank[r2] > 0 and m[M[10] + r1] == 0 and m[M[9] + 10 + r1] == 0 and m[M[10] + r2] == 1
+        assert np.array_equal(m[M[10]:M[10] + 5], (bank > 0).astype(np.float32))
+        d_bank, d_res = f(after, "bank_res") - bank, f(after, f"p{actor}_res") - f(before, f"p{actor}_res")
+        want = np.zeros(5, dtype=np.int32); want[r2] = 1
+        assert np.array_equal(d_res, want) and np.array_equal(d_bank, -want)
+        assert f(after, f"p{actor}_n_played")[0] == f(before, f"p{actor}_n_played")[0] + 1
+    else:
+        # wheat >= 2, ore >= 3 and a settlement to upgrade, but no city piece left: no city offered (wrapper.py:245-250)
+        assert event == "city_none_left"
+        res = f(before, f"p{actor}_res")
+        assert m[10] == 1 and res[4] >= 2 and res[2] >= 3 and f(before, "cities_left")[actor - 1] == 0
+        assert ((f(before, "corner_bld") == 1) & (f(before, "corner_owner") == actor)).any()
+        assert m[2] == 0 and a[0] != 2
+
+
+@pytest.mark.parametrize("name", gu.TRAJS + gu.RULE_TRAJS)
 def test_trajectory(oracle, name):
     t = gu.load(name)
     e = oracle.OracleEnv(int(t["seed"]), int(t["env_id"]))
@@ -146,7 +222,11 @@ def test_trajectory(oracle, name):
         if done:
             e.reset()
     assert np.array_equal(e.export(), t["final_blob"])
-    assert t["dones"].sum() >= 1
+    if name in gu.TRAJS:
+        assert t["dones"].sum() >= 1
+    else:
+        assert name == f"traj_rule_{gu.traj_event(t)[0]}.npz"
+        _assert_rule_event(t)
 
 
 def test_mt19937_known_answer(oracle):

@@ -6,6 +6,8 @@
                       6/8 rejection loop of board.py:79-81)
   traj_s{S}_e{E}.npz  random-policy trajectories: actions, rewards, dones, deciding player, packed masks and a crc32 of
                       the full state blob at EVERY step, full blobs + observations at sampled steps
+  traj_rule_<case>.npz  rule-case trajectories (gen_rule_trajs): action lists scouted in the CPU oracle so that they reach a rule
+                      branch the random trajectories never take, replayed and recorded by the reference (+ `event`, `event_step`)
   mt_kat.npz          the UNPATCHED reference under np.random.seed(s); random.seed(s) (global Mersenne Twisters):
                       actions + crc32 of the state at every step (config 1 known-answer test for the oracle MT mode)
   longest_road.npz    (edge_owner, corner_owner, player) -> Game.get_longest_path, harvested from play + adversarial
@@ -72,11 +74,19 @@ def gen_resets(n=192, seed=11):
     np.savez_compressed(os.path.join(OUT, "reset_states.npz"), seed=seed, blobs=np.array(blobs, dtype=np.int32))
 
 
-def gen_traj(seed, env_id, steps, sample_every=97, name=None, dense=False, anneal=1.0, trades=4, max_actions=None):
+def gen_traj(seed, env_id, steps, sample_every=97, name=None, dense=False, anneal=1.0, trades=4, max_actions=None,
+             actions=None, also_sample=(), extra=None):
     """name/dense/anneal/trades/max_actions: EnvWrapper's non-default keyword arguments (env/wrapper.py:12-13: dense shaping
     :95-106 x env.reward_annealing_factor, trade limit :284-289, max_actions_per_turn :14-17,233-234); `rewards64` holds the
-    reference's Python-float rewards."""
+    reference's Python-float rewards.  The action source: the uniform-random legal policy (`actions` None), or a fixed list
+    `actions` that is replayed (steps = its length; an action the reference's validate_action rejects raises).  `also_sample`:
+    steps whose blob and observation are stored besides every sample_every-th; `extra`: further fields of the file."""
     rng = np.random.default_rng(seed * 7919 + env_id)
+    replay = actions
+    if replay is not None:
+        steps = len(replay)
+    source = (lambda t, e: rh.random_legal_action(e.masks(), e.env, rng)) if replay is None else (lambda t, e: np.asarray(replay[t], dtype=np.int32))
+    also_sample = set(int(x) for x in also_sample)
     e = rh.RefEnv(seed, env_id, dense_reward=dense, max_proposed_trades_per_turn=trades, max_actions_per_turn=max_actions)
     e.env.reward_annealing_factor = anneal
     obs = e.reset()
@@ -86,10 +96,10 @@ def gen_traj(seed, env_id, steps, sample_every=97, name=None, dense=False, annea
         blob = e.state_blob()
         m = rh.masks_flat(e.masks())
         crcs.append(crc(blob)); masks.append(pack_masks(m)); deciding.append(e.deciding_player())
-        if t % sample_every == 0:
+        if t % sample_every == 0 or t in also_sample:
             f, lists, lens, pid = rh.obs_flat(obs)
             s_idx.append(t); s_blob.append(blob); s_obs.append(f); s_lists.append(lists); s_lens.append(lens); s_pid.append(pid)
-        a = rh.random_legal_action(e.masks(), e.env, rng)
+        a = source(t, e)
         obs, rew, done = e.step(a)
         actions.append(a); rewards.append(rew); dones.append(done); rewards64.append(e.last_reward64)
         if done:
@@ -102,9 +112,9 @@ def gen_traj(seed, env_id, steps, sample_every=97, name=None, dense=False, annea
         deciding=np.array(deciding, dtype=np.int8), masks=np.array(masks, dtype=np.uint8), state_crc=np.array(crcs, dtype=np.uint32),
         sample_idx=np.array(s_idx, dtype=np.int32), sample_blob=np.array(s_blob, dtype=np.int16),
         sample_obs=np.packbits(np.array(s_obs) != 0, axis=1),        # observation: zero/non-zero pattern ...
-        sample_obs_nz=[np.array([x[x != 0] for x in s_obs], dtype=object)][0] if False else np.concatenate([x[x != 0] for x in s_obs]).astype(np.float32),
+        sample_obs_nz=np.concatenate([x[x != 0] for x in s_obs]).astype(np.float32),        # ... and the non-zero values
         sample_lists=np.array(s_lists, dtype=np.int8), sample_lens=np.array(s_lens, dtype=np.int8), sample_pid=np.array(s_pid, dtype=np.int8),
-        final_blob=e.state_blob())
+        final_blob=e.state_blob(), **(extra or {}))
     return int(np.sum(dones))
 
 
@@ -1155,7 +1165,152 @@ def gen_ref_checks():
     return {k: v.shape for k, v in out.items()}
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Rule-case trajectories: branches of the rules that no random-policy trajectory above reaches.  The reference cannot import
+# a state, so every case is a game played from reset: the CPU oracle SCOUTS (it plays the first games of consecutive env ids
+# with the device's random policy, orc_sample_action, and the cases are recognised in its consecutive state blobs), the
+# reference JUDGES (gen_traj replays the chosen action list; everything stored is what the reference produced).
+RULE_SEED, RULE_GAMES = 23, 8192
+RULE_CASES = ["lr_takeover", "lr_tie_keep", "lr_tie_vacate", "lr_none_vacate", "lr_takeover_order", "lr_takeover_after_tie", "rb_dummy_edge",
+              "yop_bank_short", "city_none_left"]
+RULE_TAIL = 48              # steps replayed after the event (after the title is claimed again, for the two vacate cases)
+_M = dict(zip(range(12), spec.MASK_OFFSETS))
+
+
+def _scout_game(env_id, seed=RULE_SEED, limit=6000):
+    """-> (env_id, game length, [(case, step)], [(step, lr_player after it)] where the title changed hands).  One deviation from
+    the random policy: whenever Year of Plenty is playable while the bank lacks a resource, it is played with that resource as
+    the first pick (no mask offers that pick; validate_action accepts it, game.py:403-408, and apply_action skips it, :684-689)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib
+    f = spec.state_field
+    e = oracle_lib.OracleEnv(seed, env_id)
+    e.reset()
+    prev = e.export()
+    events, title, actions = [], [], []
+    for t in range(limit):
+        m = e.masks()
+        a = e.sample_action(seed, env_id, t, m)
+        p = int(f(prev, "players_go")[0])
+        bank = f(prev, "bank_res")
+        if m[4] > 0 and m[_M[4] + 2] > 0 and (bank == 0).any():                           # Year of Plenty (card 2) with a short bank
+            a[:] = 0
+            a[0], a[4], a[15], a[16] = 4, 2, int(np.flatnonzero(bank == 0)[0]), int(np.flatnonzero(bank > 0)[0])
+            assert m[_M[10] + a[15]] == 0 and m[_M[9] + 10 + a[15]] == 0       # wrapper.py:267-269
+            events.append(("yop_bank_short", t))
+        if m[1] > 0 and m[_M[2] + 72] > 0:                                    # road building, no legal edge
+            events.append(("rb_dummy_edge", t))
+        if m[10] > 0 and m[2] == 0:                                           # own turn after the roll (EndTurn offered), no city offered
+            res = f(prev, f"p{p}_res")
+            own = ((f(prev, "corner_bld") == 1) & (f(prev, "corner_owner") == p)).any()
+            if res[4] >= 2 and res[2] >= 3 and f(prev, "cities_left")[p - 1] == 0 and own:
+                events.append(("city_none_left", t))
+        actions.append(a.copy())
+        _, done = e.step(a)
+        cur = e.export()
+        h, h2 = int(f(prev, "lr_player")[0]), int(f(cur, "lr_player")[0])
+        if h != h2:
+            title.append((t, h2))
+        if a[0] == 0 and h and not f(prev, "initial_phase")[0]:               # a settlement: the only action that shortens a road
+            eo, co = f(cur, "edge_owner"), f(cur, "corner_owner")
+            ln = {q: oracle_lib.longest_path_raw(eo, co, q) for q in (1, 2, 3, 4)}
+            # (update_longest_road stores only the holder's new length: kept are the cuts after which every player's stored
+            #  current_longest_path is the true one, so that the tests can read the case off the reference's blobs alone)
+            stored = all(ln[q] == int(f(cur, "cur_longest_path")[q - 1]) for q in (1, 2, 3, 4))
+            if ln[h] < int(f(prev, "lr_count")[0]) and stored:                # the holder's road was cut
+                others = [ln[q] for q in (1, 2, 3, 4) if q != h]
+                if h2 not in (0, h):
+                    events.append(("lr_takeover_order" if sum(x > ln[h] for x in others) >= 2 else "lr_takeover", t))
+                    order = [q for q in (1, 2, 3, 4) if q != h]                # game.py:886
+                    if any(ln[o] == ln[h] for o in order[:order.index(h2)]):  # the loop met a tie with the holder before it met the winner
+                        events.append(("lr_takeover_after_tie", t))
+                elif h2 == 0:
+                    events.append(("lr_tie_vacate" if max(others) >= 5 else "lr_none_vacate", t))
+                elif ln[h] >= 5 and ln[h] in others:
+                    events.append(("lr_tie_keep", t))
+        if done:
+            break
+        prev = cur
+    return env_id, len(actions), events, title, actions
+
+
+def _scout_summary(env_id):
+    r = _scout_game(env_id)
+    return r[:4]
+
+
+def scout_rule_cases(n_games=RULE_GAMES, workers=8):
+    """-> {case: (env_id, event step, number of steps to replay, step at which the vacant title is claimed again or -1)}: per case the occurrence with the smallest step index whose
+    tail (RULE_TAIL steps; for the vacate cases RULE_TAIL steps after somebody claims the title again, game.py:874-878) lies
+    inside the game, and how many of the scouted games hold the case at all."""
+    import multiprocessing as mp
+    with mp.Pool(workers) as pool:
+        games = pool.map(_scout_summary, range(n_games), chunksize=32)
+    best, count = {}, {c: 0 for c in RULE_CASES}
+    for env_id, length, events, title in games:
+        for case in set(c for c, _ in events):
+            count[case] += 1
+        for case, step in events:
+            end, claim = step + 1 + RULE_TAIL, -1
+            if case in ("lr_tie_vacate", "lr_none_vacate"):
+                claimed = [t for t, who in title if t > step and who != 0]
+                if not claimed:
+                    continue
+                claim = claimed[0]
+                end = claim + 1 + RULE_TAIL
+            if end > length:                 # the whole tail lies inside the first game
+                continue
+            if case not in best or (step, env_id) < (best[case][1], best[case][0]):
+                best[case] = (env_id, step, end, claim)
+    return best, count
+
+
+def gen_rule_trajs(picks=None):
+    """tests/golden/traj_rule_<case>.npz: the reference's replay of the scouted action lists (`event`, `event_step` stored besides
+    the fields of every trajectory, and `claim_step`: the step at which the vacant title is claimed again, -1 elsewhere; blob and
+    observation forced at the event step, the steps around it and the claim).  As generated: seed 23, the first games of env ids
+    0..8191 scouted, every case found (`games` = how many of the 8 192 games hold it); the earliest occurrence is taken:
+
+      case                    env id  event step  steps  games  what happens at the event step
+      lr_takeover               5393         364    413    114  a settlement cuts the holder's road, ONE other player is longer: title moves
+      lr_tie_keep               4118         540    589     83  cut, another player level with the holder at >= 5: holder keeps it, smaller count
+      lr_tie_vacate              209         872    927     14  cut, two others level above the holder: title vacated, nobody gains (claimed at 878)
+      lr_none_vacate            6726         266    466     21  cut, nobody has 5 left: title vacated (claimed again at 417)
+      lr_takeover_order         3024         487    536     23  cut, TWO others longer than the holder: the longest takes the title
+      lr_takeover_after_tie      666         514    563     15  cut, the loop of game.py:886 meets a player level with the holder, then the winner
+      rb_dummy_edge              462         792    841    258  road building with no legal edge: only edge 72 offered, nothing placed
+      yop_bank_short            2482         184    233     76  Year of Plenty, bank short of a resource: mask bit 0, the forced pick is skipped
+      city_none_left            8119         664    713     37  wheat >= 2, ore >= 3, a settlement, no city piece left: no city offered
+
+    lr_takeover_after_tie is the one case in which dropping the `tied = False` of game.py:894 changes
+    the outcome.  The order of game.py:886 itself cannot change an outcome (the loop computes the maximum and whether two players
+    share it, both independent of the order), so no fixture can tell a permuted loop from the reference's.
+    """
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    if picks is None:
+        picks, count = scout_rule_cases()
+        print("games holding each case:", count)
+    out = {}
+    for case in RULE_CASES:
+        if case not in picks:
+            print(case, "NOT FOUND in", RULE_GAMES, "games")
+            continue
+        env_id, step, end, claim = picks[case]
+        actions = _scout_game(env_id)[4][:end]
+        games = gen_traj(RULE_SEED, env_id, len(actions), name=f"traj_rule_{case}.npz", actions=actions,
+                         also_sample=[s for s in (step - 1, step, step + 1, step + 2, claim, claim + 1) if 0 <= s < len(actions)],
+                         extra=dict(event=np.array(case), event_step=np.int32(step), claim_step=np.int32(claim)))
+        out[case] = dict(env_id=env_id, event_step=step, steps=len(actions), games_finished=games,
+                         bytes=os.path.getsize(os.path.join(OUT, f"traj_rule_{case}.npz")))
+        print(case, out[case])
+    return out
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "rule_scout":
+        print(scout_rule_cases()); sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "rule_cases":
+        gen_rule_trajs(); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "rollout":
         print("rollout_small (games complete, pre-advance, first-game lengths):", gen_rollout_small()); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "eval":
@@ -1201,4 +1356,5 @@ if __name__ == "__main__":
     print("forward_search", gen_forward_search())
     print("validate_cases", gen_validate_cases())
     print("ref_checks", gen_ref_checks())
+    print("rule cases", gen_rule_trajs())
     os.system(f"ls -la {OUT}; du -sh {OUT}")
