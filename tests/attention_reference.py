@@ -25,18 +25,18 @@ slices of the kernel's dqkv [B, L, 3, H * HD]).
                       (out; dq, dk, dv).
     path "fp32"       k_attn_fwd / k_attn_bwd on float32: plain fp32, no rounding - the error of fp32 arithmetic itself.
 
-Acceptance of a kernel output is te_reference.within_yardstick (bf16 paths) or `within_floor` with the fp32 floors below - the same
-rule with another floor.  `per_sequence` applies the rule to every sequence with that sequence's own yardstick error and scale."""
+Acceptance of a kernel output is the rule of tests/pin_rule.py with the floor of the path: pin_rule.BF16_FLOOR on the bf16 paths, the fp32
+floors below on the fp32 path.  `accept` applies it to a whole tensor, `per_sequence` to every sequence with that sequence's own yardstick
+error and scale."""
 import math
 
 import torch
 
-from te_reference import within_yardstick
+from pin_rule import BF16_FLOOR, per_group, whole
 
 SHAPES = ((19, 4, 16), (25, 4, 4))
 PATHS = ("mfma", "valu_bf16", "fp32")
 OUTPUTS = ("out", "dq", "dk", "dv")
-BF16_FLOOR = 2.0 ** -9                                   # te_reference.within_yardstick's
 FP32_FLOOR = {"out": 2.0 ** -17, "dq": 2.0 ** -15, "dk": 2.0 ** -15, "dv": 2.0 ** -15}
 LOG2E = 1.44269504088896340736
 # the batch sizes of the GPU tests: the MFMA kernels take 4 sequences per block, the VALU kernels 3 (L = 19) or 2 (L = 25)
@@ -124,33 +124,18 @@ def attention_yardstick(qkv, lens, dout, path, max_keys=None, half_max=False):
 
 
 # ------------------------------------------------------------------------------------------------------------------------ rule
-def within_floor(kernel, ref, yardstick, floor):
-    """te_reference.within_yardstick with `floor` in place of its 2^-9 -> (ok, kernel error, yardstick error, bound)"""
-    ref = ref.double()
-    ek = float((kernel.double() - ref).abs().max())
-    ey = float((yardstick.double() - ref).abs().max())
-    bound = 2.0 * ey + floor * float(ref.abs().max())
-    return ek <= bound, ek, ey, bound
+def path_floor(path, name):
+    return FP32_FLOOR[name] if path == "fp32" else BF16_FLOOR
 
 
 def accept(path, name, kernel, ref, yardstick):
-    """the rule of `path` for output `name` over a whole tensor"""
-    if path == "fp32":
-        return within_floor(kernel, ref, yardstick, FP32_FLOOR[name])
-    return within_yardstick(kernel, ref, yardstick)
+    """pin_rule.whole with the floor of `path` for output `name` -> (ok, kernel error, yardstick error, bound)"""
+    return whole(kernel, ref, yardstick, path_floor(path, name))
 
 
 def per_sequence(path, name, kernel, ref, yardstick):
-    """the same rule for every sequence b with ITS yardstick error and ITS scale -> (ok [B] bool, kernel error [B], bound [B]).  A
-    NaN in a sequence fails it (the comparison is false)."""
-    floor = FP32_FLOOR[name] if path == "fp32" else BF16_FLOOR
-    ref = ref.double()
-    B = ref.shape[0]
-    ek = (kernel.double() - ref).abs().reshape(B, -1)
-    ek = torch.where(torch.isnan(ek).any(1), torch.full((B,), float("nan"), dtype=torch.float64), ek.amax(1))
-    ey = (yardstick.double() - ref).abs().reshape(B, -1).amax(1)
-    bound = 2.0 * ey + floor * ref.abs().reshape(B, -1).amax(1)
-    return ek <= bound, ek, bound
+    """pin_rule.per_group with that floor: every sequence b with ITS yardstick error and ITS scale -> (ok [B], kernel error [B], bound [B])"""
+    return per_group(kernel, ref, yardstick, path_floor(path, name))
 
 
 # ----------------------------------------------------------------------------------------------------------------------- cases

@@ -23,17 +23,18 @@ restates nn_kernels.card_summary_params).
                       (list, class) contribution of the backward is rounded to fp32, their SUM is taken in fp64: the yardstick carries the
                       per-term rounding, the depth term of the rule carries the summation.  `plant=` swaps in one planted error (PLANTS).
 
-Rule (nothing in a bound comes from a kernel):
-    out       attention_reference.within_floor(kernel, fp64, yardstick, 2^-17) over the case AND per list (per_list: the list's own
+Rule (tests/pin_rule.py; nothing in a bound comes from a kernel):
+    out       pin_rule.whole with floor 2^-17 over the case (accept_out) AND pin_rule.per_group per list (per_list: the list's own
               yardstick error and scale)
-    dparams   per parameter |kernel - (pre-fill + fp64)| <= 2 |yardstick - fp64| + depth 2^-24 (abs_terms + |pre-fill|), depth = bwd_depth
+    dparams   pin_rule.accept_sum per parameter: |kernel - (pre-fill + fp64)| <= 2 |yardstick - fp64| + depth 2^-24 (abs_terms +
+              |pre-fill|), depth = bwd_depth
     dpat      per word |kernel - fp64| <= sum_depth 2^-24 sum |term|; with dout = small integers times a power of two every sum is exact
     keys      == pattern_of(counts), lookup == forward, bit for bit"""
 import math
 
 import torch
 
-import attention_reference as AR
+import pin_rule as PR
 
 VOCAB, HEADS, HD, WIDTH, MAXLEN = 6, 4, 4, 16, 25
 NPAR = 544
@@ -43,7 +44,6 @@ EPS = 1e-5
 DECK = (1, 14, 5, 2, 2, 2)                    # the most a real list holds of ids 0..5 (id 0: the placeholder of an empty list)
 PATTERNS = 2 * 15 * 6 * 3 * 3 * 3             # 4 860
 OUT_FLOOR = 2.0 ** -17
-U = 2.0 ** -24
 PLANTS = ("no_log_count", "no_count_weight", "len_plus_1", "padding_counted", "absent_class_kept", "mean_15", "eps_outside", "ds_no_dot",
           "dv_wrong_head", "dln_w_ungated_by_count", "radix_c2_5", "replica_dropped")
 REGIMES = ("unit", "saturated", "flat")
@@ -348,35 +348,13 @@ def pattern_sum_ref(keys, dout, replicas, plant=None):
 
 # ------------------------------------------------------------------------------------------------------------------------------ rule
 def accept_out(kernel, ref, yard):
-    """the rule for `out` over the case -> (ok, kernel error, yardstick error, bound)"""
-    return AR.within_floor(kernel, ref, yard, OUT_FLOOR)
+    """pin_rule.whole for `out` with its floor -> (ok, kernel error, yardstick error, bound)"""
+    return PR.whole(kernel, ref, yard, OUT_FLOOR)
 
 
 def per_list(kernel, ref, yard):
-    """the same for every list with ITS yardstick error and ITS scale -> (ok [rows], kernel error [rows], bound [rows]); a NaN fails"""
-    ref = ref.double()
-    ek = (kernel.double() - ref).abs()
-    ek = torch.where(torch.isnan(ek).any(1), torch.full_like(ek[:, 0], float("nan")), ek.amax(1))
-    bound = 2.0 * (yard.double() - ref).abs().amax(1) + OUT_FLOOR * ref.abs().amax(1)
-    return ek <= bound, ek, bound
-
-
-def param_bound(yard, ref, abs_terms, prefill, depth):
-    """per parameter: 2 |yardstick - fp64| + depth 2^-24 (abs_terms + |pre-fill|)"""
-    return 2.0 * (yard.double() - ref.double()).abs() + depth * U * (abs_terms.double() + prefill.double().abs())
-
-
-def accept_params(kernel, prefill, ref, yard, abs_terms, depth):
-    """-> (ok [544], error [544], bound [544]) of a backward that ADDED to `prefill`; a NaN fails"""
-    err = (kernel.double() - (prefill.double() + ref.double())).abs()
-    bound = param_bound(yard, ref, abs_terms, prefill, depth)
-    return err <= bound, err, bound
-
-
-def share(err, bound):
-    """the largest err / bound (inf where a bound of 0 is exceeded, 0 where both are 0)"""
-    r = torch.where(bound > 0, err / bound, torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    return float(r.max()) if r.numel() else 0.0
+    """pin_rule.per_group with that floor: every list with ITS yardstick error and ITS scale -> (ok [rows], kernel error [rows], bound [rows])"""
+    return PR.per_group(kernel, ref, yard, OUT_FLOOR)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------- cases

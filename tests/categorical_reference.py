@@ -19,9 +19,8 @@ ops only, on the CPU or the GPU, written from include/catan_hip_nn.h and the for
   cat_yardstick  the same formulas in fp32.  It shows what the number format costs against the reference; it is not an oracle.  `plant` is
                  NOT part of it: the planted errors of the CPU test's rejection cases (PLANTS).
 
-Acceptance (`row_rule`), per row r and over the whole case:  |kernel_r - ref_r| <= 2 |yardstick_r - ref_r| + floor scale_r, through
-attention_reference.within_floor for the whole case.  Floors: the attention suite's, 2^-17 for logp, entropy, lse and 2^-15 for dlogits;
-none was moved.  scale_r = max(1, largest |logp_all| over the row's legal columns with a finite one) for logp, entropy, lse (`fwd_scale`).
+Acceptance: the rule of tests/pin_rule.py per row r (per_group with scale_r, over the rows asked about) and over the whole case (whole).
+Floors: the attention suite's, 2^-17 for logp, entropy, lse and 2^-15 for dlogits; none was moved.  scale_r = max(1, largest |logp_all| over the row's legal columns with a finite one) for logp, entropy, lse (`fwd_scale`).
 For dlogits the whole case takes the case's largest reference magnitude and a row takes
     scale_r = max(the row's largest reference magnitude, |dlogp_r| + |dent_r|)                                      (`grad_scale`)
 because `onehot - p` and `p (logp + H)` are differences and products of numbers of size 1: whatever the size of the result, a row's
@@ -34,17 +33,16 @@ The yardstick returns p = 0 below the normal range (2^-126), as the kernels' __e
 whole gradient is of that size disagreed by the flushed value.  The exact cases (one legal column, an illegal given action, a row without
 a legal column) are compared as values, not through the rule.
 
-Sampled actions: the bracket rule of tests/test_gpu_heads_fp64.py with tau = heads_reference.yard_bound(ref cdf, yardstick cdf)
+Sampled actions: the bracket rule of tests/test_gpu_heads_fp64.py with tau = pin_rule.whole_bound(ref cdf, yardstick cdf, BF16_FLOOR)
 (`bracket_ok`), on every row; only where u is the largest float below 1 may the pick also be the last legal column.  tau is 2^-9 (the
 cdf's scale is 1), so the rule brackets the pick within 2^-9 of cdf mass; it cannot tell two neighbouring columns of less mass apart.  u = 0: the pick is a legal column whose fp64 probability is above 2^-152 (below it no fp32 evaluation has p > 0) and no
 legal column before it has one of 2^-125 or more (from there every fp32 evaluation has p > 0, flushed denormals or not): `first_ok`."""
 import torch
 
-from attention_reference import FP32_FLOOR as _ATT_FLOOR
-from attention_reference import within_floor
-from heads_reference import HEAD_K, MASK_OFF, U_TOP, yard_bound
+import pin_rule as PR
+from heads_reference import HEAD_K, MASK_OFF, U_TOP
 
-FLOOR = {"logp": _ATT_FLOOR["out"], "entropy": _ATT_FLOOR["out"], "lse": _ATT_FLOOR["out"], "dlogits": _ATT_FLOOR["dq"]}
+FLOOR = {"logp": 2.0 ** -17, "entropy": 2.0 ** -17, "lse": 2.0 ** -17, "dlogits": 2.0 ** -15}
 PLANTS = ("ent_all", "cdf_ge", "fall_last", "argmax_illegal", "no_max", "and_ignored", "seg_le", "bit_off")
 REGIMES = ("unit", "wide", "single", "all_legal", "ties", "empty", "neginf")
 BITS_REGIMES = ("unit", "wide", "ties", "empty", "neginf")
@@ -229,33 +227,9 @@ def grad_scale(ref_grad, dlogp, dent):
     return torch.maximum(ref_grad.double().abs().amax(1), dlogp.double().abs() + dent.double().abs())
 
 
-def row_rule(kernel, ref, yard, floor, scale, rows=None):
-    """the rule for every row ([B] or [B, K] tensors; `scale` [B]) -> (ok [B] bool, kernel error [B], bound [B]); `rows` [B] bool: the rows
-    it is asked about (the others pass with error 0).  A NaN in an asked row fails it (the comparison is false)."""
-    ref = ref.double()
-    ek, ey = (kernel.double() - ref).abs(), (yard.double() - ref).abs()
-    if ek.dim() == 2:
-        ek, ey = ek.amax(1), ey.amax(1)                               # amax propagates NaN
-    bound = 2.0 * ey + floor * scale.double()
-    ok = ek <= bound
-    if rows is not None:
-        ok = ok | ~rows
-        ek, bound = torch.where(rows, ek, torch.zeros_like(ek)), torch.where(rows, bound, torch.zeros_like(bound))
-    return ok, ek, bound
-
-
-def case_rule(kernel, ref, yard, floor, rows=None):
-    """attention_reference.within_floor over the asked rows of a [B, K] tensor whose scale is its own largest magnitude -> (ok, ek, ey, bound)"""
-    if rows is not None:
-        kernel, ref, yard = kernel[rows], ref[rows], yard[rows]
-    if ref.numel() == 0:
-        return True, 0.0, 0.0, 0.0
-    return within_floor(kernel, ref, yard, floor)
-
-
 def bracket_ok(ref, yard, action, u):
     """the bracket rule for every row -> (ok [B] bool, tau)"""
-    tau, _ = yard_bound(ref["cdf"], yard["cdf"])
+    tau, _ = PR.whole_bound(ref["cdf"], yard["cdf"], PR.BF16_FLOOR)
     cdf = ref["cdf"].double()
     uu = u.double()
     upper = cdf.gather(1, action[:, None]).squeeze(1)
@@ -388,20 +362,6 @@ def _same(a, b):
     return bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
 
 
-def _share(err, bound):
-    """the largest err / bound (inf where a bound of 0 is exceeded, 0 where both are 0)"""
-    if err.numel() == 0:
-        return 0.0
-    r = torch.where(bound > 0, err / bound, torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    return float(r.max())
-
-
-def _need(ek, ey, scale):
-    """the smallest floor under which every row passes: the largest (ek - 2 ey) / scale (0 where no row needs one)"""
-    n = torch.where(scale > 0, (ek - 2.0 * ey) / scale, torch.where(ek > 2.0 * ey, torch.full_like(ek, float("inf")), torch.zeros_like(ek)))
-    return max(0.0, float(n.max()))
-
-
 def judge(c, mode, got):
     """everything the GPU test asks of one launch (forward, and with got["dlogits"] the backward) of case `c` in `mode`; `got` = {action,
     logp, entropy, lse[, dlogits]} as the kernel (or a planted yardstick) returned them.  Reference and yardstick are evaluated at the
@@ -443,11 +403,11 @@ def judge(c, mode, got):
             bad.append((n, "NaN outside the empty rows"))
         if exact and not _same(got[n], ref[n]):
             bad.append((n, "one legal column: not the exact value"))
-        ok, ek, bnd = row_rule(got[n], ref[n], yard[n], FLOOR[n], scale, finite)
-        ey = torch.where(finite, (yard[n].double() - ref[n]).abs(), torch.zeros_like(ek))
+        ok, ek, bnd = PR.per_group(got[n], ref[n], yard[n], FLOOR[n], scale, finite)
+        ey = torch.where(finite, PR.group_error(yard[n], ref[n]), torch.zeros_like(ek))
         # the whole case: the largest error against twice the yardstick's largest plus the floor at the case's largest scale
-        whole = float(ek.max()) <= 2.0 * float(ey.max()) + FLOOR[n] * float(scale.max())
-        stats[n] = (float(ek.max()), float(ey.max()), _share(ek, bnd), _need(ek, ey, scale.double()))
+        whole = PR.whole(got[n][finite], ref[n][finite], yard[n][finite], FLOOR[n], float(scale.max()))[0]
+        stats[n] = (float(ek.max()), float(ey.max()), PR.share(ek, bnd), PR.need_floor(ek, ey, scale.double()))
         if not (bool(ok.all()) and whole):
             r = int((~ok).nonzero()[0]) if not bool(ok.all()) else -1
             bad.append((n, f"{int((~ok).sum())} rows, first {r}", float(ek[r]), float(bnd[r])))
@@ -464,10 +424,10 @@ def judge(c, mode, got):
         if exact and not _same(g, rg):
             bad.append(("dlogits", "one legal column: not exactly 0"))
         gscale = grad_scale(rg, c["dlogp"], c["dent"])
-        ok, ek, bnd = row_rule(g, rg, yg, FLOOR["dlogits"], gscale, legal_rows)
-        w_ok, w_ek, w_ey, w_b = case_rule(g, rg, yg, FLOOR["dlogits"], legal_rows)
-        ey = torch.where(legal_rows, (yg.double() - rg).abs().amax(1), torch.zeros_like(ek))
-        stats["dlogits"] = (w_ek, w_ey, max(_share(ek, bnd), w_ek / w_b if w_b > 0 else float(w_ek > 0)), _need(ek, ey, gscale))
+        ok, ek, bnd = PR.per_group(g, rg, yg, FLOOR["dlogits"], gscale, legal_rows)
+        w_ok, w_ek, w_ey, w_b = PR.whole(g[legal_rows], rg[legal_rows], yg[legal_rows], FLOOR["dlogits"])
+        ey = torch.where(legal_rows, PR.group_error(yg, rg), torch.zeros_like(ek))
+        stats["dlogits"] = (w_ek, w_ey, max(PR.share(ek, bnd), PR.whole_share(w_ek, w_b)), PR.need_floor(ek, ey, gscale))
         if not (bool(ok.all()) and w_ok):
             r = int((~ok).nonzero()[0]) if not bool(ok.all()) else -1
             bad.append(("dlogits", f"{int((~ok).sum())} rows, first {r}", float(ek[r]), float(bnd[r]), w_ek, w_b))
@@ -479,8 +439,7 @@ def stats_line(stats):
     out = []
     for n in ("logp", "entropy", "lse", "dlogits"):
         if n in stats:
-            ek, ey, share, need = stats[n]
-            out.append(f"{n} {ek:.2e} {ey:.2e} {ek / ey if ey > 0 else (float('inf') if ek > 0 else 0.0):.2f} {share:.2f} {need:.1e}")
+            out.append(PR.fmt_stat(n, stats[n]))
     if "tau" in stats:
         out.append(f"tau {stats['tau']:.2e}")
     return " | ".join(out)

@@ -15,10 +15,11 @@ bf16 (head_case's `cond_op`), so the kernel's own cast of them is required, not 
 `trade` and its features unrounded while the kernel (and the yardstick) round them: there the cast is part of what the yardstick
 measures - the module in double, which chain_ref must equal to 1e-9, does not round them either.
 tests/test_heads_reference_cpu.py holds the reference against the unfused module, the golden statistics and a direct formula;
-tests/test_gpu_heads_fp64.py holds the kernels against the reference with te_reference.within_yardstick."""
+tests/test_gpu_heads_fp64.py holds the kernels against the reference with the rule of tests/pin_rule.py (`whole`, floor BF16_FLOOR)."""
 import torch
 
-from te_reference import _ln_stats, _modes, within_yardstick
+from pin_rule import BF16_FLOOR, whole_bound
+from te_reference import _ln_stats, _modes
 
 # include/catan_hip_nn.h (catan_head_fwd): wts = W2 [128][128] | W3 [80][128] (rows >= K zero) | W1e^T [32][128]; vec = ln_w, ln_b, b2 [128 each], b3 [80]
 KP, NCP = 80, 32
@@ -215,12 +216,6 @@ def chain_ref(actions, pre_all, packs, custom, masks, cur_res, trade, forced, ro
 
 
 # ----------------------------------------------------------------------------------------------- bounds the GPU tests derive
-def yard_bound(ref, yard):
-    """within_yardstick's bound for a tensor, from the reference and the yardstick alone -> (bound, yardstick error)"""
-    _, _, ey, bound = within_yardstick(ref, ref, yard)
-    return bound, ey
-
-
 def top2_gap(ref_logits, mask):
     """-> (arg-max over the legal columns [B], best legal logit minus the second best [B]; inf with one legal column)"""
     z = torch.where(mask > 0, ref_logits.double(), torch.full_like(ref_logits.double(), float("-inf")))
@@ -329,7 +324,7 @@ def legal_or_zero(x, mask):
 def ambiguous_rows(ref, yard, mask, rows):
     """-> (delta, arg-max [B], ambiguous [B]) over the rows selected by `rows` (bool [B]): delta = the yardstick bound of the logits on
     those rows, ambiguous = the two best legal reference logits closer than 2 delta"""
-    delta = yard_bound(ref["logits"][rows], yard["logits"][rows])[0] if bool(rows.any()) else 0.0
+    delta = whole_bound(ref["logits"][rows], yard["logits"][rows], BF16_FLOOR)[0] if bool(rows.any()) else 0.0
     best, gap = top2_gap(ref["logits"], mask)
     return delta, best, (gap < 2 * delta) & rows
 

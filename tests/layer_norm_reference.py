@@ -13,22 +13,18 @@ tests/test_gpu_layer_norm_fp64.py share.  No call into the library or into nn_ke
                             what the number formats cost against the reference; it is not an oracle.  `plant` is NOT part of it: the planted
                             errors of the CPU test's rejection cases (PLANTS).
 
-Acceptance.  y, dx: te_reference.within_yardstick (bf16) / attention_reference.within_floor with the attention suite's fp32 floors, over the
-whole case (`accept`) and for every row with that row's own yardstick error and scale (`per_row`).  dw, db, per column j (`column_bound`):
-    |kernel_j - ref_j| <= 2 |yardstick_j - ref_j| + depth 2^-24 sum_r |term_rj|
-the any-order summation bound of a chain of `depth` fp32 additions (`depth` = iterations per lane + rows per block + blocks, from the
-launch table below).  The value the accumulator is pre-filled with is one more addend of that chain, so |pre-fill_j| is one of the terms."""
+Acceptance: the rule of tests/pin_rule.py.  y, dx: floor pin_rule.BF16_FLOOR (bf16) / FP32_FLOOR (fp32), over the whole case (`accept`)
+and for every row with that row's own yardstick error and scale (`per_row`).  dw, db: pin_rule.sum_bound per column, with `depth` =
+iterations per lane + rows per block + blocks (`launch_depth`, from the launch table below)."""
 import math
 
 import torch
 
-from attention_reference import within_floor
-from te_reference import within_yardstick
+from pin_rule import BF16_FLOOR, per_group, rbf, whole, whole_bound
 
 EPS = 1e-5
 WIDTHS = (16, 25, 32, 64, 128, 256, 512)
-BF16_FLOOR = 2.0 ** -9                                   # te_reference.within_yardstick's
-FP32_FLOOR = {"y": 2.0 ** -17, "dx": 2.0 ** -15}        # attention_reference.FP32_FLOOR's out / dq
+FP32_FLOOR = {"y": 2.0 ** -17, "dx": 2.0 ** -15}        # the attention suite's for out / dq: the same kind of arithmetic
 PLANTS = ("one_pass", "d_minus_1", "eps_outside", "no_m2", "gate_lt", "dw_ungated", "swap_pairs", "drop_last", "dw_scale")
 
 # ------------------------------------------------------------------------------------------------------------------- launch table
@@ -79,10 +75,6 @@ def launch_depth(align, D, rows):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- formulas
-def _rbf(t):
-    return t.to(torch.bfloat16).to(t.dtype)
-
-
 def _core(x, w, b, dy, eps, relu, wd, plant=None):
     """everything in dtype wd -> {pre, y, dx, dw, db, aw, ab} (aw, ab = sum_r |term| in fp64); dy None: forward only"""
     x, w, b = x.to(wd), w.to(wd), b.to(wd)
@@ -149,9 +141,9 @@ def ln_ref(x, w, b, dy, eps, relu):
 def ln_yardstick(x, w, b, dy, eps, relu, bf16, plant=None):
     o = _core(x, w, b, dy, eps, relu, torch.float32, plant)
     if bf16:
-        o["y"] = _rbf(o["y"])
+        o["y"] = rbf(o["y"])
         if "dx" in o:
-            o["dx"] = _rbf(o["dx"])
+            o["dx"] = rbf(o["dx"])
     return o
 
 
@@ -159,7 +151,7 @@ def gate_delta(x, w, b, eps):
     """the rule's bound on an fp32 pre-activation of the case: 2 maxabs(fp32 - fp64) + 2^-17 maxabs(fp64)"""
     p64 = _core(x, w, b, None, eps, False, torch.float64)["pre"]
     p32 = _core(x, w, b, None, eps, False, torch.float32)["pre"]
-    return 2.0 * float((p32.double() - p64).abs().max()) + FP32_FLOOR["y"] * float(p64.abs().max())
+    return whole_bound(p64, p32, FP32_FLOOR["y"])[0]
 
 
 def near_gate(x, w, b, eps, delta):
@@ -180,24 +172,13 @@ def gated_dy(case):
 
 # -------------------------------------------------------------------------------------------------------------------------- rule
 def accept(bf16, name, kernel, ref, yardstick):
-    """the rule over a whole tensor (y or dx) -> (ok, kernel error, yardstick error, bound)"""
-    return within_yardstick(kernel, ref, yardstick) if bf16 else within_floor(kernel, ref, yardstick, FP32_FLOOR[name])
+    """pin_rule.whole for y or dx with the floor of the storage type -> (ok, kernel error, yardstick error, bound)"""
+    return whole(kernel, ref, yardstick, BF16_FLOOR if bf16 else FP32_FLOOR[name])
 
 
 def per_row(bf16, name, kernel, ref, yardstick):
-    """the same rule for every row with ITS yardstick error and ITS scale -> (ok [rows] bool, kernel error [rows], bound [rows]).  A NaN
-    in a row fails it (the comparison is false)."""
-    floor = BF16_FLOOR if bf16 else FP32_FLOOR[name]
-    ref = ref.double()
-    ek = (kernel.double() - ref).abs().amax(1)                     # amax propagates NaN
-    ey = (yardstick.double() - ref).abs().amax(1)
-    bound = 2.0 * ey + floor * ref.abs().amax(1)
-    return ek <= bound, ek, bound
-
-
-def column_bound(yardstick, ref, abs_terms, prefill, depth):
-    """[D] fp64: the dw / db bound of the module docstring"""
-    return 2.0 * (yardstick.double() - ref.double()).abs() + depth * 2.0 ** -24 * (abs_terms.double() + prefill.double().abs())
+    """pin_rule.per_group with that floor: every row with ITS yardstick error and ITS scale -> (ok [rows], kernel error [rows], bound [rows])"""
+    return per_group(kernel, ref, yardstick, BF16_FLOOR if bf16 else FP32_FLOOR[name])
 
 
 # ------------------------------------------------------------------------------------------------------------------------- cases

@@ -28,16 +28,15 @@ Two regimes.
                   mode 2 adds 2^-8 (|a + aux| + that);  2^-8 = a bf16 half-ulp relative to the bottom of its binade
             dw,db |kernel - (pre-fill + ref)| <= depth U (sum_r |dy x| + |pre-fill|), depth = per + nb + 1 (k_wgrad / k_wgrad_tr) or
                   per + groups + 1 (k_wgrad_big) from the launch table
-          and te_reference.within_yardstick over the case and for every row.
+          and the rule of tests/pin_rule.py (floor BF16_FLOOR) over the case and for every row.
 At ~10^5 rows the real-regime bound on a weight gradient is wider than one row's term - a dropped row would pass - so the exact regime
 runs at EVERY row count and the real regime only below REAL_BELOW = 5 000 rows.  Nothing in a bound comes from a kernel."""
 import torch
 
-from te_reference import within_yardstick
+import pin_rule as PR
 
 U = 2.0 ** -23
 HALF_ULP_BF16 = 2.0 ** -8
-BF16_FLOOR = 2.0 ** -9                                   # te_reference.within_yardstick's
 REAL_BELOW = 5000
 WG_KT = 64
 WG_MAX_UNITS = 24
@@ -194,11 +193,6 @@ def grouped_problems():
 
 
 # ---------------------------------------------------------------------------------------------------------------------- formulas
-def _rbf(t):
-    """round to bf16 (fp64 passes through fp32 first: only used where that is exact)"""
-    return t.float().to(torch.bfloat16).to(t.dtype)
-
-
 def linear_terms(x, W, b):
     """-> (a, S) in fp64: a = x W^T + b, S = sum_k |x_k W_nk| + |b_n|"""
     xd, Wd = x.double(), W.double()
@@ -234,14 +228,14 @@ def linear_yardstick(x, W, b, aux, mode, wd=torch.float32, plant=None):
     if b is not None:
         a = a + b.to(wd) * (_cdiv(K, 32) if plant == "bias_per_kstep" else 1)
     if plant == "relu_before_round" and mode == 1:
-        y = _rbf(a.clamp_min(0.0))
+        y = PR.rbf(a.clamp_min(0.0))
     elif plant == "no_second_round" and mode == 2:
-        y = _rbf(a + aux.to(wd))
+        y = PR.rbf(a + aux.to(wd))
     elif plant == "gate_ge" and mode == 3:
-        y = torch.where(aux >= 0, _rbf(a), torch.zeros((), dtype=wd, device=a.device))
+        y = torch.where(aux >= 0, PR.rbf(a), torch.zeros((), dtype=wd, device=a.device))
     else:
-        y = epilogue(_rbf(a), aux, mode)
-        y = _rbf(y) if mode == 2 else y
+        y = epilogue(PR.rbf(a), aux, mode)
+        y = PR.rbf(y) if mode == 2 else y
     y = y.to(torch.bfloat16)
     R = y.shape[0]
     if plant == "perm_tile_rows":                                  # rows 4 g + r of every 16-row tile leave as 4 r + g
@@ -337,24 +331,6 @@ def forward_bound(a, S, aux, mode, K):
     return bound
 
 
-def per_row(kernel, ref, yardstick):
-    """within_yardstick for every row with ITS yardstick error and ITS scale -> (ok [rows], kernel error [rows], bound [rows])"""
-    ref = ref.double()
-    ek = (kernel.double() - ref).abs().amax(1)                     # amax propagates NaN
-    ey = (yardstick.double() - ref).abs().amax(1)
-    bound = 2.0 * ey + BF16_FLOOR * ref.abs().amax(1)
-    return ek <= bound, ek, bound
-
-
-def share(err, bound):
-    """the largest err / bound (inf where a bound of 0 is exceeded or the error is NaN, 0 where both are 0)"""
-    if err.numel() == 0:
-        return 0.0
-    inf = torch.full_like(err, float("inf"))
-    r = torch.where(bound > 0, err / bound, torch.where(err == 0, torch.zeros_like(err), inf))
-    return float(torch.where(torch.isnan(r), inf, r).max())
-
-
 def judge_forward(y, x, W, b, aux, mode, regime, terms=None):
     """one forward output against the rule of its regime -> (failures [str], kernel error, yardstick error, largest share of a bound)"""
     a, S = terms if terms is not None else linear_terms(x, W, b)
@@ -375,11 +351,11 @@ def judge_forward(y, x, W, b, aux, mode, regime, terms=None):
         return bad, ek, ey, float("inf") if bad else 0.0
     bound = forward_bound(a, S, aux, mode, x.shape[1])
     err = (y.double() - ref).abs()
-    sh = share(err, bound)
+    sh = PR.share(err, bound)
     if not bool((err <= bound).all()):
         bad.append(f"{int((~(err <= bound)).sum())} elements over their bound, share {sh:.2f}")
-    ok, _, _, _ = within_yardstick(y, ref, yard)
-    oks = per_row(y, ref, yard)[0]
+    ok = PR.whole(y, ref, yard, PR.BF16_FLOOR)[0]
+    oks = PR.per_group(y, ref, yard, PR.BF16_FLOOR)[0]
     if not ok:
         bad.append("within_yardstick over the case")
     if not bool(oks.all()):
@@ -399,8 +375,8 @@ def judge_wgrad(got, pre, ref, abs_terms, regime, depth):
         if not torch.equal(got.double(), want):
             bad.append(f"{int((got.double() != want).sum())} elements differ from the exact result")
         return bad, ek, float("inf") if bad else 0.0
-    bound = depth * U * (abs_terms + pre.double().abs())
-    sh = share(err, bound)
+    bound = PR.sum_bound(abs_terms, depth, pre, unit=U)
+    sh = PR.share(err, bound)
     if not bool((err <= bound).all()):
         bad.append(f"{int((~(err <= bound)).sum())} elements over their bound, share {sh:.2f}")
     return bad, ek, sh
@@ -419,12 +395,7 @@ def wgrad_headroom(rows):
 
 
 def _gen(device, *key):
-    g = torch.Generator(device=device)
-    s = 12345
-    for k in key:
-        s = (s * 1000003 + int(k)) % (2 ** 31 - 1)
-    g.manual_seed(s)
-    return g
+    return PR.gen(*key, start=12345, device=device)
 
 
 def _no_subnormals(*ts):

@@ -18,20 +18,17 @@ include/catan_hip_nn.h and torch.nn.LSTM's cell.
                   A change to sigmoid_f / tanh_f in csrc/catan_nn.hip has to be mirrored in `_core` by hand.
                   `plant` is NOT part of it: the planted errors of the CPU test's rejection cases (PLANTS).
 
-Acceptance, per row and over the whole case: |kernel - ref| <= 2 |yardstick - ref| + floor scale, scale = the largest reference magnitude
-(of the row / of the case).  fp32 outputs through attention_reference.within_floor with the attention suite's floors, 2^-17 for h, c and
-2^-15 for dgates, dc_prev; bf16 dgates through te_reference.within_yardstick, floor 2^-9.  No floor was moved: on the MI355X the kernels use
+Acceptance: the rule of tests/pin_rule.py per row and over the whole case, scale = the largest reference magnitude (of the row / of the
+case).  fp32 outputs with the attention suite's floors, 2^-17 for h, c and 2^-15 for dgates, dc_prev; bf16 dgates with
+pin_rule.BF16_FLOOR.  No floor was moved: on the MI355X the kernels use
 at most half of a bound (saturated; 0.16 of one in the unit regime) and their rows would need a floor of 3.8e-6 at most
 (profiles/lstm_cell_kernel_tests.txt).  The exact cases (`zero`; the masked rows of `masked` against
 the same case with c_prev = 0 there) are compared as values and bit for bit."""
 import torch
 
-from attention_reference import FP32_FLOOR as _ATT_FLOOR
-from attention_reference import within_floor
-from te_reference import within_yardstick
+import pin_rule as PR
 
-FLOOR = {"h": _ATT_FLOOR["out"], "c": _ATT_FLOOR["out"], "dgates": _ATT_FLOOR["dq"], "dc_prev": _ATT_FLOOR["dq"]}
-BF16_FLOOR = 2.0 ** -9                                   # te_reference.within_yardstick's
+FLOOR = {"h": 2.0 ** -17, "c": 2.0 ** -17, "dgates": 2.0 ** -15, "dc_prev": 2.0 ** -15}
 PLANTS = ("gate_order", "mask_on_c", "dcp_no_mask", "one_minus_tc")
 REGIMES = ("unit", "saturated", "zero", "masked")
 FLT_MIN = 2.0 ** -126
@@ -69,10 +66,6 @@ def cap_cases():
 
 
 # ---------------------------------------------------------------------------------------------------------------------- formulas
-def _rbf(t):
-    return t.to(torch.bfloat16).to(t.dtype)
-
-
 def _core(gx, gh, c_prev, mask, dh, dc, wd, plant=None):
     """everything in dtype wd -> {h, c, and with dh: dgates, dc_prev}"""
     L = c_prev.shape[1]
@@ -119,33 +112,13 @@ def lstm_ref(gx, gh, c_prev, mask, dh=None, dc=None):
 def lstm_yardstick(gx, gh, c_prev, mask, dh=None, dc=None, plant=None):
     o = _core(gx, gh, c_prev, mask, dh, dc, torch.float32, plant)
     if gx.dtype == torch.bfloat16 and "dgates" in o:
-        o["dgates"] = _rbf(o["dgates"])
+        o["dgates"] = PR.rbf(o["dgates"])
     return o
 
 
 # -------------------------------------------------------------------------------------------------------------------------- rule
-def accept(bf16, name, kernel, ref, yardstick):
-    """the rule over a whole tensor -> (ok, kernel error, yardstick error, bound)"""
-    if bf16 and name == "dgates":
-        return within_yardstick(kernel, ref, yardstick)
-    return within_floor(kernel, ref, yardstick, FLOOR[name])
-
-
-def per_row(bf16, name, kernel, ref, yardstick):
-    """the same rule for every row with ITS yardstick error and ITS scale -> (ok [rows] bool, kernel error [rows], bound [rows]).  A NaN
-    in a row fails it (the comparison is false)."""
-    floor = BF16_FLOOR if (bf16 and name == "dgates") else FLOOR[name]
-    ref = ref.double()
-    ek = (kernel.double() - ref).abs().amax(1)
-    ey = (yardstick.double() - ref).abs().amax(1)
-    bound = 2.0 * ey + floor * ref.abs().amax(1)
-    return ek <= bound, ek, bound
-
-
-def _share(err, bound):
-    """the largest err / bound (inf where a bound of 0 is exceeded, 0 where both are 0)"""
-    r = torch.where(bound > 0, err / bound, torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    return float(r.max())
+def floor_of(bf16, name):
+    return PR.BF16_FLOOR if (bf16 and name == "dgates") else FLOOR[name]
 
 
 def judge(bf16, got, ref, yard):
@@ -155,12 +128,11 @@ def judge(bf16, got, ref, yard):
     for n in ("h", "c", "dgates", "dc_prev"):
         if n not in got:
             continue
-        ok, ek, ey, bound = accept(bf16, n, got[n], ref[n], yard[n])
-        oks, eks, bnds = per_row(bf16, n, got[n], ref[n], yard[n])
+        ok, ek, ey, bound = PR.whole(got[n], ref[n], yard[n], floor_of(bf16, n))
+        oks, eks, bnds = PR.per_group(got[n], ref[n], yard[n], floor_of(bf16, n))
         finite = bool(torch.isfinite(got[n].float()).all())
-        eys, scale = (yard[n].double() - ref[n].double()).abs().amax(1), ref[n].double().abs().amax(1)
-        need = torch.where(scale > 0, (eks - 2.0 * eys) / scale, torch.where(eks > 2.0 * eys, torch.full_like(eks, float("inf")), torch.zeros_like(eks)))
-        stats[n] = (ek, ey, max(ek / bound if bound > 0 else float(ek > 0), _share(eks, bnds)), max(0.0, float(need.max())))
+        need = PR.need_floor(eks, PR.group_error(yard[n], ref[n]), PR.group_scale(ref[n]))
+        stats[n] = (ek, ey, max(PR.whole_share(ek, bound), PR.share(eks, bnds)), need)
         if not (ok and finite):
             bad.append((n, "whole", ek, ey, bound, "finite" if finite else "NOT FINITE"))
         if not bool(oks.all()):
@@ -171,8 +143,7 @@ def judge(bf16, got, ref, yard):
 
 def stats_line(stats):
     """per output: kernel error, yardstick error, their ratio, the largest share of a bound used, the floor the rows need"""
-    return " | ".join(f"{n} {ek:.2e} {ey:.2e} {ek / ey if ey > 0 else (float('inf') if ek > 0 else 0.0):.2f} {share:.2f} {need:.1e}"
-                      for n, (ek, ey, share, need) in stats.items())
+    return " | ".join(PR.fmt_stat(n, s) for n, s in stats.items())
 
 
 # ------------------------------------------------------------------------------------------------------------------------- cases

@@ -5,7 +5,7 @@ into the library: torch ops only, on the CPU.
 
 Every operation has a REFERENCE (fp64 throughout, from the fp32 inputs as stored) and a YARDSTICK (the same formula in torch fp32: what
 the number format costs; it is not an oracle).  `plant` is not part of either: the planted arithmetic slips of the CPU test's rejection
-cases (PLANTS).  Acceptance of an output, per element (`judge`):
+cases (PLANTS).  Acceptance of an output, per element (pin_rule.per_element, the rule of tests/pin_rule.py):
 
     |kernel - fp64| <= 2 |yardstick - fp64| + floor * scale          floor: FLOOR["value"] = 2^-17, FLOOR["grad"] = 2^-15
 
@@ -61,65 +61,13 @@ import math
 
 import torch
 
+import pin_rule as PR
+
 FLOOR = {"value": 2.0 ** -17, "grad": 2.0 ** -15}
 PLANTS = ("mask_t", "gl_gamma", "cnt", "inside_only", "vin_lt", "no_half", "bias_eps", "no_bias1")
 FLT_MAX = 3.4028234663852886e38
 NAN, INF = float("nan"), float("inf")
 BAND = 2.0 ** -18
-
-# ---------------------------------------------------------------------------------------------------------------------------- rule
-
-
-def judge(kernel, ref, yard, floor, scale):
-    """the rule for every element -> (number of failures, index of the first or -1, (kernel error, yardstick error, largest share of a
-    bound used, the smallest floor under which every element would pass)).  `scale`: a tensor like ref, or a number."""
-    ref = ref.double().reshape(-1)
-    k, y = kernel.double().reshape(-1), yard.double().reshape(-1)
-    scale = (scale.double().reshape(-1) if isinstance(scale, torch.Tensor) else torch.full_like(ref, float(scale)))
-    fin = torch.isfinite(ref)
-    zero = torch.zeros_like(ref)
-    ek = torch.where(fin, (k - ref).abs(), zero)
-    ey = torch.where(fin, (y - ref).abs(), zero)
-    ey = torch.where(torch.isfinite(ey), ey, zero)                         # (a yardstick that left the finite range widens nothing)
-    bound = 2.0 * ey + floor * scale
-    same = (k == ref) | (torch.isnan(k) & torch.isnan(ref))
-    ok = torch.where(fin, ek <= bound, same)                               # NaN where the reference is finite: the comparison is false
-    ekf = torch.where(torch.isnan(ek), torch.full_like(ek, INF), ek)
-    share = torch.where(bound > 0, ekf / bound, torch.where(ekf > 0, torch.full_like(ek, INF), zero))
-    need = torch.where(scale > 0, (ekf - 2.0 * ey) / scale, torch.where(ekf > 2.0 * ey, torch.full_like(ek, INF), zero))
-    n_bad = int((~ok).sum())
-    first = int((~ok).nonzero()[0]) if n_bad else -1
-    if ref.numel() == 0:
-        return 0, -1, (0.0, 0.0, 0.0, 0.0)
-    return n_bad, first, (float(ekf.max()), float(ey.max()), float(share.max()), max(0.0, float(need.max())))
-
-
-def stat(name, s):
-    """one output of a printed line: kernel error, yardstick error, their ratio, largest share of a bound, the floor the elements need"""
-    ek, ey, share, need = s
-    return f"{name} {ek:.2e} {ey:.2e} {ek / ey if ey > 0 else (INF if ek > 0 else 0.0):.2f} {share:.2f} {need:.1e}"
-
-
-def merge(total, name, s):
-    t = total.get(name, (0.0, 0.0, 0.0, 0.0))
-    total[name] = tuple(max(a, b) for a, b in zip(t, s))
-
-
-def same_bits(a, b):
-    a, b = a.contiguous(), b.contiguous()
-    if a.dtype == torch.float32:
-        a, b = a.view(torch.int32), b.view(torch.int32)
-    elif a.dtype == torch.float64:
-        a, b = a.view(torch.int64), b.view(torch.int64)
-    return a.shape == b.shape and torch.equal(a, b)
-
-
-def _gen(*key):
-    s = 0
-    for k in key:
-        s = (s * 1000003 + (k if isinstance(k, int) else sum(ord(ch) * (i + 1) for i, ch in enumerate(str(k))))) % (2 ** 31 - 1)
-    return torch.Generator().manual_seed(s)
-
 
 # ----------------------------------------------------------------------------------------------------------------------------- GAE
 # catan_gae: ceil(N / 256) blocks of 256 lanes, one lane per column; k_adv_stats: ONE block whose lanes stride over the per-block
@@ -138,7 +86,7 @@ def edge_masks(T, N):
 
 def gae_inputs(T, N, regime):
     """-> rewards [T, N], values [T + 1, N], masks [T + 1, N], fp32"""
-    g = _gen("gae", T, N, regime)
+    g = PR.gen("gae", T, N, regime)
     r = (torch.rand(T, N, generator=g) < 0.01).float() * 500.0 * (1.0 - 2.0 * (torch.rand(T, N, generator=g) < 0.5).float())
     v = 150.0 + 50.0 * torch.randn(T + 1, N, generator=g)
     m = (torch.rand(T + 1, N, generator=g) > 0.01).float()
@@ -199,9 +147,9 @@ def gae_judge(c, got, label=""):
     T, N = c["T"], c["N"]
     bad, st = [], {}
     for n, y, rf in (("ret", c["yard_ret"], c["ref_ret"]), ("raw", c["yard_raw"], c["ref_raw"])):
-        if not same_bits(got[n], y):
+        if not PR.same_bits(got[n], y):
             bad.append((label, n, "not bit-equal to the fp32 recurrence", int((got[n] != y).sum())))
-        nb, first, st[n] = judge(got[n], rf, y, FLOOR["value"], rf.abs().clamp(min=1.0))
+        nb, first, st[n] = PR.per_element(got[n], rf, y, FLOOR["value"], rf.abs().clamp(min=1.0))
         if nb:
             bad.append((label, n, "against fp64", nb, first))
     s = [float(x) for x in got["stats"]]
@@ -230,7 +178,7 @@ def gae_judge_adv(c, adv, st, label="", name="adv"):
             bad.append((label, name, "a constant advantage does not normalise to exactly 0", float(adv.abs().max())))
         st[name] = (float(adv.abs().max()), 0.0, 0.0, 0.0)
         return bad
-    nb, first, st[name] = judge(adv, c["ref_adv"], c["yard_adv"], FLOOR["value"], c["ref_adv"].abs().clamp(min=1.0))
+    nb, first, st[name] = PR.per_element(adv, c["ref_adv"], c["yard_adv"], FLOOR["value"], c["ref_adv"].abs().clamp(min=1.0))
     if nb:
         bad.append((label, name, "against fp64", nb, first))
     return bad
@@ -284,7 +232,7 @@ def plant_positions(B):
 
 def loss_inputs(B, regime, use_norm):
     """-> {logp, old, adv, v, v_old, ret (fp32 [B]), planted (bool [B])}"""
-    g = _gen("loss", B, regime, int(use_norm))
+    g = PR.gen("loss", B, regime, int(use_norm))
     old = OLD0 + 0.4 * torch.randn(B, generator=g)
     d = 0.3 * torch.randn(B, generator=g)
     if regime == "onpolicy":
@@ -403,7 +351,7 @@ def loss_judge(c, got):
     bad, st = [], {}
     for i, (n, t) in enumerate((("action_loss", "ta"), ("value_loss", "tv"))):
         scale = float(ref[t].abs().mean())
-        nb, _, st[n] = judge(got["losses"][i:i + 1], ref["losses"][i:i + 1], yard["losses"][i:i + 1], FLOOR["value"], scale)
+        nb, _, st[n] = PR.per_element(got["losses"][i:i + 1], ref["losses"][i:i + 1], yard["losses"][i:i + 1], FLOOR["value"], scale)
         if nb:
             bad.append((n, float(got["losses"][i]), float(ref["losses"][i]), float(yard["losses"][i])))
     near_p, near_v = c["near"]["ratio"], c["near"]["vclip"] | c["near"]["l1l2"]
@@ -416,7 +364,7 @@ def loss_judge(c, got):
             if not bool(ok.all()):
                 bad.append((n, "near-boundary rows on neither branch", near.nonzero().flatten()[~ok].tolist()[:8]))
             k[near] = ref[n][near].float()                                 # (judged above)
-        nb, first, st[n] = judge(k, ref[n], yard[n], FLOOR["grad"], ref[n].abs())
+        nb, first, st[n] = PR.per_element(k, ref[n], yard[n], FLOOR["grad"], ref[n].abs())
         if nb:
             bad.append((n, f"{nb} rows, first {first}", float(got[n][first]), float(ref[n][first]), float(yard[n][first])))
     if c["regime"] == "onpolicy":
@@ -472,7 +420,7 @@ def to_threshold(grads):
 def adam_case(name, regime, max_norm):
     """-> {sizes, p0, m0, v0 (lists of fp32), steps0, grads [ADAM_STEPS][tensor] (fp32 or None), none_is_zero, max_norm}"""
     sizes = ADAM_LISTS[name]
-    g = _gen("adam", name, regime, 0 if max_norm is None else 1)
+    g = PR.gen("adam", name, regime, 0 if max_norm is None else 1)
     scale = {"unit": 0.05, "small": 1e-15, "large": 1e15, "zero": 0.05, "mixed": 1e-4, "threshold": 0.05, "none_skip": 0.05, "none_zero": 0.05}[regime]
     scales = [1e3 if (regime == "mixed" and i == LOUD_TENSOR) else scale for i in range(len(sizes))]
     steps0 = [step_count(i) for i in range(len(sizes))]
@@ -555,11 +503,11 @@ def adam_judge(c, ref, yard, k, got):
     for i in range(len(c["sizes"])):
         pscale = before[i].double().abs().clamp(min=HYPER["lr"])
         for n, scale in (("p", pscale), ("m", ref[k]["m"][i].abs()), ("v", ref[k]["v"][i].abs())):
-            nb, first, s = judge(got[n][i], ref[k][n][i], yard[k][n][i], FLOOR["grad"], scale)
-            merge(st, n, s)
+            nb, first, s = PR.per_element(got[n][i], ref[k][n][i], yard[k][n][i], FLOOR["grad"], scale)
+            PR.merge_stat(st, n, s)
             if nb:
                 bad.append((k, n, i, f"{nb} elements, first {first}", float(got[n][i][first]), float(ref[k][n][i][first]), float(yard[k][n][i][first])))
-    nb, _, st["norm"] = judge(torch.tensor([got["norm"]]), torch.tensor([ref[k]["norm"]], dtype=torch.float64), torch.tensor([yard[k]["norm"]]),
+    nb, _, st["norm"] = PR.per_element(torch.tensor([got["norm"]]), torch.tensor([ref[k]["norm"]], dtype=torch.float64), torch.tensor([yard[k]["norm"]]),
                               FLOOR["value"], ref[k]["norm"])
     if nb:
         bad.append((k, "norm", got["norm"], ref[k]["norm"], yard[k]["norm"]))

@@ -8,10 +8,12 @@ Every function has two modes.
                     comments and repeated at each function).  It shows what bf16 storage alone costs against the reference; it is
                     not an oracle.
 tests/test_te_reference_cpu.py holds the reference against autograd and against the module; tests/test_gpu_te_backward.py holds the
-kernels against the reference with `within_yardstick`."""
+kernels against the reference with `within_yardstick`: the rule of tests/pin_rule.py over a whole tensor, with the bf16 floor."""
 import math
 
 import torch
+
+from pin_rule import BF16_FLOOR, whole
 
 # catan_te_saves_t's fields in the struct's order (pointer i of the struct = entry i), with their widths
 TE_FIELDS = (("tiles64", 64), ("a0", 64), ("xin0", 64), ("xin1", 64), ("n1_0", 64), ("n1_1", 64), ("qkv0", 192), ("qkv1", 192), ("o0", 64), ("o1", 64),
@@ -131,14 +133,7 @@ def tile_encoder_ref(te, tiles, round_bf16=False):
     return out
 
 
+
 def within_yardstick(kernel, ref, yardstick):
-    """The acceptance rule of the per-kernel tests, for one output tensor -> (ok, kernel error, yardstick error, bound):
-        maxabs(kernel - ref) <= 2 * maxabs(yardstick - ref) + 2^-9 * maxabs(ref)
-    The factor 2 covers the different fp32 summation order inside MFMA and the atomics, which can turn a bf16 rounding the other way;
-    the floor is half a bf16 ulp of the tensor's scale, for tiny cases where the yardstick happens to land exact.  No element is
-    excluded; a NaN anywhere fails."""
-    ref = ref.double()
-    ek = float((kernel.double() - ref).abs().max())
-    ey = float((yardstick.double() - ref).abs().max())
-    bound = 2.0 * ey + 2.0 ** -9 * float(ref.abs().max())
-    return ek <= bound, ek, ey, bound
+    """pin_rule.whole with the floor of a bf16 output, half a bf16 ulp of the tensor's scale -> (ok, kernel error, yardstick error, bound)"""
+    return whole(kernel, ref, yardstick, BF16_FLOOR)

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import card_summary_reference as CS
+import pin_rule as PR
 
 ROWS = 240
 NONE7 = (None,) * 7
@@ -173,7 +174,7 @@ def _judged(c, yard):
     """the rules with `yard` in the kernel's place -> accepted?"""
     ok, _, _, _ = CS.accept_out(yard["out"], c["tok"]["out"], c["yard"]["out"])
     oks, _, _ = CS.per_list(yard["out"], c["tok"]["out"], c["yard"]["out"])
-    okp, _, _ = CS.accept_params(yard["dparams"], torch.zeros(CS.NPAR), c["tok"]["dparams"], c["yard"]["dparams"], c["cls"]["abs_terms"],
+    okp, _, _ = PR.accept_sum(yard["dparams"], torch.zeros(CS.NPAR), c["tok"]["dparams"], c["yard"]["dparams"], c["cls"]["abs_terms"],
                                  CS.bwd_depth(c["ids"].shape[0]))
     return ok and bool(oks.all()) and bool(okp.all())
 

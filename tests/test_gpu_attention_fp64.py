@@ -3,7 +3,7 @@ fp64, on every path of attn_dispatch (csrc/catan_abi.hip), through the C ABI (ca
 
 reference = tests/attention_reference.py: attention_ref in fp64 from the inputs as stored; yardstick = attention_yardstick in fp32 with a
 bf16 rounding where the kernel of the path rounds (its docstring places them).  Acceptance of an output tensor (out, dq, dk, dv):
-    bf16 paths: te_reference.within_yardstick, unchanged: maxabs(kernel - ref) <= 2 maxabs(yardstick - ref) + 2^-9 maxabs(ref)
+    bf16 paths: the rule of tests/pin_rule.py: maxabs(kernel - ref) <= 2 maxabs(yardstick - ref) + 2^-9 maxabs(ref)
     fp32 path : the same rule with the fp32 yardstick and the floor 2^-17 maxabs(ref) for out, 2^-15 maxabs(ref) for the gradients
 over the whole case AND for every sequence with that sequence's own yardstick error and scale (a wrong short sequence cannot hide behind
 a long one).  Nothing in a bound comes from the kernel.  Per case and output one `ATTN` line is printed (kernel error, yardstick error,
@@ -35,26 +35,19 @@ card lists go through catan_card_summary_*), so length 0 is not run.  The mask i
     unless their dO is zero - which is how the net uses a masked sequence (the padding's outputs are dropped).  So this rerun zeroes dO's
     rows >= len in both launches and then holds ALL of: out and dq rows < len, dk and dv rows < len bit-identical; dq, dk, dv rows >= len == 0.
   * lens = L everywhere equals the launch without lens bit for bit."""
-import ctypes as C
-
 import pytest
 import torch
 
 import attention_reference as A
+import guarded as G
+import pin_rule as PR
+from guarded import ptr as P, stream as _stream
+from pin_rule import same_bits
 
 pytestmark = pytest.mark.gpu
 
 GUARD_SEQ = 4
 SENTINEL = 0x5A5B
-NAN = float("nan")
-
-
-def P(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _takes_mfma(is_bf16, *tensors):
@@ -62,33 +55,19 @@ def _takes_mfma(is_bf16, *tensors):
     return is_bf16 and all(t is None or t.data_ptr() % 16 == 0 for t in tensors)
 
 
-def _alloc(path, n, seq, dtype):
-    """-> (whole, view): `view` = n elements that begin 8 bytes into `whole` on the valu_bf16 path (at its start otherwise) and are followed
-    by GUARD_SEQ sequences of `seq` elements"""
-    lead = 4 if path == "valu_bf16" else 0
-    whole = torch.empty(lead + n + GUARD_SEQ * seq, dtype=dtype, device="cuda")
-    assert whole.data_ptr() % 16 == 0
-    return whole, whole[lead:lead + n]
+def _lead(path):
+    """the view begins 8 bytes into its allocation on the valu_bf16 path, at its start otherwise"""
+    return 4 if path == "valu_bf16" else 0
 
 
 def _input(path, t):
-    whole, view = _alloc(path, t.numel(), t[0].numel(), t.dtype)
-    whole.fill_(NAN)
-    view.copy_(t.reshape(-1))
-    return whole, view
+    """t in front of GUARD_SEQ sequences of NaN"""
+    return G.guarded_input(t, GUARD_SEQ * t[0].numel(), _lead(path))
 
 
 def _output(path, n, seq, dtype):
-    whole, view = _alloc(path, n, seq, dtype)
-    whole.view(torch.int16).fill_(SENTINEL)
-    return whole, view
-
-
-def _margins_intact(whole, view):
-    lead = (view.data_ptr() - whole.data_ptr()) // whole.element_size()
-    w16 = whole.view(torch.int16)
-    k = whole.element_size() // 2
-    return bool((w16[:lead * k] == SENTINEL).all()) and bool((w16[(lead + view.numel()) * k:] == SENTINEL).all())
+    """n elements in front of GUARD_SEQ sequences of `seq` sentinel elements"""
+    return G.sentinel_output(n, dtype, GUARD_SEQ * seq, _lead(path), SENTINEL)
 
 
 def _launch(lib, path, qkv, lens, dout):
@@ -111,17 +90,9 @@ def _launch(lib, path, qkv, lens, dout):
     _lib.check(lib.catan_attention_fwd(P(q_d), P(lens_d), P(o_d), B, L, H, HD, is_bf16, _stream()))
     _lib.check(lib.catan_attention_bwd(P(q_d), P(lens_d), P(g_d), P(dq_d), B, L, H, HD, is_bf16, _stream()))
     torch.cuda.synchronize()
-    assert _margins_intact(whole_o, o_d) and _margins_intact(whole_dq, dq_d), (path, L, B, "a write outside the result")
+    assert G.intact(whole_o, o_d) and G.intact(whole_dq, dq_d), (path, L, B, "a write outside the result")
     dqkv = dq_d.view(B, L, 3, D).cpu()
     return {"out": o_d.view(B, L, D).cpu(), "dq": dqkv[:, :, 0].contiguous(), "dk": dqkv[:, :, 1].contiguous(), "dv": dqkv[:, :, 2].contiguous()}
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 # ------------------------------------------------------------------------------------------------------------------------ cases
@@ -162,9 +133,8 @@ def _judge(path, c, got):
         ok, ek, ey, bound = A.accept(path, o, got[o], ref[o], yard[o])
         oks, eks, bounds = A.per_sequence(path, o, got[o], ref[o], yard[o])
         finite = bool(torch.isfinite(got[o].float()).all())
-        ratio = torch.where(bounds > 0, eks / bounds, torch.where(eks > 0, torch.full_like(eks, float("inf")), torch.zeros_like(eks)))
-        print(f"ATTN {_name(path, c)} {o}: kernel {ek:.4e} yardstick {ey:.4e} ratio {ek / ey if ey > 0 else float('inf'):.3f} bound {bound:.4e} "
-              f"scale {float(ref[o].abs().max()):.4e} worst-seq {float(ratio.max()):.3f}")
+        print(f"ATTN {_name(path, c)} {o}: kernel {ek:.4e} yardstick {ey:.4e} ratio {PR.ratio(ek, ey, PR.INF):.3f} bound {bound:.4e} "
+              f"scale {float(ref[o].abs().max()):.4e} worst-seq {PR.share(eks, bounds):.3f}")
         if not (ok and finite):
             bad.append((_name(path, c), o, "whole", ek, ey, bound, "finite" if finite else "NOT FINITE"))
         if not bool(oks.all()):
@@ -188,17 +158,17 @@ def _mask_checks(lib, path, c, got):
         return
     # K and V behind the mask replaced
     alt = _launch(lib, path, A.replace_masked_rows(c, 1), c["lens"], c["dout"])
-    assert _same_bits(got["out"], alt["out"]) and _same_bits(got["dq"], alt["dq"]), (name, "masked K / V rows reach out or dq")
+    assert same_bits(got["out"], alt["out"]) and same_bits(got["dq"], alt["dq"]), (name, "masked K / V rows reach out or dq")
     for o in ("dk", "dv"):
-        assert _same_bits(got[o][keep], alt[o][keep]), (name, o, "masked K / V rows reach the rows < len")
+        assert same_bits(got[o][keep], alt[o][keep]), (name, o, "masked K / V rows reach the rows < len")
         assert bool((alt[o][~keep] == 0).all()), (name, o, "rows >= len are not zero")
     # ... and the Q rows behind it, with the gradient of their outputs zero
     dz = torch.where(keep, c["dout"], torch.zeros((), dtype=c["dout"].dtype))
     base = _launch(lib, path, c["qkv"], c["lens"], dz)
     alt = _launch(lib, path, A.replace_masked_rows(c, 2, ("q", "k", "v")), c["lens"], dz)
-    assert _same_bits(base["out"], got["out"]), (name, "out depends on dout")
+    assert same_bits(base["out"], got["out"]), (name, "out depends on dout")
     for o in A.OUTPUTS:
-        assert _same_bits(base[o][keep], alt[o][keep]), (name, o, "masked Q / K / V rows reach the rows < len")
+        assert same_bits(base[o][keep], alt[o][keep]), (name, o, "masked Q / K / V rows reach the rows < len")
         if o != "out":
             assert bool((base[o][~keep] == 0).all()) and bool((alt[o][~keep] == 0).all()), (name, o, "rows >= len are not zero")
         assert bool(torch.isfinite(alt[o].float()).all()), (name, o)
@@ -232,10 +202,10 @@ def test_attention_kernel_vs_fp64(hip_lib, path, L, H, HD, masked):
         elif regime == "unit":
             full = _launch(hip_lib, path, c["qkv"], torch.full((B,), L, dtype=torch.int32), c["dout"])
             for o in A.OUTPUTS:
-                assert _same_bits(got[o], full[o]), (_name(path, c), o, "lens = L differs from no lens")
+                assert same_bits(got[o], full[o]), (_name(path, c), o, "lens = L differs from no lens")
         if regime == "single":
             v0 = c["qkv"][:, 0, 2].reshape(B, 1, H * HD).expand(B, L, H * HD)
-            assert _same_bits(got["out"], v0), (_name(path, c), "one key: out is not V's row 0")
+            assert same_bits(got["out"], v0), (_name(path, c), "one key: out is not V's row 0")
             assert bool((got["dq"] == 0).all()) and bool((got["dk"] == 0).all()), (_name(path, c), "one key: dq, dk are not zero")
     assert not bad, bad
 

@@ -2,8 +2,8 @@
 k_card_pattern_sum) list by list against fp64, through the C ABI (catan_card_summary_fwd / _lookup / _bwd, catan_card_pattern_sum); only
 the two glue tests at the end go through nn_kernels / policy.
 
-reference = tests/card_summary_reference.py (its docstring has the operation, the yardstick's roundings and the rule):
-    out       within_floor(kernel, fp64 per token, yardstick, 2^-17) over the case AND per list
+reference = tests/card_summary_reference.py (its docstring has the operation and the yardstick's roundings; the rule is tests/pin_rule.py's):
+    out       pin_rule.whole(kernel, fp64 per token, yardstick, 2^-17) over the case AND pin_rule.per_group per list
     dparams   per parameter |kernel - (pre-fill + fp64)| <= 2 |yardstick - fp64| + bwd_depth 2^-24 (abs_terms + |pre-fill|)
     dpat      per word |kernel - fp64| <= sum_depth 2^-24 sum |term|; exact where dout holds small integers times 2^-4
     keys      == pattern_of(counts); lookup == forward bit for bit
@@ -15,47 +15,27 @@ the pattern-sum lines add the rows that provably went to global memory.  profile
 Buffers: the ids lie in a wider allocation of LIVE ids 1..5 (in front, behind the last row and in the pitch gap, and every position at or
 behind a list's length holds one too: read by mistake they change the counts); float inputs are followed by NaN; out, keys and dpat lie
 between sentinel margins; dparams is pre-filled with a non-constant pattern, which the backward must add to."""
-import ctypes as C
-
 import pytest
 import torch
 
 import card_summary_reference as CS
+import guarded as G
+import pin_rule as PR
+from guarded import NAN, ptr as P, stream as _stream
+from pin_rule import same_bits
 
 pytestmark = pytest.mark.gpu
 
 EPS = CS.EPS
 GUARD = 64                       # rows behind (and in front of) every buffer
 SENTINEL = 0x5A5B5A5B
-NAN = float("nan")
 NONE7 = (None,) * 7
 EINVAL = -1
-
-
-def P(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check(rc):
     from settlers_of_catan_rl_amd import _lib
     _lib.check(rc)
-
-
-def _pattern(n, k):
-    """a non-constant fp32 pre-fill of an accumulator (tests/test_gpu_te_backward.py's)"""
-    return torch.sin(torch.arange(n, device="cuda", dtype=torch.float32) * 0.37 + k) * 1.5 + 0.25 * k
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
 def _ids_buffer(ids, dtype, strided=False):
@@ -75,26 +55,17 @@ def _ids_buffer(ids, dtype, strided=False):
 
 def _float_input(t):
     """t followed by NaN"""
-    hold = torch.full((t.numel() + GUARD * CS.WIDTH,), NAN, device="cuda")
-    view = hold[:t.numel()].view(t.shape)
-    view.copy_(t)
-    return hold, view
+    hold, view = G.guarded_input(t.float(), GUARD * CS.WIDTH)
+    return hold, view.view(t.shape)
 
 
 def _between_sentinels(shape, dtype, fill=None):
-    n = 1
-    for s in shape:
-        n *= s
-    hold = torch.full((n + 2 * GUARD * CS.WIDTH,), SENTINEL, dtype=torch.int32, device="cuda")
-    view = hold[GUARD * CS.WIDTH:GUARD * CS.WIDTH + n].view(dtype).view(shape)
+    """`shape` elements of a 32-bit `dtype` with GUARD rows of the sentinel in front and behind -> (hold, view)"""
+    hold, view = G.sentinel_output(torch.Size(shape).numel(), dtype, GUARD * CS.WIDTH, GUARD * CS.WIDTH, SENTINEL)
+    view = view.view(shape)
     if fill is not None:
         view.fill_(fill)
     return hold, view
-
-
-def _margins_intact(hold, view):
-    n, lead = view.numel(), GUARD * CS.WIDTH
-    return bool((hold[:lead] == SENTINEL).all()) and bool((hold[lead + n:] == SENTINEL).all())
 
 
 class _Lists:
@@ -114,8 +85,8 @@ def _fwd(lib, b, want_keys=True, rows=None):
     hold_k, keys = _between_sentinels((rows,), torch.int32) if want_keys else (None, None)
     _check(lib.catan_card_summary_fwd(P(b.ids), b.esz, b.pitch, P(b.lens), P(b.params), EPS, P(out), P(keys), rows, _stream()))
     torch.cuda.synchronize()
-    assert _margins_intact(hold_o, out), "a write outside out"
-    assert keys is None or _margins_intact(hold_k, keys), "a write outside keys"
+    assert G.intact(hold_o, out), "a write outside out"
+    assert keys is None or G.intact(hold_k, keys), "a write outside keys"
     return out.clone(), None if keys is None else keys.clone()
 
 
@@ -124,7 +95,7 @@ def _lookup(lib, b, table):
     hold_t, tab = _float_input(table)
     _check(lib.catan_card_summary_lookup(P(b.ids), b.esz, b.pitch, P(b.lens), P(tab), P(b.params), EPS, P(out), b.rows, _stream()))
     torch.cuda.synchronize()
-    assert _margins_intact(hold_o, out), "a write outside out (lookup)"
+    assert G.intact(hold_o, out), "a write outside out (lookup)"
     return out.clone()
 
 
@@ -132,11 +103,11 @@ def _bwd(lib, b, dout, only=None, n_unk=None, k=1, into=None):
     """catan_card_summary_bwd alone into a pre-filled dparams (or on into `into`) -> (dparams, the pre-fill)"""
     hold_d, d = _float_input(dout)
     hold_g, g = _between_sentinels((CS.NPAR,), torch.float32)
-    g.copy_(_pattern(CS.NPAR, k) if into is None else into)
+    g.copy_(G.pattern(CS.NPAR, k) if into is None else into)
     pre = g.clone()
     _check(lib.catan_card_summary_bwd(P(b.ids), b.esz, b.pitch, P(b.lens), P(b.params), EPS, P(d), P(g), P(only), P(n_unk), b.rows, _stream()))
     torch.cuda.synchronize()
-    assert _margins_intact(hold_g, g), "a write outside dparams"
+    assert G.intact(hold_g, g), "a write outside dparams"
     return g.clone(), pre
 
 
@@ -146,7 +117,7 @@ def _pattern_sum(lib, keys, dout, replicas, n_unk):
     hold_p, dpat = _between_sentinels((replicas, CS.PATTERNS, CS.WIDTH), torch.float32, fill=0.0)
     _check(lib.catan_card_pattern_sum(P(keys), P(d), P(dpat), replicas, P(n_unk), rows, _stream()))
     torch.cuda.synchronize()
-    assert _margins_intact(hold_p, dpat), "a write outside dpat"
+    assert G.intact(hold_p, dpat), "a write outside dpat"
     return dpat.clone()
 
 
@@ -185,7 +156,7 @@ def _references(ids, lens, p, d):
 
 
 def _fmt(n, ek, ey, sh):
-    return f"{n} {ek:.2e} {ey:.2e} {ek / ey if ey > 0 else float('inf') if ek > 0 else 0.0:.2f} {sh:.3f}"
+    return f"{n} {ek:.2e} {ey:.2e} {PR.ratio(ek, ey):.2f} {sh:.3f}"
 
 
 def _judge_out(name, out, c, line):
@@ -194,7 +165,7 @@ def _judge_out(name, out, c, line):
     ok, ek, ey, bound = CS.accept_out(out, c["out"], c["yard_out"])
     oks, eks, bnds = CS.per_list(out, c["out"], c["yard_out"])
     finite = bool(torch.isfinite(out).all())
-    line.append(_fmt("out", ek, ey, max(ek / bound if bound > 0 else float(ek > 0), CS.share(eks, bnds))))
+    line.append(_fmt("out", ek, ey, max(PR.whole_share(ek, bound), PR.share(eks, bnds))))
     if not (ok and finite):
         bad.append((name, "out", "whole", ek, ey, bound, "finite" if finite else "NOT FINITE"))
     if not bool(oks.all()):
@@ -204,9 +175,9 @@ def _judge_out(name, out, c, line):
 
 
 def _judge_params(name, g, pre, ref, yard, abs_terms, depth, line, label="dparams"):
-    ok, err, bound = CS.accept_params(g, pre, ref, yard, abs_terms, depth)
+    ok, err, bound = PR.accept_sum(g, pre, ref, yard, abs_terms, depth)
     finite = bool(torch.isfinite(g).all())
-    line.append(_fmt(label, float(err.max()), float((yard - ref).abs().max()), CS.share(err, bound)) + f" depth {depth}")
+    line.append(_fmt(label, float(err.max()), float((yard - ref).abs().max()), PR.share(err, bound)) + f" depth {depth}")
     if finite and bool(ok.all()):
         return [], bound
     j = int((~ok).nonzero()[0])
@@ -249,7 +220,7 @@ def test_card_forward_and_lookup_vs_fp64(hip_lib, regime):
         name = f"fwd {regime} {kind} rows={rows} {str(dtype)[6:]} pitch={pitch}{' strided' if strided else ''}"
         out, keys = _fwd(hip_lib, b, want_keys=True)
         out_nokeys, _ = _fwd(hip_lib, b, want_keys=False)
-        assert _same_bits(out, out_nokeys), (name, "out depends on keys being asked for")
+        assert same_bits(out, out_nokeys), (name, "out depends on keys being asked for")
         line = []
         bad += _judge_out(name, out, c, line)
         want_keys = CS.pattern_of(c["cnt"]).to(torch.int32)
@@ -257,16 +228,16 @@ def test_card_forward_and_lookup_vs_fp64(hip_lib, regime):
         if kind == "patterns":
             k = torch.arange(CS.PATTERNS, device="cuda", dtype=torch.int32)
             assert torch.equal(keys[:-1], k[:-1]) and int(keys[-1]) == CS.PATTERNS - 1 - 1620
-            assert _same_bits(out, table), (name, "the live padding of the pattern lists changed a row")
+            assert same_bits(out, table), (name, "the live padding of the pattern lists changed a row")
         if rows >= 255 and kind == "mixed":
             assert bool((keys >= 0).any()) and bool((keys < 0).any()), name
         looked = _lookup(hip_lib, b, table)
-        assert _same_bits(looked, out), (name, "lookup differs from forward", int((_bits(looked) != _bits(out)).any(1).sum()))
+        assert same_bits(looked, out), (name, "lookup differs from forward", int((looked.view(torch.int32) != out.view(torch.int32)).any(1).sum()))
         empty = c["lens"] == 0
-        assert not bool(_bits(out[empty]).any()) and not bool(keys[empty].any()), (name, "an empty list")
+        assert not bool(out[empty].view(torch.int32).any()) and not bool(keys[empty].any()), (name, "an empty list")
         if regime == "flat":
             want = c["lens"].clamp(max=25).float()[:, None] * c["params"][CS.OFF_LB:][None, :] + 0.0      # (+ 0.0: an empty list's row is +0)
-            assert _same_bits(out, want), (name, "flat: out is not len * ln_b to the bit")
+            assert same_bits(out, want), (name, "flat: out is not len * ln_b to the bit")
         print(f"CARD {name}: " + " | ".join(line) + f" | keyed {int((keys >= 0).sum())} of {rows}")
     assert not bad, bad
 
@@ -287,13 +258,13 @@ def test_card_forward_exact_gates(hip_lib):
             shuffled = ids.gather(1, order)
             assert not torch.equal(shuffled, ids) and torch.equal(shuffled[pos.expand_as(ids) >= n], ids[pos.expand_as(ids) >= n])
             out2, keys2 = _fwd(hip_lib, _Lists(shuffled, lens, c["params"], dtype, strided))
-            assert _same_bits(out, out2) and torch.equal(keys, keys2), (regime, pitch, "a permuted prefix changed the result")
+            assert same_bits(out, out2) and torch.equal(keys, keys2), (regime, pitch, "a permuted prefix changed the result")
             other = torch.where(pos < n, ids, ids % 5 + 1)                   # another live id at every position behind the length
             assert bool((other != ids).any())
             out3, keys3 = _fwd(hip_lib, _Lists(other, lens, c["params"], dtype, strided))
-            assert _same_bits(out, out3) and torch.equal(keys, keys3), (regime, pitch, "the ids behind lens are read")
+            assert same_bits(out, out3) and torch.equal(keys, keys3), (regime, pitch, "the ids behind lens are read")
             sub, subk = _fwd(hip_lib, _Lists(ids[:257], lens[:257], c["params"], dtype, strided))
-            assert _same_bits(sub, out[:257]) and torch.equal(subk, keys[:257]), (regime, pitch, "the first 257 rows depend on the grid")
+            assert same_bits(sub, out[:257]) and torch.equal(subk, keys[:257]), (regime, pitch, "the first 257 rows depend on the grid")
         # single-class lists
         c = _case(regime, "single", 300, 25, grads=False)
         out, _ = _fwd(hip_lib, _Lists(c["ids"], c["lens"], c["params"]))
@@ -302,7 +273,7 @@ def test_card_forward_exact_gates(hip_lib):
         cls = c["cnt"].argmax(1)
         want = c["cnt"].amax(1).float()[:, None] * one[cls]
         assert int(c["cnt"].amax(1).max()) == 25
-        assert _same_bits(out, want), (regime, "a single-class list is not n times its count-1 output")
+        assert same_bits(out, want), (regime, "a single-class list is not n times its count-1 output")
 
 
 # ------------------------------------------------------------------------------------------------------------------------ pattern sum
@@ -360,7 +331,7 @@ def test_card_pattern_sum_vs_fp64(hip_lib, exact):
                 assert int(n_unk) == 7 + unkeyed, (name, int(n_unk), unkeyed)
                 assert bool(torch.isfinite(dpat).all()), (name, "a row with key -1 was read")
                 used = CS.sum_launch(rows, replicas)["workgroups"]
-                assert not bool(_bits(dpat[used:]).any()), (name, "a copy no workgroup writes is not zero")
+                assert not bool(dpat[used:].view(torch.int32).any()), (name, "a copy no workgroup writes is not zero")
                 fallback = CS.provable_fallback_rows(keys)
                 if exact:
                     assert torch.equal(dpat.double(), copies), (name, int((dpat.double() != copies).sum()))
@@ -368,10 +339,10 @@ def test_card_pattern_sum_vs_fp64(hip_lib, exact):
                     continue
                 depth = CS.sum_depth(rows, replicas, _most_shared(keys))
                 err = (dpat.double().sum(0) - total).abs()
-                bound = depth * CS.U * ab
-                print(f"CARD {name}: dpat {float(err.max()):.2e} share {CS.share(err, bound):.3f} depth {depth} | fallback rows >= {fallback}")
+                bound = PR.sum_bound(ab, depth)
+                print(f"CARD {name}: dpat {float(err.max()):.2e} share {PR.share(err, bound):.3f} depth {depth} | fallback rows >= {fallback}")
                 if not bool((err <= bound).all()):
-                    bad.append((name, float(err.max()), CS.share(err, bound)))
+                    bad.append((name, float(err.max()), PR.share(err, bound)))
     assert not bad, bad
 
 
@@ -411,14 +382,14 @@ def test_card_backward_skips_zero_rows(hip_lib, rows):
     c = _case("unit", "single", rows, 25)
     b = _Lists(c["ids"], c["lens"], c["params"])
     g, pre = _bwd(hip_lib, b, torch.zeros_like(c["dout"]), k=2)
-    assert _same_bits(g, pre), "an all-zero dout changed dparams"
+    assert same_bits(g, pre), "an all-zero dout changed dparams"
     cls = c["cnt"].argmax(1)
     for a in (0, 4):
         d = torch.where((cls == a)[:, None], c["dout"], torch.zeros_like(c["dout"]))
         g, pre = _bwd(hip_lib, b, d, k=3)
         S, S0 = g[:CS.OFF_V].view(4, 6, 6), pre[:CS.OFF_V].view(4, 6, 6)
         others = [x for x in range(6) if x != a]
-        assert _same_bits(S[:, others], S0[:, others]), (rows, a, "another query class's rows of dS were written")
+        assert same_bits(S[:, others], S0[:, others]), (rows, a, "another query class's rows of dS were written")
         ref = _references(c["ids"], c["lens"], c["params"], d)
         line = []
         bad, _ = _judge_params(f"bwd one-class a={a} rows={rows}", g, pre, ref["dparams"], ref["yard_dparams"], ref["abs_terms"], CS.bwd_depth(rows), line)
@@ -448,12 +419,12 @@ def test_card_backward_skip_list(hip_lib, rows):
         assert not bad, bad
     zero = torch.zeros((1,), dtype=torch.int32, device="cuda")
     g, pre = _bwd(hip_lib, b, torch.full_like(c["dout"], NAN), only=keys, n_unk=zero, k=5)
-    assert _same_bits(g, pre), "*n_unkeyed == 0 did not return at once"
-    dp = _pattern(CS.NPAR, 6)
+    assert same_bits(g, pre), "*n_unkeyed == 0 did not return at once"
+    dp = G.pattern(CS.NPAR, 6)
     rc = hip_lib.catan_card_summary_bwd(P(b.ids), b.esz, b.pitch, P(b.lens), P(b.params), EPS, P(c["dout"]), P(dp), None, P(zero), rows, _stream())
     assert rc == EINVAL and b"bad arguments" in hip_lib.catan_last_error()
     torch.cuda.synchronize()
-    assert _same_bits(dp, _pattern(CS.NPAR, 6))
+    assert same_bits(dp, G.pattern(CS.NPAR, 6))
 
 
 # ------------------------------------------------------------------------------------------------------------------------ composition
@@ -500,9 +471,9 @@ def test_card_backward_composition(hip_lib, kind):
         bad, bound_c = _judge_params(name, g, pre, ref["dparams"], ref["yard_dparams"], ref["abs_terms"], composition_depth(rows, replicas), line)
         gd, pred = _bwd(hip_lib, b, d, k=2)
         bad_d, bound_d = _judge_params(name, gd, pred, ref["dparams"], ref["yard_dparams"], ref["abs_terms"], CS.bwd_depth(rows), line, "direct")
-        assert _same_bits(pre, pred)
+        assert same_bits(pre, pred)
         gap = (g.double() - gd.double()).abs()
-        print(f"CARD {name}: " + " | ".join(line) + f" | composition - direct share {CS.share(gap, bound_c + bound_d):.3f} | unkeyed {unkeyed}")
+        print(f"CARD {name}: " + " | ".join(line) + f" | composition - direct share {PR.share(gap, bound_c + bound_d):.3f} | unkeyed {unkeyed}")
         assert not bad and not bad_d, (bad, bad_d)
         assert bool((gap <= bound_c + bound_d).all())
 
@@ -540,14 +511,14 @@ def test_card_summary_glue_vs_fp64(hip_lib, rows):
     CS.params_from_weights(*wy).backward(yard["dparams"].float())
     jac = torch.autograd.functional.jacobian(lambda *a: CS.params_from_weights(*a), tuple(t.detach().double() for t in w))
     reps = 8 if rows >= 32768 else 1
-    bound_p = composition_depth(rows, reps) * CS.U * cls["abs_terms"]
+    bound_p = PR.sum_bound(cls["abs_terms"], composition_depth(rows, reps))
     for nme, gk, gr, gy, j in zip(("emb", "wqkv", "bqkv", "wo", "bo", "ln_w", "ln_b"), got, ref["dweights"], [t.grad for t in wy], jac):
         carried = (j.abs() * bound_p.view(-1, *([1] * gr.dim()))).sum(0)
         err = (gk.double() - gr).abs()
         bound = 2.0 * (gy.double() - gr).abs() + carried
-        line.append(_fmt(nme, float(err.max()), float((gy.double() - gr).abs().max()), CS.share(err, bound)))
+        line.append(_fmt(nme, float(err.max()), float((gy.double() - gr).abs().max()), PR.share(err, bound)))
         if not bool((err <= bound).all()):
-            bad.append((name, nme, float(err.max()), CS.share(err, bound)))
+            bad.append((name, nme, float(err.max()), PR.share(err, bound)))
     print(f"CARD {name}: " + " | ".join(line))
     assert not bad, bad
 
@@ -569,7 +540,7 @@ def test_card_summary_table_is_rebuilt_after_a_weight_change(hip_lib):
         after = policy._card_summary(ids, lens, emb, mha, norm).clone()
     fresh = policy._card_summary(ids, lens, emb, mha, norm).detach()
     assert not torch.equal(before, after)
-    assert _same_bits(after, fresh)
+    assert same_bits(after, fresh)
     ref = CS.card_ref_tokens(ids.long(), lens, emb.weight, torch.cat([n.weight for n in mha.qkv_nets], 0), torch.cat([n.bias for n in mha.qkv_nets], 0),
                              mha.out_proj_net.weight, mha.out_proj_net.bias, norm.weight, norm.bias, norm.eps, None)
     from settlers_of_catan_rl_amd import nn_kernels

@@ -26,21 +26,15 @@ import pytest
 import torch
 
 import categorical_reference as CR
+import guarded as G
+from guarded import NAN, ptr as P, stream as _stream
+from pin_rule import merge_stat, same_bits
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 512                      # elements behind every buffer
 SENTINEL = 0x5A5B5A5B
-NAN = float("nan")
 OUTS = ("action", "logp", "entropy", "lse", "dlogits")
-
-
-def P(t, byte_offset=0):
-    return None if t is None else C.c_void_p(t.data_ptr() + byte_offset)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check(rc):
@@ -50,22 +44,15 @@ def _check(rc):
 
 def _input(t, guard):
     """-> (whole, view): t's elements followed by GUARD elements of `guard`"""
-    whole = torch.full((t.numel() + GUARD,), guard, dtype=t.dtype, device="cuda")
-    view = whole[:t.numel()]
-    view.copy_(t.reshape(-1))
-    return whole, view
+    return G.guarded_input(t, GUARD, guard=guard)
 
 
 def _output(n, dtype):
-    whole = torch.empty(n + GUARD, dtype=dtype, device="cuda")
-    whole.view(torch.int32).fill_(SENTINEL)
-    return whole, whole[:n]
+    return G.sentinel_output(n, dtype, GUARD, sentinel=SENTINEL)
 
 
 def _written_and_guarded(whole, view):
-    w = whole.view(torch.int32)
-    k = whole.element_size() // 4
-    return bool((w[view.numel() * k:] == SENTINEL).all()) and not bool((w[:view.numel() * k] == SENTINEL).any())
+    return G.intact(whole, view) and G.written(whole, view, SENTINEL)
 
 
 def _device(c):
@@ -136,21 +123,12 @@ def _launch_bits(lib, c, mode):
     return _finish((c["regime"], B, K, mode, "bits"), B, K, outs, True)
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
 def _merge(total, stats):
     for n, v in stats.items():
         if n == "tau":
             total[n] = max(total.get(n, 0.0), v)
         else:
-            t = total.get(n, (0.0, 0.0, 0.0, 0.0))
-            total[n] = tuple(max(x, y) for x, y in zip(t, v))
+            merge_stat(total, n, v)
 
 
 def float_cases(K):
@@ -222,7 +200,7 @@ def test_categorical_bits_kernel_vs_fp64(hip_lib, K):
             _merge(total, stats)
             flt = _launch(hip_lib, c, mode, False)
             for n in OUTS:
-                assert _same_bits(got[n], flt[n]), (regime, B, K, n0n1, with_idx, mode, n, "the bits form and the float form differ")
+                assert same_bits(got[n], flt[n]), (regime, B, K, n0n1, with_idx, mode, n, "the bits form and the float form differ")
         print(f"CAT bits K={K} B={B} {regime} segs={n0n1} idx={int(with_idx)} given_ld={given_ld}: " + CR.stats_line(total))
     assert not bad, bad[:12]
 
@@ -241,11 +219,11 @@ def test_rows_do_not_depend_on_the_grid(hip_lib, K):
         big = _launch(hip_lib, c, mode, True)
         mid = _launch(hip_lib, _rows_of(c, 0, 257), mode, False)
         for n in OUTS:
-            assert _same_bits(big[n][:257], mid[n]), (K, mode, n, "the first 257 rows depend on the grid")
+            assert same_bits(big[n][:257], mid[n]), (K, mode, n, "the first 257 rows depend on the grid")
         for r in (0, 255, 256):
             one = _launch(hip_lib, _rows_of(c, r, r + 1), mode, True)
             for n in OUTS:
-                assert _same_bits(one[n], mid[n][r:r + 1]), (K, mode, n, r, "a row alone differs from the row in a launch")
+                assert same_bits(one[n], mid[n][r:r + 1]), (K, mode, n, r, "a row alone differs from the row in a launch")
 
 
 def test_abi_refusals_launch_nothing(hip_lib):

@@ -2,7 +2,7 @@
 (catan_head_fwd, catan_head_fwd_entropy) and chained (catan_head_chain, catan_head_chain_ex through nn_kernels.heads_chain).
 
 reference = tests/heads_reference.py in fp64 from the same inputs; yardstick = the same in fp32 with a bf16 rounding where the kernel's
-header rounds.  Acceptance of a value (te_reference.within_yardstick, its factor 2 and 2^-9 floor kept so that both files mean the same):
+header rounds.  Acceptance of a value (the rule of tests/pin_rule.py over the whole tensor, with the floor of a bf16 output):
     maxabs(kernel - reference) <= 2 * maxabs(yardstick - reference) + 2^-9 * maxabs(reference)
 Nothing in a bound comes from the kernel's output.  Per case and output one `HEADS` line is printed (kernel error, yardstick error,
 ratio, bound, scale): profiles/heads_kernel_tests.txt is that output.
@@ -22,44 +22,30 @@ it did not use (the (257, 256) pairs of heads_reference.head_case cancel only as
 reach +-100, are judged as a group of their own: inside the others' bound their scale alone would be a floor of 0.2.
 Reference and yardstick of the per-head cases are computed on the CPU, where the inputs are drawn: the ambiguous rows are then the
 very rows tests/test_heads_reference_cpu.py counted."""
-import ctypes as C
-
 import pytest
 import torch
 
+import guarded as G
 import heads_reference as H
-from te_reference import within_yardstick
+import pin_rule as PR
+from guarded import NAN, ptr as P, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 64                       # rows behind every buffer: NaN behind the inputs, the sentinel behind the outputs
 SENTINEL = 0x5A5B
 AMBIGUOUS_CAP = 0.15
-NAN = float("nan")
-
-
-def P(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _out_buffer(rows, dtype):
-    buf = torch.empty(rows + GUARD, dtype=dtype, device="cuda")
-    buf.view(torch.int16).fill_(SENTINEL)
-    return buf
-
-
-def _guard_intact(buf, rows):
-    return bool((buf[rows:].view(torch.int16) == SENTINEL).all())
+    """-> (whole, view): one element per row in front of GUARD sentinel rows"""
+    return G.sentinel_output(rows, dtype, GUARD, sentinel=SENTINEL)
 
 
 def _record(case, name, kernel, ref, yard):
-    ok, ek, ey, bound = within_yardstick(kernel, ref, yard)
+    ok, ek, ey, bound = PR.whole(kernel, ref, yard, PR.BF16_FLOOR)
     finite = bool(torch.isfinite(kernel).all())
-    print(f"HEADS {case} {name}: kernel {ek:.4e} yardstick {ey:.4e} ratio {ek / ey if ey > 0 else float('inf'):.3f} bound {bound:.4e} scale {float(ref.abs().max()):.4e}")
+    print(f"HEADS {case} {name}: kernel {ek:.4e} yardstick {ey:.4e} ratio {PR.ratio(ek, ey, PR.INF):.3f} bound {bound:.4e} scale {float(ref.abs().max()):.4e}")
     return [] if (ok and finite) else [(case, name, ek, ey, bound, "finite" if finite else "NOT FINITE")]
 
 
@@ -103,20 +89,18 @@ def _run_head(L, c, rows, sampled, entropy, windowed):
         cond[:rows, :ncond] = c["cond"][:rows].cuda()
     u = None
     if sampled:
-        u = torch.full((rows + GUARD,), NAN, dtype=torch.float32, device="cuda")
-        u[:rows] = c["u"][:rows].cuda()
-    wts = torch.cat([c["wts"].cuda(), torch.full((1024,), NAN, dtype=torch.bfloat16, device="cuda")])       # (the packs end in NaN too)
-    vec = torch.cat([c["vec"].cuda(), torch.full((GUARD,), NAN, dtype=torch.float32, device="cuda")])
-    action, logp = _out_buffer(rows, torch.int64), _out_buffer(rows, torch.float32)
-    ent = _out_buffer(rows, torch.float32) if entropy else None
+        u = G.guarded_input(c["u"][:rows], GUARD)[0]
+    wts, vec = G.guarded_input(c["wts"], 1024)[0], G.guarded_input(c["vec"], GUARD)[0]            # (the packs end in NaN too)
+    (hold_a, action), (hold_l, logp) = _out_buffer(rows, torch.int64), _out_buffer(rows, torch.float32)
+    hold_e, ent = _out_buffer(rows, torch.float32) if entropy else (None, None)
     head = (P(pre_v), pre.stride(0), P(cond), cond.stride(0) if ncond else 0, ncond, P(wts), P(vec), H.EPS, K, P(mask_v), mask.stride(0), P(u), P(action), P(logp))
     if entropy:
         _lib.check(L.catan_head_fwd_entropy(*head, P(ent), rows, _stream()))
     else:
         _lib.check(L.catan_head_fwd(*head, rows, _stream()))
     torch.cuda.synchronize()
-    assert _guard_intact(action, rows) and _guard_intact(logp, rows) and (ent is None or _guard_intact(ent, rows)), (K, ncond, rows, sampled, entropy, windowed)
-    return action[:rows].cpu(), logp[:rows].cpu(), None if ent is None else ent[:rows].cpu()
+    assert G.intact(hold_a, action) and G.intact(hold_l, logp) and (ent is None or G.intact(hold_e, ent)), (K, ncond, rows, sampled, entropy, windowed)
+    return action.cpu(), logp.cpu(), None if ent is None else ent.cpu()
 
 
 def _check_values(case, c, ref, yard, is_uf, action, logp, ent):
@@ -161,7 +145,7 @@ def _check_sampled(case, c, ref, yard, is_uf, action, u, mask=None):
     for tag, rows in (("", ~is_uf), (" underflow rows", is_uf)):
         if not bool(rows.any()):
             continue
-        tau, ey = H.yard_bound(ref["cdf"][rows], yard["cdf"][rows])
+        tau, ey = PR.whole_bound(ref["cdf"][rows], yard["cdf"][rows], PR.BF16_FLOOR)
         print(f"HEADS {case}{tag} cdf: yardstick {ey:.4e} bound {tau:.4e}")
         a, uu = action[rows], u[rows].double()
         upper = cdf[rows].gather(1, a[:, None]).squeeze(1)
@@ -288,7 +272,7 @@ def _chain_eval_rules(case, e, yard_e, A, u, deterministic):
         short = z.gather(1, best[:, None]).squeeze(1) - z.gather(1, a[:, None]).squeeze(1)
         assert bool((short[amb] <= 2 * delta).all()), name
         return float(amb.float().sum() / rows.float().sum().clamp(min=1))
-    tau, _ = H.yard_bound(e["cdf"][rows], yard_e["cdf"][rows])
+    tau, _ = PR.whole_bound(e["cdf"][rows], yard_e["cdf"][rows], PR.BF16_FLOOR)
     cdf = e["cdf"].double()
     upper = cdf.gather(1, a[:, None]).squeeze(1)
     lower = torch.where(a > 0, cdf.gather(1, (a - 1).clamp(min=0)[:, None]).squeeze(1), torch.zeros_like(upper))

@@ -1,7 +1,7 @@
 """GPU: the LayerNorm kernels of csrc/catan_nn.hip (k_ln_fwd / k_ln_bwd, k_lnw_fwd / k_lnw_bwd, k_lnr_fwd / k_lnr_bwd) row by row against
 fp64 on every path of ln_dispatch (csrc/catan_abi.hip), through the C ABI (catan_layer_norm_fwd / catan_layer_norm_bwd), with relu 0 and 1.
 
-reference = tests/layer_norm_reference.py (its docstring has the formulas, the yardstick's roundings and the rule):
+reference = tests/layer_norm_reference.py (its docstring has the formulas and the yardstick's roundings; the rule is tests/pin_rule.py's):
     y, dx   maxabs(kernel - fp64) <= 2 maxabs(yardstick - fp64) + floor maxabs(fp64), floor 2^-9 (bf16) / 2^-17 for y, 2^-15 for dx (fp32, the
             attention suite's), over the whole case AND for every row with that row's own yardstick error and scale
     dw, db  per column: |kernel - fp64| <= 2 |yardstick - fp64| + depth 2^-24 (sum_r |term| + |pre-fill|), depth = launch_depth
@@ -30,64 +30,42 @@ path agree within the sum of their bounds.
 
 Last, the autograd functions nn_kernels builds on these entry points (_SmallLayerNorm, _PreNorm): what autograd returns for x, w and b
 against torch's own layer_norm differentiated in fp64, under the same rule (_judge_function)."""
-import ctypes as C
-
 import pytest
 import torch
 
+import guarded as G
 import layer_norm_reference as LN
+import pin_rule as PR
+from guarded import ptr as P, stream as _stream
+from pin_rule import same_bits
 
 pytestmark = pytest.mark.gpu
 
 EPS = LN.EPS
 GUARD = 64                       # rows behind every row-major buffer
 SENTINEL = 0x5A5B
-NAN = float("nan")
 OFFSET_BELOW = 5000
 
 
-def P(t):
-    return C.c_void_p(t.data_ptr())
+def _margins(mis, D):
+    """-> (lead, tail): the view begins one element into the allocation on the misaligned path (at its start otherwise) and is followed
+    by GUARD rows (and 8 elements more on the misaligned path)"""
+    return (1, GUARD * D + 8) if mis else (0, GUARD * D)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _pattern(n, k):
-    """a non-constant fp32 pre-fill of an accumulator (tests/test_gpu_te_backward.py's)"""
-    return torch.sin(torch.arange(n, device="cuda", dtype=torch.float32) * 0.37 + k) * 1.5 + 0.25 * k
-
-
-def _alloc(mis, rows, D, dtype):
-    """-> (whole, view): `view` = rows * D elements that begin one element into `whole` on the misaligned path (at its start otherwise)
-    and are followed by GUARD rows"""
-    lead = 1 if mis else 0
-    whole = torch.empty(lead + (rows + GUARD) * D + (8 if mis else 0), dtype=dtype, device="cuda")
-    assert whole.data_ptr() % 16 == 0
-    view = whole[lead:lead + rows * D]
+def _placed(mis, whole, view):
     assert view.data_ptr() % 16 == (whole.element_size() if mis else 0)
     return whole, view
 
 
 def _input(mis, t):
-    whole, view = _alloc(mis, t.shape[0], t.shape[1], t.dtype)
-    whole.fill_(NAN)
-    view.copy_(t.reshape(-1))
-    return whole, view
+    lead, tail = _margins(mis, t.shape[1])
+    return _placed(mis, *G.guarded_input(t, tail, lead))
 
 
 def _output(mis, rows, D, dtype):
-    whole, view = _alloc(mis, rows, D, dtype)
-    whole.view(torch.int16).fill_(SENTINEL)
-    return whole, view
-
-
-def _margins_intact(whole, view):
-    lead = (view.data_ptr() - whole.data_ptr()) // whole.element_size()
-    w16 = whole.view(torch.int16)
-    k = whole.element_size() // 2
-    return bool((w16[:lead * k] == SENTINEL).all()) and bool((w16[(lead + view.numel()) * k:] == SENTINEL).all())
+    lead, tail = _margins(mis, D)
+    return _placed(mis, *G.sentinel_output(rows * D, dtype, tail, lead, SENTINEL))
 
 
 def _launch(lib, mis, x, w, b, dy, relu):
@@ -103,36 +81,22 @@ def _launch(lib, mis, x, w, b, dy, relu):
     if dy is not None:
         hold_g, g_d = _input(mis, dy)
         whole_dx, dx_d = _output(mis, rows, D, x.dtype)
-        dw, db = _pattern(D, 1), _pattern(D, 2)
+        dw, db = G.pattern(D, 1), G.pattern(D, 2)
         out["dw0"], out["db0"] = dw.clone(), db.clone()
         _lib.check(lib.catan_layer_norm_bwd(P(x_d), P(w), P(b), P(g_d), P(dx_d), P(dw), P(db), rows, D, EPS, relu, is_bf16, _stream()))
     torch.cuda.synchronize()
-    assert _margins_intact(whole_y, y_d), (mis, rows, D, "a write outside y")
+    assert G.intact(whole_y, y_d), (mis, rows, D, "a write outside y")
     out["y"] = y_d.view(rows, D).clone()
     if dy is not None:
-        assert _margins_intact(whole_dx, dx_d), (mis, rows, D, "a write outside dx")
+        assert G.intact(whole_dx, dx_d), (mis, rows, D, "a write outside dx")
         out["dx"], out["dw"], out["db"] = dx_d.view(rows, D).clone(), dw, db
     return out
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _share(err, bound):
-    """the largest err / bound (inf where a bound of 0 is exceeded, 0 where both are 0)"""
-    r = torch.where(bound > 0, err / bound, torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    return float(r.max())
 
 
 def _judge(name, bf16, got, ref, yard, depth, note=""):
     """the rule over the case, per row and per column; one LN line -> (failures, {output: whole-case bound})"""
     bad, bounds, line = [], {}, []
-    fmt = lambda n, ek, ey, share: f"{n} {ek:.2e} {ey:.2e} {ek / ey if ey > 0 else float('inf'):.2f} {share:.2f}"
+    fmt = lambda n, ek, ey, share: f"{n} {ek:.2e} {ey:.2e} {PR.ratio(ek, ey, PR.INF):.2f} {share:.2f}"
     for n in ("y", "dx"):
         if n not in got:
             continue
@@ -140,7 +104,7 @@ def _judge(name, bf16, got, ref, yard, depth, note=""):
         oks, eks, bnds = LN.per_row(bf16, n, got[n], ref[n], yard[n])
         finite = bool(torch.isfinite(got[n].float()).all())
         bounds[n] = bound
-        line.append(fmt(n, ek, ey, max(ek / bound if bound > 0 else float(ek > 0), _share(eks, bnds))))
+        line.append(fmt(n, ek, ey, max(PR.whole_share(ek, bound), PR.share(eks, bnds))))
         if not (ok and finite):
             bad.append((name, n, "whole", ek, ey, bound, "finite" if finite else "NOT FINITE"))
         if not bool(oks.all()):
@@ -149,16 +113,14 @@ def _judge(name, bf16, got, ref, yard, depth, note=""):
     for n, a in (("dw", "aw"), ("db", "ab")):
         if n not in got:
             continue
-        pre = got[n + "0"]
-        ek = (got[n].double() - (pre.double() + ref[n])).abs()
+        oks, ek, bnd = PR.accept_sum(got[n], got[n + "0"], ref[n], yard[n], ref[a], depth)
         ey = (yard[n].double() - ref[n]).abs()
-        bnd = LN.column_bound(yard[n], ref[n], ref[a], pre, depth)
         finite = bool(torch.isfinite(got[n]).all())
         bounds[n] = bnd
-        line.append(fmt(n, float(ek.max()), float(ey.max()), _share(ek, bnd)))
-        if not (finite and bool((ek <= bnd).all())):
-            j = int((~(ek <= bnd)).nonzero()[0]) if finite else -1
-            bad.append((name, n, f"{int((~(ek <= bnd)).sum())} columns, first {j}", float(ek[j]), float(bnd[j]), "finite" if finite else "NOT FINITE"))
+        line.append(fmt(n, float(ek.max()), float(ey.max()), PR.share(ek, bnd)))
+        if not (finite and bool(oks.all())):
+            j = int((~oks).nonzero()[0]) if finite else -1
+            bad.append((name, n, f"{int((~oks).sum())} columns, first {j}", float(ek[j]), float(bnd[j]), "finite" if finite else "NOT FINITE"))
     print(f"LN {name}: " + " | ".join(line) + note)
     return bad, bounds
 
@@ -167,7 +129,7 @@ def _exact_row_checks(name, c, relu, got):
     """the planted rows: y = relu?(b) as stored, to the bit"""
     want = (c["b"].clamp_min(0.0) if relu else c["b"]).to(got["y"].dtype)
     for r in c["exact_rows"]:
-        assert _same_bits(got["y"][r], want), (name, r, "an exact row's y is not relu?(b) to the bit")
+        assert same_bits(got["y"][r], want), (name, r, "an exact row's y is not relu?(b) to the bit")
 
 
 def _run_case(lib, align, c, relu, fwd_only):
@@ -220,7 +182,7 @@ def test_layer_norm_kernel_vs_fp64(hip_lib, align, D, dtype):
                     sub = _launch(hip_lib, mis, c["x"][:n].contiguous(), c["w"], c["b"], None if dyr is None else dyr[:n].contiguous(), relu)
                     for o in ("y", "dx"):
                         if o in sub:
-                            assert _same_bits(sub[o], got[o][:n]), (name, o, f"the first {n} rows depend on the grid")
+                            assert same_bits(sub[o], got[o][:n]), (name, o, f"the first {n} rows depend on the grid")
         del c
     # relu = 1 where no pre-activation is <= 0
     for rows in sorted({r for r, f in LN.path_rows(align, D, dtype) if not f})[2:5]:
@@ -230,7 +192,7 @@ def test_layer_norm_kernel_vs_fp64(hip_lib, align, D, dtype):
         a0 = _launch(hip_lib, mis, c["x"], c["w"], bpos, c["dy"], 0)
         a1 = _launch(hip_lib, mis, c["x"], c["w"], bpos, c["dy"], 1)
         for o in ("y", "dx"):
-            assert _same_bits(a0[o], a1[o]), (align, D, dtype, rows, o, "relu = 1 with every pre-activation > 0 differs from relu = 0")
+            assert same_bits(a0[o], a1[o]), (align, D, dtype, rows, o, "relu = 1 with every pre-activation > 0 differs from relu = 0")
     # every row all-zero: dw keeps its pre-fill to the bit, db takes exactly the gated dy (its yardstick is exact, so the column bound is
     # the summation bound alone), and with relu the columns where b == 0 decide `<=` against `<`
     for rows in (edge + 1, 257) if align != "lnr" else (4097,):
@@ -240,7 +202,7 @@ def test_layer_norm_kernel_vs_fp64(hip_lib, align, D, dtype):
         for relu in (0, 1):
             name, got, dyr, b, _ = _run_case(hip_lib, align, c, relu, False)
             bad += b
-            assert _same_bits(got["dw"], got["dw0"]), (name, "all-zero rows changed dw")
+            assert same_bits(got["dw"], got["dw0"]), (name, "all-zero rows changed dw")
             assert torch.equal(dyr, c["dy"]), (name, "an exact row's dy was zeroed")
     assert not bad, bad
 
@@ -344,7 +306,7 @@ def test_pre_norm_function_vs_torch_fp64(hip_lib, rows, dtype):
         x = c["x"].clone().requires_grad_()
         assert nn_kernels.pre_norm_supported(x, ln)
         y, res = nn_kernels.pre_norm(x, ln)
-        assert _same_bits(res.detach(), c["x"])
+        assert same_bits(res.detach(), c["x"])
         outs, grads = zip(*[p for p, used in (((y, c["dy"]), use_y), ((res, dres), use_res)) if used])
         dx, dw, db = torch.autograd.grad(outs, (x, ln.weight, ln.bias), grads, allow_unused=True)
         return y.detach(), dx, dw, db
@@ -354,7 +316,7 @@ def test_pre_norm_function_vs_torch_fp64(hip_lib, rows, dtype):
     y, dx, dw, db = run(True, False)
     _judge_function(name + " norm only", c, 0, c["dy"], {"y": y, "dx": dx, "dw": dw, "db": db})
     _, dx, dw, db = run(False, True)
-    assert _same_bits(dx, dres), (name, "only the residual stream used: x's gradient is not dres")
+    assert same_bits(dx, dres), (name, "only the residual stream used: x's gradient is not dres")
     assert all(g is None or not bool(g.any()) for g in (dw, db))
     # the backward's own branches for a missing gradient
     out = nn_kernels._PreNorm.backward(None, None, dres)

@@ -18,27 +18,20 @@ instantiation test_cases_cover_every_instantiation asserts).
 Buffers: every input lies in front of 64 guard rows of NaN (W and bias: a NaN tail); y, dw, db and the workspace lie between sentinel
 margins that must be intact afterwards; dw and db are pre-filled with a non-constant pattern (integer-valued in the exact regime); a
 windowed dw is a column window of a wider pre-filled matrix whose other columns must keep their bits."""
-import ctypes as C
-
 import pytest
 import torch
 
+import guarded as G
 import linear_reference as L
+from guarded import NAN, ptr as P, stream as _stream
+from pin_rule import same_bits
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 64
 SENTINEL = 0x5A5B
-NAN = float("nan")
+MARGIN = 512                     # elements of sentinel in front of and behind every output: a multiple of 16 bytes
 BF = torch.bfloat16
-
-
-def P(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check(rc):
@@ -48,41 +41,18 @@ def _check(rc):
 
 def _guarded(t, tail=None):
     """a copy of `t` that is followed by NaN: GUARD rows of it (a matrix) or GUARD elements (a vector) -> (whole, view)"""
-    n = t.numel()
     tail = GUARD * (t.shape[-1] if t.dim() == 2 else 1) if tail is None else tail
-    whole = torch.full((n + tail + 8,), NAN, dtype=t.dtype, device="cuda")
-    assert whole.data_ptr() % 16 == 0
-    view = whole[:n]
-    view.copy_(t.reshape(-1))
-    return whole, view
+    return G.guarded_input(t, tail + 8)
 
 
 def _between_sentinels(n, dtype, fill=None):
     """n elements between two sentinel margins (each a multiple of 16 bytes) -> (whole, view); `fill` [n] is copied in, otherwise the
     view holds the sentinel too (an element the kernel leaves unwritten then shows as 1.5e13)"""
-    lead = 512
-    whole = torch.empty(lead + n + lead, dtype=dtype, device="cuda")
-    whole.view(torch.int16).fill_(SENTINEL)
-    view = whole[lead:lead + n]
+    whole, view = G.sentinel_output(n, dtype, MARGIN, MARGIN, SENTINEL)
     assert view.data_ptr() % 16 == 0
     if fill is not None:
         view.copy_(fill.reshape(-1))
     return whole, view
-
-
-def _margins_intact(whole, view):
-    lead = (view.data_ptr() - whole.data_ptr()) // whole.element_size()
-    k = whole.element_size() // 2
-    w16 = whole.view(torch.int16)
-    return bool((w16[:lead * k] == SENTINEL).all()) and bool((w16[(lead + view.numel()) * k:] == SENTINEL).all())
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _mx(a, b):
@@ -128,7 +98,7 @@ class _FwdBuffers:
         else:
             _check(lib.catan_linear_rows_fused(P(self.x), P(self.W), b, P(y), rows, c["K"], c["N"], P(self.aux) if mode >= 2 else None, mode, _stream()))
         torch.cuda.synchronize()
-        assert _margins_intact(whole, y), (c["K"], c["N"], rows, mode, "a write outside y")
+        assert G.intact(whole, y), (c["K"], c["N"], rows, mode, "a write outside y")
         return y.view(rows, c["N"]).clone()
 
 
@@ -143,10 +113,10 @@ def _forward_case(lib, K, N, rows, regime, lin):
         b, ek, ey, sh = L.judge_forward(y, c["x"], c["W"], c["b"] if bias else None, c["aux"], mode, regime, terms=terms[bias])
         lin.add(f"rows K={K} N={N} {regime}", "y", f"rows={rows} mode={mode} bias={int(bias)}", ek, ey, sh, b)
     if (2, True) in ys:                    # mode 2 = mode 0 followed by a separate bf16 add
-        assert _same_bits(ys[(2, True)], ys[(0, True)] + c["aux"]), (K, N, rows, regime, "mode 2 differs from mode 0 + a separate bf16 add")
+        assert same_bits(ys[(2, True)], ys[(0, True)] + c["aux"]), (K, N, rows, regime, "mode 2 differs from mode 0 + a separate bf16 add")
     if rows == L.FWD_FULL_GRID + 1:        # rows do not depend on the grid
         for mode, bias in L.fwd_modes(N, with_nobias=False):
-            assert _same_bits(buf.launch(lib, mode, bias, rows=65), ys[(mode, bias)][:65]), (K, N, mode, "the first 65 rows depend on the grid")
+            assert same_bits(buf.launch(lib, mode, bias, rows=65), ys[(mode, bias)][:65]), (K, N, mode, "the first 65 rows depend on the grid")
 
 
 @pytest.mark.parametrize("K,N", L.FWD_CASES, ids=[f"K{K}-N{N}" for K, N in L.FWD_CASES])
@@ -197,8 +167,8 @@ def _wgrad_alone(lib, xv, gv, rows, I, O, dw0, db0):
     hb, db = _between_sentinels(O, torch.float32, db0) if db0 is not None else (None, None)
     _check(lib.catan_linear_wgrad(P(xv), P(gv), P(dw), P(db), rows, I, O, _stream()))
     torch.cuda.synchronize()
-    assert _margins_intact(hw, dw), (rows, I, O, "a write outside dw")
-    assert db is None or _margins_intact(hb, db), (rows, I, O, "a write outside db")
+    assert G.intact(hw, dw), (rows, I, O, "a write outside dw")
+    assert db is None or G.intact(hb, db), (rows, I, O, "a write outside db")
     return dw.view(O, I).clone(), None if db is None else db.clone()
 
 
@@ -267,11 +237,11 @@ def test_linear_wgrad_grouped_vs_fp64(hip_lib, regime):
         c, hx, xv, hg, gv, dw0, db0, hw, dw, hb, db = keep[k]
         I, O, rows, ld, col0 = p["I"], p["O"], p["rows"], p["ld"] or p["I"], p["col0"]
         name = f"grouped #{k} I={I} O={O} ld={p['ld']} col0={col0} {regime}"
-        assert _margins_intact(hw, dw) and (db is None or _margins_intact(hb, db)), (name, "a write outside dw or db")
+        assert G.intact(hw, dw) and (db is None or G.intact(hb, db)), (name, "a write outside dw or db")
         dw = dw.view(O, ld)
         outside = torch.ones(ld, dtype=torch.bool, device="cuda")
         outside[col0:col0 + I] = False
-        assert _same_bits(dw[:, outside], dw0[:, outside]), (name, "a column outside the window changed")
+        assert same_bits(dw[:, outside], dw0[:, outside]), (name, "a column outside the window changed")
         ref = L.wgrad_ref(c["x"], c["dy"])
         depth = L.wgrad_depth(rows, I, O)
         yw, yb = L.wgrad_yardstick(c["x"], c["dy"])
@@ -283,7 +253,7 @@ def test_linear_wgrad_grouped_vs_fp64(hip_lib, regime):
             lin.add(name, "db", f"rows={rows}", ek, float((yb.double() - ref["db"]).abs().max()), sh, b)
         if regime == "exact":
             aw, ab = _wgrad_alone(hip_lib, xv, gv, rows, I, O, win0, db0)
-            assert _same_bits(aw, win) and (db is None or _same_bits(ab, db)), (name, "grouped differs from catan_linear_wgrad run alone")
+            assert same_bits(aw, win) and (db is None or same_bits(ab, db)), (name, "grouped differs from catan_linear_wgrad run alone")
     lin.done()
 
 
@@ -296,7 +266,7 @@ def _big(lib, xv, gv, rows, I, O, ld, dw_fill, db_fill, accumulate):
     hb, db = _between_sentinels(O, torch.float32, db_fill) if db_fill is not None else (None, None)
     _check(lib.catan_linear_wgrad_big(P(xv), P(gv), P(dw), ld, P(db), P(ws), rows, I, O, accumulate, _stream()))
     torch.cuda.synchronize()
-    assert _margins_intact(hs, ws) and _margins_intact(hw, dw) and (db is None or _margins_intact(hb, db)), (rows, I, O, "a write outside the workspace, dw or db")
+    assert G.intact(hs, ws) and G.intact(hw, dw) and (db is None or G.intact(hb, db)), (rows, I, O, "a write outside the workspace, dw or db")
     return dw.view(O, ld).clone(), None if db is None else db.clone()
 
 
@@ -321,11 +291,11 @@ def test_linear_wgrad_big_vs_fp64(hip_lib, I, O):
             runs = []
             dw, db = _big(hip_lib, xv, gv, rows, I, O, I, nan(O, I), nan(O), 0)
             dw2, db2 = _big(hip_lib, xv, gv, rows, I, O, I, nan(O, I), nan(O), 0)
-            assert _same_bits(dw, dw2) and _same_bits(db, db2), (I, O, rows, regime, "two runs differ")
+            assert same_bits(dw, dw2) and same_bits(db, db2), (I, O, rows, regime, "two runs differ")
             runs.append(("acc=0", dw, zw, db, zb))
             w0 = L.prefill((O, I + 8), regime, 3, "cuda")
             dw, _ = _big(hip_lib, xv, gv, rows, I, O, I + 8, w0, None, 1)
-            assert _same_bits(dw[:, I:], w0[:, I:]), (I, O, rows, regime, "a column behind the window changed")
+            assert same_bits(dw[:, I:], w0[:, I:]), (I, O, rows, regime, "a column behind the window changed")
             runs.append(("acc=1 ld=I+8 db=NULL", dw[:, :I].contiguous(), w0[:, :I].contiguous(), None, None))
             w0, b0 = L.prefill((O, I), regime, 4, "cuda"), L.prefill((O,), regime, 5, "cuda")
             dw, db = _big(hip_lib, xv, gv, rows, I, O, I, w0, b0, 1)

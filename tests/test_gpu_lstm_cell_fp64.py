@@ -17,27 +17,19 @@ compared bit for bit with a 4 096-row launch of their own.
 
 Buffers: 16-byte aligned; every input lies in front of NaN, every output starts as a sentinel pattern, none of which may be left, in
 front of guard elements that must be intact."""
-import ctypes as C
-
 import pytest
 import torch
 
+import guarded as G
 import lstm_cell_reference as LS
+from guarded import ptr as P, stream as _stream
+from pin_rule import same_bits
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 1024                     # elements behind every buffer
 SENTINEL = 0x5A5B5A5B
-NAN = float("nan")
 FWD, BWD = ("h", "c"), ("dgates", "dc_prev")
-
-
-def P(t, byte_offset=0):
-    return None if t is None else C.c_void_p(t.data_ptr() + byte_offset)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check(rc):
@@ -46,28 +38,15 @@ def _check(rc):
 
 
 def _input(t):
-    whole = torch.full((t.numel() + GUARD,), NAN, dtype=t.dtype, device="cuda")
-    assert whole.data_ptr() % 16 == 0
-    view = whole[:t.numel()]
-    view.copy_(t.reshape(-1))
-    return whole, view
+    return G.guarded_input(t, GUARD)
 
 
 def _output(n, dtype):
-    whole = torch.empty(n + GUARD, dtype=dtype, device="cuda")
-    assert whole.data_ptr() % 16 == 0
-    (whole.view(torch.int32) if dtype == torch.float32 else whole.view(torch.int16)).fill_(SENTINEL if dtype == torch.float32 else SENTINEL & 0xFFFF)
-    return whole, whole[:n]
+    return G.sentinel_output(n, dtype, GUARD, sentinel=SENTINEL)
 
 
 def _written_and_guarded(whole, view):
-    w = whole.view(torch.int32) if whole.dtype == torch.float32 else whole.view(torch.int16)
-    s = SENTINEL if whole.dtype == torch.float32 else SENTINEL & 0xFFFF
-    # (a bf16 value may equal the 16-bit pattern by chance; a run of eight cannot)
-    left = w[:view.numel()] == s
-    if whole.dtype != torch.float32:
-        left = left.view(-1, 8).all(1) if view.numel() % 8 == 0 else left.new_zeros(1)
-    return bool((w[view.numel():] == s).all()) and not bool(left.any())
+    return G.intact(whole, view) and G.written(whole, view, SENTINEL)
 
 
 def _launch(lib, c, bwd=True):
@@ -89,14 +68,6 @@ def _launch(lib, c, bwd=True):
         assert _written_and_guarded(whole, view), (c["regime"], n, L, k, "an element left unwritten, or a write behind the output")
         got[k] = view.view(n, -1)
     return got
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _device(c):
@@ -150,7 +121,7 @@ def test_lstm_cell_kernel_vs_fp64(hip_lib, L, dtype):
             c0 = dict(c, c_prev=torch.where(c["masked_rows"][:, None], torch.zeros_like(c["c_prev"]), c["c_prev"]))
             got0 = _launch(hip_lib, c0)
             for k in FWD + BWD:
-                assert _same_bits(got[k], got0[k]), (name, k, "a masked row's c_prev = 1e30 shows")
+                assert same_bits(got[k], got0[k]), (name, k, "a masked row's c_prev = 1e30 shows")
             assert not bool(got["dc_prev"][c["masked_rows"]].any()), (name, "dc_prev of a masked row is not 0")
     assert not bad, bad[:12]
 
@@ -163,11 +134,11 @@ def test_rows_do_not_depend_on_the_grid(hip_lib, L, dtype):
     c = _device(LS.make_case("unit", 4099, L, getattr(torch, dtype), True))
     big, mid = _launch(hip_lib, c), _launch(hip_lib, _rows_of(c, 0, 257))
     for k in FWD + BWD:
-        assert _same_bits(big[k][:257], mid[k]), (L, dtype, k, "the first 257 rows depend on the grid")
+        assert same_bits(big[k][:257], mid[k]), (L, dtype, k, "the first 257 rows depend on the grid")
     for r in (0, 85, 255, 256):
         one = _launch(hip_lib, _rows_of(c, r, r + 1))
         for k in FWD + BWD:
-            assert _same_bits(one[k], mid[k][r:r + 1]), (L, dtype, k, r, "a row alone differs from the row in a launch")
+            assert same_bits(one[k], mid[k][r:r + 1]), (L, dtype, k, r, "a row alone differs from the row in a launch")
 
 
 @pytest.mark.parametrize("dtype,n,mp", LS.cap_cases(), ids=[f"{dt}-{n}-mask{int(mp)}" for dt, n, mp in LS.cap_cases()])
@@ -190,7 +161,7 @@ def test_lstm_cell_at_the_launch_cap(hip_lib, dtype, n, mp):
         print(f"LSTM {name}: " + LS.stats_line(stats))
         own = _launch(hip_lib, s)
         for k in FWD + BWD:
-            assert _same_bits(part[k], own[k]), (name, k, "the rows differ from a launch of their own")
+            assert same_bits(part[k], own[k]), (name, k, "the rows differ from a launch of their own")
     assert not bad, bad
 
 

@@ -12,11 +12,11 @@ import torch
 
 import playout_reference as pr
 import scripted_reference as sr
+from guarded import ptr as P, stream as _stream
 from settlers_of_catan_rl_amd import _lib, spec
 
 pytestmark = pytest.mark.gpu
 
-P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
 SIM_GAMES = 300                 # 7 x 5 x 3 = 105 and 3 x 8 x 12 = 288 slots in use: a tail of untouched slots either way
 ROWS7 = [0, 3, 5, 7, 9, 11, 16]  # initial, initial, respond, turn, turn, discard, the planted position
 ROWS3 = [2, 16, 10]
@@ -26,10 +26,6 @@ F = pr.FIELDS
 def _env(n, seed, **kw):
     from settlers_of_catan_rl_amd.env import VecCatanEnv
     return VecCatanEnv(n, seed=seed, **kw)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 @functools.lru_cache(maxsize=None)

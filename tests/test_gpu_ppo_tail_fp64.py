@@ -18,27 +18,19 @@ guard elements that must be intact (the workspaces too; the parameters are views
 behind them; the pad elements between the tensors' slices of FusedAdam's flat state must stay 0).
 Every case prints one line (GAE / LOSS / ADAM): per output the kernel's error, the yardstick's, their ratio, the largest share of a bound
 used and the floor its elements would need.  Measured on the MI355X: profiles/ppo_tail_kernel_tests.txt is that output."""
-import ctypes as C
-
 import pytest
 import torch
 
+import guarded as G
+import pin_rule as PR
 import ppo_tail_reference as R
+from guarded import NAN, ptr as P, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 512                      # elements behind every buffer
 SENTINEL = 0x5A5B5A5B
-NAN = float("nan")
 F32, F64 = torch.float32, torch.float64
-
-
-def P(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check(rc):
@@ -48,30 +40,19 @@ def _check(rc):
 
 def _input(t, guard=NAN):
     """-> (whole, view): t's elements on the device followed by GUARD elements of `guard`"""
-    whole = torch.full((t.numel() + GUARD,), guard, dtype=t.dtype, device="cuda")
-    view = whole[:t.numel()]
-    view.copy_(t.reshape(-1))
-    return whole, view
+    return G.guarded_input(t, GUARD, guard=guard)
 
 
 def _output(n, dtype=F32):
-    whole = torch.empty(n + GUARD, dtype=dtype, device="cuda")
-    whole.view(torch.int32).fill_(SENTINEL)
-    return whole, whole[:n]
-
-
-def _guarded(whole, view):
-    k = whole.element_size() // 4
-    return bool((whole.view(torch.int32)[view.numel() * k:] == SENTINEL).all())
+    return G.sentinel_output(n, dtype, GUARD, sentinel=SENTINEL)
 
 
 def _written(whole, view):
-    k = whole.element_size() // 4
-    return not bool((whole.view(torch.int32)[:view.numel() * k] == SENTINEL).any())
+    return G.written(whole, view, SENTINEL)
 
 
 def _line(tag, st, order):
-    return tag + ": " + " | ".join(R.stat(n, st[n]) for n in order if n in st)
+    return tag + ": " + " | ".join(PR.fmt_stat(n, st[n]) for n in order if n in st)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------- GAE
@@ -86,8 +67,8 @@ def _gae(lib, r, v, m):
     _check(lib.catan_gae(P(hold[0][1]), P(hold[1][1]), P(hold[2][1]), T, N, R.GAMMA, R.LAM, P(ret[1]), P(raw[1]), P(ws[1]), P(stats[1]), _stream()))
     torch.cuda.synchronize()
     for n, (whole, view) in (("returns", ret), ("adv_raw", raw), ("stats3", stats)):
-        assert _written(whole, view) and _guarded(whole, view), (T, N, n, "an element left unwritten, or a write behind the output")
-    assert _guarded(*ws) and _written(ws[0], ws[1][:2 * nb]), (T, N, "workspace")
+        assert _written(whole, view) and G.intact(whole, view), (T, N, n, "an element left unwritten, or a write behind the output")
+    assert G.intact(*ws) and _written(ws[0], ws[1][:2 * nb]), (T, N, "workspace")
     return ret[1], raw[1], stats
 
 
@@ -97,7 +78,7 @@ def _normalise(lib, raw, stats_view):
     view.copy_(raw)
     _check(lib.catan_adv_normalise(P(view), raw.numel(), P(stats_view), _stream()))
     torch.cuda.synchronize()
-    assert _written(whole, view) and _guarded(whole, view), "catan_adv_normalise wrote behind its array"
+    assert _written(whole, view) and G.intact(whole, view), "catan_adv_normalise wrote behind its array"
     return view
 
 
@@ -125,7 +106,7 @@ def test_gae_kernels_vs_fp64(hip_lib, T, N):
             halves = [_normalise(hip_lib, p[1], total[1]).cpu().view(T, -1) for p in parts]
             for n, k in (("ret", 0), ("raw", 1)):
                 both = torch.cat([parts[0][k].cpu().view(T, -1), parts[1][k].cpu().view(T, -1)], 1)
-                if not R.same_bits(both, got[n]):
+                if not PR.same_bits(both, got[n]):
                     bad.append((regime, n, "the two halves differ from the whole"))
             ts = total[1].cpu().tolist()
             u = T * N * 2.0 ** -52
@@ -158,14 +139,14 @@ def _loss(lib, c, ws, clip=None, value_coef=None, use_norm=None):
                               P(outs["d_values"][1]), P(ws[1]), _stream()))
     torch.cuda.synchronize()
     for n, (whole, view) in outs.items():
-        assert _written(whole, view) and _guarded(whole, view), (B, n, "an element left unwritten, or a write behind the output")
-    assert _guarded(*ws), (B, "a write behind the workspace")
+        assert _written(whole, view) and G.intact(whole, view), (B, n, "an element left unwritten, or a write behind the output")
+    assert G.intact(*ws), (B, "a write behind the workspace")
     assert ws[1].view(torch.int64)[-1].item() == 0, (B, "the arrival counter is not back at 0")
     return {n: v[1].cpu() for n, v in outs.items()}
 
 
 def _same(a, b):
-    return all(R.same_bits(a[n], b[n]) for n in ("losses", "d_logp", "d_values"))
+    return all(PR.same_bits(a[n], b[n]) for n in ("losses", "d_logp", "d_values"))
 
 
 @pytest.mark.parametrize("B", R.LOSS_ROWS)
@@ -229,8 +210,8 @@ def test_ppo_loss_passes_non_finite_rows_on(hip_lib):
     assert bool(torch.isnan(got["losses"][0])) and bool(torch.isnan(got["d_logp"][3])), "a NaN logp is swallowed"
     assert bool(torch.isnan(got["losses"][1])) and bool(torch.isnan(got["d_values"][256])), "a NaN value is swallowed"
     keep_p, keep_v = torch.arange(B) != 3, torch.arange(B) != 256
-    assert R.same_bits(got["d_logp"][keep_p], clean["d_logp"][keep_p]) and R.same_bits(got["d_values"][keep_v], clean["d_values"][keep_v])
-    assert R.same_bits(got["d_values"][3:4], clean["d_values"][3:4]) and R.same_bits(got["d_logp"][256:], clean["d_logp"][256:])
+    assert PR.same_bits(got["d_logp"][keep_p], clean["d_logp"][keep_p]) and PR.same_bits(got["d_values"][keep_v], clean["d_values"][keep_v])
+    assert PR.same_bits(got["d_values"][3:4], clean["d_values"][3:4]) and PR.same_bits(got["d_logp"][256:], clean["d_logp"][256:])
 
 
 # --------------------------------------------------------------------------------------------------------------------------- Adam
@@ -279,9 +260,7 @@ class _Run(object):
             if g is None:
                 p.grad = None
             elif i == unaligned:                                          # a view 4 bytes into a larger buffer
-                whole = torch.full((g.numel() + 1 + GUARD,), NAN, dtype=F32, device="cuda")
-                whole[1:1 + g.numel()].copy_(g)
-                p.grad = whole[1:1 + g.numel()]
+                whole, p.grad = G.guarded_input(g, GUARD, lead=1)
                 assert p.grad.data_ptr() % 16 == 4
                 self.hold.append(whole)
             else:
@@ -311,10 +290,10 @@ def test_fused_adam_vs_fp64(hip_lib, name, regime, max_norm):
         b, st = R.adam_judge(c, ref, yard, k, got)
         bad += b
         for n, s in st.items():
-            R.merge(total, n, s)
+            PR.merge_stat(total, n, s)
         for i, g in enumerate(c["grads"][k]):
             if g is None and not c["none_is_zero"]:                       # no gradient, no step: every bit stays
-                if not (R.same_bits(got["p"][i], c["p0"][i]) and R.same_bits(got["m"][i], c["m0"][i]) and R.same_bits(got["v"][i], c["v0"][i])
+                if not (PR.same_bits(got["p"][i], c["p0"][i]) and PR.same_bits(got["m"][i], c["m0"][i]) and PR.same_bits(got["v"][i], c["v0"][i])
                         and got["steps"][i] == c["steps0"][i]):
                     bad.append((k, i, "a tensor without a gradient changed"))
     assert run.opt.copied_grads == 0
@@ -330,5 +309,5 @@ def test_fused_adam_unaligned_gradient_is_copied(hip_lib):
     ga, gb = a.step(0), b.step(0, unaligned=4)
     assert a.opt.copied_grads == 0 and b.opt.copied_grads == 1
     for n in ("p", "m", "v"):
-        assert all(R.same_bits(x, y) for x, y in zip(ga[n], gb[n])), n
+        assert all(PR.same_bits(x, y) for x, y in zip(ga[n], gb[n])), n
     assert ga["norm"] == gb["norm"] and ga["steps"] == gb["steps"]

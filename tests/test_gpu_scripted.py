@@ -1,7 +1,6 @@
 """GPU: the rule-based "builder" player - k_sample_scripted against the numpy restatement of the rule
 (tests/scripted_reference.py), game lists and streams, stepping its actions, its strength against uniform-random players, and its
 place in the evaluation protocol and the rollout collector."""
-import ctypes as C
 import random
 
 import numpy as np
@@ -9,6 +8,7 @@ import pytest
 import torch
 
 import scripted_reference as sr
+from guarded import ptr as P, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -188,9 +188,8 @@ def test_bad_arguments_name_the_entry_point(hip_lib):
     from settlers_of_catan_rl_amd import _lib
     L = _lib.lib()
     env = _env(64, 0)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = stream()
     out = torch.zeros((128, 18), dtype=torch.int32, device="cuda")
-    P = lambda t: C.c_void_p(t.data_ptr())
 
     def err(rc):
         assert rc == -1                                  # CATAN_EINVAL (include/catan_hip.h)

@@ -2,7 +2,7 @@
 (k_qkv_bwd_w), the activations catan_tile_encoder_fwd_train stores, and catan_layer_norm_bwd_res at every width it is built for -
 called through the C ABI directly.
 
-Acceptance, for every output tensor (tests/te_reference.py::within_yardstick):
+Acceptance, for every output tensor (te_reference.within_yardstick: the rule of tests/pin_rule.py with the bf16 floor):
     maxabs(kernel - reference) <= 2 * maxabs(yardstick - reference) + 2^-9 * maxabs(reference)
 reference = the operation in fp64 from the same bf16 inputs; yardstick = fp32 with a bf16 rounding where the kernel rounds.  The
 bound is computed inside the test from those two; nothing in it comes from a kernel's output.  Every case prints one `TE_BWD` line
@@ -24,7 +24,10 @@ import ctypes as C
 import pytest
 import torch
 
+import guarded as G
+import pin_rule as PR
 import te_reference as R
+from guarded import ptr as P, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
@@ -34,35 +37,18 @@ SENTINEL = 0x5A5B                # (a bf16 bit pattern no kernel result is likel
 ROWS = [1, 15, 16, 17, 19, 63, 64, 65, 133, 1984, 2047, 2048, 2071, 19703]
 
 
-def P(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _guarded(t):
-    """bf16 [rows, W] -> the first `rows` rows of a buffer with GUARD further rows of NaN: a read past `rows` that is used poisons a result"""
-    buf = torch.full((t.shape[0] + GUARD, t.shape[1]), float("nan"), dtype=torch.bfloat16, device=t.device)
-    buf[:t.shape[0]] = t
-    return buf
+    """[rows, W] -> the first `rows` rows of a buffer with GUARD further rows of NaN: a read past `rows` that is used poisons a result"""
+    return G.guarded_input(t, GUARD * t.shape[1], device=t.device)[0].view(-1, t.shape[1])
 
 
-def _out_buffer(rows, W, dtype=torch.bfloat16):
-    """an output of `rows` rows followed by GUARD rows of the sentinel (every 16-bit word of the buffer starts as the sentinel)"""
-    buf = torch.empty((rows + GUARD, W), dtype=dtype, device="cuda")
-    buf.view(torch.int16).fill_(SENTINEL)
-    return buf
+def _out_buffer(rows, W, dtype=torch.bfloat16, guard=GUARD):
+    """[rows + guard, W]: an output of `rows` rows followed by `guard` rows of the sentinel (every 16-bit word of the buffer starts as the sentinel)"""
+    return G.sentinel_output(rows * W, dtype, guard * W, sentinel=SENTINEL)[0].view(rows + guard, W)
 
 
 def _guard_intact(buf, rows):
-    return bool((buf[rows:].view(torch.int16) == SENTINEL).all())
-
-
-def _pattern(n, k):
-    """a non-constant fp32 pre-fill of an accumulator"""
-    return torch.sin(torch.arange(n, device="cuda", dtype=torch.float32) * 0.37 + k) * 1.5 + 0.25 * k
+    return G.intact(buf, buf[:rows])
 
 
 def _check(case, got, ref, yard):
@@ -71,7 +57,7 @@ def _check(case, got, ref, yard):
     for n in ref:
         ok, ek, ey, bound = R.within_yardstick(got[n], ref[n], yard[n])
         finite = bool(torch.isfinite(got[n]).all())
-        print(f"TE_BWD {case} {n}: kernel {ek:.4e} yardstick {ey:.4e} ratio {ek / ey if ey > 0 else float('inf'):.3f} bound {bound:.4e} scale {float(ref[n].abs().max()):.4e}")
+        print(f"TE_BWD {case} {n}: kernel {ek:.4e} yardstick {ey:.4e} ratio {PR.ratio(ek, ey, PR.INF):.3f} bound {bound:.4e} scale {float(ref[n].abs().max()):.4e}")
         if not (ok and finite):
             bad.append((case, n, ek, ey, "finite" if finite else "NOT FINITE"))
     assert not bad, bad
@@ -129,7 +115,7 @@ _QKV_ACC = (("dw", (192, 64)), ("db", (192,)), ("dln_w", (64,)), ("dln_b", (64,)
 
 
 def _accumulators(spec, prefill):
-    return {n: (_pattern(torch.Size(s).numel(), k + 1).view(s).contiguous() if prefill else torch.zeros(s, device="cuda")) for k, (n, s) in enumerate(spec)}
+    return {n: (G.pattern(torch.Size(s).numel(), k + 1).view(s).contiguous() if prefill else torch.zeros(s, device="cuda")) for k, (n, s) in enumerate(spec)}
 
 
 def _run_ffn(L, i, rows, prefill=False):
@@ -247,11 +233,9 @@ def _run_te(L, B, skip=(), pitch=475):
     bufs = {}
     for n, w in R.TE_FIELDS:
         if n not in skip:
-            bufs[n] = torch.empty((T + 8, w), dtype=torch.bfloat16, device="cuda")
-            bufs[n].view(torch.int16).fill_(SENTINEL)
+            bufs[n] = _out_buffer(T, w, guard=8)
     ptrs = (C.c_void_p * len(R.TE_FIELDS))(*[bufs[n].data_ptr() if n in bufs else None for n, _ in R.TE_FIELDS])
-    out = torch.empty((B + 1, pitch), dtype=torch.bfloat16, device="cuda")
-    out.view(torch.int16).fill_(SENTINEL)
+    out = _out_buffer(B, pitch, guard=1)
     tiles = s["tiles"][:B].contiguous()
     _lib.check(L.catan_tile_encoder_fwd_train(P(tiles), P(s["wts"]), P(s["vecs"]), P(out), pitch, C.cast(ptrs, C.c_void_p), B, _stream()))
     torch.cuda.synchronize()
@@ -272,8 +256,8 @@ def test_tile_encoder_training_saves_vs_fp64(hip_lib, B):
     got["out"] = out[:B].float()
     _check(f"tile_encoder_fwd_train B={B}", got, ref, yard)
     for n, _ in R.TE_FIELDS:
-        assert bool((bufs[n][T:].view(torch.int16) == SENTINEL).all()), n
-    assert bool((out[B:].view(torch.int16) == SENTINEL).all())
+        assert _guard_intact(bufs[n], T), n
+    assert _guard_intact(out, B)
     assert torch.equal(got["tiles64"][:, :60], _te_setup()["tiles"][:B].reshape(T, 60).float())
     assert bool((bufs["tiles64"][:T, 60:].view(torch.int16) == 0).all())
     # the optional saves left out: everything else bit-equal
@@ -308,10 +292,9 @@ def test_layer_norm_bwd_res_vs_fp64(hip_lib, D, dtype, rows):
     dres = (torch.randn((rows, D), device="cuda", generator=g) * torch.linspace(1.5, 0.5, D, device="cuda") - 0.05).to(dt)
     w = (1.0 + 0.6 * torch.randn(D, device="cuda", generator=g)) * 1.7
     b = 0.8 * torch.randn(D, device="cuda", generator=g) - 0.4
-    nan_tail = lambda t: torch.cat([t, torch.full((GUARD, D), float("nan"), dtype=dt, device="cuda")])
-    xg, dyg, dresg = nan_tail(x), nan_tail(dy), nan_tail(dres)
+    xg, dyg, dresg = _guarded(x), _guarded(dy), _guarded(dres)
     dx = _out_buffer(rows, D, dt)
-    dw, db = _pattern(D, 1), _pattern(D, 2)
+    dw, db = G.pattern(D, 1), G.pattern(D, 2)
     dw0, db0 = dw.clone(), db.clone()
     _lib.check(hip_lib.catan_layer_norm_bwd_res(P(xg), P(w), P(b), P(dyg), P(dresg), P(dx), P(dw), P(db), rows, D, EPS, 0, int(dt == torch.bfloat16), _stream()))
     torch.cuda.synchronize()

@@ -2,7 +2,6 @@
 twin (tests/action_complete_reference.py), teacher labels in the rollout collector's loops, catan_imitation_loss against fp64,
 evaluate_actions(teacher_actions=) against the CPU, and one PPO update with the imitation term."""
 import copy
-import ctypes as C
 import math
 
 import numpy as np
@@ -13,21 +12,17 @@ import action_complete_reference as acr
 import policy_fixture as pf
 import rollout_fixture as rf
 import scripted_reference as sr
+from guarded import ptr as P, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
 N, SEED = 64, 5
 STORAGE_KEYS = ("obs_f", "lists", "lens", "masks", "rewards", "actions", "action_log_probs", "action_masks")
-P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _env(n, seed, **kw):
     from settlers_of_catan_rl_amd.env import VecCatanEnv
     return VecCatanEnv(n, seed=seed, **kw)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ---------------------------------------------------------------------------------------------- 1. the completion kernel

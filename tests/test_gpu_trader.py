@@ -12,6 +12,7 @@ import torch
 import action_complete_reference as acr
 import scripted_reference as sr
 import trader_reference as tr
+from guarded import ptr as P, stream as _stream
 from test_trader_cpu import base, _offer, _seller, _banker, _action, _put, BRICK, WOOD, ORE, SHEEP, WHEAT  # noqa: F401 (base is a fixture)
 from settlers_of_catan_rl_amd import spec
 
@@ -19,16 +20,11 @@ pytestmark = pytest.mark.gpu
 
 N, SEED = 96, 7          # as tests/test_gpu_scripted.py: a partial wave and a partial workgroup
 ENDTURN_ROW = [sr.ENDTURN] + [0] * 17
-P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _env(n, seed, **kw):
     from settlers_of_catan_rl_amd.env import VecCatanEnv
     return VecCatanEnv(n, seed=seed, **kw)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def test_kernel_equals_the_twin_over_600_steps(hip_lib):

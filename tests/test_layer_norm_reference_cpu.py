@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import layer_norm_reference as LN
+import pin_rule as PR
 import te_reference as R
 
 EPS = LN.EPS
@@ -54,7 +55,7 @@ def _rejected(c, relu, bf16, plant, align="aligned"):
             if not ok:
                 out.add(n)
         for n, a in (("dw", "aw"), ("db", "ab")):
-            ok = bool(((o[n].double() - ref[n]).abs() <= LN.column_bound(yard[n], ref[n], ref[a], torch.zeros(D), depth)).all())
+            ok = bool(((o[n].double() - ref[n]).abs() <= PR.sum_bound(ref[a], depth, torch.zeros(D), yard[n], ref[n])).all())
             assert ok or who == "planted"
             if not ok:
                 out.add(n)
