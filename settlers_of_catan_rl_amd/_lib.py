@@ -207,6 +207,7 @@ def build_library(force=False, verbose=False):
 
 
 _lib = None
+_foreign = False                            # use_library: LIB_PATH is another commit's build
 _vp = C.c_void_p
 
 _SIGS = {
@@ -372,17 +373,28 @@ def declared_symbols():
     return sorted(_SIGS)
 
 
-def bind(L, names=None):
+def bind(L, names=None, missing_ok=False):
     """Gives the entry points `names` (None: every declared one) of the loaded library L their ctypes signatures; an _OPTIONAL one that L
-    does not export is skipped (oracle/libcatan_cpu.so), any other missing one raises AttributeError.  -> the names bound"""
+    does not export is skipped (oracle/libcatan_cpu.so), any other missing one raises AttributeError - unless missing_ok, which skips
+    every one that L lacks (another commit's library: use_library).  -> the names bound"""
     bound = []
     for name in (_SIGS if names is None else names):
-        if name in _OPTIONAL and not hasattr(L, name):
+        if (missing_ok or name in _OPTIONAL) and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = _SIGS[name]
         bound.append(name)
     return bound
+
+
+def use_library(path):
+    """Runs this Python over another commit's build of the library (the parent-comparison tools: tools/parent_compare.py): lib() will
+    load `path`, accept a build hash that is not the sources', and bind only the entry points that library exports - calling one it
+    lacks is an AttributeError (env._entry: a CatanHipError).  Before the first lib() of the process only."""
+    global LIB_PATH, _foreign
+    if _lib is not None:
+        raise CatanHipError(f"use_library({path!r}): {LIB_PATH} is already loaded in this process")
+    LIB_PATH, _foreign = os.path.abspath(path), True
 
 
 def lib():
@@ -395,9 +407,9 @@ def lib():
         # process ends up with two HIP runtimes and device pointers / streams cannot be shared.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        bind(L)
+        bind(L, missing_ok=_foreign)
         have, want = L.catan_build_hash().decode(), source_hash()
-        if have != want and not os.environ.get("CATAN_ALLOW_STALE_LIB"):
+        if have != want and not _foreign and not os.environ.get("CATAN_ALLOW_STALE_LIB"):
             raise CatanHipError(f"{LIB_PATH} was built from other sources (binary {have}, sources {want}): rebuild with "
                                 "`python -c 'import __graft_entry__ as g; g.build()'`")
         _lib = L

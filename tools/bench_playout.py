@@ -19,54 +19,7 @@ import os
 import random
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-NEW_SYMBOLS = {"catan_playout_actions"}
-
-
-def bench_child(a):
-    """bench.py as it stands, in this process, under the given library (the parent's lacks the new entry point: never called here)"""
-    import runpy
-    if a.library:
-        os.environ["CATAN_ALLOW_STALE_LIB"] = "1"
-        from settlers_of_catan_rl_amd import _lib
-        _lib.LIB_PATH = os.path.abspath(a.library)
-        _lib._OPTIONAL |= NEW_SYMBOLS
-    sys.argv = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(a.bench_steps), "--warmup", str(a.bench_warmup)]
-    runpy.run_path(sys.argv[0], run_name="__main__")
-
-
-def bench_pairs(a, out):
-    """alternating fresh-process runs of bench.py: parent, change, change, parent, ...; a failed run ends the tool"""
-    import subprocess
-    sides, runs = [("parent", a.parent_library), ("change", None)], []
-    out.write("\nbench.py --gpus 1 --steps {} --warmup {} with the player unused, a fresh process per run, the parent's library and this\n"
-              "commit's alternating: env-steps/s, ms per pass, status\n".format(a.bench_steps, a.bench_warmup))
-    for r in range(a.bench_pairs):
-        for label, lib in (sides if r % 2 == 0 else sides[::-1]):
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--bench-child", "--bench-steps", str(a.bench_steps), "--bench-warmup",
-                                str(a.bench_warmup)] + (["--library", lib] if lib else []), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-            text = p.stdout.decode("utf-8", "replace")
-            res = [ln for ln in text.splitlines() if ln.startswith("{") and '"value"' in ln]
-            if p.returncode != 0 or not res:
-                print(text)
-                raise SystemExit(f"bench.py run {r} {label} failed with exit code {p.returncode}")      # nothing more is started on the device
-            j = json.loads(res[-1])
-            runs.append((label, j.get("value"), j.get("ms_per_step"), j.get("status")))
-            line = "  {} {} {} {}".format(*runs[-1])
-            print(line, flush=True)
-            out.write(line + "\n")
-            out.flush()
-    parent, change = [v for l, v, _, _ in runs if l == "parent"], [v for l, v, _, _ in runs if l == "change"]
-    mean = sum(change) / len(change)
-    where = "inside" if min(parent) <= mean <= max(parent) else ("ABOVE" if mean > max(parent) else "BELOW")
-    line = "  the change's mean {:.5e} lies {} the parent's spread {:.5e}..{:.5e} (parent's mean {:.5e})".format(
-        mean, where, min(parent), max(parent), sum(parent) / len(parent))
-    print(line, flush=True)
-    out.write(line + "\n")
-    out.flush()
+import parent_compare as pc
 
 
 def games(args, emit, np):
@@ -108,17 +61,9 @@ def call_times(args, emit, torch):
             root.step(root.sample_scripted_actions(style="trader"))
         sim = VecCatanEnv(rows * C * K, seed=0, env_id0=1 << 40, auto_reset=False)
         kw = dict(candidates=pol.candidates, playouts=K, depth=D, playout_style=pol.playout_style, determinise=pol.determinise)
-        for i in range(3):
-            root.playout_actions(sim, step_idx=i, **kw)
-        torch.cuda.synchronize()
-        ms = []
-        for i in range(args.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            root.playout_actions(sim, step_idx=3 + i, **kw)
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
+        idx = iter(range(3 + args.reps))             # three warm-up calls, then `reps` timed ones, events around each
+        t = pc.event_call_times({"call": lambda: root.playout_actions(sim, step_idx=next(idx), **kw)}, 1, args.reps, warm=3)
+        ms = [us / 1e3 for us in t["call"]["device_us"]]          # min, median, max
         # the replica: the same fork, the playout style in every seat from the first step on, finished games frozen
         src = torch.arange(rows, device=root.device).repeat_interleave(C * K)
         off = ((torch.arange(rows * C * K, device=root.device) % K) + 1) << 22
@@ -138,9 +83,9 @@ def call_times(args, emit, torch):
                 evs.append((e0, e1))
             torch.cuda.synchronize()
             step_ms.append(sum(x.elapsed_time(y) for x, y in evs))
-        call, steps = sorted(ms)[len(ms) // 2], sorted(step_ms)[len(step_ms) // 2]
+        call, steps = ms[1], sorted(step_ms)[len(step_ms) // 2]
         emit({"measurement": "ms_per_call", "rows": rows, "candidates": list(pol.candidates), "playouts": K, "depth": D, "sims": rows * C * K,
-              "playout_style": pol.playout_style, "determinise": pol.determinise, "reps": args.reps, "call_ms_min_median_max": mmm(ms),
+              "playout_style": pol.playout_style, "determinise": pol.determinise, "reps": args.reps, "call_ms_min_median_max": ms,
               "replica_step_ms_sum_min_median_max": mmm(step_ms), "share_of_catan_step": steps / call,
               "us_per_sim_step": call * 1e3 / (rows * C * K * D)})
         assert root.invalid_action_count() == 0
@@ -161,23 +106,22 @@ def main():
     ap.add_argument("--mix-steps", type=int, default=300, help="untimed steps that spread the roots over the phases of play")
     ap.add_argument("--skip-games", action="store_true")
     ap.add_argument("--skip-calls", action="store_true")
-    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "playout_policy_bench.txt"))
+    ap.add_argument("--out", type=str, default=os.path.join(pc.ROOT, "profiles", "playout_policy_bench.txt"))
     ap.add_argument("--commit", type=str, default=None, help="the commit of this tree (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.bench_child:
-        return bench_child(args)
+        return pc.bench_py_child(args.library, args.bench_steps, args.bench_warmup)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     out = open(args.out, "a")
     if args.parent_library:                 # first, while this process has not touched the device
-        bench_pairs(args, out)
+        pc.bench_py_section(args, out, "player", __file__)
     import numpy as np
     import torch
-    from bench_scripted import commit_of_tree
     out.write("\nPlayout player (catan_playout_actions, scripted.PlayoutPolicy): measurements of tools/bench_playout.py\n"
               "commit: {}\ndevice: {}\ncommand: bench_playout.py {}\n"
               "One JSON line per measurement.  win_share_of_seat_0: the share of the games won by the player named first in `measurement`\n"
               "(seat orders drawn by evaluation.sample_orders).  ms_per_call: hipEvents around single calls through Python and ctypes.\n\n".format(
-                  args.commit or commit_of_tree(), torch.cuda.get_device_name(0), " ".join(a for i, a in enumerate(sys.argv[1:]) if a != "--commit" and sys.argv[i] != "--commit")))
+                  args.commit or pc.commit_of_tree(), torch.cuda.get_device_name(0), " ".join(a for i, a in enumerate(sys.argv[1:]) if a != "--commit" and sys.argv[i] != "--commit")))
 
     def emit(rec):
         line = json.dumps(rec)

@@ -16,23 +16,10 @@ import argparse
 import json
 import os
 import random
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def commit_of_tree():
-    """`git rev-parse HEAD` of the tree this file lies in (+ a mark when the tree has uncommitted changes); a tree without git metadata
-    must be told its commit (--commit)"""
-    try:
-        head = subprocess.run(["git", "rev-parse", "HEAD"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout.decode().strip()
-        dirty = subprocess.run(["git", "status", "--porcelain"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout.strip()
-        return head + (" + uncommitted changes" if dirty else "")
-    except (OSError, subprocess.CalledProcessError):
-        return "unknown (no git metadata beside this tree; pass --commit)"
+import parent_compare as pc
 
 
 def main():
@@ -44,7 +31,7 @@ def main():
     ap.add_argument("--mix-steps", type=int, default=400, help="untimed steps that spread the games over the phases of play")
     ap.add_argument("--max-steps", type=int, default=2500)
     ap.add_argument("--skip-protocol", action="store_true")
-    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "scripted_policy_bench.txt"))
+    ap.add_argument("--out", type=str, default=os.path.join(pc.ROOT, "profiles", "scripted_policy_bench.txt"))
     ap.add_argument("--commit", type=str, default=None, help="the commit of this tree (default: git rev-parse HEAD)")
     args = ap.parse_args()
     import numpy as np
@@ -63,7 +50,7 @@ def main():
               "is launch-bound and the figure only bounds the kernel's time from above.  wall_s: the games of one protocol entry\n"
               "(run_evaluation_episodes, bf16 nets), env creation left out.  policy0_win_share: the share of games won by the first policy\n"
               "named in `measurement`; a player no better than the other three wins 0.25.\n\n".format(
-                  args.commit or commit_of_tree(), torch.cuda.get_device_name(0), " ".join(a for a in sys.argv[1:] if not a.startswith("--commit"))))
+                  args.commit or pc.commit_of_tree(), torch.cuda.get_device_name(0), " ".join(a for a in sys.argv[1:] if not a.startswith("--commit"))))
 
     def emit(rec):
         line = json.dumps(rec)
@@ -79,27 +66,11 @@ def main():
         env.step(torch.where((((g + s) % 3) == 0)[:, None], r, a))
     buf = torch.empty((args.envs, 18), dtype=torch.int32, device=env.device)
     calls = {"scripted": lambda: env.sample_scripted_actions(out=buf), "random": lambda: env.sample_random_actions(7, out=buf)}
-    for fn in calls.values():
-        for _ in range(10):
-            fn()
-    torch.cuda.synchronize()
-    us, host = {k: [] for k in calls}, {k: [] for k in calls}
-    for _ in range(args.rounds):
-        for k, fn in calls.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            t0 = time.perf_counter()
-            for _ in range(args.reps):
-                fn()
-            host[k].append((time.perf_counter() - t0) * 1e6 / args.reps)
-            e1.record()
-            e1.synchronize()
-            us[k].append(e0.elapsed_time(e1) * 1e3 / args.reps)
-    mmm = lambda xs: [min(xs), sorted(xs)[len(xs) // 2], max(xs)]
+    t = pc.event_call_times(calls, args.reps, args.rounds)
     types = torch.bincount(env.sample_scripted_actions()[:, 0].long(), minlength=13).tolist()
     emit({"measurement": "us_per_call", "envs": args.envs, "reps": args.reps, "rounds": args.rounds,
-          "scripted_min_median_max": mmm(us["scripted"]), "random_min_median_max": mmm(us["random"]),
-          "scripted_host_issue_us_min_median_max": mmm(host["scripted"]), "random_host_issue_us_min_median_max": mmm(host["random"]),
+          "scripted_min_median_max": t["scripted"]["device_us"], "random_min_median_max": t["random"]["device_us"],
+          "scripted_host_issue_us_min_median_max": t["scripted"]["host_issue_us"], "random_host_issue_us_min_median_max": t["random"]["host_issue_us"],
           "bot_action_types_on_these_states": types, "fallback_count": env.scripted_fallback_count()})
     assert env.invalid_action_count() == 0
     del env
@@ -109,19 +80,6 @@ def main():
     # ---- (2), (3) evaluation games
     torch.manual_seed(0)
     net = CatanPolicy().cuda().eval()
-
-    class UniformRandom(object):
-        wants_games, include_lstm = True, False
-
-        def rebind(self, e):
-            self.env, self.passes = e, 0
-
-        def act(self, f, lists, lens, masks, games=None, **_kw):
-            a = self.env.sample_random_actions(self.passes).long()
-            self.passes += 1
-            a = a if games is None else a[games.long()]
-            z = torch.zeros((a.shape[0], 1), device=a.device)
-            return z, a, z
 
     def games(first, others, n, seed, order_seed, autocast):
         e = VecCatanEnv(n, seed=seed, auto_reset=False)
@@ -136,7 +94,7 @@ def main():
         assert e.invalid_action_count() == 0
         return res, time.perf_counter() - t0
 
-    bot, rnd, n = ScriptedPolicy(), UniformRandom(), args.episodes
+    bot, rnd, n = ScriptedPolicy(), pc.UniformRandom(), args.episodes
     for name, first, other, m, seed, order_seed, ac in (
             ("net_vs_3_scripted", net, bot, n, 100, 100, torch.bfloat16),
             ("net_vs_3_random_init_nets", net, CatanPolicy().cuda().eval(), n, 100, 100, torch.bfloat16),

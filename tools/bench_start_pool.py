@@ -14,19 +14,13 @@ host clock around K calls that end in a device synchronise.  The pool's entries 
 import argparse
 import json
 import os
-import subprocess
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import parent_compare as pc
 
 
 def child(a):
-    if a.library:                                   # the parent commit's library under this commit's Python (the off-path uses nothing new)
-        os.environ["CATAN_ALLOW_STALE_LIB"] = "1"
-        from settlers_of_catan_rl_amd import _lib
-        _lib.LIB_PATH = os.path.abspath(a.library)
+    pc.use_library(a.library)                       # the parent commit's library under this commit's Python (the off-path uses nothing new)
     import torch
     from settlers_of_catan_rl_amd.env import VecCatanEnv
     env = VecCatanEnv(a.games, seed=1)
@@ -45,31 +39,12 @@ def child(a):
             env.set_start_pool(blobs, a.fresh)          # (ends in a stream synchronise of its own: the finished-position check)
             sets.append((time.perf_counter() - t0) * 1e6)
         out["set_us"] = sets
-    step_idx = 0
-    for name in ("catan_step", "catan_step_deferred"):
-        deferred = name == "catan_step_deferred"
 
-        def run(k):
-            nonlocal step_idx
-            for _ in range(k):
-                acts = env.sample_random_actions(step_idx)
-                step_idx += 1
-                if deferred:
-                    env.step_deferred(acts, window=4)
-                else:
-                    env.step(acts)
-            if deferred:
-                env.step_flush()
-            torch.cuda.synchronize()
-        run(a.warmup)
-        if a.entries:
-            env.start_pool_counts(reset=True)
-        t0 = time.perf_counter()
-        run(a.calls)
-        out[name + "_us"] = (time.perf_counter() - t0) / a.calls * 1e6
-        if a.entries:
-            c = env.start_pool_counts(reset=True)
+    def between(name, phase):                       # the deals of the timed calls alone
+        c = env.start_pool_counts(reset=True)
+        if phase == "timed":
             out[name + "_deals"] = [c["pool"], c["fresh"]]
+    out.update(pc.step_call_times(env, a.calls, a.warmup, between if a.entries else None))
     print("RESULT " + json.dumps(out), flush=True)
 
 
@@ -81,7 +56,7 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--entries", type=int, default=4096)
     ap.add_argument("--parent-library")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "start_pool_bench.txt"))
+    ap.add_argument("--out", default=os.path.join(pc.ROOT, "profiles", "start_pool_bench.txt"))
     ap.add_argument("--off-only", action="store_true", help="only the configurations without a pool (the comparison with the parent)")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--fresh", type=float, default=0.0)
@@ -96,24 +71,13 @@ def main():
         configs = [c for c in configs if c[1] == 0]
     rows = {c[0]: [] for c in configs}
     for r in range(a.runs):
-        # (the order rotates from round to round: no configuration always runs behind the same neighbour)
-        for label, entries, fresh, lib in configs[r % len(configs):] + configs[:r % len(configs)]:
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--games", str(a.games), "--calls", str(a.calls), "--warmup", str(a.warmup),
-                   "--entries", str(entries), "--fresh", str(fresh)] + (["--library", lib] if lib else [])
-            p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
-            text = p.stdout.decode("utf-8", "replace")
-            res = [ln for ln in text.splitlines() if ln.startswith("RESULT ")]
-            if p.returncode != 0 or not res:
-                print(text)
-                raise SystemExit(f"run {r} of {label!r} failed with exit code {p.returncode}")      # nothing more is started on the device
-            rows[label].append(json.loads(res[-1][7:]))
-            print(f"run {r} {label:26s} {res[-1][7:]}", flush=True)
-    try:
-        commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode().strip()
-    except OSError:
-        commit = ""
+        for label, entries, fresh, lib in pc.order(configs, r, "rotate"):  # (no configuration always runs behind the same neighbour)
+            res = pc.run_child(__file__, ["--child", "--games", str(a.games), "--calls", str(a.calls), "--warmup", str(a.warmup), "--entries", str(entries),
+                                          "--fresh", str(fresh)] + (["--library", lib] if lib else []), 300, "RESULT ")
+            rows[label].append(res)
+            print(f"run {r} {label:26s} {json.dumps(res)}", flush=True)
     lines = ["Start pool: what a pool costs a step (tools/bench_start_pool.py)",
-             f"commit {commit or 'unknown (no git checkout where it ran)'}; {a.games} games, {a.calls} timed calls behind {a.warmup} warm-up calls, {a.runs} runs each,",
+             f"commit {pc.commit_of_tree()}; {a.games} games, {a.calls} timed calls behind {a.warmup} warm-up calls, {a.runs} runs each,",
              "a fresh process per run, configurations alternating; a call = catan_sample_random_actions + the step; host clock around the calls,",
              "ending in a device synchronise.  Microseconds per call.", ""]
     for key in ("catan_step_us", "catan_step_deferred_us"):
@@ -122,10 +86,7 @@ def main():
             v = [x[key] for x in rows[label]]
             lines.append(f"  {label:26s} runs {' '.join(f'{x:8.2f}' for x in v)}   mean {sum(v) / len(v):8.2f}   min {min(v):8.2f}   max {max(v):8.2f}")
         if a.parent_library:
-            pv, ov = [x[key] for x in rows["parent, off"]], [x[key] for x in rows["off"]]
-            mean = sum(ov) / len(ov)
-            where = "inside" if min(pv) <= mean <= max(pv) else ("BELOW (faster than)" if mean < min(pv) else "ABOVE (slower than)")
-            lines.append(f"  off against the parent: mean {mean:.2f} {where} the parent's spread {min(pv):.2f}..{max(pv):.2f}")
+            lines.append("  off against the parent: " + pc.sentence([x[key] for x in rows["off"]], [x[key] for x in rows["parent, off"]], False))
         lines.append("")
     for label, entries, _, _ in configs:
         if entries:

@@ -16,24 +16,13 @@ random steps; the weights are M seeded values in 0..65 535, every eighth of them
 import argparse
 import json
 import os
-import subprocess
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _use_library(path):
-    """the parent commit's library under this commit's Python"""
-    os.environ["CATAN_ALLOW_STALE_LIB"] = "1"
-    from settlers_of_catan_rl_amd import _lib
-    _lib.LIB_PATH = os.path.abspath(path)
+import parent_compare as pc
 
 
 def child(a):
-    if a.library:
-        _use_library(a.library)
+    pc.use_library(a.library)
     import numpy as np
     import torch
     from settlers_of_catan_rl_amd.env import VecCatanEnv
@@ -60,50 +49,17 @@ def child(a):
         if a.mode == "weighted+outcomes":
             env.enable_start_pool_outcomes(torch.arange(a.games, device=env.device) % 4 + 1)
         env.reset()
-    step_idx = 0
-    for name in ("catan_step", "catan_step_deferred"):
-        deferred = name == "catan_step_deferred"
 
-        def run(k):
-            nonlocal step_idx
-            for _ in range(k):
-                acts = env.sample_random_actions(step_idx)
-                step_idx += 1
-                if deferred:
-                    env.step_deferred(acts, window=4)
-                else:
-                    env.step(acts)
-            if deferred:
-                env.step_flush()
-            torch.cuda.synchronize()
-        run(a.warmup)
-        if a.mode != "off":
-            env.start_pool_counts(reset=True)
-        t0 = time.perf_counter()
-        run(a.calls)
-        out[name + "_us"] = (time.perf_counter() - t0) / a.calls * 1e6
-        if a.mode != "off":
-            c = env.start_pool_counts(reset=True)
+    def between(name, phase):                       # the deals and tallies of the timed calls alone
+        c = env.start_pool_counts(reset=True)
+        if phase == "timed":
             out[name + "_deals"] = [c["pool"], c["fresh"]]
             out[name + "_entries_hit"] = int((c["per_entry"] > 0).sum())
-        if a.mode == "weighted+outcomes":
-            o = env.start_pool_outcomes(reset=True)
-            out[name + "_tallied"] = [o["seen"], o["skipped"]]
+            if a.mode == "weighted+outcomes":
+                o = env.start_pool_outcomes(reset=True)
+                out[name + "_tallied"] = [o["seen"], o["skipped"]]
+    out.update(pc.step_call_times(env, a.calls, a.warmup, between if a.mode != "off" else None))
     print("RESULT " + json.dumps(out), flush=True)
-
-
-def bench_child(a):
-    """bench.py as it stands, in this process, under the given library"""
-    import runpy
-    if a.library:
-        _use_library(a.library)
-    sys.argv = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(a.bench_steps), "--warmup", str(a.bench_warmup)]
-    runpy.run_path(sys.argv[0], run_name="__main__")
-
-
-def _spawn(args, timeout):
-    p = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
-    return p.returncode, p.stdout.decode("utf-8", "replace")
 
 
 def main():
@@ -117,7 +73,7 @@ def main():
     ap.add_argument("--bench-runs", type=int, default=3, help="pairs of bench.py runs (0: none)")
     ap.add_argument("--bench-steps", type=int, default=4096)
     ap.add_argument("--bench-warmup", type=int, default=256)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "start_pool_weighted_bench.txt"))
+    ap.add_argument("--out", default=os.path.join(pc.ROOT, "profiles", "start_pool_weighted_bench.txt"))
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--bench-child", action="store_true")
     ap.add_argument("--mode", default="off", choices=["off", "uniform", "weighted", "weighted+outcomes"])
@@ -126,40 +82,21 @@ def main():
     if a.child:
         return child(a)
     if a.bench_child:
-        return bench_child(a)
+        return pc.bench_py_child(a.library, a.bench_steps, a.bench_warmup)
     configs = [("off", "off", None), (f"uniform, {a.entries} entries", "uniform", None), (f"weighted, {a.entries} entries", "weighted", None),
                ("weighted + outcomes", "weighted+outcomes", None)]
     if a.parent_library:
         configs = [c for label, mode, _ in configs for c in ((f"parent, {label}", mode, a.parent_library), (label, mode, None))]
     rows = {c[0]: [] for c in configs}
     for r in range(a.runs):
-        # (the order rotates from round to round: no configuration always runs behind the same neighbour)
-        for label, mode, lib in configs[r % len(configs):] + configs[:r % len(configs)]:
-            rc, text = _spawn(["--child", "--games", str(a.games), "--calls", str(a.calls), "--warmup", str(a.warmup), "--entries", str(a.entries),
-                               "--mode", mode] + (["--library", lib] if lib else []), 300)
-            res = [ln for ln in text.splitlines() if ln.startswith("RESULT ")]
-            if rc != 0 or not res:
-                print(text)
-                raise SystemExit(f"run {r} of {label!r} failed with exit code {rc}")      # nothing more is started on the device
-            rows[label].append(json.loads(res[-1][7:]))
-            print(f"run {r} {label:34s} {res[-1][7:]}", flush=True)
-    bench = []
-    for r in range(a.bench_runs):
-        for label, lib in ([("parent", a.parent_library)] if a.parent_library else []) + [("change", None)]:
-            rc, text = _spawn(["--bench-child", "--bench-steps", str(a.bench_steps), "--bench-warmup", str(a.bench_warmup)] + (["--library", lib] if lib else []), 900)
-            res = [ln for ln in text.splitlines() if ln.startswith("{") and '"value"' in ln]
-            if rc != 0 or not res:
-                print(text)
-                raise SystemExit(f"bench.py run {r} ({label}) failed with exit code {rc}")
-            j = json.loads(res[-1])
-            bench.append((label, j.get("value"), j.get("ms_per_step"), j.get("status")))
-            print(f"bench.py run {r} {label} {j.get('value')} {j.get('ms_per_step')} {j.get('status')}", flush=True)
-    try:
-        commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode().strip()
-    except OSError:
-        commit = ""
+        for label, mode, lib in pc.order(configs, r, "rotate"):  # (no configuration always runs behind the same neighbour)
+            res = pc.run_child(__file__, ["--child", "--games", str(a.games), "--calls", str(a.calls), "--warmup", str(a.warmup), "--entries", str(a.entries),
+                                          "--mode", mode] + (["--library", lib] if lib else []), 300, "RESULT ")
+            rows[label].append(res)
+            print(f"run {r} {label:34s} {json.dumps(res)}", flush=True)
+    bench = pc.bench_py_runs(a.parent_library, a.bench_runs, a.bench_steps, a.bench_warmup, __file__, how="fixed", timeout=900)
     lines = ["Start pool, weighted picks and outcome tallies: what they cost a step (tools/bench_start_pool_weighted.py)",
-             f"commit {commit or 'unknown (no git checkout where it ran)'}; {a.games} games, {a.calls} timed calls behind {a.warmup} warm-up calls, {a.runs} runs each,",
+             f"commit {pc.commit_of_tree()}; {a.games} games, {a.calls} timed calls behind {a.warmup} warm-up calls, {a.runs} runs each,",
              "a fresh process per run, configurations alternating; a call = catan_sample_random_actions + the step; host clock around the calls,",
              "ending in a device synchronise.  Microseconds per call.", ""]
     for key in ("catan_step_us", "catan_step_deferred_us"):
@@ -170,10 +107,7 @@ def main():
         for label, _, lib in configs if a.parent_library else []:
             if lib:
                 continue
-            pv, ov = [x[key] for x in rows["parent, " + label]], [x[key] for x in rows[label]]
-            mean = sum(ov) / len(ov)
-            where = "inside" if min(pv) <= mean <= max(pv) else ("BELOW (faster than)" if mean < min(pv) else "ABOVE (slower than)")
-            lines.append(f"  {label} against the parent: mean {mean:.2f} {where} the parent's spread {min(pv):.2f}..{max(pv):.2f}")
+            lines.append(f"  {label} against the parent: " + pc.sentence([x[key] for x in rows[label]], [x[key] for x in rows["parent, " + label]], False))
         lines.append("")
     for label, mode, _ in configs:
         if mode == "off":
@@ -192,11 +126,8 @@ def main():
         lines += ["", f"bench.py --gpus 1 --steps {a.bench_steps} --warmup {a.bench_warmup} (no pool, as always there), the parent's library and this commit's in turn,",
                   "a fresh process per run: env-steps/s, ms per pass, status"]
         lines += [f"{label} {value} {ms} {status}" for label, value, ms, status in bench]
-        pv, cv = [b[1] for b in bench if b[0] == "parent"], [b[1] for b in bench if b[0] == "change"]
-        if pv and cv:
-            mean = sum(cv) / len(cv)
-            where = "inside" if min(pv) <= mean <= max(pv) else ("ABOVE (faster than)" if mean > max(pv) else "BELOW (slower than)")
-            lines.append(f"the change's mean {mean:.6g} lies {where} the parent's spread {min(pv):.6g}..{max(pv):.6g}")
+        if a.parent_library:
+            lines.append(pc.bench_py_sentence(bench, ".6g"))
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

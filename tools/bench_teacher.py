@@ -12,27 +12,13 @@ never called with no teacher configured).  A learner run is two updates of E epo
 import argparse
 import json
 import os
-import subprocess
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-TEACHER_SYMBOLS = {"catan_complete_action_rows", "catan_collector_label", "catan_imitation_loss_words", "catan_imitation_loss_workspace_doubles",
-                   "catan_imitation_loss"}
-
-
-def _use_library(path):
-    """the parent commit's library under this commit's Python"""
-    os.environ["CATAN_ALLOW_STALE_LIB"] = "1"
-    from settlers_of_catan_rl_amd import _lib
-    _lib.LIB_PATH = os.path.abspath(path)
-    _lib._OPTIONAL |= TEACHER_SYMBOLS
+import parent_compare as pc
 
 
 def ppo_child(a):
-    if a.library:
-        _use_library(a.library)
+    pc.use_library(a.library)
     import torch
     from settlers_of_catan_rl_amd.env import VecCatanEnv
     from settlers_of_catan_rl_amd.policy import CatanPolicy
@@ -67,27 +53,6 @@ def ppo_child(a):
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def bench_child(a):
-    """bench.py as it stands, in this process, under the given library"""
-    import runpy
-    if a.library:
-        _use_library(a.library)
-    sys.argv = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(a.bench_steps), "--warmup", str(a.bench_warmup)]
-    runpy.run_path(sys.argv[0], run_name="__main__")
-
-
-def _spawn(args, timeout):
-    p = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout)
-    return p.returncode, p.stdout.decode("utf-8", "replace")
-
-
-def _where(mean, parent, higher_is_better):
-    if min(parent) <= mean <= max(parent):
-        return "inside"
-    better = mean > max(parent) if higher_is_better else mean < min(parent)
-    return ("ABOVE" if mean > max(parent) else "BELOW") + (" (better than)" if better else " (WORSE than)")
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536)
@@ -100,7 +65,7 @@ def main():
     ap.add_argument("--bench-steps", type=int, default=4096)
     ap.add_argument("--bench-warmup", type=int, default=256)
     ap.add_argument("--parent-library")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "teacher_bench.txt"))
+    ap.add_argument("--out", default=os.path.join(pc.ROOT, "profiles", "teacher_bench.txt"))
     ap.add_argument("--ppo-child", action="store_true")
     ap.add_argument("--bench-child", action="store_true")
     ap.add_argument("--teacher-coef", type=float, default=0.0)
@@ -109,43 +74,28 @@ def main():
     if a.ppo_child:
         return ppo_child(a)
     if a.bench_child:
-        return bench_child(a)
+        return pc.bench_py_child(a.library, a.bench_steps, a.bench_warmup)
     sides = ([("parent", a.parent_library)] if a.parent_library else []) + [("change", None)]
     common = ["--envs", str(a.envs), "--num-steps", str(a.num_steps), "--ppo-epoch", str(a.ppo_epoch)]
-    ppo, on, bench = [], [], []
+    ppo, on = [], []
 
-    def run(label, args, timeout, pick):
-        rc, text = _spawn(args, timeout)
-        res = [ln for ln in text.splitlines() if pick(ln)]
-        if rc != 0 or not res:
-            print(text)
-            raise SystemExit(f"{label} failed with exit code {rc}")      # nothing more is started on the device
-        print(label, res[-1], flush=True)
-        return res[-1]
-    for r in range(a.bench_pairs):
-        for label, lib in (sides if r % 2 == 0 else sides[::-1]):
-            j = json.loads(run(f"bench.py run {r} {label}", ["--bench-child", "--bench-steps", str(a.bench_steps), "--bench-warmup", str(a.bench_warmup)]
-                               + (["--library", lib] if lib else []), 600, lambda ln: ln.startswith("{") and '"value"' in ln))
-            bench.append((label, j.get("value"), j.get("ms_per_step"), j.get("status")))
+    def learner(label, args):
+        res = pc.run_child(__file__, ["--ppo-child"] + args + common, 900, "RESULT ")
+        print(label, json.dumps(res), flush=True)
+        return res
+    bench = pc.bench_py_runs(a.parent_library, a.bench_pairs, a.bench_steps, a.bench_warmup, __file__)
     for r in range(a.pairs):
-        for label, lib in (sides if r % 2 == 0 else sides[::-1]):
-            ppo.append((label, json.loads(run(f"learner run {r} {label}", ["--ppo-child"] + common + (["--library", lib] if lib else []), 900,
-                                              lambda ln: ln.startswith("RESULT "))[7:])))
+        for label, lib in pc.order(sides, r, "alternate"):
+            ppo.append((label, learner(f"learner run {r} {label}", ["--library", lib] if lib else [])))
     for r in range(a.on_runs):
-        on.append(json.loads(run(f"learner run {r} teacher on", ["--ppo-child", "--teacher-coef", str(a.on_coef)] + common, 900, lambda ln: ln.startswith("RESULT "))[7:]))
-    try:
-        commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode().strip()
-    except OSError:
-        commit = ""
+        on.append(learner(f"learner run {r} teacher on", ["--teacher-coef", str(a.on_coef)]))
     lines = ["Kickstarting from the rule-based player: what it costs off and on (tools/bench_teacher.py)",
-             f"commit {commit or 'unknown (no git checkout where it ran)'}; one MI355X, a fresh process per run, the parent's library and this commit's alternating.", ""]
+             f"commit {pc.commit_of_tree()}; one MI355X, a fresh process per run, the parent's library and this commit's alternating.", ""]
     if bench:
         lines += [f"OFF: bench.py --gpus 1 --steps {a.bench_steps} --warmup {a.bench_warmup}: env-steps/s, ms per pass, status"]
         lines += [f"  {label} {value} {ms} {status}" for label, value, ms, status in bench]
-        pv, cv = [b[1] for b in bench if b[0] == "parent"], [b[1] for b in bench if b[0] == "change"]
-        if pv and cv:
-            mean = sum(cv) / len(cv)
-            lines.append(f"  the change's mean {mean:.6g} lies {_where(mean, pv, True)} the parent's spread {min(pv):.6g}..{max(pv):.6g}")
+        if a.parent_library:
+            lines.append("  " + pc.bench_py_sentence(bench, ".6g"))
         lines.append("")
     if ppo:
         lines += [f"OFF: the PPO learner, {a.envs} games x T = {a.num_steps}, bf16 autocast, {a.ppo_epoch} epoch(s) x 64 minibatches of {a.envs * a.num_steps // 64} rows,",
@@ -154,8 +104,7 @@ def main():
         for key, name in (("minibatch_step_ms", "minibatch-step ms"), ("rollout_s", "rollout s")):
             pv, cv = [x[key] for l, x in ppo if l == "parent"], [x[key] for l, x in ppo if l == "change"]
             if pv and cv:
-                mean = sum(cv) / len(cv)
-                lines.append(f"  {name}: the change's mean {mean:.4f} lies {_where(mean, pv, False)} the parent's spread {min(pv):.4f}..{max(pv):.4f}")
+                lines.append(f"  {name}: " + pc.sentence(cv, pv, False, ".4f"))
         lines.append("")
     if on:
         lines += [f"ON (reported, not bounded): RolloutCollector(teacher=ScriptedPolicy(env)), PPOConfig(teacher_coef={a.on_coef}); the same learner run:",

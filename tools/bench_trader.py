@@ -20,57 +20,8 @@ import json
 import os
 import random
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-
-TRADER_SYMBOLS = {"catan_sample_scripted_actions_style", "catan_scripted_trade_counts"}
-
-
-def bench_child(a):
-    """bench.py as it stands, in this process, under the given library (the parent's lacks the trader's entry points: never called here)"""
-    import runpy
-    if a.library:
-        os.environ["CATAN_ALLOW_STALE_LIB"] = "1"
-        from settlers_of_catan_rl_amd import _lib
-        _lib.LIB_PATH = os.path.abspath(a.library)
-        _lib._OPTIONAL |= TRADER_SYMBOLS
-    sys.argv = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(a.bench_steps), "--warmup", str(a.bench_warmup)]
-    runpy.run_path(sys.argv[0], run_name="__main__")
-
-
-def bench_pairs(a, out):
-    """alternating fresh-process runs of bench.py: parent, change, change, parent, ...; a failed run ends the tool"""
-    import subprocess
-    sides, runs = [("parent", a.parent_library), ("change", None)], []
-    out.write("\nbench.py --gpus 1 --steps {} --warmup {} with the style unused, a fresh process per run, the parent's library and this\n"
-              "commit's alternating: env-steps/s, ms per pass, status\n".format(a.bench_steps, a.bench_warmup))
-    for r in range(a.bench_pairs):
-        for label, lib in (sides if r % 2 == 0 else sides[::-1]):
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--bench-child", "--bench-steps", str(a.bench_steps), "--bench-warmup",
-                                str(a.bench_warmup)] + (["--library", lib] if lib else []), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-            text = p.stdout.decode("utf-8", "replace")
-            res = [ln for ln in text.splitlines() if ln.startswith("{") and '"value"' in ln]
-            if p.returncode != 0 or not res:
-                print(text)
-                raise SystemExit(f"bench.py run {r} {label} failed with exit code {p.returncode}")      # nothing more is started on the device
-            j = json.loads(res[-1])
-            runs.append((label, j.get("value"), j.get("ms_per_step"), j.get("status")))
-            line = "  {} {} {} {}".format(*runs[-1])
-            print(line, flush=True)
-            out.write(line + "\n")
-            out.flush()
-    parent, change = [v for l, v, _, _ in runs if l == "parent"], [v for l, v, _, _ in runs if l == "change"]
-    mean = sum(change) / len(change)
-    where = "inside" if min(parent) <= mean <= max(parent) else ("ABOVE" if mean > max(parent) else "BELOW")
-    line = "  the change's mean {:.5e} lies {} the parent's spread {:.5e}..{:.5e} (parent's mean {:.5e})".format(
-        mean, where, min(parent), max(parent), sum(parent) / len(parent))
-    print(line, flush=True)
-    out.write(line + "\n")
-    out.flush()
+import parent_compare as pc
 
 
 def main():
@@ -89,18 +40,17 @@ def main():
     ap.add_argument("--mix-steps", type=int, default=400, help="untimed steps that spread the games over the phases of play")
     ap.add_argument("--max-steps", type=int, default=2500)
     ap.add_argument("--skip-games", action="store_true")
-    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "trader_policy_bench.txt"))
+    ap.add_argument("--out", type=str, default=os.path.join(pc.ROOT, "profiles", "trader_policy_bench.txt"))
     ap.add_argument("--commit", type=str, default=None, help="the commit of this tree (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.bench_child:
-        return bench_child(args)
+        return pc.bench_py_child(args.library, args.bench_steps, args.bench_warmup)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     out = open(args.out, "a")
     if args.parent_library:                 # first, while this process has not touched the device
-        bench_pairs(args, out)
+        pc.bench_py_section(args, out, "style", __file__)
     import numpy as np
     import torch
-    from bench_scripted import commit_of_tree
     from settlers_of_catan_rl_amd import evaluation as ev
     from settlers_of_catan_rl_amd.env import VecCatanEnv
     from settlers_of_catan_rl_amd.scripted import ScriptedPolicy, TraderPolicy
@@ -110,7 +60,7 @@ def main():
               "One JSON line per measurement.  us_per_call as in profiles/scripted_policy_bench.txt (hipEvents around `reps` calls through\n"
               "Python and ctypes; close to host_issue_us = launch-bound).  win shares: the share of games won by the policies named first in\n"
               "`measurement`; trade_counts: catan_scripted_trade_counts over those games.\n\n".format(
-                  args.commit or commit_of_tree(), torch.cuda.get_device_name(0), " ".join(a for a in sys.argv[1:] if not a.startswith("--commit"))))
+                  args.commit or pc.commit_of_tree(), torch.cuda.get_device_name(0), " ".join(a for a in sys.argv[1:] if not a.startswith("--commit"))))
 
     def emit(rec):
         line = json.dumps(rec)
@@ -135,49 +85,20 @@ def call_times(args, emit, VecCatanEnv, torch):
     env.scripted_trade_counts(reset=True)
     buf = torch.empty((args.envs, 18), dtype=torch.int32, device=env.device)
     calls = {"trader": lambda: env.sample_scripted_actions(out=buf, style="trader"), "builder": lambda: env.sample_scripted_actions(out=buf)}
-    for fn in calls.values():
-        for _ in range(10):
-            fn()
-    torch.cuda.synchronize()
-    us, host = {k: [] for k in calls}, {k: [] for k in calls}
-    for _ in range(args.rounds):
-        for k, fn in calls.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            t0 = time.perf_counter()
-            for _ in range(args.reps):
-                fn()
-            host[k].append((time.perf_counter() - t0) * 1e6 / args.reps)
-            e1.record()
-            e1.synchronize()
-            us[k].append(e0.elapsed_time(e1) * 1e3 / args.reps)
-    mmm = lambda xs: [min(xs), sorted(xs)[len(xs) // 2], max(xs)]
+    t = pc.event_call_times(calls, args.reps, args.rounds)
     counts = env.scripted_trade_counts()
     per_call = {k: v / (10 + args.rounds * args.reps) for k, v in counts.items()}
     emit({"measurement": "us_per_call", "envs": args.envs, "reps": args.reps, "rounds": args.rounds,
-          "trader_min_median_max": mmm(us["trader"]), "builder_min_median_max": mmm(us["builder"]),
-          "trader_host_issue_us_min_median_max": mmm(host["trader"]), "builder_host_issue_us_min_median_max": mmm(host["builder"]),
+          "trader_min_median_max": t["trader"]["device_us"], "builder_min_median_max": t["builder"]["device_us"],
+          "trader_host_issue_us_min_median_max": t["trader"]["host_issue_us"], "builder_host_issue_us_min_median_max": t["builder"]["host_issue_us"],
           "trader_decisions_per_call_on_these_states": per_call})
     assert env.invalid_action_count() == 0
 
 
 def games(args, emit, VecCatanEnv, ScriptedPolicy, TraderPolicy, ev, np, torch):
     """(2) evaluation games: the seeds and seat orders of tests/test_gpu_scripted.py's strength test"""
-    class UniformRandom(object):
-        wants_games, include_lstm = True, False
-
-        def rebind(self, e):
-            self.env, self.passes = e, 0
-
-        def act(self, f, lists, lens, masks, games=None, **_kw):
-            a = self.env.sample_random_actions(self.passes).long()
-            self.passes += 1
-            a = a if games is None else a[games.long()]
-            z = torch.zeros((a.shape[0], 1), device=a.device)
-            return z, a, z
-
     n = args.episodes
-    trader, builder, rnd = TraderPolicy(), ScriptedPolicy(), UniformRandom()
+    trader, builder, rnd = TraderPolicy(), ScriptedPolicy(), pc.UniformRandom()
     for name, seats, first in (("trader_vs_3_uniform_random", [trader, rnd, rnd, rnd], 1),
                                ("builder_vs_3_uniform_random", [builder, rnd, rnd, rnd], 1),
                                ("2_traders_vs_2_builders", [trader, trader, builder, builder], 2),
