@@ -127,6 +127,37 @@ int catan_league_stats_enable(catan_env_t* env, int on, const int32_t* slot_of_p
 int catan_league_stats_read(catan_env_t* env, uint64_t* out_host, int reset, catan_stream_t stream);
 int catan_league_stats_count(catan_env_t* env, const int32_t* games, int64_t m, catan_stream_t stream);
 
+/* ---- tournament ----
+ * Round-robin games of M players in lineups of four, seated and booked on the device (csrc/catan_hooks.hip).  The
+ * caller passes L lineups (1..65536), each four player ids in [0, M), repeats allowed, and E, the episodes every game slot plays (0:
+ * unlimited).  Per game the handle keeps
+ *    lineup_of   int32 [n]      the lineup the game's current episode plays, -1: unseated
+ *    pos_of_pid  int32 [n][4]   the lineup position 0..3 that PlayerId p+1 plays (-1: unseated)
+ * and an episode count.  Game g opens its k-th episode (from 0) with s = (env_id0 + g) * E + k, or (env_id0 + g) + k * 2^32 when E == 0,
+ * modulo 2^64: lineup s mod L, seats by the ((s div L) mod 24)-th permutation of (0, 1, 2, 3) in lexicographic order.  No draw is made;
+ * every 24 L consecutive s meet every (lineup, permutation) once; the seating is that of every schedule and every sharding.  With
+ * k == E > 0 the game becomes unseated for good (retired): the caller steps it with the no-op from then on.
+ * Seated: by catan_reset (the selected games) and behind every re-deal of a finished game.  Booked: every finished game in front of its
+ * re-deal, and every seated game catan_reset is about to deal again - without a winner, a draw.
+ * The table is (L + 1) rows of catan_tourney_words() = 16 uint64 sums.  Row l < L, the games of lineup l:
+ *    [0] games   [1] draws   [2..5] wins by lineup position   [6..9] victory points by lineup position
+ *    [10..13] wins by the winner's place in the turn order   [14] turns   [15] spare
+ * (everything from [2] on over the decided games).  Row L, the totals:
+ *    [0] games seen   [1] tallied (seated, a winner)   [2] draws   [3] finished without a seating (retired games)   [4] episodes seated
+ *    [5] games retired
+ * catan_tourney_enable copies the lineups from HOST memory, leaves every game unseated and the table zero, and waits for the stream; the
+ * caller's next catan_reset seats the games.  Enabled again it starts over.  catan_tourney_disable frees everything; off, the default,
+ * not one kernel more is launched and no buffer exists.  catan_tourney_read copies the table, (L + 1) * 16 words, to HOST memory, zeroes
+ * it behind the copy when reset != 0, and synchronises the stream.  catan_tourney_seating gives the two DEVICE arrays above, valid until
+ * the next enable or disable; read them on the stream of the handle's step calls.
+ * CATAN_EINVAL: a null handle or argument; a handle with auto_reset = 0; a handle under the MT19937 contract; an open deferred sequence
+ * (not catan_tourney_seating); L outside 1..65536, M < 1, E < 0, a player id outside [0, M); read and seating while off. */
+int32_t catan_tourney_words(void);
+int catan_tourney_enable(catan_env_t* env, const int32_t* lineups_host, int32_t L, int32_t M, int32_t E, catan_stream_t stream);
+int catan_tourney_disable(catan_env_t* env, catan_stream_t stream);
+int catan_tourney_read(catan_env_t* env, uint64_t* out_host, int32_t reset, catan_stream_t stream);
+int catan_tourney_seating(catan_env_t* env, int32_t** lineup_of_dev, int32_t** pos_of_pid_dev);
+
 /* ---- game records ----
  * Whole games recorded on the device and replayed step by step (csrc/catan_hooks.hip).  A game's draws come from Philox
  * keyed by (seed, global game id) and counted in the state itself (blob word rng_draws), so a start blob, the applied actions, the seed,

@@ -351,6 +351,11 @@ _SIGS = {
     "catan_start_pool_outcomes_words": (C.c_int32, []),
     "catan_start_pool_outcomes_enable": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "catan_start_pool_outcomes_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, _vp]),
+    "catan_tourney_words": (C.c_int32, []),
+    "catan_tourney_enable": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "catan_tourney_disable": (C.c_int, [_vp, _vp]),
+    "catan_tourney_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int32, _vp]),
+    "catan_tourney_seating": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "catan_complete_action_rows": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
     "catan_collector_label": (C.c_int, [C.c_int64, C.c_int32] + [_vp] * 8),
     "catan_imitation_loss_words": (C.c_int64, []),
@@ -365,7 +370,8 @@ _OPTIONAL = {"catan_set_board_configs", "catan_episode_stats_words", "catan_epis
              "catan_record_enable", "catan_record_arm", "catan_record_status", "catan_record_read",
              "catan_start_pool_set", "catan_start_pool_clear", "catan_start_pool_read", "catan_start_pool_size",
              "catan_start_pool_set_weights", "catan_start_pool_outcomes_words", "catan_start_pool_outcomes_enable",
-             "catan_start_pool_outcomes_read"}
+             "catan_start_pool_outcomes_read",
+             "catan_tourney_words", "catan_tourney_enable", "catan_tourney_disable", "catan_tourney_read", "catan_tourney_seating"}
 
 
 def declared_symbols():

@@ -111,6 +111,8 @@ struct catan_env {
     unsigned long long* pool_out;   // ... the table of PO_HEAD + (pool.m + 1) x PO_WORDS sums
     const i32* pool_out_focus;   // ... the caller's focus array (device int32 [n]) or NULL
     int pool_out_on;
+    TourneyBuf tourney;          // catan_tourney_enable: the lineups, the per-game seating and the table (catan_hooks.h); not in `owned`: freed and re-made by every enable
+    int tourney_on;
 };
 static_assert(sizeof(BoardCfg) == sizeof(catan_board_cfg_t) && sizeof(catan_board_cfg_t) == 56 &&
               offsetof(BoardCfg, terrain) == offsetof(catan_board_cfg_t, terrain) &&
@@ -469,6 +471,18 @@ static void enqueue_start_pool_origin_clear(catan_env_t* e, const long* idx, lon
     if (!e->pool_out_on) return;
     (void)pool_launch_origin_clear(e->pool_origin, e->n, idx, cnt, st);
 }
+// Tournament (catan_tourney_enable).  The tally: at the hook of the league results, in front of the consumer of a re-deal
+// list, or (count_p == nullptr) in front of catan_reset's deal over the games with sel[g] != 0 (sel == nullptr: every game).  The seat:
+// behind the consumer or that deal, at the sites of the start pool's install; it writes the handle's three per-game arrays and nothing of
+// a game.  Off (the default): nothing is launched.
+static void enqueue_tourney_tally(catan_env_t* e, const u32* count_p, const i32* list, const u8* sel, hipStream_t st) {
+    if (!e->tourney_on) return;
+    (void)tourney_launch_tally(e->ctx, e->tourney, count_p, list, sel, st);
+}
+static void enqueue_tourney_seat(catan_env_t* e, const u32* count_p, const i32* list, const u8* sel, hipStream_t st) {
+    if (!e->tourney_on) return;
+    (void)tourney_launch_seat(e->ctx, e->tourney, count_p, list, sel, st);
+}
 // k_step with G games per wave in one-wave workgroups; pend.sample (fused-sampling rollouts): actions from / to the side rows
 template <int G>
 static void launch_step(catan_env_t* e, const int32_t* actions, float* reward, uint8_t* done, hipStream_t st, const StepCfg& sc, const u32* bins) {
@@ -596,6 +610,7 @@ int catan_create(catan_env_t** out, int device, int64_t n_envs, uint64_t seed, u
 
 static void record_free(catan_env_t* e);
 static void start_pool_free(catan_env_t* e);
+static void tourney_free(catan_env_t* e);
 void catan_destroy(catan_env_t* e) {
     if (!e) return;
     hipSetDevice(e->device);
@@ -606,6 +621,7 @@ void catan_destroy(catan_env_t* e) {
     if (e->lstats) hipFree(e->lstats);
     record_free(e);
     start_pool_free(e);
+    tourney_free(e);
     for (hipStream_t st : { e->fstream, e->sstream, e->side }) if (st) hipStreamDestroy(st);
     for (hipEvent_t ev : { e->ev_fready[0], e->ev_fready[1], e->ev_fready[2], e->ev_fdone[0], e->ev_fdone[1], e->ev_fdone[2], e->ev_sdone[0], e->ev_sdone[1],
                            e->ev_fork, e->ev_join })
@@ -628,11 +644,13 @@ int catan_reset(catan_env_t* e, const uint8_t* reset_mask, catan_stream_t stream
     NOT_DEFERRED(e, "catan_reset");
     int r = mt_refill(e, S(stream));
     if (r != CATAN_OK) return r;
+    enqueue_tourney_tally(e, nullptr, nullptr, reset_mask, S(stream));   // (in front of the deal: the selected games' records are still what they ended as)
     hipLaunchKernelGGL(k_reset, dim3((unsigned)(e->N < 16384 ? e->N : 16384)), dim3(64), 0, S(stream), e->ctx, reset_mask, 0);
     HIPCHK(hipGetLastError());
     r = launch_masks(e, S(stream));
     if (r != CATAN_OK) return r;
     enqueue_start_pool_sel(e, reset_mask, S(stream));            // (behind the masks of the fresh deals: an installed game takes its entry's)
+    enqueue_tourney_seat(e, nullptr, nullptr, reset_mask, S(stream));
     HIPCHK(hipGetLastError());
     return CATAN_OK;
 }
@@ -842,18 +860,19 @@ static int enqueue_tier1(catan_env_t* e, float* reward, uint8_t* done, hipStream
 // One re-deal list (its length at *count_p) and everything that hangs on the moment it is consumed, on stream st.  The order is a correctness
 // condition, and this is the one place that states it:
 //   in front of the consumer, the hooks that READ the listed games' final states, which the consumer overwrites: the finished-game
-//     statistics, the league results, the start pool's per-entry outcomes (they also read the origins the pool install rewrites) and the
-//     recorder's seal;
+//     statistics, the league results, the start pool's per-entry outcomes (they also read the origins the pool install rewrites), the
+//     tournament's tally (it reads the seating the seat hook rewrites) and the recorder's seal;
 //   the consumer: a fresh deal (k_reset_list), a fresh deal that also deals step_impl's speculative successors into the shadow arrays
 //     (pend.spec; they are no episodes, so the hooks see the real list only), or the install of those shadows (k_install_list);
 //   behind it, the hooks that WRITE the fresh games: the start pool's install, then the recorder's opening, whose start blob is the state
-//     the install left.
+//     the install left; and the tournament's seat, which writes the games' next seating and nothing of the games.
 // All of it stands in front of whatever the caller records or waits for on st to publish the re-deal.  Every hook that is off launches nothing.
 enum Redeal { REDEAL_FRESH, REDEAL_FRESH_AND_SPEC, REDEAL_INSTALL };
 static void enqueue_redeal(catan_env_t* e, Redeal how, const u32* count_p, const i32* list, u8* busy, hipStream_t st) {
     enqueue_episode_stats(e, count_p, list, st);
     enqueue_league_stats(e, count_p, list, st);
     enqueue_start_pool_outcomes(e, count_p, list, st);
+    enqueue_tourney_tally(e, count_p, list, nullptr, st);
     enqueue_record_seal(e, count_p, list, st);
     if (how == REDEAL_INSTALL)
         hipLaunchKernelGGL(k_install_list, dim3(256), dim3(64), 0, st, e->ctx, e->mpk, limits_of(e), count_p, list, busy,
@@ -866,6 +885,7 @@ static void enqueue_redeal(catan_env_t* e, Redeal how, const u32* count_p, const
                            (const u32*)nullptr, (const u64*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u, e->pend);
     enqueue_start_pool(e, count_p, list, st);
     enqueue_record_open(e, count_p, list, st);
+    enqueue_tourney_seat(e, count_p, list, nullptr, st);
 }
 // tier 2 (+ the completion of its games) and the re-deals of window slot pend.sa on stream st.
 //   deferred window: the games that ended in k_step / k_lr_finish (list 0) are re-dealt on the side stream while tier 2 runs,
@@ -2504,6 +2524,73 @@ int catan_start_pool_outcomes_read(catan_env_t* e, uint64_t* out_host, int32_t r
     if (!e->pool_out_on) return fail(CATAN_EINVAL, "catan_start_pool_outcomes_read: outcomes are not enabled on this handle (catan_start_pool_outcomes_enable)");
     NOT_DEFERRED(e, "catan_start_pool_outcomes_read");          // (the side streams of an open sequence are joined by catan_step_flush)
     return read_counters(out_host, e->pool_out, start_pool_outcome_words(e->pool.m) * sizeof(unsigned long long), reset, S(stream));
+}
+
+// ---- tournament (the kernels are catan_hooks.hip's, the hooks that launch them stand beside enqueue_start_pool)
+static void tourney_free(catan_env_t* e) {
+    for (void* p : { (void*)e->tourney.lineups, (void*)e->tourney.lineup_of, (void*)e->tourney.pos_of_pid, (void*)e->tourney.episode, (void*)e->tourney.table })
+        if (p) hipFree(p);
+    e->tourney = TourneyBuf{};
+    e->tourney_on = 0;
+}
+static size_t tourney_table_bytes(int L) { return ((size_t)L + 1) * TY_WORDS * sizeof(unsigned long long); }
+int32_t catan_tourney_words(void) { return TY_WORDS; }
+int catan_tourney_enable(catan_env_t* e, const int32_t* lineups_host, int32_t L, int32_t M, int32_t E, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_tourney_enable: null handle");
+    if (!e->cfg.auto_reset) return fail(CATAN_EINVAL, "catan_tourney_enable: the handle has auto_reset = 0 (no game is re-dealt, so none would be booked or seated anew)");
+    NOT_DEFERRED(e, "catan_tourney_enable");
+    NOT_MT(e, "catan_tourney_enable");
+    if (L < 1 || L > TOURNEY_MAX_LINEUPS) return fail(CATAN_EINVAL, "catan_tourney_enable: L must be in 1..65536");
+    if (M < 1) return fail(CATAN_EINVAL, "catan_tourney_enable: M must be at least 1");
+    if (E < 0) return fail(CATAN_EINVAL, "catan_tourney_enable: E must be 0 (unlimited) or positive");
+    if (!lineups_host) return fail(CATAN_EINVAL, "catan_tourney_enable: null lineups");
+    for (long i = 0; i < 4l * L; i++)
+        if (lineups_host[i] < 0 || lineups_host[i] >= M)
+            return fail(CATAN_EINVAL, "catan_tourney_enable: lineup " + std::to_string(i / 4) + " names player " + std::to_string(lineups_host[i]) + ", outside 0.." + std::to_string(M - 1));
+    const hipStream_t st = S(stream);
+    if (e->tourney_on) OK_OR_RETURN(sync_hook_streams(e, st));   // hooks in flight read and write the old arrays
+    tourney_free(e);
+    TourneyBuf tb{};
+    tb.L = L; tb.E = (u32)E;
+    i32* lineups = nullptr;
+    hipError_t rc = hipMalloc((void**)&lineups, (size_t)L * 4 * sizeof(i32));
+    tb.lineups = lineups;
+    if (rc == hipSuccess) rc = hipMalloc((void**)&tb.lineup_of, (size_t)e->n * sizeof(i32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&tb.pos_of_pid, (size_t)e->n * 4 * sizeof(i32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&tb.episode, (size_t)e->n * sizeof(u32));
+    if (rc == hipSuccess) rc = hipMalloc((void**)&tb.table, tourney_table_bytes(L));
+    e->tourney = tb;                                             // (tourney_free drops whatever was allocated)
+    if (rc != hipSuccess) { tourney_free(e); return fail(CATAN_ENOMEM, std::string("catan_tourney_enable: hipMalloc: ") + hipGetErrorString(rc)); }
+    // every game unseated, no episode opened: the caller's catan_reset seats them
+    rc = hipMemcpyAsync(lineups, lineups_host, (size_t)L * 4 * sizeof(i32), hipMemcpyHostToDevice, st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(tb.lineup_of, 0xFF, (size_t)e->n * sizeof(i32), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(tb.pos_of_pid, 0xFF, (size_t)e->n * 4 * sizeof(i32), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(tb.episode, 0, (size_t)e->n * sizeof(u32), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(tb.table, 0, tourney_table_bytes(L), st);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(st);         // (the lineups are the caller's host memory)
+    if (rc != hipSuccess) { tourney_free(e); return fail(CATAN_EHIP, std::string("catan_tourney_enable: ") + hipGetErrorString(rc)); }
+    e->tourney_on = 1;
+    return CATAN_OK;
+}
+int catan_tourney_disable(catan_env_t* e, catan_stream_t stream) {
+    if (!e) return fail(CATAN_EINVAL, "catan_tourney_disable: null handle");
+    NOT_DEFERRED(e, "catan_tourney_disable");
+    if (!e->tourney_on) return CATAN_OK;
+    OK_OR_RETURN(sync_hook_streams(e, S(stream)));
+    tourney_free(e);
+    return CATAN_OK;
+}
+int catan_tourney_read(catan_env_t* e, uint64_t* out_host, int32_t reset, catan_stream_t stream) {
+    if (!e || !out_host) return fail(CATAN_EINVAL, "catan_tourney_read: null argument");
+    if (!e->tourney_on) return fail(CATAN_EINVAL, "catan_tourney_read: no tournament is enabled on this handle (catan_tourney_enable)");
+    NOT_DEFERRED(e, "catan_tourney_read");             // (the side streams of an open sequence are joined by catan_step_flush)
+    return read_counters(out_host, e->tourney.table, tourney_table_bytes(e->tourney.L), reset, S(stream));
+}
+int catan_tourney_seating(catan_env_t* e, int32_t** lineup_of_dev, int32_t** pos_of_pid_dev) {
+    if (!e || !lineup_of_dev || !pos_of_pid_dev) return fail(CATAN_EINVAL, "catan_tourney_seating: null argument");
+    if (!e->tourney_on) return fail(CATAN_EINVAL, "catan_tourney_seating: no tournament is enabled on this handle (catan_tourney_enable)");
+    *lineup_of_dev = e->tourney.lineup_of; *pos_of_pid_dev = e->tourney.pos_of_pid;
+    return CATAN_OK;
 }
 
 // ---- the players that read the games themselves.  Host code only, but for k_sample_scripted (catan_scripted.hip,

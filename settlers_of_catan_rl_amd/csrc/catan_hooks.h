@@ -1,10 +1,10 @@
 // catan_hooks.h - what catan_abi.hip sees of catan_hooks.hip: the launch functions of the recorder's kernels, of the
-// start pool's (8.11) and of its weighted pick and outcome tallies (8.12), and the layouts both sides share.  catan_hooks.hip is the
+// start pool's (8.11), of its weighted pick and outcome tallies (8.12) and of the tournament's (8.16), and the layouts both sides share.  catan_hooks.hip is the
 // library's third translation unit and third gfx950 code object; the ABI's entry points - argument checks, the handles' fields,
 // allocation, the order of the launches and synchronisations - stand in catan_abi.hip and launch through these functions.
 //
 // What a launch function returns.  Those an entry point calls and checks on the spot return hipGetLastError().  Those of the hooks
-// that enqueue_redeal and the stepping calls run (append, seal, open, install, outcomes, origin_clear) return hipPeekAtLastError(): the
+// that enqueue_redeal and the stepping calls run (append, seal, open, install, outcomes, origin_clear, tally, seat) return hipPeekAtLastError(): the
 // hooks are void, the status stays pending for the hipGetLastError at the end of the caller's sequence, where it has always been read.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -86,5 +86,46 @@ hipError_t pool_launch_install(const Ctx& c, u32* mpk, const StartPoolBuf& pb, c
 hipError_t pool_launch_origin_clear(i32* origin, long n, const long* idx, long cnt, hipStream_t stream);
 // focus: device int32 [n] PlayerId per game (0: none), or null; table: 2 + (m + 1) x PO_WORDS uint64 sums
 hipError_t pool_launch_outcomes(const Ctx& c, const u32* count_p, const i32* list, const i32* origin, const i32* focus, unsigned long long* table, int m, hipStream_t stream);
+
+// ---- tournament
+// Columns of a lineup's row of the table (restated in include/catan_hip_tuning.h and spec.py TOURNAMENT_FIELDS); row L is the totals'.
+// Every column but the first two is a sum over the row's DECIDED games (games - draws).
+constexpr int TY_GAMES = 0;              // finished games of the lineup
+constexpr int TY_DRAWS = 1;              // ... without a winner: reset before their end
+constexpr int TY_WINS = 2;               // +lineup position (4)
+constexpr int TY_VP = 6;                 // +lineup position (4): victory points
+constexpr int TY_WINS_BY_TURN = 10;      // +the winner's place in player_order (4)
+constexpr int TY_TURNS = 14;             // sum of the final W_TURN
+constexpr int TY_SPARE = 15;
+constexpr int TY_WORDS = 16;
+constexpr int TT_SEEN = 0;               // games the tally was handed
+constexpr int TT_TALLIED = 1;            // of them seated, with a winner 1..4
+constexpr int TT_DRAWS = 2;              // seated, without a winner
+constexpr int TT_SKIPPED_UNSEATED = 3;   // finished without a seating (retired games, padding games)
+constexpr int TT_SEATED = 4;             // episodes opened by the seat hook
+constexpr int TT_RETIRED = 5;            // games retired by it: each game once
+constexpr int TOURNEY_MAX_LINEUPS = 65536;
+// The LDS budget of the on-chip table: 8 KiB = 64 rows of 16 uint64, i.e. up to 63 lineups and the totals (all_lineups(6) is 15 rows,
+// versus_anchors of a candidate and three anchors 4); a larger table - all_lineups(8) is 70 - goes to HBM directly.
+constexpr int TOURNEY_LDS_ROWS = 64;
+constexpr int TOURNEY_LDS_MAX_LINEUPS = TOURNEY_LDS_ROWS - 1;
+constexpr int TOURNEY_GRID = 8;          // as LEAGUE_STATS_GRID: a pass finishes tens of games
+constexpr int TOURNEY_SEL_GRID_MAX = 1024;   // catan_reset's forms: one lane per game of the handle, up to this many waves
+
+struct TourneyBuf {
+    const i32* lineups;          // [L][4] player ids
+    i32* lineup_of;              // [n] the game's lineup, -1: unseated
+    i32* pos_of_pid;             // [n][4] the lineup position 0..3 that PlayerId p+1 plays (-1: unseated)
+    u32* episode;                // [n] episodes opened so far; E + 1 once retired
+    unsigned long long* table;   // [(L + 1)][TY_WORDS]
+    int L;
+    u32 E;                       // episodes per game slot, 0: unlimited
+};
+
+// The tally in front of a re-deal and the seating behind it.  count_p != null: the games of `list` (its length at *count_p); count_p ==
+// null: the games with sel[g] != 0, or every game (sel == null) - catan_reset's forms, where an unseated game is no finished one and is
+// passed over.
+hipError_t tourney_launch_tally(const Ctx& c, const TourneyBuf& tb, const u32* count_p, const i32* list, const u8* sel, hipStream_t stream);
+hipError_t tourney_launch_seat(const Ctx& c, const TourneyBuf& tb, const u32* count_p, const i32* list, const u8* sel, hipStream_t stream);
 
 }  // namespace catan

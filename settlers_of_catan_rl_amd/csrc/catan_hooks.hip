@@ -1,6 +1,7 @@
 // catan_hooks.hip - the opt-in hooks of a finished game and of a re-deal: whole games recorded on the device, re-dealt
-// games started from a pool of saved positions (8.11), the pool's weighted pick and its per-entry outcome tallies (8.12).  All opt-in:
-// with no recorder enabled and no pool installed nothing here is launched.
+// games started from a pool of saved positions (8.11), the pool's weighted pick and its per-entry outcome tallies (8.12), round-robin
+// tournaments seated and booked at the re-deal (8.16).  All opt-in: with no recorder enabled, no pool installed and no tournament enabled
+// nothing here is launched.
 //
 // The library's THIRD translation unit and gfx950 code object, for the reason at the top of catan_players.hip: the first code object holds
 // k_step and the learner's kernels and stays, byte for byte in .text, what it is without these hooks (profiles/hooks_unit.txt).  Nothing of
@@ -351,6 +352,147 @@ hipError_t pool_launch_origin_clear(i32* origin, long n, const long* idx, long c
 }
 hipError_t pool_launch_outcomes(const Ctx& c, const u32* count_p, const i32* list, const i32* origin, const i32* focus, unsigned long long* table, int m, hipStream_t stream) {
     hipLaunchKernelGGL(k_pool_outcomes, dim3(POOL_OUTCOMES_GRID), dim3(64), 0, stream, c, count_p, list, origin, focus, table, m);
+    return hipPeekAtLastError();
+}
+
+// ================================================================================================ tournament
+// A table of L lineups, each four player ids; per game the handle keeps its lineup (-1: unseated), the lineup position that each
+// PlayerId plays, and the number of episodes it has opened.  Both hooks take one lane per game and read or write nothing of the game's
+// state but - the tally - the final record's winner, points, turn and order.
+//
+// The seating, in integers and without a draw.  Game g opens its k-th episode (k = episode[g], counted from 0) with
+//   s = (env_id0 + g) * E + k          (E > 0: every game slot plays E episodes, so the s of all games and episodes are 0, 1, 2, ...)
+//   s = (env_id0 + g) + k * 2^32       (E == 0: unlimited)
+// both modulo 2^64; the lineup is s mod L and the seat permutation the ((s div L) mod 24)-th permutation of (0, 1, 2, 3) in
+// lexicographic order: entry p of it is the lineup position PlayerId p+1 plays.  Any 24 L consecutive s meet every (lineup, permutation)
+// pair once.  s depends on the global game id and the episode number alone: every schedule and every sharding seats alike.
+// k == E > 0: the game becomes unseated - retired -, is counted once, and stays so.
+//
+// The permutation by its factorial digits: digit j picks among the positions still free, in ascending order (2 bits each in `avail`).
+DEVI u32 tourney_perm(u32 idx) {
+    const u32 d[3] = { idx / 6u, (idx % 6u) / 2u, idx & 1u };
+    u32 avail = 0xE4u, out = 0u;                       // positions 3, 2, 1, 0
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const u32 sh = 2u * d[j];
+        out |= ((avail >> sh) & 3u) << (2 * j);
+        avail = (avail & ((1u << sh) - 1u)) | ((avail >> (sh + 2u)) << sh);
+    }
+    return out | ((avail & 3u) << 6);                  // 2 bits per PlayerId-1
+}
+
+// one lane, one freshly dealt game g (0 <= g < c.n)
+DEVI void tourney_seat_game(const Ctx& c, const TourneyBuf& tb, long g) {
+    unsigned long long* const tot = tb.table + (size_t)tb.L * TY_WORDS;
+    const u32 k = tb.episode[g];
+    if (tb.E != 0u && k >= tb.E) {
+        tb.lineup_of[g] = -1;
+        reinterpret_cast<int4*>(tb.pos_of_pid)[g] = make_int4(-1, -1, -1, -1);
+        if (k == tb.E) { tb.episode[g] = tb.E + 1u; atomicAdd(&tot[TT_RETIRED], 1ull); }
+        return;
+    }
+    const u64 id = c.env_id0 + (u64)g;
+    const u64 s = tb.E != 0u ? id * (u64)tb.E + (u64)k : id + ((u64)k << 32);
+    const u32 perm = tourney_perm((u32)((s / (u64)tb.L) % 24ull));
+    tb.lineup_of[g] = (i32)(s % (u64)tb.L);
+    reinterpret_cast<int4*>(tb.pos_of_pid)[g] = make_int4((int)(perm & 3u), (int)((perm >> 2) & 3u), (int)((perm >> 4) & 3u), (int)(perm >> 6));
+    tb.episode[g] = k + 1u;
+    atomicAdd(&tot[TT_SEATED], 1ull);
+}
+// Behind the consumer of a re-deal list, same stream, same list (count_p != null: its length at *count_p), and behind catan_reset's deal
+// (count_p == null): the games with sel[g] != 0, or every game (sel == null).  One lane per game.
+__global__ __launch_bounds__(64) void k_tourney_seat(Ctx c, TourneyBuf tb, const u32* __restrict__ count_p, const i32* __restrict__ list, const u8* __restrict__ sel) {
+    const u32 count = count_p != nullptr ? *count_p : (u32)c.n;
+    for (u32 r = (u32)blockIdx.x * 64u + threadIdx.x; r < count; r += gridDim.x * 64u) {
+        const long g = count_p != nullptr ? (long)list[r] : (long)r;
+        if (g < 0 || g >= c.n) continue;
+        if (count_p == nullptr && sel != nullptr && sel[g] == 0) continue;
+        tourney_seat_game(c, tb, g);
+    }
+}
+
+// one finished game e into `acc` (the table or its LDS copy; `tot` its totals row).  skip_unseated: catan_reset's forms
+DEVI void tourney_tally_game(const Ctx& c, const TourneyBuf& tb, unsigned long long* acc, unsigned long long* tot, long e, bool skip_unseated) {
+    int lineup = -1, pos[4] = { -1, -1, -1, -1 }, used = 0;
+    if (e < c.n) {                                        // (the arrays have n rows; a padding game has none)
+        lineup = tb.lineup_of[e];
+        const int4 v = reinterpret_cast<const int4*>(tb.pos_of_pid)[e];
+        pos[0] = v.x; pos[1] = v.y; pos[2] = v.z; pos[3] = v.w;
+#pragma unroll
+        for (int p = 0; p < 4; p++) used |= (pos[p] >= 0 && pos[p] <= 3) ? 1 << pos[p] : 0;
+    }
+    const bool seated = lineup >= 0 && lineup < tb.L && used == 15;
+    if (!seated && skip_unseated) return;
+    atomicAdd(&tot[TT_SEEN], 1ull);
+    if (!seated) { atomicAdd(&tot[TT_SKIPPED_UNSEATED], 1ull); return; }
+    const St s(c.R, c.N, e);
+    const int winner = s.b(B_WINNER);
+    unsigned long long* const row = acc + (size_t)lineup * TY_WORDS;
+    atomicAdd(&row[TY_GAMES], 1ull);
+    if (winner < 1 || winner > 4) { atomicAdd(&row[TY_DRAWS], 1ull); atomicAdd(&tot[TT_DRAWS], 1ull); return; }
+    atomicAdd(&tot[TT_TALLIED], 1ull);
+    const int w0 = winner - 1;
+    int wpos = 0;
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        wpos = w0 == p ? pos[p] : wpos;
+        const int vp = s.pb(p, P_VP);
+        if (vp) atomicAdd(&row[TY_VP + pos[p]], (unsigned long long)vp);
+    }
+    atomicAdd(&row[TY_WINS + wpos], 1ull);
+    atomicAdd(&row[TY_WINS_BY_TURN + ((s.b(B_SEATOF) >> (2 * w0)) & 3)], 1ull);
+    const unsigned long long turn = s.w(W_TURN);
+    if (turn) atomicAdd(&row[TY_TURNS], turn);
+}
+// In front of the consumer of a re-deal list, beside k_league_stats and by its scheme: one lane per listed game; LDS_TABLE: the
+// workgroup (one wave) accumulates in an LDS copy of the table and then issues ONE global atomic per non-zero entry; otherwise
+// (L > TOURNEY_LDS_MAX_LINEUPS) every contribution is a global atomic of its own.  All sums are integer sums: the result does not
+// depend on the order of arrival.
+// count_p == null: in front of catan_reset's deal, the games with sel[g] != 0 (sel == null: every game).  The seated ones among them
+// are booked - as draws, unless they just ended, and a handle with auto_reset re-deals those itself -; an unseated one is no finished
+// game (its reset is what seats it) and is passed over.
+template <bool LDS_TABLE>
+__global__ __launch_bounds__(64) void k_tourney_tally(Ctx c, TourneyBuf tb, const u32* __restrict__ count_p, const i32* __restrict__ list, const u8* __restrict__ sel) {
+    __shared__ unsigned long long lds[LDS_TABLE ? TOURNEY_LDS_ROWS * TY_WORDS : 1];
+    const int lane = threadIdx.x;
+    const u32 count = count_p != nullptr ? *count_p : (u32)c.n;
+    if ((u32)blockIdx.x * 64u >= count) return;          // (wave-uniform: nothing listed for this wave)
+    const int words = (tb.L + 1) * TY_WORDS;             // (the host launches LDS_TABLE only where this fits)
+    unsigned long long* const acc = LDS_TABLE ? lds : tb.table;
+    if (LDS_TABLE) {
+        for (int i = lane; i < words; i += 64) lds[i] = 0ull;
+        __syncthreads();
+    }
+    for (u32 r = (u32)blockIdx.x * 64u + (u32)lane; r < count; r += gridDim.x * 64u) {
+        const long e = count_p != nullptr ? (long)list[r] : (long)r;
+        if (e < 0 || e >= c.N) continue;
+        if (count_p == nullptr && sel != nullptr && sel[e] == 0) continue;
+        tourney_tally_game(c, tb, acc, acc + (size_t)tb.L * TY_WORDS, e, count_p == nullptr);
+    }
+    if (LDS_TABLE) {
+        __syncthreads();
+        for (int i = lane; i < words; i += 64) {
+            const unsigned long long v = lds[i];
+            if (v != 0ull) atomicAdd(&tb.table[i], v);
+        }
+    }
+}
+
+// catan_reset's forms: one lane per game of the handle, up to TOURNEY_SEL_GRID_MAX waves, grid-stride beyond
+static unsigned tourney_grid(const Ctx& c, const u32* count_p) {
+    if (count_p != nullptr) return TOURNEY_GRID;
+    const unsigned b = hooks_blocks(c.n, 64);
+    return b < (unsigned)TOURNEY_SEL_GRID_MAX ? b : (unsigned)TOURNEY_SEL_GRID_MAX;
+}
+hipError_t tourney_launch_tally(const Ctx& c, const TourneyBuf& tb, const u32* count_p, const i32* list, const u8* sel, hipStream_t stream) {
+    if (tb.L <= TOURNEY_LDS_MAX_LINEUPS)
+        hipLaunchKernelGGL(k_tourney_tally<true>, dim3(tourney_grid(c, count_p)), dim3(64), 0, stream, c, tb, count_p, list, sel);
+    else
+        hipLaunchKernelGGL(k_tourney_tally<false>, dim3(tourney_grid(c, count_p)), dim3(64), 0, stream, c, tb, count_p, list, sel);
+    return hipPeekAtLastError();
+}
+hipError_t tourney_launch_seat(const Ctx& c, const TourneyBuf& tb, const u32* count_p, const i32* list, const u8* sel, hipStream_t stream) {
+    hipLaunchKernelGGL(k_tourney_seat, dim3(tourney_grid(c, count_p)), dim3(64), 0, stream, c, tb, count_p, list, sel);
     return hipPeekAtLastError();
 }
 

@@ -23,6 +23,19 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class _DeviceArray(object):
+    """int32 device memory the library owns, described for torch.as_tensor (the CUDA array interface, version 2)"""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+def _device_view(ptr, shape, device):
+    """-> an int32 tensor over the library's memory at `ptr` (no copy)"""
+    with torch.cuda.device(device):
+        return torch.as_tensor(_DeviceArray(ptr, shape), device=device)
+
+
 def board_cfg_struct(cfg):
     """a board layout dict (spec.normalise_board_config) -> catan_board_cfg_t"""
     randomise, terrain, numbers = spec.normalise_board_config(cfg)
@@ -191,6 +204,42 @@ class VecCatanEnv(object):
         g = None if games is None else torch.as_tensor(games, device=self.device).to(torch.int32).contiguous()
         m = int(g.numel()) if g is not None else (self.n if count is None else int(count))
         _lib.check(self.L.catan_league_stats_count(self.h, _ptr(g), m, _stream()))
+
+    # ---- tournament (include/catan_hip_tuning.h "tournament"; tournament.py)
+    def enable_tournament(self, lineups, num_players, episodes_per_game=0):
+        """From the next reset() on every game plays one of `lineups` - int [L, 4] player ids in [0, num_players), repeats allowed, up to
+        65536 rows - seated by the library's rule (no draw), every finished game is booked by who sat where, and a game
+        retires (tournament_seating: lineup -1; step it with the no-op) once it has played episodes_per_game episodes (0: unlimited).
+        Every game is unseated and the table zero until the caller's reset()."""
+        fn = self._entry("catan_tourney_enable")
+        a = np.ascontiguousarray(np.asarray(lineups.cpu() if torch.is_tensor(lineups) else lineups), dtype=np.int32)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError(f"tournament lineups: shape [L, 4] expected, got {tuple(a.shape)}")
+        _lib.check(fn(self.h, a.ctypes.data_as(C.c_void_p), int(a.shape[0]), int(num_players), int(episodes_per_game), _stream()))
+        self._tourney_lineups, self._tourney_seating = int(a.shape[0]), None
+
+    def disable_tournament(self):
+        """frees the tournament's buffers: nothing of it is launched from here on"""
+        _lib.check(self._entry("catan_tourney_disable")(self.h, _stream()))
+        self._tourney_lineups, self._tourney_seating = 0, None
+
+    def tournament_table(self, reset=False):
+        """-> int64 [L + 1, spec.TOURNAMENT_WORDS] (host): a row per lineup (spec.TOURNAMENT_FIELDS) and the totals row
+        (spec.TOURNAMENT_TOTALS) since enable_tournament (or the last read with reset=True); waits for the current stream"""
+        rows = getattr(self, "_tourney_lineups", 0) + 1
+        assert int(self._entry("catan_tourney_words")()) == spec.TOURNAMENT_WORDS
+        out = self._read_u64("catan_tourney_read", rows * spec.TOURNAMENT_WORDS, reset)
+        return torch.from_numpy(out.astype(np.int64).reshape(rows, spec.TOURNAMENT_WORDS))
+
+    def tournament_seating(self):
+        """-> (lineup_of int32 [n], pos_of_pid int32 [n, 4]): views of the library's own device arrays - the lineup each game plays (-1:
+        unseated) and the lineup position PlayerId p+1 plays - current on this stream behind reset() and step(); valid until the
+        tournament is enabled again or disabled"""
+        if getattr(self, "_tourney_seating", None) is None:
+            lp, pp = C.c_void_p(), C.c_void_p()
+            _lib.check(self._entry("catan_tourney_seating")(self.h, C.byref(lp), C.byref(pp)))
+            self._tourney_seating = (_device_view(lp.value, (self.n,), self.device), _device_view(pp.value, (self.n, 4), self.device))
+        return self._tourney_seating
 
     # ---- game records (include/catan_hip_tuning.h "game records"; record.py)
     def enable_recording(self, games, capacity=8192):

@@ -80,6 +80,24 @@ class TraderPolicy(ScriptedPolicy):
     default_style = "trader"
 
 
+class RandomPolicy(GamesPolicy):
+    """The uniform-random legal sampler (env.sample_random_actions) as a seat: the weakest fixed player, the floor of a rating scale.
+    Every pass draws one action for every game of the env at the next step index (the number of passes since it was bound) and hands
+    out the rows asked for: equal games and an equal pass number give equal actions."""
+
+    def __init__(self, env=None):
+        self.env, self.passes = env, 0
+
+    def rebind(self, env):
+        self.env, self.passes = env, 0
+        return self
+
+    def _rows(self, env, games):
+        a = env.sample_random_actions(self.passes)
+        self.passes += 1
+        return a if games is None else a[games.long()]
+
+
 class PlayoutPolicy(GamesPolicy):
     """The flat Monte-Carlo playout player (env.playout_actions): per decision it takes the builder's move, the trader's
     and `randoms` uniform-random legal ones, plays each out `playouts` times for `depth` env steps with the rule-based player of

@@ -282,6 +282,19 @@ def league_stats_table(words, num_nets):
     return out
 
 
+# ---------------------------------------------------------------- tournament (include/catan_hip_tuning.h catan_tourney_*)
+# one row of uint64 sums per lineup; csrc/catan_hooks.h holds the same layout as TY_* offsets.  Everything behind "draws" is summed over
+# the row's decided games; wins_pos / vp_pos are by lineup position, wins_turn by the winner's place in the turn order
+TOURNAMENT_FIELDS = ["games", "draws", "wins_pos0", "wins_pos1", "wins_pos2", "wins_pos3", "vp_pos0", "vp_pos1", "vp_pos2", "vp_pos3",
+                     "wins_turn0", "wins_turn1", "wins_turn2", "wins_turn3", "turns_sum", "spare"]
+TOURNAMENT_WORDS = len(TOURNAMENT_FIELDS)                          # 16
+TOURNAMENT_GAMES, TOURNAMENT_DRAWS, TOURNAMENT_WINS, TOURNAMENT_VP, TOURNAMENT_WINS_BY_TURN, TOURNAMENT_TURNS = 0, 1, 2, 6, 10, 14
+# ... and the last row, the totals (TT_* there)
+TOURNAMENT_TOTALS = ["seen", "tallied", "draws", "skipped_unseated", "seated", "retired"]
+TOURNAMENT_MAX_LINEUPS = 65536
+TOURNAMENT_LDS_MAX_LINEUPS = 63                                    # up to here the tally accumulates in LDS (TOURNEY_LDS_MAX_LINEUPS there)
+
+
 # ---------------------------------------------------------------- playout player (include/catan_hip_tuning.h catan_playout_actions)
 # the int64 row of one (row, candidate), in order; csrc/catan_players.h holds the same layout as PS_* offsets
 PLAYOUT_STAT_FIELDS = ["valid", "sims", "finished", "wins", "score_sum", "vp_sum", "steps_sum"]

@@ -39,6 +39,8 @@ class TrainArgs(object):
     eval_scripted_baseline = False       # opt-in: the evaluation also plays the rule-based player (scripted.ScriptedPolicy) -> log["scripted"]
     eval_trader_baseline = False         # opt-in: ... and the trading rule-based player (scripted.TraderPolicy) -> log["trader"]
     eval_playout_baseline = False        # opt-in: ... and the playout player (scripted.PlayoutPolicy) -> log["playout"]
+    eval_ladder = False                  # opt-in: ... and a tournament of the net against builder, trader and random -> log["ladder"]
+    eval_ladder_episodes = 2             # ... episodes per game slot in it
     teacher = None                       # opt-in kickstarting: "scripted" - the rule-based player labels the rollouts (make_teacher); "trader": its trading style (8.14); "playout": the playout player (8.15)
     playout_k = None                     # ... teacher "playout": PlayoutPolicy's playouts, depth and randoms (None: its defaults)
     playout_depth = None
@@ -66,6 +68,31 @@ def eval_baselines(args):
     if getattr(args, "eval_playout_baseline", False):
         out["playout"] = PlayoutPolicy
     return out or None
+
+
+LADDER_ANCHORS = ("builder", "trader", "random")
+
+
+def eval_ladder(args):
+    """The rating ladder `args` adds to every evaluation; None (the default): none.  -> ladder(policy, env, **kw): plays `policy` against
+    the rule-based builder, the trader and the uniform-random sampler on `env` (games with auto_reset, freshly made) by
+    tournament.versus_anchors - the net against three copies of each and against the three together,
+    args.eval_ladder_episodes episodes per game slot; kw goes to tournament.run_tournament - and returns the log entry: the net's
+    rating on the scale where the builder is 0 (tournament.fit_ratings, its default prior), the rating's standard error and the number
+    of decided games behind both."""
+    if not getattr(args, "eval_ladder", False):
+        return None
+    episodes = int(getattr(args, "eval_ladder_episodes", TrainArgs.eval_ladder_episodes))
+
+    def ladder(policy, env, **kw):
+        from . import tournament
+        from .scripted import RandomPolicy, ScriptedPolicy, TraderPolicy
+        players = [ScriptedPolicy(), TraderPolicy(), RandomPolicy(), policy]
+        lineups = tournament.versus_anchors([3], [0, 1, 2])
+        res = tournament.run_tournament(env, players, lineups, episodes, **kw)
+        fit = tournament.fit_ratings(res["table"], lineups, len(players), anchor=0)
+        return {"rating": float(fit["rating"][3]), "stderr": float(fit["stderr"][3]), "games": int(fit["games"])}
+    return ladder
 
 
 def make_teacher(args, env):

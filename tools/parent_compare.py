@@ -179,17 +179,7 @@ def event_call_times(calls, reps, rounds, warm=10):
     return {k: {"device_us": mmm(us[k]), "host_issue_us": mmm(host[k])} for k in calls}
 
 
-class UniformRandom(object):
-    """the uniform-random sampler as a seat of evaluation games (tests/test_gpu_scripted.py keeps its own copy)"""
-    wants_games, include_lstm = True, False
-
-    def rebind(self, e):
-        self.env, self.passes = e, 0
-
-    def act(self, f, lists, lens, masks, games=None, **_kw):
-        import torch
-        a = self.env.sample_random_actions(self.passes).long()
-        self.passes += 1
-        a = a if games is None else a[games.long()]
-        z = torch.zeros((a.shape[0], 1), device=a.device)
-        return z, a, z
+def UniformRandom():
+    """the uniform-random sampler as a seat of evaluation games: scripted.RandomPolicy, unbound (imported at the call: see the top)"""
+    from settlers_of_catan_rl_amd.scripted import RandomPolicy
+    return RandomPolicy()

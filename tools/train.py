@@ -30,6 +30,9 @@ def main():
                     help="every evaluation also plays the trading rule-based player (scripted.TraderPolicy): log[\"trader\"]")
     ap.add_argument("--eval-playout-baseline", action="store_true",
                     help="every evaluation also plays the playout player (scripted.PlayoutPolicy, at its defaults): log[\"playout\"]")
+    ap.add_argument("--eval-ladder", action="store_true",
+                    help="every evaluation also plays the net against builder, trader and random in a tournament: log[\"ladder\"] = its rating with the builder at 0, "
+                         "the standard error and the number of games")
     ap.add_argument("--checkpoint", type=str, default="")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lstm", action="store_true", help="include_lstm (build_agent_model.py:26): LSTM policy + truncated BPTT")
@@ -83,15 +86,21 @@ def main():
     random_net = CatanPolicy(include_lstm=args.lstm).cuda().eval()                                   # robust_train.py:76-78: the evaluation opponent
 
     def evaluate(policy, update_num):
-        return evaluation.run_evaluation_protocol(lambda m: VecCatanEnv(m, seed=args.seed + 1000 + update_num, env_id0=1 << 40, auto_reset=False),
-                                                  policy, random_net, args.num_eval_episodes, update_num,
-                                                  max_steps=args.eval_max_steps, autocast_dtype=torch.bfloat16,
-                                                  baselines=train_loop.eval_baselines(targs))
+        log, summary = evaluation.run_evaluation_protocol(lambda m: VecCatanEnv(m, seed=args.seed + 1000 + update_num, env_id0=1 << 40, auto_reset=False),
+                                                          policy, random_net, args.num_eval_episodes, update_num,
+                                                          max_steps=args.eval_max_steps, autocast_dtype=torch.bfloat16,
+                                                          baselines=train_loop.eval_baselines(targs))
+        ladder = train_loop.eval_ladder(targs)
+        if ladder is not None:
+            log["ladder"] = ladder(policy, VecCatanEnv(args.num_eval_episodes, seed=args.seed + 1000 + update_num, env_id0=1 << 41),
+                                   max_steps=args.eval_max_steps, autocast_dtype=torch.bfloat16)
+            summary += "Ladder (builder = 0): rating {rating:.1f} +/- {stderr:.1f} over {games} games. \n\n".format(**log["ladder"])
+        return log, summary
 
     lg = League(max_distinct=args.league, seed=rank, sampling=args.league_sampling) if args.league > 0 else None
     targs = train_loop.TrainArgs(num_steps=args.num_steps, eval_every=args.eval_every, num_eval_episodes=args.num_eval_episodes,
                                  eval_scripted_baseline=args.eval_scripted_baseline, eval_trader_baseline=args.eval_trader_baseline,
-                                 eval_playout_baseline=args.eval_playout_baseline, **teach,
+                                 eval_playout_baseline=args.eval_playout_baseline, eval_ladder=args.eval_ladder, **teach,
                                  **(dict(start_pool=args.start_pool, start_pool_fresh=args.start_pool_fresh, start_pool_outcomes=args.start_pool_outcomes,
                                         start_pool_sampling=args.start_pool_sampling) if args.start_pool else {}))
     loop = train_loop.TrainingLoop(env, net, col, tr, targs, league=lg, make_net=lambda: CatanPolicy(include_lstm=args.lstm).cuda(),
