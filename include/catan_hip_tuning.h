@@ -158,6 +158,60 @@ int catan_tourney_disable(catan_env_t* env, catan_stream_t stream);
 int catan_tourney_read(catan_env_t* env, uint64_t* out_host, int32_t reset, catan_stream_t stream);
 int catan_tourney_seating(catan_env_t* env, int32_t** lineup_of_dev, int32_t** pos_of_pid_dev);
 
+/* ---- state check ----
+ * The rules a state blob obeys in every position legal play reaches, checked on the device before anything reads the blob as player
+ * ids, tile numbers, card counts or loop bounds (csrc/catan_hooks.hip k_state_check).  Opt-in: nothing calls it unless
+ * the caller does.
+ * blob is a DEVICE int32 [736][cnt], the orientation of catan_state_import; viol is a DEVICE uint64 [cnt]: bit r of viol[i] is set when
+ * blob i breaks rule r.  n_bad may be NULL; otherwise it is a DEVICE uint64 to which the number of blobs with viol != 0 is ADDED (the
+ * caller zeroes it), so one 8-byte read answers "all good?".  No handle: no rule depends on catan_cfg_t.  One lane per blob, 2 944 bytes
+ * read and 8 written per blob, at most one atomic per wave; no synchronisation.
+ * CATAN_EINVAL, nothing launched: a null blob or viol, cnt <= 0.
+ * THE KERNEL IS TOTAL: every int32 in every word is accepted.  A word with a range rule (bits 0..2) that lies outside its range sets
+ * the range bit and IS READ AS THE LOWEST VALUE OF ITS RANGE by every other rule; no word is an index, a shift count or a loop bound
+ * before that.  Cards behind a list's length and trade resources behind a count are not looked at (catan_state_import ignores them,
+ * the export writes -1 there).  Words without a range rule are only compared, or summed in 64 bits.
+ * Player ids are 1..4 and 0 is nobody.  The rules, in bit order (spec.STATE_CHECK_RULES):
+ *    0 range_board     tile_res 0..5, tile_val 2..12, robber_tile 0..18, harbour_type 0..8, corner_bld 0..2, corner_owner / edge_owner 0..4
+ *    1 range_players   n_hidden / n_played / pile_len 0..25 and the cards inside those lengths 0..4; res, vis, bank_res, opp_min, opp_max
+ *                      >= 0; harbour flags 0..1; settlements_left 0..5, cities_left 0..4
+ *    2 range_turn      player_order entries and players_go 1..4; winner, lr_player, la_player, trade_proposer, trade_target and the four
+ *                      to_discard words 0..4; player_order_id 0..3; dice 0..6; n_to_discard, trade_n_give, trade_n_recv 0..4 and the
+ *                      resources inside those counts 1..5; road_building_count 0..2; every flag word 0..1; init_settlements / init_roads
+ *                      0..2; init_second_corner -1..53
+ *    3 terrain_multiset       1 desert, 3 hills, 4 forest, 3 mountains, 4 pastures, 4 fields
+ *    4 token_multiset         the desert holds 7, the other tiles the 18 tokens of the default order
+ *    5 harbour_permutation    harbour_type is a permutation of the harbour ids 0..8
+ *    6 building_owner         corner_bld != 0  <=>  corner_owner != 0
+ *    7 distance_rule          no two neighbouring corners are both built
+ *    8 pieces_left            per player: settlements on the board = 5 - settlements_left, cities = 4 - cities_left
+ *    9 resource_conservation  bank + the four hands = 19 of each resource
+ *   10 card_conservation      pile + hidden + played cards = 14 / 5 / 2 / 2 / 2 of card 0..4
+ *   11 army                   cur_army_size[p] = the knights among p's played cards
+ *   12 largest_army           a holder: la_count = his army >= 3 and no army is larger; none: every army < 3 and la_count = 0
+ *   13 longest_road           a holder: lr_count = his cur_longest_path >= 5 and none is larger; none: lr_count = 0
+ *   14 victory_points         pP_vp = settlements + 2 cities + 2 [holds LR] + 2 [holds LA] + played victory-point cards = curr_vps[P-1]
+ *   15 winner                 0: every curr_vps < 10; w: curr_vps[w-1] >= 10
+ *   16 turn_order             player_order is a permutation of 1..4 and players_go = player_order[player_order_id]
+ *   17 roads_attached         every road shares a corner with a building or another road of its owner
+ *   18 initial_phase          in it: init_settlements[p] / init_roads[p] = p's buildings / roads and dice_rolled = 0; after it: both are
+ *                             2 for everyone and every building touches a road of its owner
+ *   19 dice                   dice_rolled => both dice 1..6
+ *   20 discard                need_discard = (n_to_discard > 0); the first n_to_discard ids are distinct players who each hold more
+ *                             than 7 cards; the ids behind them are 0
+ *   21 trade                  must_respond: proposer and target are two different players and the proposer holds what he offers;
+ *                             otherwise proposer, target and both counts are 0
+ *   22 estimates              slot l of player p is the (l+1)-th player behind p in player_order: opp_min <= that hand <= opp_max
+ *   23 bought                 sum of bought_this_turn <= n_hidden of players_go
+ *   24 road_building          road_building_count > 0 => road_building_active
+ *   25 harbour_flags          pP_harbours[k] <=> P has a building at a harbour slot whose id maps to k (ids 0..4: Ore, Sheep, Wheat, Wood,
+ *                             Brick, i.e. flags 3, 4, 5, 2, 1; ids 5..8: flag 0, the 3:1 harbours)
+ * Necessary, not sufficient: a blob that passes need not be reachable by legal play.  Deliberately no rules: a cap on roads per player
+ * (the reference has none), vis <= res, cur_longest_path = a fresh search (the reference keeps stale values). */
+#define CATAN_STATE_CHECK_RULES 26
+int32_t catan_state_check_rules(void);
+int catan_state_check(const int32_t* blob, int64_t cnt, uint64_t* viol, uint64_t* n_bad, catan_stream_t stream);
+
 /* ---- game records ----
  * Whole games recorded on the device and replayed step by step (csrc/catan_hooks.hip).  A game's draws come from Philox
  * keyed by (seed, global game id) and counted in the state itself (blob word rng_draws), so a start blob, the applied actions, the seed,

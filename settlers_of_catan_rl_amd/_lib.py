@@ -361,6 +361,8 @@ _SIGS = {
     "catan_imitation_loss_words": (C.c_int64, []),
     "catan_imitation_loss_workspace_doubles": (C.c_int64, []),
     "catan_imitation_loss": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "catan_state_check_rules": (C.c_int32, []),
+    "catan_state_check": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp]),
     "catan_playout_actions": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(CatanPlayoutCfg), _vp, _vp, _vp, _vp]),
 }
 # bound only where the library exports them: the same callers also load oracle/libcatan_cpu.so, which implements the env ABI
@@ -371,7 +373,8 @@ _OPTIONAL = {"catan_set_board_configs", "catan_episode_stats_words", "catan_epis
              "catan_start_pool_set", "catan_start_pool_clear", "catan_start_pool_read", "catan_start_pool_size",
              "catan_start_pool_set_weights", "catan_start_pool_outcomes_words", "catan_start_pool_outcomes_enable",
              "catan_start_pool_outcomes_read",
-             "catan_tourney_words", "catan_tourney_enable", "catan_tourney_disable", "catan_tourney_read", "catan_tourney_seating"}
+             "catan_tourney_words", "catan_tourney_enable", "catan_tourney_disable", "catan_tourney_read", "catan_tourney_seating",
+             "catan_state_check_rules", "catan_state_check"}
 
 
 def declared_symbols():

@@ -2526,6 +2526,15 @@ int catan_start_pool_outcomes_read(catan_env_t* e, uint64_t* out_host, int32_t r
     return read_counters(out_host, e->pool_out, start_pool_outcome_words(e->pool.m) * sizeof(unsigned long long), reset, S(stream));
 }
 
+// ---- state check (the kernel is catan_hooks.hip's.  No handle: no rule depends on catan_cfg_t)
+static_assert(SC_RULES == CATAN_STATE_CHECK_RULES, "include/catan_hip_tuning.h restates the rules of catan_hooks.h");
+int32_t catan_state_check_rules(void) { return SC_RULES; }
+int catan_state_check(const int32_t* blob, int64_t cnt, uint64_t* viol, uint64_t* n_bad, catan_stream_t stream) {
+    if (!blob || !viol || cnt <= 0) return fail(CATAN_EINVAL, "catan_state_check: null blob or viol, or cnt <= 0");
+    HIPCHK(state_check_launch(blob, (long)cnt, (u64*)viol, (unsigned long long*)n_bad, S(stream)));
+    return CATAN_OK;
+}
+
 // ---- tournament (the kernels are catan_hooks.hip's, the hooks that launch them stand beside enqueue_start_pool)
 static void tourney_free(catan_env_t* e) {
     for (void* p : { (void*)e->tourney.lineups, (void*)e->tourney.lineup_of, (void*)e->tourney.pos_of_pid, (void*)e->tourney.episode, (void*)e->tourney.table })

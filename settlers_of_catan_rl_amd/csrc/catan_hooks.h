@@ -1,5 +1,5 @@
 // catan_hooks.h - what catan_abi.hip sees of catan_hooks.hip: the launch functions of the recorder's kernels, of the
-// start pool's (8.11), of its weighted pick and outcome tallies (8.12) and of the tournament's (8.16), and the layouts both sides share.  catan_hooks.hip is the
+// start pool's (8.11), of its weighted pick and outcome tallies (8.12), of the tournament's (8.16) and of the state check's (8.17), and the layouts both sides share.  catan_hooks.hip is the
 // library's third translation unit and third gfx950 code object; the ABI's entry points - argument checks, the handles' fields,
 // allocation, the order of the launches and synchronisations - stand in catan_abi.hip and launch through these functions.
 //
@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "catan_game.h"
+#include "catan_state_check.h"
 
 namespace catan {
 
@@ -127,5 +128,9 @@ struct TourneyBuf {
 // passed over.
 hipError_t tourney_launch_tally(const Ctx& c, const TourneyBuf& tb, const u32* count_p, const i32* list, const u8* sel, hipStream_t stream);
 hipError_t tourney_launch_seat(const Ctx& c, const TourneyBuf& tb, const u32* count_p, const i32* list, const u8* sel, hipStream_t stream);
+
+// ---- state check
+// blob: device int32 [STATE_WORDS][cnt]; viol: device uint64 [cnt]; n_bad: device word that the number of blobs with viol != 0 is added to, or null
+hipError_t state_check_launch(const i32* blob, long cnt, u64* viol, unsigned long long* n_bad, hipStream_t stream);
 
 }  // namespace catan

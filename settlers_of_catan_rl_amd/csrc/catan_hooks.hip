@@ -1,7 +1,7 @@
 // catan_hooks.hip - the opt-in hooks of a finished game and of a re-deal: whole games recorded on the device, re-dealt
 // games started from a pool of saved positions (8.11), the pool's weighted pick and its per-entry outcome tallies (8.12), round-robin
-// tournaments seated and booked at the re-deal (8.16).  All opt-in: with no recorder enabled, no pool installed and no tournament enabled
-// nothing here is launched.
+// tournaments seated and booked at the re-deal (8.16) - and, no hook but opt-in like them, the check of state blobs (8.17).  All opt-in: with no
+// recorder enabled, no pool installed, no tournament enabled and no check asked for nothing here is launched.
 //
 // The library's THIRD translation unit and gfx950 code object, for the reason at the top of catan_players.hip: the first code object holds
 // k_step and the learner's kernels and stays, byte for byte in .text, what it is without these hooks (profiles/hooks_unit.txt).  Nothing of
@@ -494,6 +494,49 @@ hipError_t tourney_launch_tally(const Ctx& c, const TourneyBuf& tb, const u32* c
 hipError_t tourney_launch_seat(const Ctx& c, const TourneyBuf& tb, const u32* count_p, const i32* list, const u8* sel, hipStream_t stream) {
     hipLaunchKernelGGL(k_tourney_seat, dim3(tourney_grid(c, count_p)), dim3(64), 0, stream, c, tb, count_p, list, sel);
     return hipPeekAtLastError();
+}
+
+// ================================================================================================ state check
+// k_state_check: the rules of spec.STATE_CHECK_RULES (restated in include/catan_hip_tuning.h) over blobs in catan_state_import's
+// orientation, int32 [736][cnt].  One lane per blob: word k of the wave's 64 blobs is 256 contiguous bytes, every load is coalesced, and
+// a blob is 2 944 bytes in and 8 bytes out.  No handle, no record, no LDS, no scratch: boards are bitboards as in catan_state.h, the
+// neighbour tests are catan_topology.inc's generated helpers, and the players' loop is NOT unrolled - what it keeps per player (hands,
+// hidden-card counts) is written by the predicated assignment k_import uses for cnt5, `x[q] = q == p ? v : x[q]`, and read by sc_pick.
+//
+// TOTAL ON EVERY INPUT.  A word that has a range rule goes through sc_range the moment it is loaded: outside the range it sets the range
+// bit and becomes THE LOWEST VALUE OF ITS RANGE for all that follows, so a shift count, a selector or a length is always inside its
+// range.  Cards behind a length and trade resources behind a count are loaded and ignored.  The words without a range rule (the four
+// counts of turns / actions / trades / draws, bought_this_turn, lr_count, la_count, cur_longest_path, cur_army_size, curr_vps, pP_vp) are
+// only compared, or summed in 64 bits.  No loop bound and no address depends on a blob word.
+//
+// The rules themselves, state_check_blob, stand in catan_state_check.h: one blob in, its violation word out, nothing of the device in it,
+// so that tools/native/state_check_host.cpp compiles the very same lines for the host (tests/test_state_check_host_cpu.py runs them
+// under the undefined-behaviour sanitizer over every single-word corruption).
+#define CATAN_TABLE static __device__ __constant__ const
+#define CATAN_FN static __device__ __forceinline__
+#define CATAN_TOPOLOGY_CODE
+}  // namespace catan
+#include "catan_topology.inc"
+#define CATAN_STATE_CHECK_CODE
+#include "catan_state_check.h"
+namespace catan {
+
+__global__ __launch_bounds__(64) void k_state_check(const i32* __restrict__ blob, long cnt, u64* __restrict__ viol, unsigned long long* __restrict__ n_bad) {
+    const long i = (long)blockIdx.x * 64 + threadIdx.x;
+    u64 v = 0ull;
+    if (i < cnt) {
+        v = state_check_blob(ScBlob{ blob, cnt, i });
+        viol[i] = v;
+    }
+    if (n_bad != nullptr) {                               // one atomic per wave that saw a bad blob
+        const unsigned long long bad_lanes = __ballot(v != 0ull);
+        if (bad_lanes != 0ull && threadIdx.x == (unsigned)(__ffsll(bad_lanes) - 1)) atomicAdd(n_bad, (unsigned long long)__popcll(bad_lanes));
+    }
+}
+
+hipError_t state_check_launch(const i32* blob, long cnt, u64* viol, unsigned long long* n_bad, hipStream_t stream) {
+    hipLaunchKernelGGL(k_state_check, dim3(hooks_blocks(cnt, 64)), dim3(64), 0, stream, blob, cnt, viol, n_bad);
+    return hipGetLastError();
 }
 
 }  // namespace catan

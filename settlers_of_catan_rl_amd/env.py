@@ -291,12 +291,14 @@ class VecCatanEnv(object):
         return out
 
     # ---- start pool (include/catan_hip_tuning.h "start pool"; start_pool.py)
-    def set_start_pool(self, blobs, fresh_share=0.0, weights=None):
+    def set_start_pool(self, blobs, fresh_share=0.0, weights=None, check=False):
         """From now on a game that is re-dealt (auto_reset) or dealt by reset() starts from one of `blobs` - [m, 736], numpy or tensor, the
         orientation of export_state, up to 65536 unfinished positions - except for the share `fresh_share` of deals, which stay fresh.
         The game keeps its own draw counter: the same position in two games rolls different dice.  The env keeps its own copy; the
         counters (start_pool_counts) start at zero.  A second call replaces the pool.  weights: see set_start_pool_weights (None: every
-        entry is equally likely; a new pool never inherits the weights of the one it replaces)."""
+        entry is equally likely; a new pool never inherits the weights of the one it replaces).
+        check=True: the blobs go through the state check first (position.check_blobs); a ValueError names the first eight that break a
+        rule and the pool in force stays as it was.  The default launches nothing new."""
         fn = self._entry("catan_start_pool_set")
         share = float(fresh_share)
         if not 0.0 <= share <= 1.0:                      # (also refuses nan)
@@ -309,6 +311,9 @@ class VecCatanEnv(object):
             raise ValueError(f"start pool blobs: shape [m, {spec.STATE_WORDS}] expected, got {tuple(b.shape)}")
         bt = b.t().contiguous()
         w = None if weights is None else self._start_pool_weights(weights, int(b.shape[0]))      # (refused before any call)
+        if check:
+            from . import position
+            position.require_legal(bt, "set_start_pool")
         _lib.check(fn(self.h, _ptr(bt) if bt.numel() else None, int(b.shape[0]), int(round(share * 65536)), _stream()))
         if w is not None:
             _lib.check(self._entry("catan_start_pool_set_weights")(self.h, _ptr(w), _stream()))
@@ -625,7 +630,10 @@ class VecCatanEnv(object):
         _lib.check(self.L.catan_state_export(self.h, _ptr(blob), _ptr(idx), cnt, _stream()))
         return blob.t().contiguous()
 
-    def import_state(self, blobs, env_idx=None):
+    def import_state(self, blobs, env_idx=None, check=False):
+        """blobs: [cnt, 736] (the orientation of export_state) into the games env_idx (None: games 0..cnt-1).  check=True: the blobs go
+        through the state check first (position.check_blobs); a ValueError names the first eight that break a rule, and nothing else is
+        launched: the games stay as they were.  The default launches nothing new."""
         b = blobs if torch.is_tensor(blobs) else torch.as_tensor(np.asarray(blobs))
         b = b.to(device=self.device, dtype=torch.int32)
         if b.dim() == 1:
@@ -636,7 +644,22 @@ class VecCatanEnv(object):
             idx = torch.as_tensor(env_idx, dtype=torch.int64, device=self.device).contiguous()
             assert idx.numel() == cnt
         bt = b.t().contiguous()
+        if check:
+            from . import position
+            position.require_legal(bt, "import_state")
         _lib.check(self.L.catan_state_import(self.h, _ptr(bt), _ptr(idx), cnt, _stream()))
+
+    def check_blobs(self, blobs):
+        """-> uint64 [cnt] device tensor: bit r set where blob i of `blobs` ([cnt, 736]) breaks rule spec.STATE_CHECK_RULES[r]
+        (position.explain names them).  Only reads the blobs."""
+        from . import position
+        return position.check_blobs(blobs, self.device)
+
+    def check_states(self, env_idx=None):
+        """The state check of the live games env_idx (None: all): exports them and checks the blobs -> uint64 [cnt] device tensor, all
+        zero while the engine's own state obeys the rules.  Not inside an open deferred sequence (export_state)."""
+        from . import position
+        return position.check_blobs(self.export_state(env_idx), self.device)
 
     def fork_from(self, src_env, src_idx, dst_idx=None, draw_offset=None):
         """catan_state_fork (include/catan_hip_tuning.h): this env's game dst_idx[j] (None: game j) becomes a copy of src_env's game

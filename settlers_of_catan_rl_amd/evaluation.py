@@ -43,7 +43,7 @@ def _stats_of(res, rows, dev):
 @torch.no_grad()
 def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=False, generator=None, autocast_dtype=None,
                             act_fn=None, assignment=None, stats=False, detailed=False, searchers=None, record=None,
-                            start_blobs=None):
+                            start_blobs=None, check_blobs=False):
     """env: freshly reset games, auto_reset off.  nets: the policies (entries may be the same object; equal objects share a
     forward); without `assignment` four of them, policy i = nets[i] in every game.  assignment int [n,4] (optional): game g's
     policy i is nets[assignment[g][i]] (the offline evaluator's opponents drawn per game).  orders int [n,4].  max_steps: the
@@ -69,14 +69,20 @@ def run_evaluation_episodes(env, nets, orders, max_steps=None, deterministic=Fal
     deal, by env.import_state - no kernel of its own, the env runs without auto-reset.  An imported blob brings its own draw counter:
     two runs on envs with the same seed and the same blobs see the same dice for as long as the same actions are played, which is what
     makes a comparison of two policies from common positions a PAIRED one.  A record (record=k) then starts from the imported position.
-    None: nothing is imported."""
+    None: nothing is imported.
+    check_blobs: the start blobs go through the state check before they are imported (VecCatanEnv.import_state(check=True)): a ValueError
+    names those that break a rule.  The default launches nothing new."""
     n, dev = env.n, env.device
     if start_blobs is not None:
         b = getattr(start_blobs, "blobs", start_blobs)
         b = (b.cpu() if torch.is_tensor(b) else torch.from_numpy(np.array(b, dtype=np.int32))).to(torch.int32).reshape(-1, spec.STATE_WORDS)
         if b.shape[0] < 1:
             raise ValueError("start_blobs: at least one position")
-        env.import_state(b[torch.arange(n) % b.shape[0]])
+        picked = b[torch.arange(n) % b.shape[0]]
+        if check_blobs:
+            env.import_state(picked, check=True)
+        else:
+            env.import_state(picked)
     if record:
         env.enable_recording(list(range(int(record))))
         env.arm_recording()

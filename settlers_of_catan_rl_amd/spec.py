@@ -295,6 +295,23 @@ TOURNAMENT_MAX_LINEUPS = 65536
 TOURNAMENT_LDS_MAX_LINEUPS = 63                                    # up to here the tally accumulates in LDS (TOURNEY_LDS_MAX_LINEUPS there)
 
 
+# ---------------------------------------------------------------- state check (include/catan_hip_tuning.h catan_state_check)
+# the rules a state blob is checked against, in bit order: bit r of a blob's uint64 word = rule r is broken.  The header restates the
+# list; csrc/catan_hooks.hip holds it as SC_* bit numbers.  Necessary conditions of a legal position, not sufficient ones.
+STATE_CHECK_RULES = [
+    "range_board", "range_players", "range_turn", "terrain_multiset", "token_multiset", "harbour_permutation", "building_owner",
+    "distance_rule", "pieces_left", "resource_conservation", "card_conservation", "army", "largest_army", "longest_road",
+    "victory_points", "winner", "turn_order", "roads_attached", "initial_phase", "dice", "discard", "trade", "estimates", "bought",
+    "road_building", "harbour_flags",
+]
+STATE_CHECK_BIT = {name: i for i, name in enumerate(STATE_CHECK_RULES)}
+DEV_CARD_COUNTS = [14, 5, 2, 2, 2]                                # knights, victory points, year of plenty, road building, monopoly
+RESOURCE_CARDS_EACH = 19
+# harbour id (a harbour_type word) -> index of the player's harbour flag: 0 the generic 3:1, r the 2:1 harbour of Resource r
+# (reference game/components/board.py:29-33)
+HARBOUR_FLAG_OF_ID = [3, 4, 5, 2, 1, 0, 0, 0, 0]
+
+
 # ---------------------------------------------------------------- playout player (include/catan_hip_tuning.h catan_playout_actions)
 # the int64 row of one (row, candidate), in order; csrc/catan_players.h holds the same layout as PS_* offsets
 PLAYOUT_STAT_FIELDS = ["valid", "sims", "finished", "wins", "score_sum", "vp_sum", "steps_sum"]
