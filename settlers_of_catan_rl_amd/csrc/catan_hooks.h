@@ -1,7 +1,8 @@
 // catan_hooks.h - what catan_abi.hip sees of catan_hooks.hip: the launch functions of the recorder's kernels, of the
 // start pool's (8.11), of its weighted pick and outcome tallies (8.12), of the tournament's (8.16) and of the state check's (8.17), and the layouts both sides share.  catan_hooks.hip is the
 // library's third translation unit and third gfx950 code object; the ABI's entry points - argument checks, the handles' fields,
-// allocation, the order of the launches and synchronisations - stand in catan_abi.hip and launch through these functions.
+// allocation, the order of the launches and synchronisations - stand in catan_abi_hooks.h, one of catan_abi.hip's host files, and launch
+// through these functions.
 //
 // What a launch function returns.  Those an entry point calls and checks on the spot return hipGetLastError().  Those of the hooks
 // that enqueue_redeal and the stepping calls run (append, seal, open, install, outcomes, origin_clear, tally, seat) return hipPeekAtLastError(): the

@@ -32,7 +32,7 @@ static inline unsigned hooks_blocks(long n, int b) { return (unsigned)((n + b - 
 // negative type is the no-op and is never logged).  A mask-ILLEGAL action may carry any int32: its words are saturated to
 // [-32 768, 32 767] (rec_sat16).  A saturated word is still outside [0, 72], so it indexes no head and the replay rejects the action as the
 // live game did; words inside the int16 range, legal or not, are stored exactly.
-// Where each kernel runs: the hooks beside enqueue_episode_stats and enqueue_redeal in catan_abi.hip.
+// Where each kernel runs: the enqueue_* hooks of catan_abi_hooks.h, in the order enqueue_redeal (catan_abi.hip) states.
 DEVI short rec_sat16(i32 v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
 DEVI void record_snapshot(const Ctx& c, long game, i32* blob) { export_game(St(c.R, c.N, game), BlobW{ blob, 1, 0, 0 }); }
 

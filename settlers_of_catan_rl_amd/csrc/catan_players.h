@@ -1,7 +1,7 @@
 // catan_players.h - what catan_abi.hip sees of catan_players.hip: the launch functions of the teacher's kernels, the
 // trader (8.14) and the playout player (8.15), and the layouts both sides share.  catan_players.hip is the library's second translation
 // unit and second gfx950 code object (the reason stands at its top); the ABI's entry points - argument checks, the handles' fields, the
-// order of the launches - stand in catan_abi.hip and launch through these functions.
+// order of the launches - stand in catan_abi_players.h, one of catan_abi.hip's host files, and launch through these functions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -52,7 +52,7 @@ FLT_MIN = 2.0 ** -126
 EMPTY_EVERY = 13
 
 # ------------------------------------------------------------------------------------------------------------------- launch table
-# catan_categorical_fwd / _bwd / _bits_fwd / _bits_bwd (csrc/catan_abi.hip): one lane per row, 256 rows per block, ceil(rows / 256) blocks,
+# catan_categorical_fwd / _bwd / _bits_fwd / _bits_bwd (csrc/catan_abi_nn.h): one lane per row, 256 rows per block, ceil(rows / 256) blocks,
 # no cap and no loop.
 BLOCK = 256
 ROWS = (1, 255, 256, 257, 4097)

@@ -28,7 +28,7 @@ FP32_FLOOR = {"y": 2.0 ** -17, "dx": 2.0 ** -15}        # the attention suite's 
 PLANTS = ("one_pass", "d_minus_1", "eps_outside", "no_m2", "gate_lt", "dw_ungated", "swap_pairs", "drop_last", "dw_scale")
 
 # ------------------------------------------------------------------------------------------------------------------- launch table
-# ln_dispatch / ln_launch / lnw_launch (csrc/catan_abi.hip): 256 threads, GL lanes per row, RPB = 256 / GL rows per block and pass; the
+# ln_dispatch / ln_launch / lnw_launch (csrc/catan_abi_nn_launch.h): 256 threads, GL lanes per row, RPB = 256 / GL rows per block and pass; the
 # grid is ceil(rows / RPB) blocks up to a cap, above which a block's grid-stride loop runs again.  k_lnr: a lane per row, 256 rows per block.
 FWD_CAP = 8192
 BWD_CAP = {"ln": 2048, "lnw": 1024, "lnr": 2048}

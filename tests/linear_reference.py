@@ -1,6 +1,6 @@
 """Plain-torch restatement of the row-split linear kernels of csrc/catan_nn.hip and csrc/catan_wgrad_big.hip - k_linear_rows<KS, NT>
 (catan_linear_rows / catan_linear_rows_fused), k_wgrad / k_wgrad_tr<OTW, IT> and their _grouped forms (catan_linear_wgrad /
-catan_linear_wgrad_grouped), k_wgrad_big + k_wgrad_big_reduce (catan_linear_wgrad_big) - with the launch table of csrc/catan_abi.hip, the
+catan_linear_wgrad_grouped), k_wgrad_big + k_wgrad_big_reduce (catan_linear_wgrad_big) - with the launch table of csrc/catan_abi_nn_launch.h, the
 seeded case builders, the bounds and the planted errors that tests/test_linear_reference_cpu.py and tests/test_gpu_linear_fp64.py share.
 No call into the library or into nn_kernels: torch ops only, on the CPU or the GPU.
 

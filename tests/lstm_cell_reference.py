@@ -35,7 +35,7 @@ FLT_MIN = 2.0 ** -126
 BIG = 1e30                                               # c_prev of a masked row in `masked`
 
 # ------------------------------------------------------------------------------------------------------------------- launch table
-# lstm_cell_launch (csrc/catan_abi.hip): an item = four consecutive hidden units of one row, a lane per item, 256 lanes per block;
+# lstm_cell_launch (csrc/catan_abi_nn_launch.h): an item = four consecutive hidden units of one row, a lane per item, 256 lanes per block;
 # ceil(rows (L / 4) / 256) blocks, at most 16 384, above which a lane's grid-stride loop runs again.
 BLOCK = 256
 CAP = 16384

@@ -132,6 +132,7 @@ N_GAMES, SEED, ENV_ID0 = 64, 23, (5 << 32) + 7        # the high and the low wor
 ENV_ID0_ZERO = 0
 STEP_CAP = 250                  # lock-step steps of a scenario; every scenario starts with reset() under its pool
 RANDOM_STEPS = 300              # the random-policy scenario (catan_random_rollout)
+REFUSED_SET_STEPS = 40          # the steps behind a refused catan_start_pool_set, under the pool of pools()[64][:2] installed before it
 POOL_SRC_GAMES, POOL_SRC_SEED, POOL_SRC_ID0, POOL_SRC_CAP = 24, 5, 1000, 1400
 LATE_VP, N_LATE, N_EARLY = 8, 60, 4
 

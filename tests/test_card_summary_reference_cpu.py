@@ -1,6 +1,6 @@
 """CPU: tests/card_summary_reference.py against itself and against the package, before tests/test_gpu_card_summary_fp64.py relies on it.
 The class form equals the per-token reference; the per-token reference equals policy._card_summary's torch branch in double; the pattern
-number, the pattern lists, the launch table, the depths and the hash facts are what csrc/catan_nn.hip and csrc/catan_abi.hip say; the
+number, the pattern lists, the launch table, the depths and the hash facts are what csrc/catan_nn.hip and csrc/catan_abi_nn.h say; the
 rule refuses every planted error and accepts the yardstick."""
 import pytest
 import torch

@@ -1,5 +1,5 @@
 """GPU: the four attention kernels of csrc/catan_nn.hip (k_attn_fwd, k_attn_bwd, k_attn_mfma_fwd, k_attn_mfma_bwd) per sequence against
-fp64, on every path of attn_dispatch (csrc/catan_abi.hip), through the C ABI (catan_attention_fwd / catan_attention_bwd).
+fp64, on every path of attn_dispatch (csrc/catan_abi_nn_launch.h), through the C ABI (catan_attention_fwd / catan_attention_bwd).
 
 reference = tests/attention_reference.py: attention_ref in fp64 from the inputs as stored; yardstick = attention_yardstick in fp32 with a
 bf16 rounding where the kernel of the path rounds (its docstring places them).  Acceptance of an output tensor (out, dq, dk, dv):

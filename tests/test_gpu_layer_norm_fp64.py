@@ -1,5 +1,5 @@
 """GPU: the LayerNorm kernels of csrc/catan_nn.hip (k_ln_fwd / k_ln_bwd, k_lnw_fwd / k_lnw_bwd, k_lnr_fwd / k_lnr_bwd) row by row against
-fp64 on every path of ln_dispatch (csrc/catan_abi.hip), through the C ABI (catan_layer_norm_fwd / catan_layer_norm_bwd), with relu 0 and 1.
+fp64 on every path of ln_dispatch (csrc/catan_abi_nn_launch.h), through the C ABI (catan_layer_norm_fwd / catan_layer_norm_bwd), with relu 0 and 1.
 
 reference = tests/layer_norm_reference.py (its docstring has the formulas and the yardstick's roundings; the rule is tests/pin_rule.py's):
     y, dx   maxabs(kernel - fp64) <= 2 maxabs(yardstick - fp64) + floor maxabs(fp64), floor 2^-9 (bf16) / 2^-17 for y, 2^-15 for dx (fp32, the

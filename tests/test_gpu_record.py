@@ -356,6 +356,32 @@ def test_error_returns(hip_lib):
     assert not rejected.any() and np.array_equal(final, plain.export_state([GAMES[3]])[0].cpu().numpy())
 
 
+def test_a_refused_enable_drops_the_old_slots_and_the_next_enable_works(hip_lib):
+    """catan_record_enable has dropped the old slots before it builds the new ones: after an enable the device refuses (a game listed
+    twice) recording is off, not back at the earlier slots, and a valid enable of two slots then records as any other"""
+    from settlers_of_catan_rl_amd.env import _ptr, _stream
+    L = hip_lib
+    env = _env(False)
+    env.enable_recording(GAMES, capacity=64)
+    assert _status(env).shape[0] == len(GAMES)
+    twice = torch.tensor([3, 4, 3], dtype=torch.int32, device=env.device)
+    assert L.catan_record_enable(env.h, _ptr(twice), 3, 64, _stream()) == EINVAL and b"list a game twice" in L.catan_last_error()
+    sp = np.zeros((16, 4), dtype=np.uint32).ctypes.data_as(C.c_void_p)
+    assert L.catan_record_status(env.h, sp, _stream()) == EINVAL and b"not enabled" in L.catan_last_error()
+    env.enable_recording([31, 32], capacity=8)
+    env.arm_recording()
+    start = env.export_state([31, 32]).cpu().numpy()
+    rows = []
+    for _ in range(3):
+        a = env.sample_scripted_actions()
+        rows.append(a[[31, 32]].cpu().numpy())
+        env.step(a)
+    st = _status(env)
+    assert st.shape == (2, 4) and (st[:, 0] == record.RECORDING).all() and st[:, 1].tolist() == [31, 32] and (st[:, 2] == 3).all(), st
+    for s, rec in enumerate(env.recordings(sealed_only=False)):
+        assert np.array_equal(rec.start_blob, start[s]) and np.array_equal(rec.actions, np.array([r[s] for r in rows])), s
+
+
 def _product_replay_reaches_the_final_blob(rec):
     """record.replay: product code only, a one-game VecCatanEnv on the device"""
     steps = list(record.replay(rec))

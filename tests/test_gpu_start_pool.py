@@ -358,6 +358,26 @@ def test_error_returns_leave_the_installed_pool_intact(hip_lib, pools):
     env.random_rollout_deferred(8, 4)
 
 
+def test_a_refused_set_leaves_the_pool_of_two_that_steps_install_from(hip_lib, pools):
+    """(11b) the new pool is built beside the one in use: a set of 4 blobs with a finished game among them is refused on the device, and
+    the pool of 2 installed before is still what catan_start_pool_size and catan_start_pool_read report and what the re-deals of the
+    following catan_step calls install from, as the twin's do"""
+    from settlers_of_catan_rl_amd.env import _ptr, _stream
+    two, four = pools[64][:2], pools[64][2:6].copy()
+    spec.state_field(four[1], "winner")[...] = 3
+    env, twin = _env(), spr.PoolTwin(N, SEED, ID0, two, 0)
+    env.set_start_pool(two)
+    bad = torch.from_numpy(four).to(env.device).t().contiguous()
+    assert hip_lib.catan_start_pool_set(env.h, _ptr(bad), 4, 0, _stream()) == EINVAL and b"1 blobs are positions of finished games" in hip_lib.catan_last_error()
+    assert hip_lib.catan_start_pool_size(env.h) == 2
+    c = env.start_pool_counts()
+    assert (c["pool"], c["fresh"], c["per_entry"].tolist()) == (0, 0, [0, 0])
+    _lockstep(env, twin, spr.REFUSED_SET_STEPS)
+    c = _same_counts(env, twin)
+    print("installs behind the refused set", c["pool"], c["per_entry"].tolist())
+    assert c["pool"] > N and c["fresh"] == 0 and c["per_entry"].shape == (2,)
+
+
 def test_collector_in_both_loops(hip_lib, pools):
     """(12) RolloutCollector(start_pool=...) on the device loop (_gather_device) and on the tensor-operation loop (_gather_tensor), the bot in
     every seat: the loops agree with each other, storage.start_pool is what the env counted during the gather (read with reset), and

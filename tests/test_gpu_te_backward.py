@@ -8,7 +8,7 @@ reference = the operation in fp64 from the same bf16 inputs; yardstick = fp32 wi
 bound is computed inside the test from those two; nothing in it comes from a kernel's output.  Every case prints one `TE_BWD` line
 per output (kernel error, yardstick error, their ratio): profiles/te_backward_kernel_tests.txt is that output.
 
-Rows of the one-pass backward kernels and the blocks they give (te_bwd_grid, csrc/catan_abi.hip: stages = ceil(rows / 64) stages of
+Rows of the one-pass backward kernels and the blocks they give (te_bwd_grid, csrc/catan_abi_nn_launch.h: stages = ceil(rows / 64) stages of
 64 rows; max(1, min(512, stages / 16)) blocks of ceil(stages / blocks) stages each, empty trailing blocks dropped; a wave takes 16 of
 a stage's rows):
     1, 15, 16, 17     one stage: less than a wave, a full wave, one row into the second wave

@@ -187,6 +187,25 @@ def test_enable_refusals_and_their_messages(hip_lib):
         env.enable_tournament(lineups[:, :3], PLAYERS)
 
 
+def test_a_refused_enable_leaves_the_earlier_tournament_as_it_was(hip_lib):
+    """a lineup that names player M is refused on the host, before anything of the tournament in force is touched: its table (made
+    non-zero by a second reset, which books every seated game as a draw) and its seating read as before"""
+    L = 5
+    env = _env(64, 9)
+    env.enable_tournament(_lineups(L), PLAYERS)
+    env.reset()
+    env.reset()
+    before, seats = env.tournament_table().numpy(), [x.clone() for x in env.tournament_seating()]
+    assert before[L][tr.T_DRAWS] == 64 and before[L][tr.T_SEATED] == 128
+    bad = np.ascontiguousarray(_lineups(3))
+    bad[2, 1] = PLAYERS
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert hip_lib.catan_tourney_enable(env.h, bad.ctypes.data_as(C.c_void_p), 3, PLAYERS, 0, st) == -1
+    assert b"lineup 2 names player 7" in hip_lib.catan_last_error()
+    _assert_table(env.tournament_table().numpy(), before, "behind the refused enable")
+    assert all(torch.equal(a, b) for a, b in zip(env.tournament_seating(), seats))
+
+
 RT_N, RT_SEED, RT_E, RT_CAP = 16, 3, 2, 1500
 RT_LINEUPS = np.array([[0, 1, 2, 2], [0, 2, 2, 2], [1, 2, 2, 2], [0, 1, 1, 2], [0, 0, 1, 2]], dtype=np.int64)     # 0 builder, 1 trader, 2 random
 

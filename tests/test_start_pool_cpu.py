@@ -306,6 +306,9 @@ def test_seed_check_for_the_gpu_scenarios():
         assert twin.counts["pool"] == redeals + spr.N_GAMES
         if m <= 3:
             assert (twin.counts["per_entry"] > 0).all()
+    twin = spr.PoolTwin(spr.N_GAMES, spr.SEED, spr.ENV_ID0, pools[64][:2], 0)               # the two late positions behind a refused set
+    spr.run_twin(twin, spr.REFUSED_SET_STEPS)
+    assert twin.counts["pool"] >= spr.N_GAMES + 8 and (twin.counts["per_entry"] > 0).all() and twin.counts["fresh"] == 0
     twin = spr.PoolTwin(spr.N_GAMES, spr.SEED, spr.ENV_ID0, pools[3], 32768)               # half fresh
     spr.run_twin(twin, spr.STEP_CAP)
     print("half fresh:", twin.counts)
